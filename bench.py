@@ -18,6 +18,12 @@ gather reads them, plus that gather.
 `extras.cfg5_strong` is BASELINE.json configs[4]: ONE 10M x 400 database cut into
 residue-balanced contiguous shards over the ranks (strong scaling), one gather.
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line: `value`, `ms_per_step`
+and the HBM roofline of the timed steps. Everything else - the HBM-resident, pageable and
+PCIe-inclusive forms, the PMC-derived figures, the CPU baseline and its agreement checks,
+the legs of `extras` including cfg5, bench_details.json - runs only with --full.
+--dump-outputs DIR writes the scores of the last timed step as DIR/scores.npy (float32).
 """
 import ctypes
 import hashlib
@@ -52,7 +58,15 @@ def parse():
                     help="N = 1 rehearsal of the N > 1 path: a 1-rank nccl group (launch under torch.distributed.run "
                          "--nproc-per-node 1), RCCL gather of device tensors, all_reduce of the elapsed time, "
                          "MIOPAL_RESERVE_CUS")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary leg and check (the other forms of the search, PMC figures, CPU baseline, "
+                         "extras, cfg5) and bench_details.json")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the scores of the last timed step (rank 0: every rank's, gathered) to DIR/scores.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -181,7 +195,7 @@ def main():
                          device=f"cuda:{local_rank}" if on_device else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        if rank == 0:
+        if rank == 0 and args.full:
             # the gathered vector of this rank's own shard is what the search wrote
             assert torch.equal(pipe.received[last][0].cpu(), out.cpu())
 
@@ -189,14 +203,18 @@ def main():
     # a sample against the scalar checker; the other legs never touch the code under oracle/)
     got = host_out.copy() if host_out is not None else out.cpu().numpy()
     checksum = int(got.astype(np.int64).sum())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step: the caller's array at N = 1, every rank's
+        # scores in rank order (the gather's result) on the collective path
+        dump_outputs(args.dump_outputs, torch.cat(pipe.received[last]).cpu().numpy() if collective else got)
     device_form = None
-    if not collective:
+    if args.full and not collective:
         # the same search with the scores left in HBM (what `value` was up to round 2)
         device_form = device_results(db, query, matrix, outs[0], stream, Q, N, L)
         assert np.array_equal(outs[0].cpu().numpy(), got)
 
     cfg5 = None
-    if not args.no_cfg5:
+    if args.full and not args.no_cfg5:
         cfg5 = cfg5_strong(args, query, matrix, rank, world, local_rank, on_device, stream, collective)
     if collective:
         # every timed region is over: the group ends here, so that the other ranks are gone (and their
@@ -213,9 +231,6 @@ def main():
         alg_bytes = float(N) * L + 12.0 * N + Q + 4 * 24 * 24
         k_ms = kernel_ms / max(n_launch, 1)
         achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        pmc = pmc_summary() if (N, L) == (1_000_000, 300) else None
-        host_form = host_results(db, query, matrix, Q, N, L) if not collective else None
-        plain_form = plain_entry(query, residues, offsets, matrix, Q, N, L, got) if not collective else None
         line = {
             "metric": "GCUPS (billion DP cells/s) SW score-only, 53aa query vs 1Mx300aa DB",
             "value": round(gcups, 1),
@@ -231,18 +246,7 @@ def main():
             # 25600; lanes that reach it are redone at int16 / int32)
             "dtype": "u16",
             "data": "synthetic",
-            # N = 1: `value` is the blocking call with the scores in the caller's pinned host array; the same
-            # call with an ordinary (pageable) array goes through the library's pinned bounce buffer and
-            # one 4 MB copy on the host; with the scores left in HBM nothing crosses PCIe
-            "value_host_results_pageable": host_form["gcups"] if host_form else None,
-            "ms_per_step_host_results_pageable": host_form["ms"] if host_form else None,
-            "value_device_results": device_form["gcups"] if device_form else None,
-            "ms_per_step_device_results": device_form["ms"] if device_form else None,
             "forced_collective": bool(args.force_collective),
-            # opalSearchDatabase exactly as the reference binds it: N host pointers in, the database
-            # uploaded and packed on every call, N result structs out (PCIe-inclusive, never `value`)
-            "value_pcie_inclusive": plain_form["gcups"] if plain_form else None,
-            "ms_per_step_pcie_inclusive": plain_form["ms"] if plain_form else None,
             "config": {
                 "workload": f"sw_score q{Q} (README.md:86) vs {N}x{L} uniform-random proteins per GPU, "
                             "BLOSUM62, gap_open 3, gap_extend 1; value: "
@@ -259,6 +263,34 @@ def main():
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 5),
+                "kernel": f"interseq_pair_biased_kernel<{max(2, (Q + 1) // 2 * 2)}, false>",
+                "kernel_ms": round(k_ms, 4),
+                "kernel_gcups": round(float(Q) * N * L / (k_ms * 1e-3) / 1e9, 1) if k_ms > 0 else None,
+                "algorithmic_bytes": alg_bytes,
+                "note": "integer-VALU-bound by construction (6.9 VALU instructions per pair of cells of a "
+                        "lane, 0.02 B/cell): see DESIGN.md",
+            },
+            "db_build_s": round(build_s, 3),
+            "score_checksum": checksum,
+        }
+        if args.full:
+            pmc = pmc_summary() if (N, L) == (1_000_000, 300) else None
+            host_form = host_results(db, query, matrix, Q, N, L) if not collective else None
+            plain_form = plain_entry(query, residues, offsets, matrix, Q, N, L, got) if not collective else None
+            line.update({
+                # N = 1: `value` is the blocking call with the scores in the caller's pinned host array; the same
+                # call with an ordinary (pageable) array goes through the library's pinned bounce buffer and
+                # one 4 MB copy on the host; with the scores left in HBM nothing crosses PCIe
+                "value_host_results_pageable": host_form["gcups"] if host_form else None,
+                "ms_per_step_host_results_pageable": host_form["ms"] if host_form else None,
+                "value_device_results": device_form["gcups"] if device_form else None,
+                "ms_per_step_device_results": device_form["ms"] if device_form else None,
+                # opalSearchDatabase exactly as the reference binds it: N host pointers in, the database
+                # uploaded and packed on every call, N result structs out (PCIe-inclusive, never `value`)
+                "value_pcie_inclusive": plain_form["gcups"] if plain_form else None,
+                "ms_per_step_pcie_inclusive": plain_form["ms"] if plain_form else None,
+            })
+            line["roofline"].update({
                 # HBM bytes per launch from separate rocprofv3 --pmc passes over THIS binary (the
                 # summary carries the sha256 of the libmiopal.so it profiled; null when it differs)
                 "traffic": pmc["hbm_traffic_bytes_per_launch"] if pmc else None,
@@ -268,32 +300,36 @@ def main():
                                   "MI355X_MICROARCH.md; library " + pmc["library_sha256"][:16] + ")" if pmc else
                                   "no PMC summary for this build of libmiopal.so (sha256 "
                                   + library_sha256()[:16] + ")",
-                "kernel": f"interseq_pair_biased_kernel<{max(2, (Q + 1) // 2 * 2)}, false>",
-                "kernel_ms": round(k_ms, 4),
-                "kernel_gcups": round(float(Q) * N * L / (k_ms * 1e-3) / 1e9, 1) if k_ms > 0 else None,
-                "algorithmic_bytes": alg_bytes,
-                "note": "integer-VALU-bound by construction (6.9 VALU instructions per pair of cells of a "
-                        "lane, 0.02 B/cell): see DESIGN.md",
                 # secondary ceiling: VALU issue, from SQ_INSTS_VALU of this binary
                 "valu_issue": valu_ceiling(Q, k_ms, N, L, pmc),
                 # LDS counters of the same PMC passes (north_star: "LDS-hit counters reported"): the pair table
                 # is read with one ds_read_b128 per four query rows of a lane; two thirds of the LDS array's
                 # busy cycles are bank conflicts of the random pair rows
                 "lds": pmc["lds"] if pmc else None,
-            },
-            "db_build_s": round(build_s, 3),
-            "score_checksum": checksum,
-        }
-        line["extras"] = {}
-        if not args.no_cpu_baseline:
-            # (N > 1: rank 0's shard against rank 0's scores - the same 1M x 300 workload per GPU)
-            line["cpu_baseline"] = cpu_baseline(query, residues, offsets, matrix, Q, N, L, got)
-            if not collective:
-                line["extras"] = extras(db, query, matrix, Q, N, L)
-        if cfg5 is not None:
-            line["extras"]["cfg5_strong"] = cfg5
-        print(json.dumps(compact_line(line)), flush=True)
+            })
+            line["extras"] = {}
+            if not args.no_cpu_baseline:
+                # (N > 1: rank 0's shard against rank 0's scores - the same 1M x 300 workload per GPU)
+                line["cpu_baseline"] = cpu_baseline(query, residues, offsets, matrix, Q, N, L, got)
+                if not collective:
+                    line["extras"] = extras(db, query, matrix, Q, N, L)
+            if cfg5 is not None:
+                line["extras"]["cfg5_strong"] = cfg5
+            line = compact_line(line)
+        print(json.dumps(line), flush=True)
     db.close()
+
+
+DUMP_VALUES = 8 << 20   # values per dumped array (32 MB of float32): beyond it, a fixed seeded sample
+
+
+def dump_outputs(where, scores):
+    """DIR/scores.npy: the scores as float32 (exact: a score of the 53-residue query stays far below 2**24);
+    a larger output is sampled at the same indices on every run with the same arguments."""
+    if len(scores) > DUMP_VALUES:
+        scores = scores[np.sort(np.random.default_rng(0).choice(len(scores), DUMP_VALUES, replace=False))]
+    os.makedirs(where, exist_ok=True)
+    np.save(os.path.join(where, "scores.npy"), scores.astype(np.float32))
 
 
 def compact_line(line, limit=8000):

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_line_small_workload():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
-                          "--warmup", "1", "--targets", "50000", "--cfg5-targets", "250000", "--cfg5-steps", "2"],
+                          "--warmup", "1", "--targets", "50000", "--cfg5-targets", "250000", "--cfg5-steps", "2", "--full"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -76,7 +76,7 @@ def test_bench_forced_collective_on_one_gpu():
         port = sock.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--targets", "50000", "--cfg5-targets", "250000", "--cfg5-steps", "2", "--force-collective"]
+           "--targets", "50000", "--cfg5-targets", "250000", "--cfg5-steps", "2", "--force-collective", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -97,7 +97,7 @@ def test_bench_starts_its_own_ranks():
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(key, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--targets", "50000", "--cfg5-targets", "250000", "--cfg5-steps", "2"],
+                          "--targets", "50000", "--cfg5-targets", "250000", "--cfg5-steps", "2", "--full"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -155,3 +155,51 @@ def test_bench_refuses_to_run_without_gpu():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0",
                           "--targets", "100"], capture_output=True, text=True, timeout=600)
     assert out.returncode != 0 and "needs a GPU" in (out.stderr + out.stdout)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    # without --full: the headline figure alone (no secondary leg, no CPU baseline, no bench_details.json) and, with
+    # --dump-outputs, the scores of the last timed step - the same on every run, equal to the CPU checker
+    import numpy as np
+    import _data
+    import _oracle
+    from pyopal_amd.matrices import ScoringMatrix
+    n = 50000
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                          "--targets", str(n), "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=600, cwd=tmp_path)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["unit"] == "GCUPS" and line["dtype"] == "u16"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert abs(line["value"] - 53.0 * n * 300 / (line["ms_per_step"] * 1e-3) / 1e9) <= 0.002 * line["value"] + 0.1
+    assert line["roofline"]["kernel_ms"] > 0
+    for key in ("cpu_baseline", "extras", "details_file", "value_device_results", "value_pcie_inclusive"):
+        assert key not in line, key
+    assert not (tmp_path / "bench_details.json").exists()
+    scores = np.load(tmp_path / "dump" / "scores.npy")
+    assert scores.dtype == np.float32 and scores.shape == (n,)
+    assert int(scores.astype(np.int64).sum()) == line["score_checksum"]
+    # the inputs are those of the command line alone: seed 1, the README query
+    residues, offsets = _data.random_db(np.random.default_rng(1), np.full(n, 300))
+    matrix = np.array(ScoringMatrix.from_name("BLOSUM62").int_array(), dtype=np.int32)
+    want = _oracle.search(_oracle.encode(_data.README_QUERY), residues[:offsets[512]], offsets[:513], matrix, 3, 1,
+                          "score", "sw")["score"]
+    assert np.array_equal(scores[:512], want.astype(np.float32))
+
+
+def test_bench_dump_of_a_large_output_is_a_fixed_sample(tmp_path):
+    import numpy as np
+    import bench
+    scores = np.arange(bench.DUMP_VALUES + 12345, dtype=np.int32)
+    for where in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / where), scores)
+    a, b = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "b" / "scores.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_VALUES,) and a.nbytes <= 64 << 20
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0)
+    small = np.array([3, 0, 583], dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "c"), small)
+    assert np.load(tmp_path / "c" / "scores.npy").tolist() == [3.0, 0.0, 583.0]

@@ -11,8 +11,8 @@ root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-args="--no-cpu-baseline --no-cfg5"
-python3 $root/bench.py > $out/${tag}_bench_line.json 2> $out/${tag}_bench_line.err
+args="--full --no-cpu-baseline --no-cfg5"
+python3 $root/bench.py --full > $out/${tag}_bench_line.json 2> $out/${tag}_bench_line.err
 rm -rf $out/prof_$tag && mkdir -p $out/prof_$tag
 rocprofv3 --kernel-trace --stats -d $out/prof_$tag/trace --output-format csv -- python3 $root/bench.py $args > $out/prof_$tag/trace.log 2>&1
 cp $(ls $out/prof_$tag/trace/*/*kernel_stats.csv | head -1) $out/${tag}_bench_kernel_stats.csv
