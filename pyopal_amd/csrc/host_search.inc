@@ -705,7 +705,9 @@ struct Search {
             // (score + ext, or ext - open) of at most 0x0400 so that a finite half cannot jump over
             // the NaN patterns, a step down (score + ext, open - ext) within the room below zero.
             // With end locations every value is scaled by 2^bits (row keys in the low bits).
-            const int pairRows = std::max(2, (Q + 1) / 2 * 2);
+            // (Smith-Waterman: the query's own rows, the biased kernel exists for odd counts too; the NW / HW / OV
+            // kernel sweeps rows in pairs)
+            const int pairRows = sw ? std::max(1, Q) : std::max(2, (Q + 1) / 2 * 2);
             // (row keys in the low bits of every value - unless the end locations come from a second sweep)
             const bool twoPass = pairStrips && sw && locate && twoPassEnds;
             const bool rowKeys = locate && !twoPass;
@@ -1160,12 +1162,41 @@ struct Search {
                     directScatter = true;
                 }
                 const PairFlavour pf = globalPair ? kPairGlobalBiased : biased ? kPairSwBiased : halfFloat ? kPairSwHalf : kPairSwInt16;
+                // (diagnostic builds of the Smith-Waterman kernel, -DMIOPAL_HEADLINE_TIMING=1: the SIMDs' finish times)
+                unsigned long long* simdFinish = nullptr;
+                const int finishSlots = 1 + 4 * pairUnits;
+                if (pf == kPairSwBiased && tuned(Tune::STRIP_TIMING)) {
+                    void* tb;
+                    RC_TRY(ws->get(kStripTiming, finishSlots * sizeof(unsigned long long), &tb));
+                    HIP_TRY(hipMemsetAsync(tb, 0, finishSlots * sizeof(unsigned long long), stream));
+                    HIP_TRY(hipMemsetAsync(tb, 0xff, sizeof(unsigned long long), stream));
+                    ia.stripTiming = simdFinish = (unsigned long long*)tb;
+                }
                 g_lastRouting[1] = 2 + (int)pf;
-                // the biased kernel exists for every even number of rows: no padding rows to 8
+                // the biased kernels exist for every number of rows (NW / HW / OV: every even number): no padding rows to 8
                 // (test switch: the launch behaves as if the runtime had refused it, e.g. its 150 KB of dynamic LDS)
                 const hipError_t pe = tuned(Tune::TEST_REFUSE_PAIR_LAUNCH)
                                           ? hipErrorInvalidValue
                                           : launchInterseqPair(ia, (biased || globalPair) ? pairRows : rows, pf, pairUnits, stream, locate);
+                if (pe == hipSuccess && simdFinish) {
+                    std::vector<unsigned long long> t((size_t)finishSlots);
+                    HIP_TRY(hipMemcpyAsync(t.data(), simdFinish, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+                    HIP_TRY(hipStreamSynchronize(stream));
+                    double sum = 0, last = 0, first = 1e30;
+                    int n = 0;
+                    for (int i = 1; i < finishSlots; ++i) {
+                        if (t[i] == 0) continue;   // (a build without stamps, or a SIMD the launch left alone)
+                        const double us = (double)(t[i] - t[0]) / 100.0;   // 100 MHz ticks -> us
+                        sum += us;
+                        last = std::max(last, us);
+                        first = std::min(first, us);
+                        ++n;
+                    }
+                    if (n > 0)
+                        fprintf(stderr, "[miopal] headline timing (%d SIMDs, %d groups, %d rows): finish mean %.1f us  first %.1f  last %.1f  "
+                                        "last - mean %.1f us\n",
+                                n, ia.nGroups, pairRows, sum / n, first, last, last - sum / n);
+                }
                 if (pe != hipSuccess) {
                     // e.g. the runtime refuses 150 KB of dynamic LDS: use the v_perm variant (the
                     // biased profile is a plain int16 profile whose padding score, -1024, cannot raise

@@ -50,8 +50,20 @@ hipError_t launchInterseqPair(const InterseqArgs& a, int rowsPerStrip, PairFlavo
             if (rowsPerStrip < 50) return launchInterseqPairGlobalC(a, rowsPerStrip, computeUnits, stream);
             return launchInterseqPairGlobalD(a, rowsPerStrip, computeUnits, stream);
         case kPairSwBiased:
-            // any even number of rows
-            if (rowsPerStrip < 2 || rowsPerStrip > 64 || (rowsPerStrip & 1)) return hipErrorInvalidValue;
+            // any number of rows: the query's length, odd ones included (a padding row is 1 / Q of the work)
+            if (rowsPerStrip < 1 || rowsPerStrip > 64) return hipErrorInvalidValue;
+            if (rowsPerStrip & 1) {
+                if (locate) {
+                    if (rowsPerStrip < 17) return launchInterseqPairSwBiasedLocOddA(a, rowsPerStrip, computeUnits, stream);
+                    if (rowsPerStrip < 33) return launchInterseqPairSwBiasedLocOddB(a, rowsPerStrip, computeUnits, stream);
+                    if (rowsPerStrip < 49) return launchInterseqPairSwBiasedLocOddC(a, rowsPerStrip, computeUnits, stream);
+                    return launchInterseqPairSwBiasedLocOddD(a, rowsPerStrip, computeUnits, stream);
+                }
+                if (rowsPerStrip < 17) return launchInterseqPairSwBiasedOddA(a, rowsPerStrip, computeUnits, stream);
+                if (rowsPerStrip < 33) return launchInterseqPairSwBiasedOddB(a, rowsPerStrip, computeUnits, stream);
+                if (rowsPerStrip < 49) return launchInterseqPairSwBiasedOddC(a, rowsPerStrip, computeUnits, stream);
+                return launchInterseqPairSwBiasedOddD(a, rowsPerStrip, computeUnits, stream);
+            }
             if (locate) {
                 if (rowsPerStrip < 18) return launchInterseqPairSwBiasedLocA(a, rowsPerStrip, computeUnits, stream);
                 if (rowsPerStrip < 34) return launchInterseqPairSwBiasedLocB(a, rowsPerStrip, computeUnits, stream);

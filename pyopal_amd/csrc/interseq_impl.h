@@ -1219,6 +1219,14 @@ struct SimdPace {
 #ifndef MIOPAL_HEADLINE_PACE
 #define MIOPAL_HEADLINE_PACE 1
 #endif
+// Diagnostic build of the one-strip Smith-Waterman kernel (tools/ab_build.sh; never the product build):
+//   -DMIOPAL_HEADLINE_TIMING=1   every wavefront stamps s_memrealtime (100 MHz, one clock for the whole device)
+//                                when it starts and when it leaves; with MIOPAL_STRIP_TIMING=1 the host hands over
+//                                InterseqArgs::stripTiming: [0] the earliest start (min), [1 + 4 * block + simd] the
+//                                last exit on that SIMD (max), and prints how the SIMDs' finish times spread
+#ifndef MIOPAL_HEADLINE_TIMING
+#define MIOPAL_HEADLINE_TIMING 0
+#endif
 
 template <int R, bool LOC>
 __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kernel(InterseqArgs a) {
@@ -1227,6 +1235,9 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
     constexpr int kBits = LOC ? locRowBits(R) : 0;
     constexpr int kRowMask = (1 << kBits) - 1;
     extern __shared__ uint4 pairs[];
+#if MIOPAL_HEADLINE_TIMING
+    const unsigned long long born = __builtin_amdgcn_s_memrealtime();
+#endif
 
     const int lane = threadIdx.x & 63;
     const int nSym = a.nSymbols;
@@ -1457,6 +1468,12 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
         }
     }
     if (MIOPAL_HEADLINE_PACE && lane == 0) *pace.mine = INT32_MAX;   // (done: nobody waits for this one)
+#if MIOPAL_HEADLINE_TIMING
+    if (a.stripTiming && lane == 0) {
+        atomicMin(a.stripTiming, born);
+        atomicMax(a.stripTiming + 1 + blockIdx.x * 4 + simd, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    }
+#endif
 }
 
 template <int R, bool LOC>
@@ -1484,8 +1501,8 @@ static hipError_t launchPairBiasedR(const InterseqArgs& a, int computeUnits, hip
 template <int kLo, bool LOC>
 static hipError_t launchPairBiased(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
     if (a.nStrips != 1) return hipErrorInvalidValue;
-    // rows: any even number in [kLo, kLo + 14]; the translation units interseq_swb16_{a,b,c,d}.hip
-    // share the 32 instantiations
+    // rows: kLo, kLo + 2, ..., kLo + 14; the translation units interseq_swb16_{a,b,c,d}[_loc].hip share the
+    // even counts 2..64, interseq_swb16_{a,b,c,d}[_loc]_odd.hip the odd ones 1..63
     switch (rowsPerStrip - kLo) {
         case 0: return launchPairBiasedR<kLo, LOC>(a, computeUnits, stream);
         case 2: return launchPairBiasedR<kLo + 2, LOC>(a, computeUnits, stream);

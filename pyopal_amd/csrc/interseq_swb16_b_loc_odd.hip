@@ -1,0 +1,12 @@
+// One arithmetic flavour of the inter-sequence kernel (see interseq_impl.h): Smith-Waterman on
+// biased integer halves, column-shifted, pair-indexed LDS profile; strips of 17..31 rows (odd), with end
+// locations (row keys in the low bits of every value).
+#include "interseq_impl.h"
+
+namespace miopal {
+
+hipError_t launchInterseqPairSwBiasedLocOddB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
+    return launchPairBiased<17, true>(a, rows, computeUnits, stream);
+}
+
+}  // namespace miopal

@@ -8,7 +8,7 @@ name=$1; flags=$2
 root=$(cd "$(dirname "$0")/.." && pwd)
 build=$root/variants/build_$name
 mkdir -p "$build"
-cp "$root"/pyopal_amd/csrc/*.hip "$root"/pyopal_amd/csrc/*.h "$root"/pyopal_amd/csrc/Makefile "$build"/
+cp "$root"/pyopal_amd/csrc/*.hip "$root"/pyopal_amd/csrc/*.h "$root"/pyopal_amd/csrc/*.inc "$root"/pyopal_amd/csrc/Makefile "$build"/
 mkdir -p "$root/variants/include_link"
 make -s -j8 -C "$build" OUT="$root/variants/libmiopal_$name.so" \
   CXXFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -I$root/pyopal_amd/csrc $flags" \
