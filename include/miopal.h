@@ -183,6 +183,31 @@ int miopalLastKernelTime(MiopalDb* db, float* ms);
 void miopalLastRouting(int64_t counts[4]);
 
 /*
+ * Many queries against one slice [start, end) of a resident handle in one call (no reference counterpart:
+ * the batch form of pyopal's thread-pool loop of searches). Query k is
+ * queries[queryOffsets[k] .. queryOffsets[k + 1]) (nQueries + 1 offsets); outputs are row-major
+ * [nQueries][end - start]: score, and for OPAL_SEARCH_SCORE_END endTarget / endQuery. Every result equals
+ * what miopalSearch returns for that query alone, and the checks are miopalSearch's, query by query (bad
+ * residues, a bad slice, a matrix of another alphabet). OPAL_SEARCH_ALIGNMENT is refused with
+ * OPAL_ERR_INVALID_MODE. nQueries = 0 or an empty slice: nothing to do, 0.
+ * Queries of 1..64 residues share persistent launches of the batch kernels (interseq_batch_impl.h); longer
+ * queries, queries of length 0, and gap / matrix models beyond the batch kernels' static range checks run
+ * through miopalSearch's own path inside the same call. Thread-safe like miopalSearch.
+ */
+int miopalSearchBatch(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                      int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType,
+                      int mode, int64_t start, int64_t end, int* score, int* endTarget, int* endQuery);
+
+/*
+ * How the calling thread's most recent miopalSearchBatch ran (diagnostics for tests):
+ *   counts[0] (query, target) pairs settled by the batch kernels
+ *   counts[1] (query, target) pairs run by the wavefront-per-pair kernel
+ *   counts[2] queries sent to the single-query path
+ *   counts[3] launches of the batch kernels
+ */
+void miopalLastBatchRouting(int64_t counts[4]);
+
+/*
  * How the passes BEHIND the score / end pass of the calling thread's most recent OPAL_SEARCH_ALIGNMENT
  * search ran (diagnostics for tests; no reference counterpart). Bits:
  *   1  start cells: one lane per pair          2  ... in the query-profile form (perpair_profile_kernel)

@@ -48,6 +48,7 @@ EXPORTS = [
     "miopalDbDestroy", "miopalDbCount", "miopalDbTotalLength", "miopalDbDeviceBytes",
     "miopalSearch", "miopalSearchFlat", "miopalSearchFlatInto", "miopalSearchDeviceScores", "miopalSetProfiling", "miopalLastKernelTime",
     "miopalLastRouting", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
+    "miopalSearchBatch", "miopalLastBatchRouting",
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
     # test hooks
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices",
@@ -119,6 +120,11 @@ def lib() -> ctypes.CDLL:
         L.miopalSearch.restype = c_int
         L.miopalSearch.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                    c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.miopalSearchBatch.restype = c_int
+        L.miopalSearchBatch.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                        c_i64, c_i64, c_vp, c_vp, c_vp]
+        L.miopalLastBatchRouting.restype = None
+        L.miopalLastBatchRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
         L.miopalSearchFlat.restype = c_int
         L.miopalSearchFlat.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                        c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -388,6 +394,44 @@ class DeviceDatabase:
             out.update(start_t=s_t, start_q=s_q, aln_flat=flat, aln_off=aoff,
                        aln=_LazyAlignments(flat, aoff), _ops_owner=owner)
         return out
+
+    def search_batch(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
+                     gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
+                     end: typing.Optional[int] = None) -> typing.Dict[str, np.ndarray]:
+        """miopalSearchBatch: every query (encoded residues) against the slice [start, end). Returns 2-D int32
+        arrays of shape (len(queries), end - start): "score", and for mode "end" also "end_t" / "end_q"; row i
+        equals search(queries[i], ...). Mode "full" is refused (OPAL_ERR_INVALID_MODE)."""
+        end = self.count if end is None else min(end, self.count)
+        n = max(end - start, 0)
+        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
+        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            np.cumsum([len(q) for q in qs], out=offsets[1:])
+        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
+        if flat.size == 0:
+            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        st = SEARCH[mode]
+        out = {"score": np.empty((len(qs), n), dtype=np.int32)}
+        et = eq = None
+        if st >= 1:
+            et = np.empty((len(qs), n), dtype=np.int32)
+            eq = np.empty((len(qs), n), dtype=np.int32)
+        rc = lib().miopalSearchBatch(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
+                                     self.alphabet_length, st, MODE[algorithm], start, end, _ptr(out["score"]),
+                                     _ptr(et), _ptr(eq))
+        raise_for(rc)
+        if st >= 1:
+            out.update(end_t=et, end_q=eq)
+        return out
+
+    @staticmethod
+    def last_batch_routing() -> typing.Tuple[int, int, int, int]:
+        """(pairs settled by the batch kernels, pairs on the wavefront-per-pair kernel, queries on the
+        single-query path, batch-kernel launches) for the calling thread's most recent search_batch."""
+        counts = (ctypes.c_int64 * 4)()
+        lib().miopalLastBatchRouting(counts)
+        return tuple(int(c) for c in counts)
 
     def search_device_scores(self, query: np.ndarray, matrix: np.ndarray, device_ptr: int,
                              stream: int = 0, gap_open: int = 3, gap_extend: int = 1,

@@ -71,6 +71,48 @@ struct InterseqArgs {
     const int64_t* boundaryOff;
 };
 
+// ---- batch forms of the one-strip pair-table kernels (interseq_batch_impl.h) ----
+// Many queries of at most 64 rows against one plain packed view in one persistent launch: units of
+// (query, run of groups), query-major; results straight into [row][target] database order.
+struct BatchArgs {
+    const uint2* pack;          // the view's packed residues, groups, lengths and ids (view order)
+    const int64_t* groupOff;
+    const int* groupChunks;
+    const int32_t* lens;
+    const int32_t* ids;         // view position -> database index
+    int nPacked;                // view positions that hold a target
+    int64_t sliceStart;
+    const int16_t* profiles;    // [query][nSymbols][R] true scores, kBiasedPad for the padding symbol / rows
+    int nSymbols;               // A + 1
+    const int* qLens;           // [query] true lengths (R - 8 < qLen <= R)
+    const int* qRows;           // [query] output row
+    int nQueries;
+    int unitsPerQuery;          // runs of groups per query
+    const int* unitFirst;       // [unitsPerQuery + 1] first group of each run (the same for every query)
+    int* unitCounter;           // zeroed before the launch
+    int gapOpen, gapExt;
+    int topGap, leftGap, region;
+    int biasedLimit;            // Smith-Waterman: a best at or above this (true score) is flagged
+    int biasedZero;             // NW / HW / OV: pattern of a true 0 at shift 0
+    int64_t outStride;          // entries per output row (the slice's length)
+    int32_t* score;             // [row][outStride], database order - sliceStart
+    int32_t* endI;              // end locations (null: scores only)
+    int32_t* endJ;
+    uint8_t* overflow;          // Smith-Waterman: [row][nPacked], view order, 1 = flagged
+    int* overflowCount;         // Smith-Waterman: [row], zeroed: flagged lane halves of the row
+};
+// row classes of the batch kernels: a query of Q rows runs in the smallest class >= Q
+constexpr int kBatchRowClasses[] = {8, 16, 24, 32, 40, 48, 56, 60, 64};
+inline int batchRowClass(int Q) {
+    for (int r : kBatchRowClasses)
+        if (Q <= r) return r;
+    return 0;
+}
+hipError_t launchInterseqBatchSw(const BatchArgs& a, int rows, int computeUnits, hipStream_t stream);
+hipError_t launchInterseqBatchSwLoc(const BatchArgs& a, int rows, int computeUnits, hipStream_t stream);
+hipError_t launchInterseqBatchGlobalA(const BatchArgs& a, int rows, int computeUnits, hipStream_t stream);  // 8 .. 32 rows
+hipError_t launchInterseqBatchGlobalB(const BatchArgs& a, int rows, int computeUnits, hipStream_t stream);  // 40 .. 64 rows
+
 // ---- intra-sequence kernel (one wavefront = one pair, int32) --------------
 struct PairJob {
     int64_t tOff;    // index of the first residue visited in the linear database

@@ -81,6 +81,7 @@ namespace {
 
 thread_local std::string g_lastError;
 thread_local int64_t g_lastRouting[4] = {0, 0, 0, 0};  // miopalLastRouting
+thread_local int64_t g_lastBatchRouting[4] = {0, 0, 0, 0};  // miopalLastBatchRouting
 thread_local int g_lastFullRouting = 0;                // miopalLastFullRouting
 thread_local int g_fault[3] = {0, 0, 0};               // miopalTestInjectFault: kind, unit, spin cap
 // miopalTestSetLogicalDevices: > 0 = that many device ordinals, mapped round-robin onto the physical
@@ -596,6 +597,11 @@ void miopalLastRouting(int64_t counts[4]) {
 
 int miopalLastFullRouting(void) { return g_lastFullRouting; }
 
+void miopalLastBatchRouting(int64_t counts[4]) {
+    if (!counts) return;
+    for (int k = 0; k < 4; ++k) counts[k] = g_lastBatchRouting[k];
+}
+
 int miopalLastKernelTime(MiopalDb* db, float* ms) {
     if (!db || !ms) return 0;
     std::lock_guard<std::mutex> g(db->timingMutex);
@@ -644,6 +650,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 }
 
 #include "host_full.inc"
+#include "host_batch.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                  int64_t end, int* score, int* endTarget, int* endQuery, int* startTarget,
@@ -652,6 +659,15 @@ int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int 
     return searchImpl(db, query, queryLength, gapOpen, gapExt, scoreMatrix, alphabetLength, searchType, mode,
                       start, end, score, endTarget, endQuery, startTarget, startQuery, alignment,
                       alignmentLength, nullptr, nullptr);
+    });
+}
+
+int miopalSearchBatch(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                      int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType, int mode,
+                      int64_t start, int64_t end, int* score, int* endTarget, int* endQuery) {
+    return guarded([&]() -> int {
+    return batchImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength, searchType, mode,
+                     start, end, score, endTarget, endQuery);
     });
 }
 

@@ -6,7 +6,8 @@ enum Slot {
     kQuery, kMatrix, kProfile, kViewScore, kViewOvf, kCounter, kBoundary0, kBoundary1,
     kScore, kEndI, kEndJ, kJobs, kPairB0, kPairB1, kAuxJobs, kAuxPairB0, kAuxPairB1, kRScore, kRI, kRJ, kDirs, kOps, kOpsOff,
     kOpsLen, kOvfHost, kWorkCounter, kViewEndI, kViewEndJ, kStartQ, kStartT, kMismatch, kCompactOps, kTraceScore, kOpsTotals, kSortBins, kSortedJobs, kScanOrder, kKeys, kHeadWaves, kHeadDirs, kUnitState, kUnitPartial, kStripKeys,
-    kPairStripState, kPairStripPartial, kPairStripSpare, kAuxPairStripState, kAuxPairStripPartial, kPairStripError, kStripTiming, kSlots
+    kPairStripState, kPairStripPartial, kPairStripSpare, kAuxPairStripState, kAuxPairStripPartial, kPairStripError, kStripTiming,
+    kBatchProfiles, kBatchMeta, kBatchOverflow, kSlots
 };
 
 // Alignment operations as they cross PCIe - two bits each, operation p in bits 2 (p % 4) of byte p / 4

@@ -691,6 +691,99 @@ class Aligner:
             lengths = np.diff(mirror.offsets[start:end + 1]) if mode == "full" else None
             return ResultArrays(mode, start, len(encoded), lengths, out)
 
+    def align_many(self, queries, database: BaseDatabase, *, mode: str = "score", algorithm: str = "sw",
+                   start: int = 0, end: int = UINT32_MAX, device: int = 0) -> typing.List[typing.List[ScoreResult]]:
+        """Extension: align every query of ``queries`` to every target of ``database[start:end]``.
+
+        Returns ``[aligner.align(q, database, mode=mode, ...) for q in queries]``, computed by one batched
+        search for the modes ``score`` and ``end`` (queries of up to 64 residues share the GPU's launches;
+        longer ones take the single-query path inside the same call). ``mode="full"`` is accepted and runs
+        query by query through `align`. This is the batch form of the reference README's thread-pool loop.
+        """
+        if mode == "full":
+            return [self.align(q, database, mode=mode, algorithm=algorithm, start=start, end=end, device=device)
+                    for q in list(queries)]
+        arrays = self.align_many_arrays(queries, database, mode=mode, algorithm=algorithm, start=start, end=end,
+                                        device=device)
+        return [list(arrays[i]) for i in range(len(arrays))]
+
+    def align_many_arrays(self, queries, database: BaseDatabase, *, mode: str = "score", algorithm: str = "sw",
+                          start: int = 0, end: int = UINT32_MAX, device: int = 0) -> "BatchResultArrays":
+        """Extension: `align_arrays` of many queries in one batched search. Returns a `BatchResultArrays`
+        whose ``score`` (and for ``mode="end"`` ``query_end`` / ``target_end``) are ``int32`` arrays of shape
+        ``(len(queries), n)``; ``arrays[i]`` is the `ResultArrays` of query ``i``, equal to
+        ``align_arrays(queries[i], ...)``. Modes ``score`` and ``end``."""
+        if mode not in _OPAL_SEARCH_MODES:
+            raise ValueError(f"invalid search mode: {mode!r}")
+        if mode == "full":
+            raise ValueError("align_many_arrays computes scores and end locations only (mode 'score' or 'end')")
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        if start < 0 or end < 0:
+            raise OverflowError("can't convert negative value to uint32_t")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        if database.alphabet != self.alphabet:
+            raise ValueError("database and score matrix have different alphabets")
+        queries = list(queries)
+        for q in queries:
+            if q is None:
+                raise TypeError("Argument 'query' must not be None")
+        encoded = [database.alphabet.encode(q) for q in queries]
+        with database.lock.read:
+            size = database._get_size()
+            if end < start:
+                raise IndexError("database slice end is lower than start")
+            end = min(end, size)
+            if start > size:
+                raise IndexError("database slice start is past the end of the database")
+            n = end - start
+            if n == 0 or not encoded:
+                out = {"score": np.zeros((len(encoded), n), dtype=np.int32)}
+                if mode == "end":
+                    out.update(end_q=np.zeros((len(encoded), n), dtype=np.int32),
+                               end_t=np.zeros((len(encoded), n), dtype=np.int32))
+                return BatchResultArrays(mode, start, [len(e) for e in encoded], out)
+            if _capi.lib().miopalDeviceCount() < 1:
+                raise RuntimeError("no supported SIMD backend available")
+            mirror = database._device_mirror(device)
+            out = mirror.search_batch([np.frombuffer(e, dtype=np.uint8) for e in encoded],
+                                      _int_matrix_array(self._int_matrix), self.gap_open, self.gap_extend, mode,
+                                      algorithm, start, end)
+            return BatchResultArrays(mode, start, [len(e) for e in encoded], out)
+
+
+class BatchResultArrays:
+    """Results of a batched search as 2-D arrays (`Aligner.align_many_arrays`): ``score`` and, for
+    ``mode="end"``, ``query_end`` / ``target_end``, ``int32`` of shape ``(queries, targets)``.
+    ``arrays[i]`` is the `ResultArrays` of query ``i``."""
+
+    def __init__(self, mode: str, start: int, query_lengths, out):
+        self.mode = mode
+        self.start = start
+        self.query_lengths = list(query_lengths)
+        self.score = out["score"]
+        self.query_end = out.get("end_q")
+        self.target_end = out.get("end_t")
+
+    def __len__(self) -> int:
+        return self.score.shape[0]
+
+    def __getitem__(self, i: int) -> "ResultArrays":
+        m = len(self)
+        if i < 0:
+            i += m
+        if i < 0 or i >= m:
+            raise IndexError(i)
+        out = {"score": self.score[i]}
+        if self.mode == "end":
+            out.update(end_q=self.query_end[i], end_t=self.target_end[i])
+        return ResultArrays(self.mode, self.start, self.query_lengths[i], None, out)
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
 
 class ResultArrays:
     """Results of one search as arrays (`Aligner.align_arrays`).
