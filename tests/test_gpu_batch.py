@@ -1,8 +1,11 @@
 """The batched search (miopalSearchBatch / DeviceDatabase.search_batch / Aligner.align_many_arrays) against the
 single-query search of each query and against the CPU checker: every mode, both search types, the row-class
-boundaries of the batch kernels, and the pairs they hand to the wavefront-per-pair kernel or the single-query path."""
+boundaries of the batch kernels, and the pairs they hand to the wavefront-per-pair kernel or the single-query path.
+tests/test_gpu_batch_edges.py compares every pair with the CPU checker where the batch path can go wrong: long targets,
+several chunks of queries, the planner's range bounds and flag threshold, other alphabets and tied end locations."""
 import os
 import threading
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
@@ -70,8 +73,9 @@ def check_rows(db, queries, got, matrix, go, ge, mode, algo, start=0, end=None):
 def check_oracle(queries, got, rows, res, off, matrix, go, ge, mode, algo, start, end):
     sub_off = off[start:end + 1] - off[start]
     sub_res = res[off[start]:off[end]]
-    for i in rows:
-        want = _oracle.search(queries[i], sub_res, sub_off, matrix, go, ge, mode, algo)
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        wants = pool.map(lambda i: _oracle.search(queries[i], sub_res, sub_off, matrix, go, ge, mode, algo), rows)
+    for i, want in zip(rows, wants):
         np.testing.assert_array_equal(got["score"][i], want["score"], err_msg=f"oracle score {i}")
         if mode == "end":
             np.testing.assert_array_equal(got["end_q"][i], want["end_q"], err_msg=f"oracle end_q {i}")
@@ -92,7 +96,9 @@ def test_batch_equals_single_searches(capi, db_set, algo, mode):
         assert got["score"].shape == (m, db.count)
         check_rows(db, queries, got, matrix, go, ge, mode, algo)
         sub = db.search_batch(queries, matrix, go, ge, mode, algo, start=0, end=1500)
-        check_oracle(queries, sub, sorted({0, m // 2, m - 1}), res, off, matrix, go, ge, mode, algo, 0, 1500)
+        # (every row of the batches of at most 64 queries)
+        rows = range(m) if m <= 64 else sorted({0, m // 2, m - 1})
+        check_oracle(queries, sub, rows, res, off, matrix, go, ge, mode, algo, 0, 1500)
         if (go, ge) == (3, 1):
             # the batch kernels settled the bulk of the pairs, in few launches
             # (61 .. 64 rows: a pair table of 25 symbols does not fit LDS, those queries take the single-query path)
