@@ -199,6 +199,38 @@ int miopalSearchBatch(MiopalDb* db, const unsigned char* queries, const int64_t*
                       int mode, int64_t start, int64_t end, int* score, int* endTarget, int* endQuery);
 
 /*
+ * The k best targets of a query in the slice [start, end), selected on the device (no reference counterpart:
+ * what pyopal's worked example does on the host with sorted(results, key=score)[:k]).
+ *   Order: score descending; equal scores by target index ascending - exactly Python's stable
+ *     sorted(aligner.align(...), key=lambda r: r.score, reverse=True).
+ *   Hits: targets whose score is >= minScore (INT_MIN: no bound).
+ *   Outputs: count = min(k, hits); targetIndex (absolute), score and, for OPAL_SEARCH_SCORE_END, endTarget /
+ *     endQuery of the first `count` hits in that order, each equal to what miopalSearch returns for that target.
+ *     Slots count .. k - 1 hold -1 in every output.
+ *   0 <= k <= MIOPAL_MAX_TOP; k > end - start is allowed. k = 0 or an empty slice: count 0, nothing launched,
+ *     the arguments are checked all the same.
+ * The checks, error codes and thread safety are miopalSearch's (OPAL_ERR_OVERFLOW included); OPAL_SEARCH_ALIGNMENT
+ * is refused with OPAL_ERR_INVALID_MODE. Only count + k entries cross PCIe: the scores stay in HBM.
+ */
+#define MIOPAL_MAX_TOP 4096
+int miopalSearchTop(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                    const int* scoreMatrix, int alphabetLength, int searchType, int mode,
+                    int64_t start, int64_t end, int k, int minScore,
+                    int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery);
+
+/*
+ * miopalSearchTop of every query of a batch (queries and queryOffsets as in miopalSearchBatch), in one call through
+ * miopalSearchBatch's chunks: each chunk's [queries][targets] rows are selected on the device before they leave.
+ * count has nQueries entries; the other outputs are [nQueries][k], row-major. Row i equals miopalSearchTop of query i
+ * alone, and miopalLastBatchRouting reports what miopalSearchBatch reports for the same inputs. nQueries = 0:
+ * nothing to do, 0.
+ */
+int miopalSearchBatchTop(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                         int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType,
+                         int mode, int64_t start, int64_t end, int k, int minScore,
+                         int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery);
+
+/*
  * How the calling thread's most recent miopalSearchBatch ran (diagnostics for tests):
  *   counts[0] (query, target) pairs settled by the batch kernels
  *   counts[1] (query, target) pairs run by the wavefront-per-pair kernel

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("MIOPAL_LIBRARY") or os.path.join(_HERE, "libmiopal.so
 OPAL_ERR_OVERFLOW = 1
 OPAL_ERR_NO_SIMD_SUPPORT = 2
 OPAL_ERR_INVALID_MODE = 3
+MIOPAL_MAX_TOP = 4096   # include/miopal.h: the largest k of miopalSearchTop / miopalSearchBatchTop
 
 SEARCH = {"score": 0, "end": 1, "full": 2}
 MODE = {"nw": 0, "hw": 1, "ov": 2, "sw": 3}
@@ -48,7 +49,7 @@ EXPORTS = [
     "miopalDbDestroy", "miopalDbCount", "miopalDbTotalLength", "miopalDbDeviceBytes",
     "miopalSearch", "miopalSearchFlat", "miopalSearchFlatInto", "miopalSearchDeviceScores", "miopalSetProfiling", "miopalLastKernelTime",
     "miopalLastRouting", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
-    "miopalSearchBatch", "miopalLastBatchRouting",
+    "miopalSearchBatch", "miopalLastBatchRouting", "miopalSearchTop", "miopalSearchBatchTop",
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
     # test hooks
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices",
@@ -123,6 +124,12 @@ def lib() -> ctypes.CDLL:
         L.miopalSearchBatch.restype = c_int
         L.miopalSearchBatch.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                         c_i64, c_i64, c_vp, c_vp, c_vp]
+        L.miopalSearchTop.restype = c_int
+        L.miopalSearchTop.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                      c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.miopalSearchBatchTop.restype = c_int
+        L.miopalSearchBatchTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                           c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.miopalLastBatchRouting.restype = None
         L.miopalLastBatchRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
         L.miopalSearchFlat.restype = c_int
@@ -423,6 +430,58 @@ class DeviceDatabase:
         raise_for(rc)
         if st >= 1:
             out.update(end_t=et, end_q=eq)
+        return out
+
+    def _top_outputs(self, rows, k, mode):
+        shape = (k,) if rows is None else (rows, k)
+        out = {"count": np.zeros(1 if rows is None else rows, dtype=np.int32),
+               "target": np.empty(shape, dtype=np.int64), "score": np.empty(shape, dtype=np.int32)}
+        if mode == "end":
+            out.update(end_t=np.empty(shape, dtype=np.int32), end_q=np.empty(shape, dtype=np.int32))
+        return out
+
+    def search_top(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
+                   mode: str = "score", algorithm: str = "sw", start: int = 0, end: typing.Optional[int] = None,
+                   k: int = 10, min_score: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+        """miopalSearchTop: the k best targets of the slice, selected on the device. Returns "count" (an int),
+        "target" (int64, absolute indices), "score" and for mode "end" "end_t" / "end_q", arrays of shape (k,):
+        best first (score descending, index ascending), -1 past the count. ``min_score``: only targets scoring at
+        least that many count (None: no bound). Mode "full" is refused (OPAL_ERR_INVALID_MODE)."""
+        end = self.count if end is None else min(end, self.count)
+        q = np.ascontiguousarray(query, dtype=np.uint8)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        out = self._top_outputs(None, k, mode)
+        rc = lib().miopalSearchTop(self._h, _ptr(q), len(q), gap_open, gap_extend, _ptr(S), self.alphabet_length,
+                                   SEARCH[mode], MODE[algorithm], start, end, k,
+                                   -(2 ** 31) if min_score is None else min_score, _ptr(out["count"]),
+                                   _ptr(out["target"]), _ptr(out["score"]), _ptr(out.get("end_t")),
+                                   _ptr(out.get("end_q")))
+        raise_for(rc)
+        out["count"] = int(out["count"][0])
+        return out
+
+    def search_batch_top(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
+                         gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
+                         end: typing.Optional[int] = None, k: int = 10,
+                         min_score: typing.Optional[int] = None) -> typing.Dict[str, np.ndarray]:
+        """miopalSearchBatchTop: search_top of every query in one batched call. "count" has one entry per query;
+        the other arrays have shape (len(queries), k); row i equals search_top(queries[i], ...)."""
+        end = self.count if end is None else min(end, self.count)
+        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
+        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            np.cumsum([len(q) for q in qs], out=offsets[1:])
+        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
+        if flat.size == 0:
+            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        out = self._top_outputs(len(qs), k, mode)
+        rc = lib().miopalSearchBatchTop(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
+                                        self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end, k,
+                                        -(2 ** 31) if min_score is None else min_score, _ptr(out["count"]),
+                                        _ptr(out["target"]), _ptr(out["score"]), _ptr(out.get("end_t")),
+                                        _ptr(out.get("end_q")))
+        raise_for(rc)
         return out
 
     @staticmethod

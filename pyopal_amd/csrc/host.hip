@@ -34,6 +34,7 @@
 
 #include "../../include/miopal.h"
 #include "common.h"
+#include "select_top.h"
 #include "tuning.h"
 
 using namespace miopal;
@@ -651,6 +652,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 
 #include "host_full.inc"
 #include "host_batch.inc"
+#include "host_top.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                  int64_t end, int* score, int* endTarget, int* endQuery, int* startTarget,
@@ -666,8 +668,27 @@ int miopalSearchBatch(MiopalDb* db, const unsigned char* queries, const int64_t*
                       int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType, int mode,
                       int64_t start, int64_t end, int* score, int* endTarget, int* endQuery) {
     return guarded([&]() -> int {
-    return batchImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength, searchType, mode,
-                     start, end, score, endTarget, endQuery);
+    return searchBatchImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength, searchType,
+                           mode, start, end, score, endTarget, endQuery);
+    });
+}
+
+int miopalSearchTop(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                    const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start, int64_t end,
+                    int k, int minScore, int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery) {
+    return guarded([&]() -> int {
+    return searchTopImpl(db, query, queryLength, gapOpen, gapExt, scoreMatrix, alphabetLength, searchType, mode, start,
+                         end, k, minScore, 0, count, targetIndex, score, endTarget, endQuery);
+    });
+}
+
+int miopalSearchBatchTop(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                         int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType,
+                         int mode, int64_t start, int64_t end, int k, int minScore,
+                         int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery) {
+    return guarded([&]() -> int {
+    return searchBatchTopImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength,
+                              searchType, mode, start, end, k, minScore, count, targetIndex, score, endTarget, endQuery);
     });
 }
 

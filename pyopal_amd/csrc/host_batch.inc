@@ -68,26 +68,43 @@ void planBatchQuery(const unsigned char* query, int Q, int open, int ext, const 
 
 }  // namespace
 
-static int batchImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries, int open,
-                     int ext, const int* matrix, int A, int searchType, int mode, int64_t start, int64_t end, int* score,
-                     int* endTarget, int* endQuery) {
-    for (int k = 0; k < 4; ++k) g_lastBatchRouting[k] = 0;
-    if (searchType == OPAL_SEARCH_ALIGNMENT)
-        return fail(OPAL_ERR_INVALID_MODE, "miopalSearchBatch: alignments are not available in a batch");
+// the checks of miopalSearch, query by query (and the model and slice once when the list is empty)
+static int validateBatch(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                         const int* matrix, int A, int searchType, int mode, int64_t start, int64_t end) {
     if (nQueries < 0 || (nQueries > 0 && (!queryOffsets || !queries)))
         return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query list");
-    // the checks of miopalSearch, query by query (and the model and slice once when the list is empty)
     if (nQueries == 0) RC_TRY(validate(db, nullptr, 0, matrix, A, searchType, mode, start, end));
     for (int i = 0; i < nQueries; ++i) {
         const int64_t len = queryOffsets[i + 1] - queryOffsets[i];
         if (queryOffsets[i] < 0 || len < 0 || len > INT32_MAX) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query offsets at %d", i);
         RC_TRY(validate(db, queries + queryOffsets[i], (int)len, matrix, A, searchType, mode, start, end));
     }
+    return 0;
+}
+
+// What a batch does with its answers: miopalSearchBatch downloads every chunk's [rows][n] rows,
+// miopalSearchBatchTop selects the k best of each row on the device first (host_top.inc).
+struct BatchSink {
+    // the caller's output arrays, checked after the arguments and before any work
+    std::function<int(bool locate)> checkOutputs;
+    // the device rows [rows][n] of queries i0 .. i0 + rows - 1 are final (rows of queries on the single-query
+    // path among them hold nothing: single() answers those afterwards)
+    std::function<int(Workspace* ws, int64_t i0, int rows, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ)> chunk;
+    // query i takes miopalSearch's own path
+    std::function<int(int i)> single;
+};
+
+static int batchImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries, int open,
+                     int ext, const int* matrix, int A, int searchType, int mode, int64_t start, int64_t end,
+                     const BatchSink& sink) {
+    for (int k = 0; k < 4; ++k) g_lastBatchRouting[k] = 0;
+    if (searchType == OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "miopalSearchBatch: alignments are not available in a batch");
+    RC_TRY(validateBatch(db, queries, queryOffsets, nQueries, matrix, A, searchType, mode, start, end));
     const int64_t n = end - start;
     if (n == 0 || nQueries == 0) return 0;
-    if (!score) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null score output");
     const bool locate = searchType >= OPAL_SEARCH_SCORE_END;
-    if (locate && (!endTarget || !endQuery)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null end-location outputs");
+    RC_TRY(sink.checkOutputs(locate));
     HIP_TRY(hipSetDevice(db->device));
 
     const int maxScore = *std::max_element(matrix, matrix + A * A);
@@ -302,26 +319,45 @@ static int batchImpl(MiopalDb* db, const unsigned char* queries, const int64_t* 
             }
             pairJobs += (int64_t)jobs.size();
             RC_TRY(s.runPairs(jobs, false, d_score, d_endI, d_endJ, nullptr));
-            // rows of this chunk -> the caller (rows of queries on the single-query path are written again below)
-            const size_t bytes = (size_t)rows * n * sizeof(int32_t);
-            RC_TRY(ws->stageDownload(score + i0 * n, d_score, bytes));
-            if (locate) {
-                RC_TRY(ws->stageDownload(endQuery + i0 * n, d_endI, bytes));
-                RC_TRY(ws->stageDownload(endTarget + i0 * n, d_endJ, bytes));
-            }
-            RC_TRY(ws->finishDownloads());
+            RC_TRY(sink.chunk(ws, i0, rows, d_score, d_endI, d_endJ));
         }
     }
     // the other queries: miopalSearch's own path, query by query
-    for (int i : single) {
-        const int64_t at = (int64_t)i * n;
-        RC_TRY(searchImpl(db, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext, matrix, A,
-                          searchType, mode, start, end, score + at, locate ? endTarget + at : nullptr,
-                          locate ? endQuery + at : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
-    }
+    for (int i : single) RC_TRY(sink.single(i));
     g_lastBatchRouting[0] = settled;
     g_lastBatchRouting[1] = pairJobs;
     g_lastBatchRouting[2] = (int64_t)single.size();
     g_lastBatchRouting[3] = launches;
     return 0;
+}
+
+// miopalSearchBatch: every row of every chunk to the caller
+static int searchBatchImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                           int open, int ext, const int* matrix, int A, int searchType, int mode, int64_t start,
+                           int64_t end, int* score, int* endTarget, int* endQuery) {
+    const int64_t n = end - start;
+    BatchSink sink;
+    sink.checkOutputs = [&](bool locate) -> int {
+        if (!score) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null score output");
+        if (locate && (!endTarget || !endQuery)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null end-location outputs");
+        return 0;
+    };
+    sink.chunk = [&](Workspace* ws, int64_t i0, int rows, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ) -> int {
+        // rows of this chunk -> the caller (rows of queries on the single-query path are written again afterwards)
+        const size_t bytes = (size_t)rows * n * sizeof(int32_t);
+        RC_TRY(ws->stageDownload(score + i0 * n, d_score, bytes));
+        if (d_endI) {
+            RC_TRY(ws->stageDownload(endQuery + i0 * n, d_endI, bytes));
+            RC_TRY(ws->stageDownload(endTarget + i0 * n, d_endJ, bytes));
+        }
+        return ws->finishDownloads();
+    };
+    sink.single = [&](int i) -> int {
+        const int64_t at = (int64_t)i * n;
+        const bool locate = searchType >= OPAL_SEARCH_SCORE_END;
+        return searchImpl(db, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext, matrix,
+                          A, searchType, mode, start, end, score + at, locate ? endTarget + at : nullptr,
+                          locate ? endQuery + at : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    };
+    return batchImpl(db, queries, queryOffsets, nQueries, open, ext, matrix, A, searchType, mode, start, end, sink);
 }

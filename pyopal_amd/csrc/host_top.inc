@@ -1,0 +1,155 @@
+// Part of host.hip (included there, not a translation unit of its own): miopalSearchTop and miopalSearchBatchTop,
+// the k best targets of a query (of every query of a batch), selected on the device (select_top.hip) from the score
+// rows the search kernels leave in HBM. Only count + k entries per query cross PCIe.
+
+static_assert(kTopMaxK == MIOPAL_MAX_TOP, "select_top.h mirrors miopal.h");
+
+// checks shared by both entry points (after validate(), which has refused a bad search type already)
+static int checkTopArgs(int searchType, int k, const int* count, const int64_t* targetIndex, const int* score,
+                        const int* endTarget, const int* endQuery) {
+    if (searchType == OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "miopalSearchTop: alignments are not selected on the device");
+    if (k < 0 || k > MIOPAL_MAX_TOP) return fail(MIOPAL_ERR_BAD_ARGUMENT, "k = %d outside [0, %d]", k, MIOPAL_MAX_TOP);
+    if (!count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null count output");
+    if (k > 0 && (!targetIndex || !score)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null target / score outputs");
+    if (k > 0 && searchType == OPAL_SEARCH_SCORE_END && (!endTarget || !endQuery))
+        return fail(MIOPAL_ERR_BAD_ARGUMENT, "null end-location outputs");
+    return 0;
+}
+
+// rows [from, to) of the outputs: nothing chosen
+static void emptyTopRows(int from, int to, int k, int* count, int64_t* targetIndex, int* score, int* endTarget,
+                         int* endQuery) {
+    for (int r = from; r < to; ++r) {
+        count[r] = 0;
+        const size_t at = (size_t)r * k;
+        std::fill(targetIndex + at, targetIndex + at + k, (int64_t)-1);
+        std::fill(score + at, score + at + k, -1);
+        if (endTarget) std::fill(endTarget + at, endTarget + at + k, -1);
+        if (endQuery) std::fill(endQuery + at, endQuery + at + k, -1);
+    }
+}
+
+// The selection on `rows` device rows of n scores (and end locations), enqueued on the workspace's stream behind
+// what produced them, and ONE download of the [rows] counts and [rows][k] entries into the caller's arrays, which
+// hold row 0 of the selection at their row `outRow`. `s`: the search whose strip error is checked with it (or null).
+static int selectTopRows(Workspace* ws, Search* s, const int32_t* d_score, const int32_t* d_endI,
+                         const int32_t* d_endJ, int rows, int64_t n, int64_t start, int k, int minScore, int64_t outRow,
+                         int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery) {
+    const bool ends = d_endI != nullptr;
+    const size_t rk = (size_t)rows * k;
+    auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // one slot: [error, count[rows]] [target] [score] ([endQuery] [endTarget]) | the selection's scratch
+    const size_t offTarget = a256(sizeof(int) * ((size_t)rows + 1));
+    const size_t offScore = offTarget + a256(sizeof(int64_t) * rk);
+    const size_t offEndQ = offScore + a256(sizeof(int) * rk);
+    const size_t offEndT = offEndQ + (ends ? a256(sizeof(int) * rk) : 0);
+    const size_t outBytes = offEndT + (ends ? a256(sizeof(int) * rk) : 0);
+    void* p;
+    RC_TRY(ws->get(kTopScratch, outBytes + topScratchBytes(rows, n, k), &p));
+    char* base = (char*)p;
+    HIP_TRY(hipMemsetAsync(base, 0, sizeof(int), ws->stream));
+    TopArgs a{};
+    a.score = d_score;
+    a.endI = d_endI;
+    a.endJ = d_endJ;
+    a.stride = n;
+    a.rows = rows;
+    a.k = k;
+    a.minScore = minScore;
+    a.start = start;
+    a.scratch = base + outBytes;
+    a.error = (int*)base;
+    a.count = (int32_t*)base + 1;
+    a.target = (int64_t*)(base + offTarget);
+    a.outScore = (int32_t*)(base + offScore);
+    a.outEndQ = ends ? (int32_t*)(base + offEndQ) : nullptr;
+    a.outEndT = ends ? (int32_t*)(base + offEndT) : nullptr;
+    const hipError_t e = launchSelectTop(a, ws->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MIOPAL_ERR_HIP, "top-k selection launch: %s", hipGetErrorString(e));
+    }
+    std::vector<char> host(outBytes);
+    RC_TRY(ws->stageDownload(host.data(), base, outBytes));
+    if (s && s->d_stripError) RC_TRY(ws->stageDownload(&s->stripErrorHost, s->d_stripError, sizeof(int)));
+    RC_TRY(ws->finishDownloads());
+    if (s) RC_TRY(s->checkStripError());
+    int error;
+    memcpy(&error, host.data(), sizeof(int));
+    if (error) return fail(MIOPAL_ERR_INTERNAL, "top-k selection: %d blocks gave up waiting for the blocks before them", error);
+    const size_t at = (size_t)outRow * k;
+    memcpy(count + outRow, host.data() + sizeof(int), sizeof(int) * (size_t)rows);
+    memcpy(targetIndex + at, host.data() + offTarget, sizeof(int64_t) * rk);
+    memcpy(score + at, host.data() + offScore, sizeof(int) * rk);
+    if (ends) {
+        memcpy(endQuery + at, host.data() + offEndQ, sizeof(int) * rk);
+        memcpy(endTarget + at, host.data() + offEndT, sizeof(int) * rk);
+    }
+    return 0;
+}
+
+// miopalSearchTop: searchImpl's score / end pass with the results left in the workspace's device slots, then the
+// selection on the same stream (the score pass has joined its side-stream jobs and flagged lanes into it).
+// Writes row `outRow` of the outputs.
+static int searchTopImpl(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                         const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
+                         int64_t end, int k, int minScore, int64_t outRow, int* count, int64_t* targetIndex, int* score,
+                         int* endTarget, int* endQuery) {
+    RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, searchType, mode, start, end));
+    RC_TRY(checkTopArgs(searchType, k, count, targetIndex, score, endTarget, endQuery));
+    const bool locate = searchType == OPAL_SEARCH_SCORE_END;
+    const int64_t n = end - start;
+    if (k == 0 || n == 0) {
+        emptyTopRows((int)outRow, (int)outRow + 1, k, count, targetIndex, score, locate ? endTarget : nullptr,
+                     locate ? endQuery : nullptr);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(db->device));
+    WorkspaceLease lease(db);
+    RC_TRY(lease.acquireInternal());
+    Workspace* ws = lease.ws;
+    Search s{db, ws, ws->stream, query, queryLength, gapOpen, gapExt, alphabetLength, searchType, mode,
+             scoreMatrix, start, end, n};
+    RC_TRY(s.prepare());
+    void *ps, *pi = nullptr, *pj = nullptr;
+    RC_TRY(ws->get(kScore, (size_t)n * sizeof(int32_t), &ps));
+    if (locate) {
+        RC_TRY(ws->get(kEndI, (size_t)n * sizeof(int32_t), &pi));
+        RC_TRY(ws->get(kEndJ, (size_t)n * sizeof(int32_t), &pj));
+    }
+    RC_TRY(s.scorePass((int32_t*)ps, (int32_t*)pi, (int32_t*)pj));
+    return selectTopRows(ws, &s, (int32_t*)ps, (int32_t*)pi, (int32_t*)pj, 1, n, start, k, minScore, outRow, count,
+                         targetIndex, score, endTarget, endQuery);
+}
+
+// miopalSearchBatchTop: batchImpl's chunks, each chunk's final [rows][n] device rows selected before they leave
+static int searchBatchTopImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                              int open, int ext, const int* matrix, int A, int searchType, int mode, int64_t start,
+                              int64_t end, int k, int minScore, int* count, int64_t* targetIndex, int* score,
+                              int* endTarget, int* endQuery) {
+    for (int c = 0; c < 4; ++c) g_lastBatchRouting[c] = 0;
+    if (searchType == OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "miopalSearchBatchTop: alignments are not selected on the device");
+    RC_TRY(validateBatch(db, queries, queryOffsets, nQueries, matrix, A, searchType, mode, start, end));
+    if (nQueries == 0) return 0;
+    RC_TRY(checkTopArgs(searchType, k, count, targetIndex, score, endTarget, endQuery));
+    const bool locate = searchType == OPAL_SEARCH_SCORE_END;
+    if (k == 0 || end == start) {
+        emptyTopRows(0, nQueries, k, count, targetIndex, score, locate ? endTarget : nullptr, locate ? endQuery : nullptr);
+        return 0;
+    }
+    const int64_t n = end - start;
+    BatchSink sink;
+    sink.checkOutputs = [](bool) { return 0; };
+    sink.chunk = [&](Workspace* ws, int64_t i0, int rows, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ) -> int {
+        return selectTopRows(ws, nullptr, d_score, d_endI, d_endJ, rows, n, start, k, minScore, i0, count, targetIndex,
+                             score, endTarget, endQuery);
+    };
+    sink.single = [&](int i) -> int {
+        return searchTopImpl(db, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext,
+                             matrix, A, searchType, mode, start, end, k, minScore, i, count, targetIndex, score,
+                             endTarget, endQuery);
+    };
+    return batchImpl(db, queries, queryOffsets, nQueries, open, ext, matrix, A, searchType, mode, start, end, sink);
+}

@@ -7,7 +7,9 @@ enum Slot {
     kScore, kEndI, kEndJ, kJobs, kPairB0, kPairB1, kAuxJobs, kAuxPairB0, kAuxPairB1, kRScore, kRI, kRJ, kDirs, kOps, kOpsOff,
     kOpsLen, kOvfHost, kWorkCounter, kViewEndI, kViewEndJ, kStartQ, kStartT, kMismatch, kCompactOps, kTraceScore, kOpsTotals, kSortBins, kSortedJobs, kScanOrder, kKeys, kHeadWaves, kHeadDirs, kUnitState, kUnitPartial, kStripKeys,
     kPairStripState, kPairStripPartial, kPairStripSpare, kAuxPairStripState, kAuxPairStripPartial, kPairStripError, kStripTiming,
-    kBatchProfiles, kBatchMeta, kBatchOverflow, kSlots
+    kBatchProfiles, kBatchMeta, kBatchOverflow,
+    kTopScratch,   // miopalSearchTop / miopalSearchBatchTop: the selection's outputs and scratch (rows x (bins + blocks + k))
+    kSlots
 };
 
 // Alignment operations as they cross PCIe - two bits each, operation p in bits 2 (p % 4) of byte p / 4

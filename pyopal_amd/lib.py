@@ -753,6 +753,99 @@ class Aligner:
                                       algorithm, start, end)
             return BatchResultArrays(mode, start, [len(e) for e in encoded], out)
 
+    def top_hits(self, query, database: BaseDatabase, k: int = 10, *, mode: str = "score", algorithm: str = "sw",
+                 min_score: typing.Optional[int] = None, start: int = 0, end: int = UINT32_MAX,
+                 device: int = 0) -> typing.List[ScoreResult]:
+        """Extension: the ``k`` best targets of ``database[start:end]``, best first, selected on the GPU
+        (include/miopal.h, miopalSearchTop): only ``k`` entries leave the device. Equal to
+        ``[r for r in sorted(self.align(query, database, mode=mode, ...), key=lambda r: r.score, reverse=True)
+        if min_score is None or r.score >= min_score][:k]``. ``mode="full"`` selects on the scores, then aligns the
+        chosen targets only, through a subset of the database gathered on the device."""
+        return self._top(query, [query], database, k, mode, algorithm, min_score, start, end, device, False)[0]
+
+    def top_hits_many(self, queries, database: BaseDatabase, k: int = 10, *, mode: str = "score",
+                      algorithm: str = "sw", min_score: typing.Optional[int] = None, start: int = 0,
+                      end: int = UINT32_MAX, device: int = 0) -> typing.List[typing.List[ScoreResult]]:
+        """Extension: `top_hits` of every query of ``queries`` in one batched search
+        (miopalSearchBatchTop); returns one list per query."""
+        return self._top(None, queries, database, k, mode, algorithm, min_score, start, end, device, True)
+
+    def _top(self, query, queries, database, k, mode, algorithm, min_score, start, end, device, many):
+        if mode not in _OPAL_SEARCH_MODES:
+            raise ValueError(f"invalid search mode: {mode!r}")
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"k must be an integer, not {type(k).__name__}")
+        k = int(k)
+        if k < 0 or k > _capi.MIOPAL_MAX_TOP:
+            raise ValueError(f"k must be between 0 and {_capi.MIOPAL_MAX_TOP} (MIOPAL_MAX_TOP), got {k}")
+        if min_score is not None:
+            min_score = int(min_score)
+        if start < 0 or end < 0:
+            raise OverflowError("can't convert negative value to uint32_t")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        if database.alphabet != self.alphabet:
+            raise ValueError("database and score matrix have different alphabets")
+        queries = list(queries)
+        for q in queries:
+            if q is None:
+                raise TypeError("Argument 'query' must not be None")
+        encoded = [database.alphabet.encode(q) for q in queries]
+        with database.lock.read:
+            size = database._get_size()
+            if end < start:
+                raise IndexError("database slice end is lower than start")
+            end = min(end, size)
+            if start > size:
+                raise IndexError("database slice start is past the end of the database")
+            if end == start or k == 0 or not encoded:
+                return [[] for _ in encoded]
+            if _capi.lib().miopalDeviceCount() < 1:
+                raise RuntimeError("no supported SIMD backend available")
+            mirror = database._device_mirror(device)
+            matrix = _int_matrix_array(self._int_matrix)
+            search_mode = "score" if mode == "full" else mode
+            arrays = [np.frombuffer(e, dtype=np.uint8) for e in encoded]
+            if many:
+                out = mirror.search_batch_top(arrays, matrix, self.gap_open, self.gap_extend, search_mode, algorithm,
+                                              start, end, k, min_score)
+                counts = [int(c) for c in out["count"]]
+                rows = [{key: out[key][i] for key in out if key != "count"} for i in range(len(encoded))]
+            else:
+                out = mirror.search_top(arrays[0], matrix, self.gap_open, self.gap_extend, search_mode, algorithm,
+                                        start, end, k, min_score)
+                counts = [out["count"]]
+                rows = [out]
+            results = []
+            for q, c, row in zip(arrays, counts, rows):
+                target = row["target"][:c]
+                if mode == "score":
+                    results.append([ScoreResult(int(t), int(s)) for t, s in zip(target, row["score"][:c])])
+                elif mode == "end":
+                    results.append([EndResult(int(t), int(s), int(qe), int(te)) for t, s, qe, te in
+                                    zip(target, row["score"][:c], row["end_q"][:c], row["end_t"][:c])])
+                else:
+                    results.append(self._realign(q, mirror, matrix, target, algorithm))
+            return results
+
+    def _realign(self, query: np.ndarray, mirror, matrix: np.ndarray, target: np.ndarray, algorithm: str):
+        """``full`` results of the chosen targets, in their order: one search of a subset handle holding
+        only them (gathered on the device from the mirror's residues)."""
+        if len(target) == 0:
+            return []
+        sub = mirror.subset(target)
+        try:
+            out = sub.search(query, matrix, self.gap_open, self.gap_extend, "full", algorithm, 0, len(target))
+        finally:
+            sub.close()
+        arrays = ResultArrays("full", 0, len(query), np.diff(sub.offsets), out)
+        return [FullResult(int(t), int(arrays.score[j]), int(arrays.query_end[j]), int(arrays.target_end[j]),
+                           int(arrays.query_start[j]), int(arrays.target_start[j]), len(query),
+                           int(arrays.target_length[j]), arrays.alignment(j)) for j, t in enumerate(target)]
+
 
 class BatchResultArrays:
     """Results of a batched search as 2-D arrays (`Aligner.align_many_arrays`): ``score`` and, for
