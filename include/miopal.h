@@ -231,6 +231,39 @@ int miopalSearchBatchTop(MiopalDb* db, const unsigned char* queries, const int64
                          int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery);
 
 /*
+ * A list of (query, target) pairs in one call: pair p aligns query pairQuery[p] (queries / queryOffsets as in
+ * miopalSearchBatch) with target pairTarget[p] (absolute index into the handle). Any order, repeats allowed; all three
+ * search types and all four modes. No reference counterpart (its callers loop over queries); an extension of the
+ * resident-handle ABI like miopalSearchBatch.
+ * Every output has nPairs entries, in pair order, and entry p equals what miopalSearch returns for query pairQuery[p]
+ * against the slice [pairTarget[p], pairTarget[p] + 1) with the same search type, mode, gaps and matrix - score, end
+ * and start locations, operations, and the -1 locations / empty operations of an empty alignment (empty queries and
+ * targets included). The alignments have miopalSearchFlat's shape: ONE malloc'ed buffer (*operations, caller frees)
+ * and operationOffsets[nPairs + 1]. Arrays a search type does not produce may be NULL.
+ * Checked before any work, with miopalSearch's codes: every query, the matrix and the alphabet, pairQuery[p] in
+ * [0, nQueries) and pairTarget[p] in [0, miopalDbCount) (MIOPAL_ERR_BAD_ARGUMENT, the message names the first bad
+ * pair), null outputs, and miopalSearch's 32-bit range check for the longest query and the longest target the list
+ * names (OPAL_ERR_OVERFLOW). nPairs = 0: the arguments are checked, nothing is launched, operationOffsets[0] = 0,
+ * *operations = NULL, 0. Thread-safe like miopalSearch. Device memory is bounded whatever the list's length: the list
+ * is processed in chunks sized from the workspace budgets of an OPAL_SEARCH_ALIGNMENT search.
+ */
+int miopalAlignPairs(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                     const int32_t* pairQuery, const int64_t* pairTarget, int64_t nPairs,
+                     int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength,
+                     int searchType, int mode,
+                     int* score, int* endTarget, int* endQuery, int* startTarget, int* startQuery,
+                     unsigned char** operations, int64_t* operationOffsets);
+
+/*
+ * How the calling thread's most recent miopalAlignPairs ran (diagnostics for tests):
+ *   counts[0] pairs whose forward pass ran in the lane-per-pair kernel (pairlist_forward_kernel)
+ *   counts[1] pairs whose forward pass ran in the wavefront-per-pair kernel
+ *   counts[2] pairs answered without a DP (empty query or target)
+ *   counts[3] chunks
+ */
+void miopalLastPairRouting(int64_t counts[4]);
+
+/*
  * How the calling thread's most recent miopalSearchBatch ran (diagnostics for tests):
  *   counts[0] (query, target) pairs settled by the batch kernels
  *   counts[1] (query, target) pairs run by the wavefront-per-pair kernel

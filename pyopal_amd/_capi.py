@@ -50,6 +50,7 @@ EXPORTS = [
     "miopalSearch", "miopalSearchFlat", "miopalSearchFlatInto", "miopalSearchDeviceScores", "miopalSetProfiling", "miopalLastKernelTime",
     "miopalLastRouting", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
     "miopalSearchBatch", "miopalLastBatchRouting", "miopalSearchTop", "miopalSearchBatchTop",
+    "miopalAlignPairs", "miopalLastPairRouting",
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
     # test hooks
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices",
@@ -130,6 +131,11 @@ def lib() -> ctypes.CDLL:
         L.miopalSearchBatchTop.restype = c_int
         L.miopalSearchBatchTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                            c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.miopalAlignPairs.restype = c_int
+        L.miopalAlignPairs.argtypes = [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_int,
+                                       c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp]
+        L.miopalLastPairRouting.restype = None
+        L.miopalLastPairRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
         L.miopalLastBatchRouting.restype = None
         L.miopalLastBatchRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
         L.miopalSearchFlat.restype = c_int
@@ -483,6 +489,61 @@ class DeviceDatabase:
                                         _ptr(out.get("end_q")))
         raise_for(rc)
         return out
+
+    def align_pairs(self, queries: typing.Sequence[np.ndarray], pair_query, pair_target, matrix: np.ndarray,
+                    gap_open: int = 3, gap_extend: int = 1, mode: str = "score",
+                    algorithm: str = "sw") -> typing.Dict[str, typing.Any]:
+        """miopalAlignPairs: pair p aligns ``queries[pair_query[p]]`` (encoded residues) with target
+        ``pair_target[p]`` (absolute index), in one call. Returns `search`'s keys with one entry per pair, in pair
+        order: "score", for "end" and "full" also "end_t" / "end_q", for "full" also "start_t" / "start_q",
+        "aln_flat", "aln_off" and "aln"; entry p equals ``search(queries[i], ..., start=j, end=j + 1)``."""
+        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
+        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            np.cumsum([len(q) for q in qs], out=offsets[1:])
+        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
+        if flat.size == 0:
+            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
+        pq = np.ascontiguousarray(pair_query, dtype=np.int32).ravel()
+        pt = np.ascontiguousarray(pair_target, dtype=np.int64).ravel()
+        if len(pq) != len(pt):
+            raise ValueError("pair_query and pair_target differ in length")
+        n = len(pq)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        st = SEARCH[mode]
+        out = {"score": np.empty(n, dtype=np.int32)}
+        et = eq = s_t = s_q = aoff = None
+        ops_ptr = ctypes.c_void_p()
+        if st >= 1:
+            et = np.empty(n, dtype=np.int32)
+            eq = np.empty(n, dtype=np.int32)
+        if st == 2:
+            s_t = np.empty(n, dtype=np.int32)
+            s_q = np.empty(n, dtype=np.int32)
+            aoff = np.zeros(n + 1, dtype=np.int64)
+        rc = lib().miopalAlignPairs(self._h, _ptr(flat), _ptr(offsets), len(qs), _ptr(pq) if n else None,
+                                    _ptr(pt) if n else None, n, gap_open, gap_extend, _ptr(S), self.alphabet_length,
+                                    st, MODE[algorithm], _ptr(out["score"]), _ptr(et), _ptr(eq), _ptr(s_t), _ptr(s_q),
+                                    ctypes.byref(ops_ptr), _ptr(aoff))
+        raise_for(rc)
+        if st >= 1:
+            out.update(end_t=et, end_q=eq)
+        if st == 2:
+            total = int(aoff[-1])
+            if ops_ptr.value:
+                flat_ops = np.asarray(_MallocBytes(ops_ptr.value, total))
+            else:
+                flat_ops = np.zeros(0, dtype=np.uint8)
+            out.update(start_t=s_t, start_q=s_q, aln_flat=flat_ops, aln_off=aoff, aln=_LazyAlignments(flat_ops, aoff))
+        return out
+
+    @staticmethod
+    def last_pair_routing() -> typing.Tuple[int, int, int, int]:
+        """(pairs on the lane-per-pair forward kernel, pairs on the wavefront-per-pair kernel, pairs answered without
+        a DP, chunks) for the calling thread's most recent align_pairs."""
+        counts = (ctypes.c_int64 * 4)()
+        lib().miopalLastPairRouting(counts)
+        return tuple(int(c) for c in counts)
 
     @staticmethod
     def last_batch_routing() -> typing.Tuple[int, int, int, int]:

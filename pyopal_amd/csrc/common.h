@@ -194,7 +194,7 @@ struct PerPairArgs {
     int nJobs;
     const uint8_t* residues;
     const uint8_t* query;
-    int queryLength;          // <= 4096 (staged in LDS)
+    int queryLength;          // <= 4096: staged in LDS; longer (pair lists): perpair_kernel reads its rows from global memory
     const int* matrix;
     int alphabet;
     int gapOpen, gapExt;
@@ -374,9 +374,10 @@ hipError_t launchWalk(const WalkArgs& a, hipStream_t stream);
 hipError_t launchStartCells(int n, int mode, int open, int ext, const int32_t* score, const int32_t* endQ,
                             const int32_t* endT, const int32_t* rScore, const int32_t* rI, const int32_t* rJ,
                             int32_t* startQ, int32_t* startT, int* mismatch, hipStream_t stream);
+// (queryBase, optional: the origin of job k's query in the query buffer - pair lists, every pair with its own query)
 hipError_t launchTraceJobs(int n, int rules, const int32_t* startQ, const int32_t* startT, const int32_t* endQ,
                            const int32_t* endT, const int64_t* offsets, int64_t dirStride, int64_t wsStride,
-                           PairJob* jobs, hipStream_t stream);
+                           PairJob* jobs, hipStream_t stream, const int32_t* queryBase = nullptr);
 // Counting sort by tLen, longest first (lengths are coarsened so that at most 8192 bins are needed).
 // queryRows > 8: the window's rows in groups of eight as a minor key, tallest first (what a direction wavefront
 // sweeps is its tallest window times its longest). bins: 8192 ints.
@@ -394,7 +395,16 @@ hipError_t launchGatherOps(int n, const uint8_t* slots, int64_t slotBytes, const
                            hipStream_t stream);
 hipError_t launchReverseJobs(int n, const int32_t* score, const int32_t* endQ, const int32_t* endT,
                              const int64_t* offsets, int rules, int64_t wsStride, PairJob* jobs,
-                             hipStream_t stream);
+                             hipStream_t stream, const int32_t* queryBase = nullptr);
+// pairlist.hip: the jobs of a chunk of a pair list (whole query pairQuery[k] against whole target pairTarget[k];
+// queryOff: [queries + 1] into the concatenated queries) with the pairs' target and query origins, and the forward
+// pass of such jobs with one lane per pair: the mode's own border rules from job.rules, `region` where the answer is
+// taken, end cells with `locate`; a.query = the concatenated queries (global memory, any length), a.skipWaves as in
+// perpair_kernel
+hipError_t launchPairListJobs(int n, const int32_t* pairQuery, const int64_t* pairTarget, const int32_t* queryOff,
+                              const int64_t* dbOffsets, int rules, int64_t wsStride, PairJob* jobs,
+                              int64_t* targetOff, int32_t* queryBase, hipStream_t stream);
+hipError_t launchPairListForward(const PerPairArgs& a, int region, bool locate, hipStream_t stream);
 hipError_t launchPack(const PackArgs& a, int64_t totalChunks, hipStream_t stream);
 // segmented views with end locations (pack.hip): keyed atomicMax per window, then unpack
 hipError_t launchScatterKeyed(const int32_t* viewScore, const int32_t* viewEndI, const int32_t* viewEndJ,

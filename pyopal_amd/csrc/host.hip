@@ -653,6 +653,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_full.inc"
 #include "host_batch.inc"
 #include "host_top.inc"
+#include "host_pairs.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                  int64_t end, int* score, int* endTarget, int* endQuery, int* startTarget,
@@ -690,6 +691,33 @@ int miopalSearchBatchTop(MiopalDb* db, const unsigned char* queries, const int64
     return searchBatchTopImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength,
                               searchType, mode, start, end, k, minScore, count, targetIndex, score, endTarget, endQuery);
     });
+}
+
+int miopalAlignPairs(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                     const int32_t* pairQuery, const int64_t* pairTarget, int64_t nPairs, int gapOpen, int gapExt,
+                     const int* scoreMatrix, int alphabetLength, int searchType, int mode, int* score, int* endTarget,
+                     int* endQuery, int* startTarget, int* startQuery, unsigned char** operations,
+                     int64_t* operationOffsets) {
+    return guarded([&]() -> int {
+    HostBytes ops;
+    const bool full = searchType == OPAL_SEARCH_ALIGNMENT;
+    RC_TRY(alignPairsImpl(db, queries, queryOffsets, nQueries, pairQuery, pairTarget, nPairs, gapOpen, gapExt, scoreMatrix,
+                          alphabetLength, searchType, mode, score, endTarget, endQuery, startTarget, startQuery,
+                          full && operations ? &ops : nullptr, operationOffsets));
+    if (full) {
+        *operations = nullptr;
+        if (nPairs > 0) {
+            if (!ops.data && !ops.resize(0)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+            *operations = ops.release();
+        }
+    }
+    return 0;
+    });
+}
+
+void miopalLastPairRouting(int64_t counts[4]) {
+    if (!counts) return;
+    for (int k = 0; k < 4; ++k) counts[k] = g_lastPairRouting[k];
 }
 
 int miopalSearchFlat(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,

@@ -8,6 +8,9 @@ enum Slot {
     kOpsLen, kOvfHost, kWorkCounter, kViewEndI, kViewEndJ, kStartQ, kStartT, kMismatch, kCompactOps, kTraceScore, kOpsTotals, kSortBins, kSortedJobs, kScanOrder, kKeys, kHeadWaves, kHeadDirs, kUnitState, kUnitPartial, kStripKeys,
     kPairStripState, kPairStripPartial, kPairStripSpare, kAuxPairStripState, kAuxPairStripPartial, kPairStripError, kStripTiming,
     kBatchProfiles, kBatchMeta, kBatchOverflow,
+    // miopalAlignPairs (host_pairs.inc): a chunk's pair list, its pairs' target / query origins, the queries' offsets,
+    // and the lane-per-pair kernels' strip boundaries
+    kPairListQ, kPairListT, kPairListTOff, kPairListQBase, kPairListQOff, kPairListBoundary,
     kTopScratch,   // miopalSearchTop / miopalSearchBatchTop: the selection's outputs and scratch (rows x (bins + blocks + k))
     kSlots
 };

@@ -848,7 +848,8 @@ __global__ __launch_bounds__(64) void walk_planes_kernel(WalkArgs a) {
 // reversed prefixes q[0..endQ], t[0..endT] anchored on the end cell. Targets without an
 // end cell get an empty job (its outputs are ignored by the host).
 __global__ void reverse_jobs_kernel(int n, const int32_t* score, const int32_t* endQ, const int32_t* endT,
-                                    const int64_t* offsets, int rules, int64_t wsStride, PairJob* jobs) {
+                                    const int64_t* offsets, int rules, int64_t wsStride, PairJob* jobs,
+                                    const int32_t* queryBase) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const int qe = endQ[k], te = endT[k];
@@ -866,7 +867,7 @@ __global__ void reverse_jobs_kernel(int n, const int32_t* score, const int32_t* 
     if (qe >= 0 && te >= 0) {
         j.tOff = offsets[k] + te;
         j.tLen = te + 1;
-        j.qOff = qe;
+        j.qOff = qe + (queryBase ? queryBase[k] : 0);
         j.qLen = qe + 1;
     }
     jobs[k] = j;
@@ -941,7 +942,7 @@ __global__ void start_cells_kernel(int n, int mode, int open, int ext, const int
 // Traceback jobs on the [start..end] rectangles; job k owns direction slot k.
 __global__ void trace_jobs_kernel(int n, int rules, const int32_t* startQ, const int32_t* startT,
                                   const int32_t* endQ, const int32_t* endT, const int64_t* offsets,
-                                  int64_t dirStride, int64_t wsStride, PairJob* jobs) {
+                                  int64_t dirStride, int64_t wsStride, PairJob* jobs, const int32_t* queryBase) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     PairJob j{};
@@ -954,7 +955,7 @@ __global__ void trace_jobs_kernel(int n, int rules, const int32_t* startQ, const
     if (endQ[k] >= 0 && endT[k] >= 0) {
         j.tOff = offsets[k] + startT[k];
         j.tLen = endT[k] - startT[k] + 1;
-        j.qOff = startQ[k];
+        j.qOff = startQ[k] + (queryBase ? queryBase[k] : 0);
         j.qLen = endQ[k] - startQ[k] + 1;
     }
     jobs[k] = j;
@@ -1225,10 +1226,10 @@ hipError_t launchStartCells(int n, int mode, int open, int ext, const int32_t* s
 
 hipError_t launchTraceJobs(int n, int rules, const int32_t* startQ, const int32_t* startT, const int32_t* endQ,
                            const int32_t* endT, const int64_t* offsets, int64_t dirStride, int64_t wsStride,
-                           PairJob* jobs, hipStream_t stream) {
+                           PairJob* jobs, hipStream_t stream, const int32_t* queryBase) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(trace_jobs_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, rules, startQ, startT,
-                       endQ, endT, offsets, dirStride, wsStride, jobs);
+                       endQ, endT, offsets, dirStride, wsStride, jobs, queryBase);
     return hipGetLastError();
 }
 
@@ -1245,10 +1246,10 @@ hipError_t launchGatherOps(int n, const uint8_t* slots, int64_t slotBytes, const
 
 hipError_t launchReverseJobs(int n, const int32_t* score, const int32_t* endQ, const int32_t* endT,
                              const int64_t* offsets, int rules, int64_t wsStride, PairJob* jobs,
-                             hipStream_t stream) {
+                             hipStream_t stream, const int32_t* queryBase) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(reverse_jobs_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, score, endQ, endT,
-                       offsets, rules, wsStride, jobs);
+                       offsets, rules, wsStride, jobs, queryBase);
     return hipGetLastError();
 }
 

@@ -39,18 +39,25 @@ constexpr int kBlock = 256;
 
 constexpr int kQueryLds = 4096;  // longest query the kernel stages in LDS
 
-template <int MODE>  // kAllCells / kLastRow / kLastRowCol: start-location scan; kPerPairTrace: directions
+// GLOBALQ (pair lists, miopalAlignPairs): the query buffer - every pair's own query, end to end - is longer than
+// kQueryLds; the lane's rows are read from global memory, once per strip, instead of from an LDS copy
+template <int MODE, bool GLOBALQ = false>  // kAllCells / kLastRow / kLastRowCol: start-location scan; kPerPairTrace: directions
 __global__ __launch_bounds__(kBlock) void perpair_kernel(PerPairArgs a) {
     __shared__ int smat[kStride * kStride];
-    __shared__ uint8_t qlds[kQueryLds];
+    __shared__ uint8_t qlds[GLOBALQ ? 4 : kQueryLds];
     const int A = a.alphabet;
     for (int idx = threadIdx.x; idx < kStride * kStride; idx += kBlock) {
         const int q = idx / kStride, t = idx % kStride;
         // `open` is folded into the scores: the columns keep H - open (see the cell update)
         smat[idx] = (q < A && t < A) ? a.matrix[q * A + t] + a.gapOpen : kPadScore;
     }
-    for (int x = threadIdx.x; x < a.queryLength; x += kBlock) qlds[x] = a.query[x];
+    if constexpr (!GLOBALQ)
+        for (int x = threadIdx.x; x < a.queryLength; x += kBlock) qlds[x] = a.query[x];
     __syncthreads();
+    auto queryAt = [&](int x) -> int {
+        if constexpr (GLOBALQ) return a.query[x];
+        else return qlds[x];
+    };
 
     const int lane = threadIdx.x & 63;
     const int idx = blockIdx.x * kBlock + threadIdx.x;
@@ -95,8 +102,8 @@ __global__ __launch_bounds__(kBlock) void perpair_kernel(PerPairArgs a) {
         uint32_t qo[kLanes / 2];
 #pragma unroll
         for (int i = 0; i < kLanes; i += 2) {
-            const int q0 = row0 + i < Q ? qlds[job.qOff + (row0 + i) * job.qStep] : A;
-            const int q1 = row0 + i + 1 < Q ? qlds[job.qOff + (row0 + i + 1) * job.qStep] : A;
+            const int q0 = row0 + i < Q ? queryAt(job.qOff + (row0 + i) * job.qStep) : A;
+            const int q1 = row0 + i + 1 < Q ? queryAt(job.qOff + (row0 + i + 1) * job.qStep) : A;
             qo[i >> 1] = (uint32_t)(q0 * kStride * 4) | ((uint32_t)(q1 * kStride * 4) << 16);
         }
         // Previous column, kept as HM = H - open: the same number opens a gap to the right (E of
@@ -820,6 +827,16 @@ hipError_t launchPerPair(const PerPairArgs& a, int mode, hipStream_t stream) {
         else if (mode == kLastRow) hipLaunchKernelGGL((perpair_profile_kernel<kLastRow>), grid, block, lds, stream, a);
         else if (mode == kLastRowCol) hipLaunchKernelGGL((perpair_profile_kernel<kLastRowCol>), grid, block, lds, stream, a);
         else hipLaunchKernelGGL((perpair_profile_kernel<kPerPairTrace>), grid, block, lds, stream, a);
+        return hipGetLastError();
+    }
+    if (a.queryLength > kQueryLds) {
+        switch (mode) {
+            case kAllCells: hipLaunchKernelGGL((perpair_kernel<kAllCells, true>), grid, block, 0, stream, a); break;
+            case kLastRow: hipLaunchKernelGGL((perpair_kernel<kLastRow, true>), grid, block, 0, stream, a); break;
+            case kLastRowCol: hipLaunchKernelGGL((perpair_kernel<kLastRowCol, true>), grid, block, 0, stream, a); break;
+            case kPerPairTrace: hipLaunchKernelGGL((perpair_kernel<kPerPairTrace, true>), grid, block, 0, stream, a); break;
+            default: return hipErrorInvalidValue;
+        }
         return hipGetLastError();
     }
     switch (mode) {

@@ -753,6 +753,67 @@ class Aligner:
                                       algorithm, start, end)
             return BatchResultArrays(mode, start, [len(e) for e in encoded], out)
 
+    def align_pairs(self, queries, database: BaseDatabase, pairs, *, mode: str = "score", algorithm: str = "sw",
+                    device: int = 0) -> typing.List[ScoreResult]:
+        """Extension: align a list of (query, target) pairs in one call (include/miopal.h, miopalAlignPairs).
+
+        ``pairs`` is a sequence of ``(query_index, target_index)`` or an ``(n, 2)`` integer array: indices into
+        ``queries`` and into the database, in any order, repeats allowed. Returns one `ScoreResult` / `EndResult` /
+        `FullResult` per pair, in pair order, each equal to
+        ``self.align(queries[i], database, mode=mode, algorithm=algorithm, start=j, end=j + 1)[0]``: the hits of
+        `top_hits_many`, the survivors of a prefilter, the candidate pairs of a clustering step."""
+        if mode not in _OPAL_SEARCH_MODES:
+            raise ValueError(f"invalid search mode: {mode!r}")
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        if database.alphabet != self.alphabet:
+            raise ValueError("database and score matrix have different alphabets")
+        queries = list(queries)
+        for q in queries:
+            if q is None:
+                raise TypeError("Argument 'query' must not be None")
+        encoded = [database.alphabet.encode(q) for q in queries]
+        pairs = np.asarray(pairs if len(pairs) else np.zeros((0, 2), dtype=np.int64))
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
+            raise ValueError("pairs must be a sequence of (query_index, target_index) integers")
+        pairs = pairs.astype(np.int64, copy=False)
+        with database.lock.read:
+            size = database._get_size()
+            if len(pairs):
+                if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= len(queries):
+                    raise IndexError("query index of a pair outside the queries")
+                if pairs[:, 1].min() < 0 or pairs[:, 1].max() >= size:
+                    raise IndexError("target index of a pair outside the database")
+            if len(pairs) == 0:
+                return []
+            if _capi.lib().miopalDeviceCount() < 1:
+                raise RuntimeError("no supported SIMD backend available")
+            mirror = database._device_mirror(device)
+            return self._pair_results([np.frombuffer(e, dtype=np.uint8) for e in encoded], mirror,
+                                      _int_matrix_array(self._int_matrix), pairs[:, 0], pairs[:, 1], mode, algorithm)
+
+    def _pair_results(self, arrays, mirror, matrix, pair_query, pair_target, mode, algorithm):
+        """One `align_pairs` call on the mirror; its arrays as result objects, in pair order."""
+        out = mirror.align_pairs(arrays, pair_query, pair_target, matrix, self.gap_open, self.gap_extend, mode,
+                                 algorithm)
+        score = out["score"].tolist()
+        target = np.asarray(pair_target).tolist()
+        if mode == "score":
+            return [ScoreResult(t, s) for t, s in zip(target, score)]
+        end_q, end_t = out["end_q"].tolist(), out["end_t"].tolist()
+        if mode == "end":
+            return [EndResult(t, s, qe, te) for t, s, qe, te in zip(target, score, end_q, end_t)]
+        start_q, start_t = out["start_q"].tolist(), out["start_t"].tolist()
+        off = out["aln_off"].tolist()
+        text = out["aln_flat"].tobytes().translate(_OPS_TO_TEXT).decode("ascii")
+        lengths = np.diff(mirror.offsets)
+        return [FullResult(t, score[p], end_q[p], end_t[p], start_q[p], start_t[p], len(arrays[q]), int(lengths[t]),
+                           text[off[p]:off[p + 1]])
+                for p, (q, t) in enumerate(zip(np.asarray(pair_query).tolist(), target))]
+
     def top_hits(self, query, database: BaseDatabase, k: int = 10, *, mode: str = "score", algorithm: str = "sw",
                  min_score: typing.Optional[int] = None, start: int = 0, end: int = UINT32_MAX,
                  device: int = 0) -> typing.List[ScoreResult]:
@@ -760,14 +821,15 @@ class Aligner:
         (include/miopal.h, miopalSearchTop): only ``k`` entries leave the device. Equal to
         ``[r for r in sorted(self.align(query, database, mode=mode, ...), key=lambda r: r.score, reverse=True)
         if min_score is None or r.score >= min_score][:k]``. ``mode="full"`` selects on the scores, then aligns the
-        chosen targets only, through a subset of the database gathered on the device."""
+        chosen targets only, in one pair-list call (miopalAlignPairs)."""
         return self._top(query, [query], database, k, mode, algorithm, min_score, start, end, device, False)[0]
 
     def top_hits_many(self, queries, database: BaseDatabase, k: int = 10, *, mode: str = "score",
                       algorithm: str = "sw", min_score: typing.Optional[int] = None, start: int = 0,
                       end: int = UINT32_MAX, device: int = 0) -> typing.List[typing.List[ScoreResult]]:
         """Extension: `top_hits` of every query of ``queries`` in one batched search
-        (miopalSearchBatchTop); returns one list per query."""
+        (miopalSearchBatchTop); returns one list per query. ``mode="full"`` selects on the scores, then aligns
+        all chosen (query, target) pairs in ONE pair-list call (miopalAlignPairs)."""
         return self._top(None, queries, database, k, mode, algorithm, min_score, start, end, device, True)
 
     def _top(self, query, queries, database, k, mode, algorithm, min_score, start, end, device, many):
@@ -819,6 +881,16 @@ class Aligner:
                                         start, end, k, min_score)
                 counts = [out["count"]]
                 rows = [out]
+            if mode == "full":
+                # every chosen (query, target) pair in one pair-list call, cut back into one list per query
+                chosen = [row["target"][:c] for c, row in zip(counts, rows)]
+                pair_target = np.concatenate(chosen) if chosen else np.zeros(0, dtype=np.int64)
+                if len(pair_target) == 0:
+                    return [[] for _ in encoded]
+                pair_query = np.repeat(np.arange(len(encoded), dtype=np.int32), counts)
+                flat = self._pair_results(arrays, mirror, matrix, pair_query, pair_target, "full", algorithm)
+                bounds = np.concatenate(([0], np.cumsum(counts))).tolist()
+                return [flat[bounds[i]:bounds[i + 1]] for i in range(len(encoded))]
             results = []
             for q, c, row in zip(arrays, counts, rows):
                 target = row["target"][:c]
@@ -827,24 +899,7 @@ class Aligner:
                 elif mode == "end":
                     results.append([EndResult(int(t), int(s), int(qe), int(te)) for t, s, qe, te in
                                     zip(target, row["score"][:c], row["end_q"][:c], row["end_t"][:c])])
-                else:
-                    results.append(self._realign(q, mirror, matrix, target, algorithm))
             return results
-
-    def _realign(self, query: np.ndarray, mirror, matrix: np.ndarray, target: np.ndarray, algorithm: str):
-        """``full`` results of the chosen targets, in their order: one search of a subset handle holding
-        only them (gathered on the device from the mirror's residues)."""
-        if len(target) == 0:
-            return []
-        sub = mirror.subset(target)
-        try:
-            out = sub.search(query, matrix, self.gap_open, self.gap_extend, "full", algorithm, 0, len(target))
-        finally:
-            sub.close()
-        arrays = ResultArrays("full", 0, len(query), np.diff(sub.offsets), out)
-        return [FullResult(int(t), int(arrays.score[j]), int(arrays.query_end[j]), int(arrays.target_end[j]),
-                           int(arrays.query_start[j]), int(arrays.target_start[j]), len(query),
-                           int(arrays.target_length[j]), arrays.alignment(j)) for j, t in enumerate(target)]
 
 
 class BatchResultArrays:
