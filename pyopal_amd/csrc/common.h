@@ -414,11 +414,9 @@ hipError_t launchScatterKeyed(const int32_t* viewScore, const int32_t* viewEndI,
 hipError_t launchDecodeKeys(const unsigned long long* keys, int n, int32_t* score, int32_t* endI, int32_t* endJ,
                             hipStream_t stream, int scoreBias = 0);
 hipError_t launchFillInt32(int32_t* out, int n, int32_t value, hipStream_t stream);
-// subset of a resident database: dst[dstOff[k] ...] = src[srcStart[k] ...] for every sequence k (dstOff has n + 1 entries)
-// device -> pinned host copy by a small kernel of our own (see pack.hip)
-hipError_t launchCopyOut(const void* src, void* dst, int64_t bytes, hipStream_t stream);
 // units of 64 one-byte operations of `src` -> 16 bytes each of `dst`, two bits per operation (both 16-byte aligned)
 hipError_t launchCopyOutPacked(const void* src, void* dst, int64_t firstUnit, int64_t lastUnit, hipStream_t stream);
+// subset of a resident database: dst[dstOff[k] ...] = src[srcStart[k] ...] for every sequence k (dstOff has n + 1 entries)
 hipError_t launchGatherSequences(const uint8_t* src, const int64_t* srcStart, const int64_t* dstOff, int64_t n,
                                  uint8_t* dst, hipStream_t stream);
 // takeMax: several view positions (segments) may belong to one target; `out` starts at 0

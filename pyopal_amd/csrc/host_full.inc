@@ -92,7 +92,7 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
     // A `full` search whose later passes stay on the device leaves the scores and end locations in the staging
     // buffer until its end: copying 12 MB into the caller's (fresh) pages here kept the device idle for 0.35 ms
     // between the end pass and the start-cell scan. (Whatever takes the host's paths below flushes first.)
-    const bool deferResults = searchType == OPAL_SEARCH_ALIGNMENT && !tuned(Tune::NO_DEFERRED_RESULTS);
+    const bool deferResults = searchType == OPAL_SEARCH_ALIGNMENT;
     constexpr size_t kDeferFrom = 64u << 10;
     // scores and end locations of a `full` search that have not been sent on their way to the host yet, and the copies
     // themselves: on the side stream, behind whatever the main stream has been given so far
@@ -130,18 +130,13 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
         const bool beside = deferResults && n * sizeof(int) >= kDeferFrom && !tuned(Tune::NO_SIDE_COPIES);
         // (round 5: LATER still - beside the first direction kernel, which does not mind them; the small kernels between
         // the passes crawl beside a copy: the 30-us job list of the scan took 94 us, a 2-us fill 76 us)
-        if (beside && !tuned(Tune::NO_LATE_RESULT_COPIES)) {
+        if (beside) {
             resultsPending = true;
         } else {
-            if (beside) {
-                RC_TRY(ws->ensureAux());
-                HIP_TRY(hipEventRecord(ws->evFork, stream));
-                HIP_TRY(hipStreamWaitEvent(ws->aux, ws->evFork, 0));
-            }
-            RC_TRY(ws->stageDownload(score, ps, (size_t)n * sizeof(int), beside));
+            RC_TRY(ws->stageDownload(score, ps, (size_t)n * sizeof(int)));
             if (wantEnd) {
-                RC_TRY(ws->stageDownload(endQuery, pi, (size_t)n * sizeof(int), beside));
-                RC_TRY(ws->stageDownload(endTarget, pj, (size_t)n * sizeof(int), beside));
+                RC_TRY(ws->stageDownload(endQuery, pi, (size_t)n * sizeof(int)));
+                RC_TRY(ws->stageDownload(endTarget, pj, (size_t)n * sizeof(int)));
             }
         }
     }
@@ -407,8 +402,9 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                 int64_t batch = batchLane;
                 const int64_t opsCap = n * slotOps;
                 // (the pinned staging buffer holds the worst case, n x slotOps: Q = 300 on 1M x 300 asks for 664 MB)
-                const bool overlapOps = opsCap <= (1024ll << 20) && !tuned(Tune::NO_OPS_OVERLAP);
-                const bool packedOps = overlapOps && !tuned(Tune::NO_PACKED_OPS);
+                // (within it the operations leave batch by batch, two bits each; a larger result is downloaded whole, in bytes,
+                // after the last batch)
+                const bool overlapOps = opsCap <= (1024ll << 20);
                 void *pd, *pslots, *pbins = nullptr, *psorted = nullptr;
                 // Direction pass: one lane per pair needs ~64 x fewer instructions per cell but a
                 // lane walks its whole window alone (strips x columns x 64 rows, ~0.4 us per strip
@@ -507,11 +503,9 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                     }
                 } batchDone, traceStart, copyDone;
                 size_t opsBase = 0;
-                // operations of the staged stream -> the caller's buffer (a copy, or the unpacking of two-bit codes)
+                // operations of the staged stream -> the caller's buffer (the unpacking of two-bit codes)
                 auto opsToCaller = [&](uint8_t* out, int64_t from, int64_t to, int threads) {
-                    if (to <= from) return;
-                    if (packedOps) unpack::ops(out, (const uint8_t*)ws->pinned + opsBase, from, to, threads);
-                    else Workspace::copyOut(out + from, (const char*)ws->pinned + opsBase + from, (size_t)(to - from));
+                    if (to > from) unpack::ops(out, (const uint8_t*)ws->pinned + opsBase, from, to, threads);
                 };
                 int64_t opsFetched = 0;
                 int64_t opsCopiedOut = 0;   // of the fetched operations: already in the caller's buffer
@@ -529,7 +523,7 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                     // follow, reserved in one go (a later drain would reset the staging buffer)
                     // (the operations cross PCIe two bits each - copy_out_packed_kernel - a quarter of a byte per operation)
                     const size_t head = 256 + (((size_t)nBatches * 8 + 255) & ~(size_t)255);
-                    const size_t stagedOps = packedOps ? ((size_t)opsCap + 63) / 64 * 16 : (size_t)opsCap;
+                    const size_t stagedOps = ((size_t)opsCap + 63) / 64 * 16;
                     // (with the scores and end locations when they are still to be sent: sendResults)
                     RC_TRY(ws->reserveStaging(head + stagedOps + 256 + (size_t)n * (resultsPending ? 36 : 20) + 8192 + (size_t)nBatches * 1024));
                     fetchedTotal = (int64_t*)((char*)ws->pinned + ws->pinnedUsed);
@@ -603,9 +597,9 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                 const double shareClock0 = PhaseTimer::now();
                 unpack::AsyncWork sharer, arrayer;   // (declared behind everything their tasks refer to: drained first on every way out)
                 auto hostShare = [&](int64_t landed, int64_t upToBatch) -> int {
-                    // (packed: up to the last whole unit of what has landed - the unit a batch ends in is written again,
+                    // (up to the last whole unit of what has landed - the unit a batch ends in is written again,
                     // complete, by the next batch's copy)
-                    const int64_t settled = packedOps ? landed & ~(int64_t)63 : landed;
+                    const int64_t settled = landed & ~(int64_t)63;
                     const int64_t from = opsCopiedOut;
                     int64_t to = from;
                     if (copyOutEarly && settled > opsCopiedOut) {
@@ -667,24 +661,16 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                     if (upTo < opsFetched || upTo > opsCap) return fail(MIOPAL_ERR_INTERNAL, "bad operation count");
                     // Two things about a device-to-host copy beside the next batch (kernel traces of cfg3,
                     // profiles/r03_full_copy_overlap.txt). The runtime's copy is a kernel that fills the chip: a
-                    // direction kernel of 0.49 ms beside it lasted 0.78 ms; copy_out_kernel keeps to 64 workgroups
-                    // (MIOPAL_RUNTIME_COPY=1: as before). And while either copy runs, the SMALL kernels of the main
+                    // direction kernel of 0.49 ms beside it lasted 0.78 ms; copy_out_packed_kernel keeps to 64 workgroups.
+                    // And while either copy runs, the SMALL kernels of the main
                     // stream crawl (the 12-us sort and the 12-us outlier pass: 240-350 us each, whichever came
                     // first), the direction kernel does not (+ 30 us): so the copy starts with the next batch's
                     // direction kernel, not before.
                     if (upTo > opsFetched && b + 1 < nBatches)
                         HIP_TRY(hipStreamWaitEvent(ws->aux, traceStart.ev[(size_t)b + 1], 0));
-                    if (upTo > opsFetched && packedOps) {
+                    if (upTo > opsFetched) {
                         // (whole units of 64 operations: the unit a batch ends in is packed again, complete, with the next)
                         HIP_TRY(launchCopyOutPacked(pcompact, (char*)ws->pinned + opsBase, opsFetched / 64, (upTo + 63) / 64, ws->aux));
-                    } else if (upTo > opsFetched) {
-                        const bool runtimeCopy = tuned(Tune::RUNTIME_COPY) != nullptr;
-                        if (runtimeCopy)
-                            HIP_TRY(hipMemcpyAsync((char*)ws->pinned + opsBase + opsFetched, (const char*)pcompact + opsFetched,
-                                                   (size_t)(upTo - opsFetched), hipMemcpyDeviceToHost, ws->aux));
-                        else
-                            HIP_TRY(launchCopyOut((const char*)pcompact + opsFetched, (char*)ws->pinned + opsBase + opsFetched,
-                                                  upTo - opsFetched, ws->aux));
                     }
                     opsFetched = upTo;
                     // (round 4, first form: the share of the batch before, here - behind this batch's gather)
@@ -890,7 +876,7 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                 }
                 // (the threads that will unpack the last share, started while the device is at work on the last batch)
                 std::unique_ptr<unpack::Crew> crew;
-                if (overlapOps && packedOps && copyOutEarly && !tuned(Tune::NO_UNPACK_CREW) &&
+                if (overlapOps && copyOutEarly && !tuned(Tune::NO_UNPACK_CREW) &&
                     (nBatches > 1 ? opsFetched / (nBatches - 1) : opsCap / 4) >= (4 << 20)) {
                     try {
                         crew.reset(new unpack::Crew(7));

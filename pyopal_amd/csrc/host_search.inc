@@ -142,7 +142,7 @@ struct Search {
         a.score = d_score;
         a.endI = d_endI;
         a.endJ = d_endJ;
-        a.raisePriority = (on != stream && !tuned(Tune::NO_PRIORITY)) ? 1 : 0;
+        a.raisePriority = on != stream ? 1 : 0;
         // Pairs of several strips, scores / end locations: one wavefront per (pair, strip), the strips of
         // a pair side by side (intraseq.hip) - a pair is then a chain of L + 63 steps, not strips x that.
         // Worth it while the pairs are few against the chip (a chain is what is waited for); thousands of
@@ -176,12 +176,12 @@ struct Search {
             a.error = d_stripError;
             a.stripWaitCap = faultSpinCap;
             a.faultUnit1 = faultKind == 2 ? faultUnit + 1 : 0;
-            a.fatBlocks = besidePersistent && !tuned(Tune::THIN_SIDE) ? 1 : 0;
+            a.fatBlocks = besidePersistent ? 1 : 0;
             HIP_TRY(launchIntraseqStrips(a, on));
             return 0;
         }
         // pairs of one strip without the stop rule or direction bytes: two columns a step (intraseq_wide_kernel, round 4)
-        bool wide = !trace && !tuned(Tune::NO_WIDE_PAIRS);
+        bool wide = !trace;
         for (const auto& j : jobs)
             if (j.qLen > kLanes || (j.rules & kRuleStop)) wide = false;
         a.wide = wide ? 1 : 0;
@@ -275,18 +275,14 @@ struct Search {
             const int64_t strips = ((int64_t)Q + kLanes - 1) / kLanes;
             const int64_t residues = db->offsets[(size_t)end] - db->offsets[(size_t)start];
             const int64_t steps = strips * (residues + (int64_t)(kLanes - 1) * n);
-            if (const char* asked = tuned(Tune::SMALL_STEPS)) {
-                small = steps <= atoll(asked);   // (a plain bound on the steps instead of the estimate)
-            } else {
-                const double perPair = 0.075 + std::max((double)steps / 7e6, (double)(db->maxLen + kLanes * strips) * 0.00025);
-                // (round 4: ... and the packed kernels sweep the longest target column by column, about 0.3 us each with
-                // the strips of a group pipelined over a workgroup: a thousand log-normal targets at Q = 65 .. 300 took
-                // 0.6 - 1.1 ms packed and 0.43 - 0.53 ms one wavefront per pair, profiles/r04e_routing_table.txt)
-                // (queries up to ~500 residues: beyond, the strips kernels run a group's strips side by side and the packed
-                // side wins again - a thousand targets at Q = 1000: 1.4 ms packed, 1.75 one wavefront per pair)
-                const double packed = 0.26 + 0.0006 * (double)Q + (Q <= 512 ? 0.0003 * (double)db->maxLen : 0.0);
-                small = perPair < packed;
-            }
+            const double perPair = 0.075 + std::max((double)steps / 7e6, (double)(db->maxLen + kLanes * strips) * 0.00025);
+            // (round 4: ... and the packed kernels sweep the longest target column by column, about 0.3 us each with
+            // the strips of a group pipelined over a workgroup: a thousand log-normal targets at Q = 65 .. 300 took
+            // 0.6 - 1.1 ms packed and 0.43 - 0.53 ms one wavefront per pair, profiles/r04e_routing_table.txt)
+            // (queries up to ~500 residues: beyond, the strips kernels run a group's strips side by side and the packed
+            // side wins again - a thousand targets at Q = 1000: 1.4 ms packed, 1.75 one wavefront per pair)
+            const double packed = 0.26 + 0.0006 * (double)Q + (Q <= 512 ? 0.0003 * (double)db->maxLen : 0.0);
+            small = perPair < packed;
         }
         if (!interseqUsable() || (small && smallSearchAllowed(db))) {
             g_lastRouting[0] = n;
@@ -305,15 +301,14 @@ struct Search {
         // target has to leave the packed kernel for the 14x dearer wavefront-per-pair kernel.
         // (The aligned pairs are bounded by the query itself: every residue is aligned at most once, at best with
         // its most favourable partner - 280 for the 53-aa README query under BLOSUM62, where Q * max(S) says 583:
-        // windows that overlap by 384 columns instead of 640. MIOPAL_LOOSE_REACH=1: the bound of before.)
+        // windows that overlap by 384 columns instead of 640.)
         int64_t queryBest = 0;
         for (int i = 0; i < Q; ++i) {
             int rowMax = 0;
             for (int t = 0; t < A; ++t) rowMax = std::max(rowMax, matrix[query[i] * A + t]);
             queryBest += rowMax;
         }
-        const int64_t pairsBest = tuned(Tune::LOOSE_REACH) ? (int64_t)Q * std::max(maxScore, 0)
-                                                               : std::min<int64_t>((int64_t)Q * std::max(maxScore, 0), queryBest);
+        const int64_t pairsBest = std::min<int64_t>((int64_t)Q * std::max(maxScore, 0), queryBest);
         int overlap = 0;
         if (mode == OPAL_MODE_SW && std::min(open, ext) > 0 && maxScore > 0 && (int64_t)Q * maxScore < (1 << 23) &&
             Q < 65536 && db->maxLen < (1 << 24) && !tuned(Tune::NO_SEGMENTS)) {
@@ -330,9 +325,7 @@ struct Search {
             // with windows wherever the new bound allows them: 172 cells up, 42 down).
             const int64_t looseReach = Q + (int64_t)Q * maxScore / std::min(open, ext) + 1;
             const int64_t looseRounded = (looseReach + 127) / 128 * 128;
-            const bool cut = tuned(Tune::WINDOWS_WHENEVER_POSSIBLE)
-                                 ? true
-                                 : looseRounded <= 2048 && db->maxLen > segmentStride((int)looseRounded) + looseRounded;
+            const bool cut = looseRounded <= 2048 && db->maxLen > segmentStride((int)looseRounded) + looseRounded;
             if (cut && rounded <= 2048 && db->maxLen > segmentStride((int)rounded) + rounded) overlap = (int)rounded;
         }
         // HW (the whole query, free ends in the target) can be cut the same way. Its optimum is at least
@@ -350,9 +343,7 @@ struct Search {
             const int64_t lowest = 2 * (int64_t)open + ((int64_t)Q + rounded + 8) * ext + (int64_t)Q * std::max(0, -minScore);
             const int64_t looseGaps = ((int64_t)Q * std::max(maxScore, 0) + open + ((int64_t)Q - 1) * ext) / std::min(open, ext);
             const int64_t looseRounded = (Q + looseGaps + 1 + 127) / 128 * 128;
-            const bool cut = tuned(Tune::WINDOWS_WHENEVER_POSSIBLE)
-                                 ? true
-                                 : looseRounded <= 2048 && db->maxLen > segmentStride((int)looseRounded) + looseRounded;
+            const bool cut = looseRounded <= 2048 && db->maxLen > segmentStride((int)looseRounded) + looseRounded;
             if (cut && rounded <= 2048 && db->maxLen > segmentStride((int)rounded) + rounded && lowest < (1 << 21)) {
                 overlap = (int)rounded;
                 keyBias = 1 << 22;   // scores above -2^22 in the key's 24-bit score field
@@ -365,7 +356,7 @@ struct Search {
         // targets thirty times as long as the rest: 5.3 TCUPS for Smith-Waterman at Q = 53 where NW, which
         // cannot cut them, ran at 9.6 - a window may be as long as 1.5 balanced shares of a wavefront slot.
         int stride = overlap > 0 ? segmentStride(overlap) : 0;
-        if (overlap > 0 && !tuned(Tune::SHORT_STRIDE)) {
+        if (overlap > 0) {
             const double share = db->count > 0 ? (double)n / (double)db->count : 1.0;
             const double balancedColumns = (double)db->total * share / ((double)kGroupTargets * 12.0 * db->computeUnits);
             const int64_t want = (int64_t)(1.5 * balancedColumns) - overlap;
@@ -636,10 +627,6 @@ struct Search {
             };
             if (cutView == view.get()) {
                 firstGroup = cutFirstGroup;
-            } else if (const char* asked = tuned(Tune::SKIP_SHARES)) {   // (experiments: one fixed multiple)
-                firstGroup = cutAt(std::max(0.1, atof(asked)));
-            } else if (tuned(Tune::ALWAYS_SKIP)) {
-                firstGroup = cutAt(2.5);
             } else {
                 double bestCost = estimate(0);
                 firstGroup = 0;
@@ -686,7 +673,7 @@ struct Search {
             // packed launch: up to 64 leading targets more than a quarter longer than the longest of the next
             // group go there, and the first group stops at the longest target that stays.
             if ((sw || globalStrips) && overlap == 0 && Q > kLanes && view->nPacked - firstPos > 2 * kGroupTargets &&
-                !tuned(Tune::NO_SIDE_STREAM) && !tuned(Tune::NO_SKIM)) {
+                !tuned(Tune::NO_SIDE_STREAM)) {
                 const int ref = dbLen(db, view->ids[firstPos + kGroupTargets]);
                 int k = 0;
                 while (k < 64 && (int64_t)dbLen(db, view->ids[firstPos + k]) * 4 > (int64_t)ref * 5 + 1024) ++k;
@@ -805,8 +792,7 @@ struct Search {
                                                 2 * (int64_t)ext + c < 0x7C00;
                     };
                     if (c >= 0 && (int64_t)minScore + ext + open >= 0 &&
-                        0x0400 + below + 64 <= kUnsignedDiagZero &&   // real cells stay above the padding cells' floor
-                        !tuned(Tune::NO_UNSIGNED_DIAG)) {
+                        0x0400 + below + 64 <= kUnsignedDiagZero) {   // real cells stay above the padding cells' floor
                         const int firstU = firstThat(firstFit, fitsUnsigned);
                         if (firstU >= 0) {
                             firstFit = firstU;
@@ -866,31 +852,24 @@ struct Search {
             // The side kernel is handed to its stream BEFORE the packed launch: its wavefronts are dispatched
             // first, over the whole chip, and the persistent packed workgroups (one per CU, every register of
             // it) start on a CU when its side wavefronts are done. (Handed over after the packed launch the
-            // side kernel only finds the CUs the launch left out: cfg4 with its tail, 8 CUs: 54 against 44 ms,
-            // MIOPAL_PACKED_FIRST.) Beside a strips kernel the side units come in workgroups of 16 wavefronts,
+            // side kernel only finds the CUs the launch left out: cfg4 with its tail, 8 CUs: 54 against 44 ms.)
+            // Beside a strips kernel the side units come in workgroups of 16 wavefronts,
             // so that they hold few CUs (launchIntraseqStrips), and the packed launch takes EVERY CU: the
             // workgroups that start late simply take fewer units.
-            bool sidePending = false;
-            auto enqueueSide = [&]() -> int {
-                RC_TRY(runPairs(sideJobs, false, d_score, d_endI, d_endJ, nullptr, ws->aux, kAuxJobs - kJobs));
-                HIP_TRY(hipEventRecord(ws->evJoin, ws->aux));
-                for (const PairJob& j : sideJobs) sideDone.push_back(j.out);
-                std::sort(sideDone.begin(), sideDone.end());
-                sideJobs.clear();
-                sidePending = false;
-                sideForked = true;   // (a score pass that starts over still joins what is on the side stream)
-                spt.mark("    side jobs enqueued");
-                return 0;
-            };
             if (!sideJobs.empty() && !tuned(Tune::NO_SIDE_STREAM)) {
                 RC_TRY(ws->ensureAux());
                 RC_TRY(ensurePairInputs());
                 HIP_TRY(hipEventRecord(ws->evFork, stream));
                 HIP_TRY(hipStreamWaitEvent(ws->aux, ws->evFork, 0));
                 forked = true;
-                sidePending = true;
                 besidePersistent = pairStrips;
-                if (!tuned(Tune::PACKED_FIRST)) RC_TRY(enqueueSide());
+                RC_TRY(runPairs(sideJobs, false, d_score, d_endI, d_endJ, nullptr, ws->aux, kAuxJobs - kJobs));
+                HIP_TRY(hipEventRecord(ws->evJoin, ws->aux));
+                for (const PairJob& j : sideJobs) sideDone.push_back(j.out);
+                std::sort(sideDone.begin(), sideDone.end());
+                sideJobs.clear();
+                sideForked = true;   // (a score pass that starts over still joins what is on the side stream)
+                spt.mark("    side jobs enqueued");
             }
             void *pp, *vs, *vo, *ct;
             RC_TRY(ws->get(kProfile, prof.size() * sizeof(int16_t), &pp));
@@ -913,8 +892,7 @@ struct Search {
             // kernel fills about 1e12 cells a second, the next rung 5e12 .. 8e12 over the WHOLE view - an eighth
             // of the view's targets costs the same either way (round 3; it was 2048 whatever the size: 0.3 % of
             // 1M x 300 beyond the row keys' 384 at Q = 1000 sent the other 99.7 % through a second launch)
-            const int64_t directLimit = tuned(Tune::FIXED_DIRECT_LIMIT) ? kMaxDirectRecompute
-                                        : std::max<int64_t>(kMaxDirectRecompute, (view->nPacked - packedSkip) / 8);
+            const int64_t directLimit = std::max<int64_t>(kMaxDirectRecompute, (view->nPacked - packedSkip) / 8);
             if (mayOverflow) HIP_TRY(hipMemsetAsync(ct, 0, sizeof(int32_t), stream));
             InterseqArgs ia{};
             ia.pack = view->d_pack;
@@ -950,7 +928,7 @@ struct Search {
             ia.boundaryOff = view->d_boundaryOff;
             ia.capGroups = capGroups;
             ia.capChunks = capChunks;
-            ia.priorityChunks = tuned(Tune::NO_PRIORITY) ? INT32_MAX : (int)std::min<int64_t>(std::max<int64_t>(balancedChunks, 16), INT32_MAX);
+            ia.priorityChunks = (int)std::min<int64_t>(std::max<int64_t>(balancedChunks, 16), INT32_MAX);
             if ((nStrips + waves - 1) / waves > 1) {
                 void *b0, *b1;
                 const size_t bytes = (size_t)view->totalChunks * 4 * kLanes * sizeof(uint2);
@@ -1016,18 +994,14 @@ struct Search {
                 int pairUnits = db->computeUnits;
                 if (const int keep = reservedCus(db); keep >= 0)
                     pairUnits = std::max(1, pairUnits - keep);
-                else if (forked && tuned(Tune::STRIPS_RESERVE))
-                    // (round 2 kept CUs out of the launch for the side kernel, one per 256 pairs, at least 8;
-                    // the units are taken dynamically, so a workgroup whose CU is busy with side wavefronts
-                    // at first just starts later and takes fewer)
-                    pairUnits = std::max(1, pairUnits - (int)std::min<int64_t>(pairUnits / 4, std::max<int64_t>(8, (g_lastRouting[0] + 255) / 256)));
+                // (no CUs are kept out of the launch for the side kernel, as round 2 did: the units are taken
+                // dynamically, so a workgroup whose CU is busy with side wavefronts at first just starts later
+                // and takes fewer)
                 const PairFlavour stripsFlavour = globalStrips ? kPairGlobalStrips : kPairSwStrips;
                 g_lastRouting[1] = 2 + (int)stripsFlavour;
                 // few (group, strip) units: fewer groups per workgroup, so that every CU gets a unit and a
                 // wavefront shares its SIMD with fewer others
                 ia.batchGroups = (int)std::max<int64_t>(1, std::min<int64_t>(12, (int64_t)ia.nGroups * nStrips / std::max(1, pairUnits)));
-                if (const char* bg = tuned(Tune::BATCH_GROUPS))   // experiments
-                    ia.batchGroups = std::max(1, std::min(12, atoi(bg)));
                 // (diagnostic builds of the kernels, -DMIOPAL_STRIP_TIMING=1: their six counters, printed below)
                 unsigned long long* stripTiming = nullptr;
                 if (tuned(Tune::STRIP_TIMING)) {
@@ -1075,7 +1049,6 @@ struct Search {
                 if (pe == hipSuccess)
                     pe = tuned(Tune::TEST_REFUSE_PAIR_LAUNCH) ? hipErrorInvalidValue
                                                               : launchInterseqPair(ia, rows, stripsFlavour, pairUnits, stream, rowKeys);
-                if (pe == hipSuccess && sidePending) RC_TRY(enqueueSide());
                 if (pe == hipSuccess && stripTiming) {
                     unsigned long long t[8] = {};
                     HIP_TRY(hipMemcpyAsync(t, stripTiming, sizeof t, hipMemcpyDeviceToHost, stream));

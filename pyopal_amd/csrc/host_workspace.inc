@@ -77,7 +77,7 @@ inline void range(uint8_t* out, const uint8_t* packed, int64_t from, int64_t to)
     if (haveVbmi() && to - p >= 64) {
         // (large shares into a buffer whose lines start on multiples of four operations: one by one up to the next
         // 64-byte line of `out`, then whole lines with non-temporal stores)
-        const bool stream = to - p >= (1 << 20) && (reinterpret_cast<uintptr_t>(out) & 3) == 0 && !tuned(Tune::NO_STREAM_STORES);
+        const bool stream = to - p >= (1 << 20) && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
         if (stream)
             for (; (reinterpret_cast<uintptr_t>(out + p) & 63) != 0; ++p) out[p] = (packed[p >> 2] >> (2 * (p & 3))) & 3u;
         const int64_t n64 = (to - p) / 64;
@@ -265,7 +265,7 @@ inline void streamLines(uint8_t*, const uint8_t*, size_t) {}
 inline bool haveAvx512() { return false; }
 #endif
 inline void copyLarge(void* dst, const void* src, size_t bytes) {
-    if (bytes < (256u << 10) || !haveAvx512() || tuned(Tune::NO_STREAM_STORES)) {
+    if (bytes < (256u << 10) || !haveAvx512()) {
         memcpy(dst, src, bytes);
         return;
     }

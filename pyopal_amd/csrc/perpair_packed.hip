@@ -35,7 +35,6 @@
 //
 // Model and tie-breaks: oracle/opal_oracle.c (rules 5-7).
 #include "common.h"
-#include "tuning.h"
 
 #include <type_traits>
 
@@ -955,10 +954,8 @@ hipError_t launchPerPairPackedScan(const PerPairArgs& a, size_t ldsBytes, hipStr
     if (a.startQ != nullptr && (!a.startT || !a.startChecks)) return hipErrorInvalidValue;
     PerPairArgs b = a;
     if (b.refillLanes <= 0) b.refillLanes = 24;
-    if (const char* e = tuned(Tune::SCAN_REFILL_LANES)) b.refillLanes = std::min(128, std::max(1, atoi(e)));   // (experiments)
     // persistent wavefronts: two per SIMD, three when the strip has up to 56 rows (167 registers)
-    int perCu = a.queryLength <= 56 && a.scanLastRow == 0 ? 3 : 2;   // (HW, OV: their extra registers leave room for two)
-    if (const char* e = tuned(Tune::SCAN_BLOCKS_PER_CU)) perCu = std::max(1, std::min(atoi(e), 8));   // (experiments)
+    const int perCu = a.queryLength <= 56 && a.scanLastRow == 0 ? 3 : 2;   // (HW, OV: their extra registers leave room for two)
     const int blocks = std::min((waves + kScanWaves - 1) / kScanWaves, a.computeUnits * perCu);
     switch ((a.queryLength + 7) / 8) {
         case 1: return launchPackedScanAs<1>(b, ldsBytes, blocks, stream);

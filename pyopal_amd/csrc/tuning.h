@@ -12,17 +12,17 @@
 namespace miopal {
 
 #define MIOPAL_TUNING_SWITCHES(X)                                                                          \
-    X(ALWAYS_SKIP) X(BATCH_GROUPS) X(DEVICE) X(FIXED_DIRECT_LIMIT) X(FORCE_LANE_PER_PAIR) X(HOST_THREADS)  \
-    X(HOST_TRACEBACK) X(LOOSE_REACH) X(NO_BIASED) X(NO_CALLER_PINNED) X(NO_DEFERRED_RESULTS)               \
-    X(NO_DIAG_SHIFT) X(NO_DIRECT_SCATTER) X(NO_GLOBAL_STRIPS) X(NO_HOST_SCATTER) X(NO_HUGEPAGE)            \
-    X(NO_HYBRID_TRACE) X(NO_OPS_OVERLAP) X(NO_PAIR_STRIPS) X(NO_PAIR_STRIP_UNITS) X(NO_PAIR_TABLE)         \
-    X(NO_PERPAIR) X(NO_PERPAIR_PROFILE) X(NO_PRIORITY) X(NO_SCAN_REFILL) X(NO_SEGMENTS) X(NO_SIDE_STREAM)  \
-    X(NO_SKIM) X(NO_SMALL_SEARCH) X(NO_SW_SHIFT) X(NO_TWO_PASS_ENDS) X(NO_UNSIGNED_DIAG)                   \
-    X(NO_VIEW_PREFETCH) X(PACKED_FIRST) X(PAIR_STRIPS) X(PHASE_TIMING) X(RESERVE_CUS) X(RUNTIME_COPY)      \
-    X(SCAN_BLOCKS_PER_CU) X(SCAN_REFILL_LANES) X(SHORT_STRIDE) X(SMALL_STEPS) X(SPARE_HANDLE_MB)           \
-    X(STRIPS) X(STRIPS_RESERVE) X(TAIL_THROTTLE) X(THIN_SIDE) X(TWO_PASS_ENDS) X(UNITS)                    \
-    X(UPLOAD_PIECE_KB) X(UPLOAD_STREAMS) X(UPLOAD_THREADS) X(VERBOSE) X(VIEW_CACHE_MB)                     \
-    X(WINDOWS_WHENEVER_POSSIBLE) X(TEST_REFUSE_PAIR_LAUNCH) X(NO_PACKED_OPS) X(STRIP_TIMING) X(SKIP_SHARES) X(SEARCH_UNDER_UPLOAD) X(NO_WIDE_PAIRS) X(NO_SIDE_COPIES) X(NO_EARLY_HOST_SHARE) X(NO_UNPACK_CREW) X(NO_STREAM_STORES) X(NO_PACKED_TRACE) X(NO_PACKED_SCAN) X(NO_ONE_LAUNCH) X(ONE_LAUNCH_GROUP) X(NO_ASYNC_SHARES) X(NO_LATE_RESULT_COPIES) X(PARKED_WORKSPACE_MB) X(NO_SORT_BY_ROWS) X(NO_JOBS_AHEAD) X(NO_SCAN_ORDER) X(NO_PACKED_HW_SCAN)
+    X(DEVICE) X(FORCE_LANE_PER_PAIR) X(HOST_THREADS) X(HOST_TRACEBACK) X(NO_ASYNC_SHARES) X(NO_BIASED)     \
+    X(NO_CALLER_PINNED) X(NO_DIAG_SHIFT) X(NO_DIRECT_SCATTER) X(NO_EARLY_HOST_SHARE) X(NO_GLOBAL_STRIPS)   \
+    X(NO_HOST_SCATTER) X(NO_HUGEPAGE) X(NO_HYBRID_TRACE) X(NO_JOBS_AHEAD) X(NO_ONE_LAUNCH)                 \
+    X(NO_PACKED_HW_SCAN) X(NO_PACKED_SCAN) X(NO_PACKED_TRACE) X(NO_PAIR_STRIPS) X(NO_PAIR_STRIP_UNITS)     \
+    X(NO_PAIR_TABLE) X(NO_PERPAIR) X(NO_PERPAIR_PROFILE) X(NO_SCAN_ORDER) X(NO_SCAN_REFILL)                \
+    X(NO_SEGMENTS) X(NO_SIDE_COPIES) X(NO_SIDE_STREAM) X(NO_SMALL_SEARCH) X(NO_SORT_BY_ROWS)               \
+    X(NO_SW_SHIFT) X(NO_TWO_PASS_ENDS) X(NO_UNPACK_CREW) X(NO_VIEW_PREFETCH) X(ONE_LAUNCH_GROUP)           \
+    X(PAIR_STRIPS) X(PARKED_WORKSPACE_MB) X(PHASE_TIMING) X(RESERVE_CUS) X(SEARCH_UNDER_UPLOAD)            \
+    X(SPARE_HANDLE_MB) X(STRIPS) X(STRIP_TIMING) X(TAIL_THROTTLE) X(TEST_REFUSE_PAIR_LAUNCH)               \
+    X(TWO_PASS_ENDS) X(UNITS) X(UPLOAD_PIECE_KB) X(UPLOAD_STREAMS) X(UPLOAD_THREADS) X(VERBOSE)            \
+    X(VIEW_CACHE_MB)
 
 enum class Tune : int {
 #define X(name) name,

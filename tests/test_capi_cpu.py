@@ -117,6 +117,8 @@ def test_tuning_switches_are_arguments_not_environment(capi, monkeypatch):
     assert capi.get_tuning("NO_BIASED") is None and capi.get_tuning("NO_SMALL_SEARCH") == "1"
     assert capi.lib().miopalSetTuning(b"NO_SUCH_SWITCH", b"1") == 101
     assert "unknown tuning switch" in capi.last_error()
+    # (a retired A/B lever is refused like any other unknown name, not silently ignored)
+    assert capi.lib().miopalSetTuning(b"THIN_SIDE", b"1") == 101 and "unknown tuning switch" in capi.last_error()
     assert capi.lib().miopalDbSetOption(None, b"reserve_cus", 8) == 101
     # every switch of the table is documented by name in tuning.h and none is read with getenv elsewhere
     src = os.path.join(ROOT, "pyopal_amd", "csrc")

@@ -18,4 +18,4 @@ for mode in ("score", "end"):
     t = time.perf_counter()
     for _ in range(5): db.search(q, m, 3, 1, mode, "nw")
     nk, kms = db.last_kernel_time()
-    print(mode, f"{(time.perf_counter()-t)/5*1e3:.2f} ms", f"kernel {kms/max(nk,1):.2f} ms x{nk}", _capi.DeviceDatabase.last_routing(), os.environ.get("MIOPAL_UNITS"), os.environ.get("MIOPAL_NO_UNSIGNED_DIAG"))
+    print(mode, f"{(time.perf_counter()-t)/5*1e3:.2f} ms", f"kernel {kms/max(nk,1):.2f} ms x{nk}", _capi.DeviceDatabase.last_routing(), os.environ.get("MIOPAL_UNITS"))

@@ -1,6 +1,5 @@
 """Scratch: skewed-length databases (log-normal, the bench's extras.lognormal_lengths database; bimodal) at one query
-length: wall time, TCUPS and routing per algorithm, over the multiples of the balanced share beyond which leading
-groups leave the packed launch (MIOPAL_SKIP_SHARES). usage: quick_skewed.py [Q] [N] [dist]"""
+length: wall time, TCUPS and routing per algorithm. usage: quick_skewed.py [Q] [N] [dist]"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,19 +21,11 @@ db = _capi.DeviceDatabase(res, off, 24)
 q = _data.README_QUERY if Q == 53 else None
 q = _data.encode(q) if q else _data.random_protein(rng, Q)
 cells = float(len(q)) * float(off[-1])
-shares = [None] + [s for s in os.environ.get("QS_SHARES", "1.0,1.5,2.0,3.5,5.0,100").split(",") if s]
-want = {}
 for algo in os.environ.get("QS_ALGOS", "sw,nw,hw,ov").split(","):
-    for sh in shares:
-        _capi.set_tuning("SKIP_SHARES", sh)
-        r = db.search(q, m, 3, 1, "score", algo)
-        if algo not in want:
-            want[algo] = r["score"].copy()
-        assert np.array_equal(r["score"], want[algo]), (algo, sh)
-        ts = []
-        for _ in range(5):
-            t = time.perf_counter(); db.search(q, m, 3, 1, "score", algo); ts.append(time.perf_counter() - t)
-        dt = min(ts)
-        print(f"{dist} N={n} Q={len(q)} {algo} shares={sh or 'default':>7}: {dt*1e3:7.3f} ms {cells/dt/1e12:6.2f} TCUPS routing {_capi.DeviceDatabase.last_routing()}", flush=True)
-_capi.set_tuning("SKIP_SHARES", None)
+    db.search(q, m, 3, 1, "score", algo)
+    ts = []
+    for _ in range(5):
+        t = time.perf_counter(); db.search(q, m, 3, 1, "score", algo); ts.append(time.perf_counter() - t)
+    dt = min(ts)
+    print(f"{dist} N={n} Q={len(q)} {algo}: {dt*1e3:7.3f} ms {cells/dt/1e12:6.2f} TCUPS routing {_capi.DeviceDatabase.last_routing()}", flush=True)
 db.close()
