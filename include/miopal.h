@@ -344,6 +344,22 @@ int miopalDbSetOption(MiopalDb* db, const char* name, int64_t value);
  */
 int miopalTestSetLogicalDevices(int count);
 
+/*
+ * Test hook: the device top-k selection of miopalSearchTop / miopalSearchBatchTop alone, on rows of int32 scores the
+ * caller supplies (any int32 values), with no search and no handle in front of it. score, and endTarget / endQuery
+ * (both or neither), are host arrays [rows][stride]; entry i of a row has the index start + i. The rows are uploaded
+ * to device 0, selected by the production kernels exactly as a search's rows are (order, minScore, count and the -1
+ * of the slots past the count: miopalSearchTop's), and the outputs downloaded: count[rows], the others [rows][k]
+ * (outEndTarget / outEndQuery may be NULL without end arrays). *gaveUp receives the number of blocks that gave up
+ * waiting for the blocks before them (0 unless the device is broken; a search turns it into MIOPAL_ERR_INTERNAL).
+ * MIOPAL_ERR_BAD_ARGUMENT, before any device call: rows < 1, stride < 1, k outside [1, MIOPAL_MAX_TOP], a null
+ * input or output, one end array without the other, rows x stride above 2^27.
+ */
+int miopalTestSelectTop(const int* score, const int* endTarget, const int* endQuery,
+                        int rows, int64_t stride, int k, int minScore, int64_t start,
+                        int* count, int64_t* targetIndex, int* outScore, int* outEndTarget, int* outEndQuery,
+                        int* gaveUp);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,7 +53,7 @@ EXPORTS = [
     "miopalAlignPairs", "miopalLastPairRouting",
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
     # test hooks
-    "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices",
+    "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
 ]
 
 
@@ -131,6 +131,9 @@ def lib() -> ctypes.CDLL:
         L.miopalSearchBatchTop.restype = c_int
         L.miopalSearchBatchTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                            c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.miopalTestSelectTop.restype = c_int
+        L.miopalTestSelectTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_i64,
+                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.miopalAlignPairs.restype = c_int
         L.miopalAlignPairs.argtypes = [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_int,
                                        c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp]
@@ -224,6 +227,42 @@ class tuning:
 
 def _ptr(a: typing.Optional[np.ndarray]):
     return None if a is None else a.ctypes.data
+
+
+def select_top_rows(score: np.ndarray, k: int, min_score: typing.Optional[int] = None,
+                    end_q: typing.Optional[np.ndarray] = None, end_t: typing.Optional[np.ndarray] = None,
+                    start: int = 0) -> typing.Dict[str, typing.Any]:
+    """miopalTestSelectTop (test hook): the device top-k selection alone on the rows of ``score`` (int32,
+    (rows, stride); a 1-D array is one row), with ``end_q`` / ``end_t`` of the same shape beside them (both or
+    neither). Returns search_batch_top's dict - "count" (rows,), "target" (int64, ``start`` + index), "score" and, with
+    end arrays, "end_t" / "end_q", of shape (rows, k), best first, -1 past the count - plus "gave_up", the number of
+    blocks that gave up waiting for the blocks before them (0). The C side checks the arguments."""
+    score = np.ascontiguousarray(score, dtype=np.int32)
+    if score.ndim == 1:
+        score = score[None, :]
+    if score.ndim != 2:
+        raise ValueError("score must have shape (rows, stride)")
+    rows, stride = score.shape
+    ends = []
+    for e in (end_q, end_t):
+        if e is not None:
+            e = np.ascontiguousarray(e, dtype=np.int32).reshape(-1, e.shape[-1])
+            if e.shape != score.shape:
+                raise ValueError("end arrays must have the shape of score")
+        ends.append(e)
+    shape = (rows, max(k, 0))
+    out = {"count": np.zeros(rows, dtype=np.int32), "target": np.empty(shape, dtype=np.int64),
+           "score": np.empty(shape, dtype=np.int32)}
+    if ends[0] is not None or ends[1] is not None:
+        out.update(end_t=np.empty(shape, dtype=np.int32), end_q=np.empty(shape, dtype=np.int32))
+    gave_up = ctypes.c_int(-1)
+    rc = lib().miopalTestSelectTop(_ptr(score), _ptr(ends[1]), _ptr(ends[0]), rows, stride, k,
+                                   -(2 ** 31) if min_score is None else min_score, start, _ptr(out["count"]),
+                                   _ptr(out["target"]), _ptr(out["score"]), _ptr(out.get("end_t")),
+                                   _ptr(out.get("end_q")), ctypes.byref(gave_up))
+    raise_for(rc)
+    out["gave_up"] = int(gave_up.value)
+    return out
 
 
 class _MallocBytes:

@@ -693,6 +693,15 @@ int miopalSearchBatchTop(MiopalDb* db, const unsigned char* queries, const int64
     });
 }
 
+int miopalTestSelectTop(const int* score, const int* endTarget, const int* endQuery, int rows, int64_t stride, int k,
+                        int minScore, int64_t start, int* count, int64_t* targetIndex, int* outScore, int* outEndTarget,
+                        int* outEndQuery, int* gaveUp) {
+    return guarded([&]() -> int {
+    return testSelectTopImpl(score, endTarget, endQuery, rows, stride, k, minScore, start, count, targetIndex, outScore,
+                             outEndTarget, outEndQuery, gaveUp);
+    });
+}
+
 int miopalAlignPairs(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
                      const int32_t* pairQuery, const int64_t* pairTarget, int64_t nPairs, int gapOpen, int gapExt,
                      const int* scoreMatrix, int alphabetLength, int searchType, int mode, int* score, int* endTarget,

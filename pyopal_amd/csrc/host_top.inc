@@ -30,48 +30,75 @@ static void emptyTopRows(int from, int to, int k, int* count, int64_t* targetInd
     }
 }
 
+// One device slot of a selection: [error, count[rows]] [target] [score] ([endQuery] [endTarget]) | the selection's
+// scratch. The outputs in front of the scratch come back in one download.
+struct TopSlot {
+    size_t offTarget, offScore, offEndQ, offEndT, outBytes, rk;
+    int rows;
+    bool ends;
+    TopSlot(int rows_, int k, bool ends_) : rk((size_t)rows_ * k), rows(rows_), ends(ends_) {
+        auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        offTarget = a256(sizeof(int) * ((size_t)rows + 1));
+        offScore = offTarget + a256(sizeof(int64_t) * rk);
+        offEndQ = offScore + a256(sizeof(int) * rk);
+        offEndT = offEndQ + (ends ? a256(sizeof(int) * rk) : 0);
+        outBytes = offEndT + (ends ? a256(sizeof(int) * rk) : 0);
+    }
+    size_t bytes(int64_t n, int k) const { return outBytes + topScratchBytes(rows, n, k); }
+    // the selection's arguments for the slot at `base` (its error counter is zeroed by the caller)
+    TopArgs args(char* base, const int32_t* d_score, const int32_t* d_endI, const int32_t* d_endJ, int64_t n, int k,
+                 int minScore, int64_t start) const {
+        TopArgs a{};
+        a.score = d_score;
+        a.endI = d_endI;
+        a.endJ = d_endJ;
+        a.stride = n;
+        a.rows = rows;
+        a.k = k;
+        a.minScore = minScore;
+        a.start = start;
+        a.scratch = base + outBytes;
+        a.error = (int*)base;
+        a.count = (int32_t*)base + 1;
+        a.target = (int64_t*)(base + offTarget);
+        a.outScore = (int32_t*)(base + offScore);
+        a.outEndQ = ends ? (int32_t*)(base + offEndQ) : nullptr;
+        a.outEndT = ends ? (int32_t*)(base + offEndT) : nullptr;
+        return a;
+    }
+    // the downloaded outputs -> the caller's arrays (row 0 of the selection at their row 0); returns the error counter
+    int unpack(const char* host, int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery) const {
+        int error;
+        memcpy(&error, host, sizeof(int));
+        memcpy(count, host + sizeof(int), sizeof(int) * (size_t)rows);
+        memcpy(targetIndex, host + offTarget, sizeof(int64_t) * rk);
+        memcpy(score, host + offScore, sizeof(int) * rk);
+        if (ends) {
+            memcpy(endQuery, host + offEndQ, sizeof(int) * rk);
+            memcpy(endTarget, host + offEndT, sizeof(int) * rk);
+        }
+        return error;
+    }
+};
+
 // The selection on `rows` device rows of n scores (and end locations), enqueued on the workspace's stream behind
 // what produced them, and ONE download of the [rows] counts and [rows][k] entries into the caller's arrays, which
 // hold row 0 of the selection at their row `outRow`. `s`: the search whose strip error is checked with it (or null).
 static int selectTopRows(Workspace* ws, Search* s, const int32_t* d_score, const int32_t* d_endI,
                          const int32_t* d_endJ, int rows, int64_t n, int64_t start, int k, int minScore, int64_t outRow,
                          int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery) {
-    const bool ends = d_endI != nullptr;
-    const size_t rk = (size_t)rows * k;
-    auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // one slot: [error, count[rows]] [target] [score] ([endQuery] [endTarget]) | the selection's scratch
-    const size_t offTarget = a256(sizeof(int) * ((size_t)rows + 1));
-    const size_t offScore = offTarget + a256(sizeof(int64_t) * rk);
-    const size_t offEndQ = offScore + a256(sizeof(int) * rk);
-    const size_t offEndT = offEndQ + (ends ? a256(sizeof(int) * rk) : 0);
-    const size_t outBytes = offEndT + (ends ? a256(sizeof(int) * rk) : 0);
+    const TopSlot slot(rows, k, d_endI != nullptr);
     void* p;
-    RC_TRY(ws->get(kTopScratch, outBytes + topScratchBytes(rows, n, k), &p));
+    RC_TRY(ws->get(kTopScratch, slot.bytes(n, k), &p));
     char* base = (char*)p;
     HIP_TRY(hipMemsetAsync(base, 0, sizeof(int), ws->stream));
-    TopArgs a{};
-    a.score = d_score;
-    a.endI = d_endI;
-    a.endJ = d_endJ;
-    a.stride = n;
-    a.rows = rows;
-    a.k = k;
-    a.minScore = minScore;
-    a.start = start;
-    a.scratch = base + outBytes;
-    a.error = (int*)base;
-    a.count = (int32_t*)base + 1;
-    a.target = (int64_t*)(base + offTarget);
-    a.outScore = (int32_t*)(base + offScore);
-    a.outEndQ = ends ? (int32_t*)(base + offEndQ) : nullptr;
-    a.outEndT = ends ? (int32_t*)(base + offEndT) : nullptr;
-    const hipError_t e = launchSelectTop(a, ws->stream);
+    const hipError_t e = launchSelectTop(slot.args(base, d_score, d_endI, d_endJ, n, k, minScore, start), ws->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(MIOPAL_ERR_HIP, "top-k selection launch: %s", hipGetErrorString(e));
     }
-    std::vector<char> host(outBytes);
-    RC_TRY(ws->stageDownload(host.data(), base, outBytes));
+    std::vector<char> host(slot.outBytes);
+    RC_TRY(ws->stageDownload(host.data(), base, slot.outBytes));
     if (s && s->d_stripError) RC_TRY(ws->stageDownload(&s->stripErrorHost, s->d_stripError, sizeof(int)));
     RC_TRY(ws->finishDownloads());
     if (s) RC_TRY(s->checkStripError());
@@ -79,13 +106,8 @@ static int selectTopRows(Workspace* ws, Search* s, const int32_t* d_score, const
     memcpy(&error, host.data(), sizeof(int));
     if (error) return fail(MIOPAL_ERR_INTERNAL, "top-k selection: %d blocks gave up waiting for the blocks before them", error);
     const size_t at = (size_t)outRow * k;
-    memcpy(count + outRow, host.data() + sizeof(int), sizeof(int) * (size_t)rows);
-    memcpy(targetIndex + at, host.data() + offTarget, sizeof(int64_t) * rk);
-    memcpy(score + at, host.data() + offScore, sizeof(int) * rk);
-    if (ends) {
-        memcpy(endQuery + at, host.data() + offEndQ, sizeof(int) * rk);
-        memcpy(endTarget + at, host.data() + offEndT, sizeof(int) * rk);
-    }
+    slot.unpack(host.data(), count + outRow, targetIndex + at, score + at, slot.ends ? endTarget + at : nullptr,
+                slot.ends ? endQuery + at : nullptr);
     return 0;
 }
 
@@ -152,4 +174,74 @@ static int searchBatchTopImpl(MiopalDb* db, const unsigned char* queries, const 
                              endTarget, endQuery);
     };
     return batchImpl(db, queries, queryOffsets, nQueries, open, ext, matrix, A, searchType, mode, start, end, sink);
+}
+
+// miopalTestSelectTop (test hook): the selection alone, on rows the caller supplies - launchSelectTop as selectTopRows
+// calls it (the same TopArgs, scratch from topScratchBytes, one stream), with no search and no handle in front of
+// it, so that a test can build a row for every arm of the five kernels. Device 0.
+namespace {
+struct DeviceBytes {
+    void* p = nullptr;
+    DeviceBytes() = default;
+    DeviceBytes(const DeviceBytes&) = delete;
+    DeviceBytes& operator=(const DeviceBytes&) = delete;
+    ~DeviceBytes() {
+        if (p) (void)hipFree(p);
+    }
+};
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream&) = delete;
+    OwnedStream& operator=(const OwnedStream&) = delete;
+    ~OwnedStream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+}  // namespace
+
+static int testSelectTopImpl(const int* score, const int* endTarget, const int* endQuery, int rows, int64_t stride, int k,
+                             int minScore, int64_t start, int* count, int64_t* targetIndex, int* outScore,
+                             int* outEndTarget, int* outEndQuery, int* gaveUp) {
+    constexpr int64_t kMaxEntries = (int64_t)1 << 27;
+    if (rows < 1 || stride < 1) return fail(MIOPAL_ERR_BAD_ARGUMENT, "rows = %d, stride = %lld: both at least 1", rows, (long long)stride);
+    if (k < 1 || k > MIOPAL_MAX_TOP) return fail(MIOPAL_ERR_BAD_ARGUMENT, "k = %d outside [1, %d]", k, MIOPAL_MAX_TOP);
+    if (!score) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null score rows");
+    if ((endTarget == nullptr) != (endQuery == nullptr)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "one end array without the other");
+    const bool ends = endTarget != nullptr;
+    if (!count || !targetIndex || !outScore || !gaveUp) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null count / target / score / gaveUp outputs");
+    if (ends && (!outEndTarget || !outEndQuery)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null end-location outputs");
+    if (stride > kMaxEntries || rows > kMaxEntries / stride)
+        return fail(MIOPAL_ERR_BAD_ARGUMENT, "%d rows x %lld entries: more than 2^27", rows, (long long)stride);
+    if (physicalDeviceCount() < 1) return fail(OPAL_ERR_NO_SIMD_SUPPORT, "no usable gfx950 device");
+    HIP_TRY(hipSetDevice(usableDevices()[0]));
+
+    const size_t inBytes = sizeof(int32_t) * (size_t)rows * (size_t)stride;
+    const TopSlot slot(rows, k, ends);
+    DeviceBytes dScore, dEndI, dEndJ, dOut;
+    OwnedStream stream;
+    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(hipMalloc(&dScore.p, inBytes));
+    HIP_TRY(hipMalloc(&dOut.p, slot.bytes(stride, k)));
+    HIP_TRY(hipMemcpyAsync(dScore.p, score, inBytes, hipMemcpyHostToDevice, stream.s));
+    if (ends) {
+        HIP_TRY(hipMalloc(&dEndI.p, inBytes));
+        HIP_TRY(hipMalloc(&dEndJ.p, inBytes));
+        HIP_TRY(hipMemcpyAsync(dEndI.p, endQuery, inBytes, hipMemcpyHostToDevice, stream.s));
+        HIP_TRY(hipMemcpyAsync(dEndJ.p, endTarget, inBytes, hipMemcpyHostToDevice, stream.s));
+    }
+    char* base = (char*)dOut.p;
+    HIP_TRY(hipMemsetAsync(base, 0, sizeof(int), stream.s));
+    const TopArgs a = slot.args(base, (const int32_t*)dScore.p, (const int32_t*)dEndI.p, (const int32_t*)dEndJ.p, stride, k,
+                                minScore, start);
+    const hipError_t e = launchSelectTop(a, stream.s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MIOPAL_ERR_HIP, "top-k selection launch: %s", hipGetErrorString(e));
+    }
+    std::vector<char> host(slot.outBytes);
+    HIP_TRY(hipMemcpyAsync(host.data(), base, slot.outBytes, hipMemcpyDeviceToHost, stream.s));
+    HIP_TRY(hipStreamSynchronize(stream.s));
+    *gaveUp = slot.unpack(host.data(), count, targetIndex, outScore, outEndTarget, outEndQuery);
+    return 0;
 }

@@ -6,7 +6,8 @@
 //               minScore), max]; when the range spans 4096 or more, the bin that holds the k-th entry is
 //               counted again, 12 bits finer, by the next round. A row that is settled skips the later rounds.
 //               Result per row: threshold T and tieTake - every entry > T is chosen, and the first tieTake
-//               entries == T in index order.
+//               entries == T in index order. (When every entry of the range is chosen, T = lo - 1 and no ties;
+//               a range that starts at INT_MIN has no such T and takes its entries == INT_MIN as ties instead.)
 //   C  gather   every (row, block) counts its entries > T and == T, takes its offsets from a single-pass
 //               scan over the row's blocks in the order they started (look-back), and writes its chosen
 //               entries as (score, index) keys: at most k candidates per row, at fixed places.
@@ -247,10 +248,29 @@ __global__ __launch_bounds__(kTopThreads) void top_scan_kernel(TopArgs a, Scratc
     if (total <= (unsigned)need) {
         // every entry of the range is chosen
         if (threadIdx.x == 0) {
-            t.T = lo - 1;
-            t.tieTake = 0;
-            t.count = above + (int)total;
-            t.active = 0;
+            if (lo > INT_MIN) {
+                t.T = lo - 1;
+                t.tieTake = 0;
+                t.count = above + (int)total;
+                t.active = 0;
+            } else if (sh == 0) {
+                // (no int below INT_MIN: the entries equal to lo - bin 0, this thread's - are taken as ties)
+                t.T = lo;
+                t.tieTake = (int)mine[0];
+                t.count = above + (int)total;
+                t.active = 0;
+            } else {
+                // ... and while bin 0 is wider than one score, the next round counts it again with all of it to
+                // choose, which ends here with a smaller shift (0 in the last round)
+                const int64_t top = (int64_t)lo + ((int64_t)1 << sh) - 1;
+                const int64_t nhi = top < hi ? top : (int64_t)hi;
+                t.lo = lo;
+                t.hi = (int)nhi;
+                t.shift = shiftFor(nhi - lo);
+                t.need = (int)mine[0];
+                t.above = above + (int)(total - mine[0]);
+                t.active = 1;
+            }
         }
         return;
     }

@@ -96,3 +96,17 @@ def test_pair_table_kernels_keep_three_wavefronts_per_simd():
     low = {n: k for n, k in pair.items()
            if k.get("Occupancy [waves/SIMD]", 0) < (2 if "pair_global" in n else 3)}
     assert not low, low
+
+
+def test_selection_kernels_do_not_spill():
+    # select_top.hip: five memory-bound kernels; the gather holds a block's 16 scores per thread in registers
+    # between its count and its write, so a spill there is a fourth read of the row
+    ks = kernels()
+    if not ks:
+        pytest.skip("no resource remarks: build with make -C pyopal_amd/csrc")
+    top = {n: k for n, k in ks.items() if k["file"] == "select_top.rpt"}
+    for kernel in ("top_range_kernel", "top_hist_kernel", "top_scan_kernel", "top_gather_kernel", "top_sort_kernel"):
+        assert any(kernel in n for n in top), (kernel, sorted(top))
+    bad = {n: k for n, k in top.items()
+           if k.get("VGPRs Spill", 0) or k.get("SGPRs Spill", 0) or k.get("ScratchSize [bytes/lane]", 0)}
+    assert not bad, bad

@@ -300,3 +300,90 @@ def test_reference_examples(capi, vid):
     known = [(s, -i) for i, s in enumerate(v["score"]) if s is not None]
     if len(known) == len(v["score"]):
         assert best.score == max(known)[0]
+
+
+# ---- arms of the selection that the searches above do not reach (tests/test_gpu_select_rows.py drives the same arms on
+# synthetic rows): a second group of 1024 rows, the third histogram round, rows of more than 2^20 entries ----
+
+@pytest.mark.parametrize("algo", ["sw", "hw"])
+@pytest.mark.parametrize("mode", ["score", "end"])
+def test_batch_above_one_group_of_rows(capi, algo, mode):
+    """1100 queries in ONE chunk of the batch: the selection takes its rows in groups of 1024, so rows 1024.. come
+    from its second sequence of launches."""
+    rng = np.random.default_rng(1100)
+    res, off = _data.random_db(rng, rng.integers(20, 201, size=300))
+    db = capi.DeviceDatabase(res, off, 24)
+    lengths = [BOUNDARY_LENGTHS[i % len(BOUNDARY_LENGTHS)] for i in range(1100)]
+    for at, length in ((5, 65), (700, 0), (1023, 65), (1024, 0), (1030, 65), (1099, 0)):   # the single-query path
+        lengths[at] = length
+    queries = [_data.random_protein(rng, L) for L in lengths]
+    got = db.search_batch_top(queries, B62, 3, 1, mode, algo, k=20)
+    routing = db.last_batch_routing()
+    full = db.search_batch(queries, B62, 3, 1, mode, algo)
+    assert routing == db.last_batch_routing()
+    # which lengths the batch kernels take under this model (a 64-row class does not fit their LDS table with 24 letters)
+    single = set()
+    for length in sorted(set(lengths)):
+        db.search_batch([queries[lengths.index(length)]], B62, 3, 1, mode, algo)
+        if db.last_batch_routing()[2]:
+            single.add(length)
+    assert {0, 65} <= single and not single & set(BOUNDARY_LENGTHS[:17])
+    batch = sum(length not in single for length in lengths)
+    assert sum(length not in single for length in lengths[1024:]) >= 50
+    # every pair of the batch queries settled by the batch kernels or by their int32 pass, and in ONE chunk: as many
+    # launches of the batch kernels (one per class of query rows and chunk) as for 21 queries that hold every length
+    assert routing[2] == len(queries) - batch and routing[0] > 0 and routing[0] + routing[1] == batch * 300
+    assert lengths[21:42] == BOUNDARY_LENGTHS
+    db.search_batch(queries[21:42], B62, 3, 1, mode, algo)
+    assert db.last_batch_routing()[3] == routing[3]
+    for i in range(len(queries)):
+        row = {key: got[key][i] for key in got}
+        check_top(row, {key: full[key][i] for key in full}, 0, 20, mode)
+    db.close()
+
+
+def test_three_histogram_rounds_through_a_search(db_set):
+    """NW with gaps of 600 against a 35 000-residue target: the scores span more than 2^24, which takes all three
+    histogram rounds (12 + 12 + 8 bits)."""
+    db, res, off = db_set
+    query = _data.encode(_data.README_QUERY)
+    full = db.search(query, B62, 600, 600, "score", "nw")
+    assert int(full["score"].max()) - int(full["score"].min()) >= 2 ** 24
+    for k in (1, 50, 4096):
+        check_top(db.search_top(query, B62, 600, 600, "score", "nw", k=k), full, 0, k, "score")
+    ms = int(np.sort(full["score"])[len(full["score"]) // 2])
+    for k in (50, 4096):
+        check_top(db.search_top(query, B62, 600, 600, "score", "nw", k=k, min_score=ms), full, 0, k, "score", ms)
+    ends = db.search(query, B62, 600, 600, "end", "nw")
+    check_top(db.search_top(query, B62, 600, 600, "end", "nw", k=50), ends, 0, 50, "end")
+
+
+@pytest.fixture(scope="module")
+def long_short_db(capi):
+    """short_db's recipe with 1 100 000 targets: rows of 269 blocks of 4096 scores (68 of 16 384)."""
+    rng = np.random.default_rng(55)
+    allowed = np.array([i for i, c in enumerate(_data.NCBI[:20]) if c not in "WYF"], dtype=np.uint8)
+    lengths = rng.integers(3, 9, size=1_100_000)
+    off = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=off[1:])
+    res = allowed[rng.integers(0, len(allowed), size=int(off[-1]))]
+    w = _data.NCBI.index("W")
+    for t in (17, 123_456, 500_001, 999_990, 1_050_000, 1_099_999):
+        res[off[t] + 1] = w
+    db = capi.DeviceDatabase(res, off, 24)
+    yield db, res, off
+    db.close()
+
+
+def test_rows_of_more_than_a_million_entries(long_short_db):
+    db, res, off = long_short_db
+    query = np.array([_data.NCBI.index("W")], dtype=np.uint8)
+    full = db.search(query, B62, 3, 1, "end", "sw")
+    assert np.count_nonzero(full["score"] == 0) > 1_000_000 and np.count_nonzero(full["score"] > 0) >= 6
+    for k in (1, 5, 4096):
+        check_top(db.search_top(query, B62, 3, 1, "end", "sw", k=k), full, 0, k, "end")
+    # a slice of more than 2^20 targets that does not start on a 16-byte boundary
+    start, end = 3, 1_080_000
+    sub = db.search(query, B62, 3, 1, "end", "sw", start, end)
+    for k in (5, 4096):
+        check_top(db.search_top(query, B62, 3, 1, "end", "sw", start, end, k=k), sub, start, k, "end")
