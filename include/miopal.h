@@ -118,6 +118,38 @@ int miopalSearchFlat(MiopalDb* db, const unsigned char* query, int queryLength, 
                      unsigned char** operations, int64_t* operationOffsets);
 
 /*
+ * miopalSearchFlat with a position-specific scoring matrix (PSSM) in the place of (query, scoreMatrix):
+ * rowScores[i * alphabetLength + t] is the score of aligning query position i with target residue t
+ * (queryLength rows, row-major). gapOpen / gapExt, searchType, mode, the slice and every output as in
+ * miopalSearchFlat. For rowScores[i][t] = scoreMatrix[query[i]][t] and consensus = query every output
+ * equals miopalSearchFlat's, and the search takes the same kernels (miopalLastRouting /
+ * miopalLastFullRouting report it like any other) - with one exception, in OPAL_SEARCH_ALIGNMENT only: when the
+ * scores miss the byte profile of the lane-per-pair kernels (an entry + gapOpen outside [-127, 127]) AND
+ * (queryLength + 1) * (alphabetLength + 1) * 4 bytes exceed 64 KB less 256 (more than 493 rows at 32 letters, 651
+ * at 24), the start-cell scan and the direction pass run one wavefront per pair where the plain search keeps one
+ * lane per pair up to 4096 residues: the row-indexed lane-per-pair kernel holds all rows in LDS. Results are the
+ * same; those two passes are slower.
+ * consensus: queryLength residues (< alphabetLength, or 255 = "no residue, never a match"). Only used
+ * by OPAL_SEARCH_ALIGNMENT to tell OPAL_ALIGN_MATCH from OPAL_ALIGN_MISMATCH (position i matches target
+ * residue t iff consensus[i] == t); required there, may be NULL for the other search types.
+ * Checked before any device call, with miopalSearch's codes - first what needs no handle (mode and
+ * search type, queryLength < 0, NULL rowScores with queryLength > 0, the alphabet length's range, NULL
+ * consensus for an alignment search, a consensus entry that is neither a residue nor 255), then the
+ * handle, the alphabet length against it, the slice, and miopalSearch's 32-bit range check with the
+ * extreme entries of the rows where the matrix's stand (OPAL_ERR_OVERFLOW). An empty slice returns 0
+ * with nothing launched. Thread safety as miopalSearch.
+ * Where the scores leave the ranges of the profile-driven kernels, the 32-bit kernels stage the rows of
+ * the strip at hand in LDS instead of the matrix ("Position-specific scoring matrices").
+ * Out of scope: PSSM forms of miopalSearchBatch, miopalSearchTop, miopalSearchBatchTop and
+ * miopalAlignPairs, of opalSearchDatabase and of the multi-GPU shard driver; and building a PSSM from
+ * an alignment (pseudocounts, background frequencies) - the caller brings the numbers.
+ */
+int miopalSearchPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
+                     int gapOpen, int gapExt, int alphabetLength, int searchType, int mode,
+                     int64_t start, int64_t end, int* score, int* endTarget, int* endQuery,
+                     int* startTarget, int* startQuery, unsigned char** operations, int64_t* operationOffsets);
+
+/*
  * miopalSearchFlat with the operations written into a buffer the caller lends.
  * In: *operations is NULL, or a malloc'ed buffer of *operationsCapacity bytes
  * (the one an earlier call returned, its contents no longer needed). Out:

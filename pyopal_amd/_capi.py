@@ -47,7 +47,7 @@ EXPORTS = [
     # miopal.h
     "miopalDeviceCount", "miopalLastError", "miopalDbCreate", "miopalDbCreateFlat", "miopalDbCreateSubset",
     "miopalDbDestroy", "miopalDbCount", "miopalDbTotalLength", "miopalDbDeviceBytes",
-    "miopalSearch", "miopalSearchFlat", "miopalSearchFlatInto", "miopalSearchDeviceScores", "miopalSetProfiling", "miopalLastKernelTime",
+    "miopalSearch", "miopalSearchFlat", "miopalSearchFlatInto", "miopalSearchPssm", "miopalSearchDeviceScores", "miopalSetProfiling", "miopalLastKernelTime",
     "miopalLastRouting", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
     "miopalSearchBatch", "miopalLastBatchRouting", "miopalSearchTop", "miopalSearchBatchTop",
     "miopalAlignPairs", "miopalLastPairRouting",
@@ -143,6 +143,10 @@ def lib() -> ctypes.CDLL:
         L.miopalLastBatchRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
         L.miopalSearchFlat.restype = c_int
         L.miopalSearchFlat.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                       c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       ctypes.POINTER(c_vp), c_vp]
+        L.miopalSearchPssm.restype = c_int
+        L.miopalSearchPssm.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        ctypes.POINTER(c_vp), c_vp]
         L.miopalSearchFlatInto.restype = c_int
@@ -388,9 +392,20 @@ class DeviceDatabase:
         operations of a 300-residue query). An operations buffer that is too small stays with the earlier
         result, untouched."""
         end = self.count if end is None else min(end, self.count)
-        n = max(end - start, 0)
         q = np.ascontiguousarray(query, dtype=np.uint8)
         S = np.ascontiguousarray(matrix, dtype=np.int32)
+
+        def call(st, score, et, eq, s_t, s_q, ops_ptr, ops_cap, aoff):
+            return lib().miopalSearchFlatInto(self._h, _ptr(q), len(q), gap_open, gap_extend, _ptr(S),
+                                              self.alphabet_length, st, MODE[algorithm], start, end,
+                                              score, et, eq, s_t, s_q, ctypes.byref(ops_ptr), ctypes.byref(ops_cap), aoff)
+        return self._flat_search(call, mode, max(end - start, 0), score_out, reuse)
+
+    def _flat_search(self, call, mode, n, score_out=None, reuse=None) -> typing.Dict[str, typing.Any]:
+        """The outputs of one flat search (`search`, `search_pssm`): the per-target arrays - fresh, or an earlier
+        result's written again (``reuse``) - the C call, and the ownership of the operations buffer it returns or
+        wrote in place. ``call(search type, score, end_t, end_q, start_t, start_q, ops_ptr, ops_cap, offsets)``
+        makes the C call with these output pointers and returns its code."""
         st = SEARCH[mode]
         if score_out is not None and (score_out.dtype != np.int32 or score_out.shape != (n,) or
                                       not score_out.flags.c_contiguous):
@@ -422,10 +437,7 @@ class DeviceDatabase:
             s_t = array("start_t", n, np.int32)
             s_q = array("start_q", n, np.int32)
             aoff = array("aln_off", n + 1, np.int64, zeros=True)
-        rc = lib().miopalSearchFlatInto(self._h, _ptr(q), len(q), gap_open, gap_extend, _ptr(S),
-                                        self.alphabet_length, st, MODE[algorithm], start, end,
-                                        _ptr(out["score"]), _ptr(et), _ptr(eq), _ptr(s_t), _ptr(s_q),
-                                        ctypes.byref(ops_ptr), ctypes.byref(ops_cap), _ptr(aoff))
+        rc = call(st, _ptr(out["score"]), _ptr(et), _ptr(eq), _ptr(s_t), _ptr(s_q), ops_ptr, ops_cap, _ptr(aoff))
         raise_for(rc)
         if st >= 1:
             out.update(end_t=et, end_q=eq)
@@ -446,6 +458,32 @@ class DeviceDatabase:
             out.update(start_t=s_t, start_q=s_q, aln_flat=flat, aln_off=aoff,
                        aln=_LazyAlignments(flat, aoff), _ops_owner=owner)
         return out
+
+    def search_pssm(self, row_scores: np.ndarray, consensus: typing.Optional[np.ndarray] = None, gap_open: int = 3,
+                    gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
+                    end: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+        """miopalSearchPssm: `search` with a position-specific scoring matrix in the place of (query, matrix).
+        ``row_scores``: integers of shape (query length, alphabet length), entry [i, t] the score of query position
+        i against target residue t. ``consensus``: one residue per position (or 255, "never a match"); only mode
+        "full" reads it, to tell matches from mismatches, and requires it. Returns `search`'s dict."""
+        end = self.count if end is None else min(end, self.count)
+        n = max(end - start, 0)
+        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
+        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
+            raise ValueError(f"row_scores must have shape (query length, {self.alphabet_length})")
+        cons = None
+        if consensus is not None:
+            cons = np.ascontiguousarray(consensus, dtype=np.uint8).ravel()
+            if len(cons) != len(rows):
+                raise ValueError("consensus must have one entry per row of row_scores")
+
+        def call(st, score, et, eq, s_t, s_q, ops_ptr, ops_cap, aoff):
+            # (no lending form of this entry point: nothing is reused, the operations come in a buffer of their own)
+            return lib().miopalSearchPssm(self._h, _ptr(rows) if len(rows) else None,
+                                          _ptr(cons) if cons is not None and len(cons) else None, len(rows), gap_open,
+                                          gap_extend, self.alphabet_length, st, MODE[algorithm], start, end,
+                                          score, et, eq, s_t, s_q, ctypes.byref(ops_ptr), aoff)
+        return self._flat_search(call, mode, n)
 
     def search_batch(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
                      gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,

@@ -160,6 +160,9 @@ struct IntraseqArgs {
     int stripWaitCap;         // polls before a unit gives up on the strip above; 0 = the default
     int faultUnit1;           // test hook: unit (this - 1) publishes nothing; 0 = none
     int wide;                 // every job is a pair of one strip without the stop rule: intraseq_wide_kernel (two columns a step)
+    // position-specific scoring matrix (miopalSearchPssm): [query positions][A] scores, row job.qOff + i * job.qStep is
+    // the pair's row i; the kernels' row-indexed forms stage a strip's 64 rows per wavefront. null: matrix[query[.]]
+    const int32_t* rows;
 };
 
 struct WalkArgs {
@@ -240,6 +243,9 @@ struct PerPairArgs {
     const int32_t* fwdEndT;
     const int64_t* fwdOffsets;
     const int* order;         // ... taken in this order (null: 0, 1, 2, ...): the persistent scan, longest prefixes first
+    // position-specific scoring matrix (miopalSearchPssm): [queryLength][A] scores by query position, in the place of
+    // matrix[query[.]] wherever a profile is filled (scoreAt); null: the plain search
+    const int32_t* rows;
 };
 hipError_t launchPerPair(const PerPairArgs& a, int mode, hipStream_t stream);
 // perpair_packed.hip: the direction pass with two pairs per lane. packedTraceFits says whether it applies (rows /
@@ -262,6 +268,9 @@ inline int perPairProfileStride(int queryLength) {
 }
 // LDS bytes of the profile kernel for this query (0: too long for it), and the stride to pass
 size_t perPairProfileBytes(int queryLength, int alphabet, int* stride);
+// LDS bytes of perpair_kernel's row-indexed form (a.rows != null) for this many rows; 0: the table does not fit, the
+// wavefront-per-pair kernel takes such a search's passes
+size_t perPairPssmBytes(int queryLength, int alphabet);
 
 struct PackArgs {
     const uint8_t* residues;
@@ -470,6 +479,12 @@ static __device__ __forceinline__ int stripPoll(const int* counter) {
     const int v = __hip_atomic_load(const_cast<int*>(counter), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // (the rows are fetched after the counter)
     return __builtin_amdgcn_readfirstlane(v);
+}
+
+// Score of query position y against residue t: the matrix row of the query's residue or, with a position-specific
+// scoring matrix (rows != null), row y itself. What the profile fills of the lane-per-pair kernels read.
+static __device__ __forceinline__ int scoreAt(const int* matrix, const uint8_t* query, const int32_t* rows, int A, int y, int t) {
+    return rows ? rows[y * A + t] : matrix[(int)query[y] * A + t];
 }
 
 inline int packRules(const DpRules& r) {

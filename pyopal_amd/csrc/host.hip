@@ -749,6 +749,64 @@ int miopalSearchFlat(MiopalDb* db, const unsigned char* query, int queryLength, 
     });
 }
 
+// miopalSearchFlat with a position-specific scoring matrix as the score source (include/miopal.h). The order of the
+// checks is deliberate and part of the header's contract: what needs no handle first, then the null handle, then what
+// depends on the handle (miopalAlignPairs' order; miopalSearch looks at the handle first). The codes are
+// miopalSearch's; only which error is reported when several arguments are bad differs. A caller without a device -
+// it cannot hold a handle - is still told what is wrong with its PSSM. None of the checks touches a device.
+int miopalSearchPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
+                     int gapOpen, int gapExt, int alphabetLength, int searchType, int mode,
+                     int64_t start, int64_t end, int* score, int* endTarget, int* endQuery,
+                     int* startTarget, int* startQuery, unsigned char** operations, int64_t* operationOffsets) {
+    return guarded([&]() -> int {
+    const int Q = queryLength, A = alphabetLength;
+    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
+    if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
+    if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
+    if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
+    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    const bool full = searchType == OPAL_SEARCH_ALIGNMENT;
+    if (full && Q > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
+    if (consensus)
+        for (int i = 0; i < Q; ++i)
+            if (consensus[i] >= A && consensus[i] != 255)
+                return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %d", consensus[i], i);
+    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
+    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
+    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
+    if (full && !operations) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null alignment outputs");
+    if (operations) *operations = nullptr;
+    if (end == start) return 0;
+    {
+        // miopalSearch's range check for its 32-bit kernels, with the extreme entries of the rows
+        Search probe{db, nullptr, nullptr, nullptr, Q, gapOpen, gapExt, A, searchType, mode, nullptr, start, end, end - start};
+        if (Q > 0) {
+            probe.maxScore = *std::max_element(rowScores, rowScores + (size_t)Q * A);
+            probe.minScore = *std::min_element(rowScores, rowScores + (size_t)Q * A);
+        }
+        RC_TRY(probe.checkInt32(db->maxLen));
+    }
+    // (without a consensus - score and end searches - every position is "no residue": the kernels never read it)
+    std::vector<unsigned char> none;
+    if (!consensus) {
+        none.assign((size_t)std::max(Q, 1), 255);
+        consensus = none.data();
+    }
+    // (no rows: an empty query has no scores; the score source still says "position-specific")
+    static const int kNoRows[1] = {0};
+    HostBytes ops;
+    RC_TRY(searchImpl(db, consensus, Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, score, endTarget,
+                      endQuery, startTarget, startQuery, nullptr, nullptr, full ? &ops : nullptr,
+                      full ? operationOffsets : nullptr, Q > 0 ? rowScores : kNoRows));
+    if (full) {
+        if (!ops.data && !ops.resize(0)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+        *operations = ops.release();
+    }
+    return 0;
+    });
+}
+
 int miopalSearchFlatInto(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                          const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                          int64_t end, int* score, int* endTarget, int* endQuery, int* startTarget,

@@ -3,8 +3,10 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                       const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                       int64_t end, int* score, int* endTarget, int* endQuery, int* startTarget,
                       int* startQuery, unsigned char** alignment, int* alignmentLength,
-                      HostBytes* flatOps, int64_t* flatOff) {
-    RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, searchType, mode, start, end));
+                      HostBytes* flatOps, int64_t* flatOff, const int* pssmRows = nullptr) {
+    // (pssmRows, miopalSearchPssm: the score source is [queryLength][alphabetLength] rows, scoreMatrix is null, `query`
+    // the consensus; its caller has made miopalSearch's checks on them)
+    if (!pssmRows) RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, searchType, mode, start, end));
     const int64_t n = end - start;
     if (n == 0) return 0;
     if (!score) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null score output");
@@ -22,6 +24,7 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
     hipStream_t stream = ws->stream;
     Search s{db, ws, stream, query, queryLength, gapOpen, gapExt, alphabetLength, searchType, mode,
              scoreMatrix, start, end, n};
+    s.pssmRows = pssmRows;
     RC_TRY(s.prepare());
     pt.mark("workspace + query");
 
@@ -172,14 +175,15 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
             void *rs = nullptr, *ri = nullptr, *rj = nullptr, *pjobs, *psq, *pst, *pmis, *plen, *pcompact, *pts;
             // one lane per pair (perpair.hip) instead of one wavefront per pair (intraseq.hip)
             // (it stages the query in LDS: up to 4096 residues; longer ones keep the wavefront-per-pair kernel)
-            const bool lanePerPair = queryLength <= 4096 && !tuned(Tune::NO_PERPAIR) &&
-                                     (n > kSmallSearch || !smallSearchAllowed(db));
+            bool lanePerPair = queryLength <= 4096 && !tuned(Tune::NO_PERPAIR) &&
+                               (n > kSmallSearch || !smallSearchAllowed(db));
             RC_TRY(s.ensurePairInputs());
             PerPairArgs perPair{};
             perPair.residues = db->d_residues;
             perPair.query = s.d_query;
             perPair.queryLength = queryLength;
             perPair.matrix = s.d_matrix;
+            perPair.rows = s.d_rows;
             perPair.alphabet = alphabetLength;
             perPair.gapOpen = gapOpen;
             perPair.gapExt = gapExt;
@@ -192,6 +196,9 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                                   gapExt >= 0 && (int64_t)db->maxLen * gapExt < (1 << 27) && db->total >= 4;
             perPair.residueCount = db->total;
             if (!profiled) profileStride = 0;
+            // (position-specific scores outside the byte profile: perpair_kernel's row-indexed form stages all the rows
+            // in LDS; more rows than fit keep the wavefront-per-pair kernel, as queries beyond 4096 residues do)
+            if (!profiled && pssmRows && perPairPssmBytes(queryLength, alphabetLength) == 0) lanePerPair = false;
             RC_TRY(ws->get(kJobs, (size_t)n * sizeof(PairJob), &pjobs));
             RC_TRY(ws->get(kStartQ, (size_t)n * sizeof(int32_t), &psq));
             RC_TRY(ws->get(kStartT, (size_t)n * sizeof(int32_t), &pst));
@@ -238,7 +245,7 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                     for (int y = 0; y < queryLength; ++y) {
                         int rowMax = 0;
                         for (int t = 0; t < alphabetLength; ++t)
-                            rowMax = std::max(rowMax, scoreMatrix[(int)query[y] * alphabetLength + t]);
+                            rowMax = std::max(rowMax, s.at(y, t));
                         queryBest += rowMax;
                     }
                     const int64_t best = std::min<int64_t>(queryBest, std::min<int64_t>(queryLength, db->maxLen) * std::max(s.maxScore, 0));

@@ -22,6 +22,12 @@ struct Search {
     const int* matrix;
     int64_t start, end;
     int64_t n;
+    // The score source. Plain searches: `matrix` ([A][A]) indexed by the query's residues. A position-specific
+    // scoring matrix (miopalSearchPssm): pssmRows ([Q][A], row i = the scores of query position i), `matrix` is null
+    // and `query` is the consensus (residues or 255), which only the traceback's match / mismatch test reads.
+    // Everything on the host reads scores through at(); the kernels take d_rows where they index by row.
+    const int* pssmRows = nullptr;
+    int at(int i, int t) const { return pssmRows ? pssmRows[(size_t)i * A + t] : matrix[query[i] * A + t]; }
     int maxScore = 0, minScore = 0;
     int64_t balancedChunks = 0;
     bool globalPairRefused = false;   // the pair-table launch for NW / HW / OV failed on this device
@@ -55,6 +61,7 @@ struct Search {
 
     uint8_t* d_query = nullptr;
     int32_t* d_matrix = nullptr;
+    int32_t* d_rows = nullptr;         // pssmRows on the device ([Q][A]); null for a plain search
 
     int rulesFor(int m, DpRules* r) const {
         switch (m) {
@@ -73,6 +80,12 @@ struct Search {
             faultSpinCap = g_fault[2];
             g_fault[0] = 0;
         }
+        if (pssmRows) {
+            // (the extreme entries of the rows where the matrix's stand; no rows: no scores, as for an empty query)
+            maxScore = Q > 0 ? *std::max_element(pssmRows, pssmRows + (size_t)Q * A) : 0;
+            minScore = Q > 0 ? *std::min_element(pssmRows, pssmRows + (size_t)Q * A) : 0;
+            return 0;
+        }
         maxScore = *std::max_element(matrix, matrix + A * A);
         minScore = *std::min_element(matrix, matrix + A * A);
         return 0;
@@ -84,9 +97,16 @@ struct Search {
         void* p;
         RC_TRY(ws->get(kQuery, (size_t)std::max(Q, 1), &p));
         d_query = (uint8_t*)p;
+        RC_TRY(ws->stageUpload(d_query, query, (size_t)Q, stream));
+        if (pssmRows) {
+            // (no [A][A] matrix: the kernels' row-indexed forms read the rows, the walk the consensus)
+            RC_TRY(ws->get(kPssmRows, std::max<size_t>((size_t)Q * A, 1) * sizeof(int32_t), &p));
+            d_rows = (int32_t*)p;
+            RC_TRY(ws->stageUpload(d_rows, pssmRows, (size_t)Q * A * sizeof(int32_t), stream));
+            return 0;
+        }
         RC_TRY(ws->get(kMatrix, (size_t)A * A * sizeof(int32_t), &p));
         d_matrix = (int32_t*)p;
-        RC_TRY(ws->stageUpload(d_query, query, (size_t)Q, stream));
         RC_TRY(ws->stageUpload(d_matrix, matrix, (size_t)A * A * sizeof(int32_t), stream));
         return 0;
     }
@@ -133,6 +153,7 @@ struct Search {
         a.residues = db->d_residues;
         a.query = d_query;
         a.matrix = d_matrix;
+        a.rows = d_rows;
         a.alphabet = A;
         a.gapOpen = open;
         a.gapExt = ext;
@@ -213,6 +234,7 @@ struct Search {
         a.residues = db->d_residues;
         a.query = d_query;
         a.matrix = d_matrix;
+        a.rows = d_rows;
         a.alphabet = A;
         a.gapOpen = open;
         a.gapExt = ext;
@@ -305,7 +327,7 @@ struct Search {
         int64_t queryBest = 0;
         for (int i = 0; i < Q; ++i) {
             int rowMax = 0;
-            for (int t = 0; t < A; ++t) rowMax = std::max(rowMax, matrix[query[i] * A + t]);
+            for (int t = 0; t < A; ++t) rowMax = std::max(rowMax, at(i, t));
             queryBest += rowMax;
         }
         const int64_t pairsBest = std::min<int64_t>((int64_t)Q * std::max(maxScore, 0), queryBest);
@@ -838,7 +860,7 @@ struct Search {
                                      : halfFloat ? (int16_t)0xFC00 : (int16_t)-32768;
             std::vector<int16_t> prof((size_t)nSym * qPad, padValue);
             for (int t = 0; t < A; ++t)
-                for (int i = 0; i < Q; ++i) prof[(size_t)t * qPad + i] = enc(matrix[query[i] * A + t] + profileShift);
+                for (int i = 0; i < Q; ++i) prof[(size_t)t * qPad + i] = enc(at(i, t) + profileShift);
             // targets kept out of the packed view (too long for one lane each) are computed by the
             // int32 kernel on a side stream BESIDE the packed kernel; packed targets that need
             // the int32 kernel are redone after it, because both write the same result slots

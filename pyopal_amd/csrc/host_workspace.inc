@@ -12,6 +12,7 @@ enum Slot {
     // and the lane-per-pair kernels' strip boundaries
     kPairListQ, kPairListT, kPairListTOff, kPairListQBase, kPairListQOff, kPairListBoundary,
     kTopScratch,   // miopalSearchTop / miopalSearchBatchTop: the selection's outputs and scratch (rows x (bins + blocks + k))
+    kPssmRows,     // miopalSearchPssm: the rows, [Q][A] ints
     kSlots
 };
 

@@ -21,6 +21,30 @@ constexpr int kNegInf = INT32_MIN / 4;
 constexpr int kJobsPerBlock = 4;
 constexpr int kMatStride = kMaxAlphabet + 1;  // odd stride: rows fall on different LDS banks
 
+// ---- the row-indexed forms (PSSM: a position-specific scoring matrix, miopalSearchPssm) -----------------------
+// The plain kernels stage the [A][A] matrix once per workgroup and a lane reads the matrix row of its query residue,
+// srow = smat + qres * kMatStride. With a.rows the score of row i is a.rows[i][.] - there is no residue to index a
+// shared table by - so every wavefront stages the 64 rows of the strip it is on, one row per lane, [64][kMatStride]
+// ints (8448 bytes per wavefront, the odd stride kept: the lanes' rows start on different banks), refilled per
+// strip. A lane writes and reads its own row only, so the fill needs no barrier, and the step loop is the plain one:
+// scCur = srow[tres] stays one ds_read_b32 fetched a step ahead of the chain. A template parameter, not a branch:
+// the plain instantiations are the code they were.
+constexpr int kPssmWaveInts = kLanes * kMatStride;
+
+// rows[row][0 .. A) -> the lane's LDS row (zeros for a lane beyond the pair's rows: nothing reads its cells)
+static __device__ __forceinline__ void stagePssmRow(int* mine, const int32_t* rows, int64_t row, int A, bool active) {
+    const int32_t* src = rows + row * A;
+    if ((A & 3) == 0) {
+        // (rows of whole 16-byte pieces: hipMalloc'ed base, A * 4 bytes a row)
+        for (int t = 0; t < A; t += 4) {
+            const int4 v = active ? *reinterpret_cast<const int4*>(src + t) : make_int4(0, 0, 0, 0);
+            mine[t] = v.x; mine[t + 1] = v.y; mine[t + 2] = v.z; mine[t + 3] = v.w;
+        }
+    } else {
+        for (int t = 0; t < A; ++t) mine[t] = active ? src[t] : 0;
+    }
+}
+
 // better(a, b): does candidate a replace b in the column-major, strictly-greater scan?
 static __device__ __forceinline__ bool better(int sa, int ja, int ia, int sb, int jb, int ib) {
     if (sa != sb) return sa > sb;
@@ -28,13 +52,15 @@ static __device__ __forceinline__ bool better(int sa, int ja, int ia, int sb, in
     return ia < ib;
 }
 
-template <bool TRACE>
+template <bool TRACE, bool PSSM = false>
 __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_kernel(IntraseqArgs a) {
-    __shared__ int smat[kMaxAlphabet * kMatStride];
+    __shared__ int smat[PSSM ? kJobsPerBlock * kPssmWaveInts : kMaxAlphabet * kMatStride];
     const int A = a.alphabet;
-    for (int idx = threadIdx.x; idx < A * A; idx += blockDim.x)
-        smat[(idx / A) * kMatStride + (idx % A)] = a.matrix[idx];
-    __syncthreads();
+    if constexpr (!PSSM) {
+        for (int idx = threadIdx.x; idx < A * A; idx += blockDim.x)
+            smat[(idx / A) * kMatStride + (idx % A)] = a.matrix[idx];
+        __syncthreads();
+    }
 
     // (readfirstlane tells the compiler what it cannot see: the wavefront index, and with it the
     // job and every loop bound derived from it, is uniform - scalar loads, scalar loop control)
@@ -68,12 +94,19 @@ __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_kernel(Intras
         const bool stopEnabled = (job.rules & kRuleStop) && nStrips == 1;
         const int stopScore = job.stop;
         const uint8_t* tptr = a.residues + job.tOff;
-        const uint8_t* qptr = a.query + job.qOff;
+        [[maybe_unused]] const uint8_t* qptr = a.query + job.qOff;
         for (int s = 0; s < nStrips; ++s) {
             const int i = s * kLanes + lane;
             const bool rowActive = i < Q;
-            const int qres = rowActive ? qptr[(int64_t)i * job.qStep] : 0;
-            const int* srow = smat + qres * kMatStride;
+            const int* srow;
+            if constexpr (PSSM) {
+                int* mine = smat + (wave * kLanes + lane) * kMatStride;
+                stagePssmRow(mine, a.rows, job.qOff + (int64_t)i * job.qStep, A, rowActive);
+                srow = mine;
+            } else {
+                const int qres = rowActive ? qptr[(int64_t)i * job.qStep] : 0;
+                srow = smat + qres * kMatStride;
+            }
             // Lane state. hLeft = H[i][j-1] doubles as the value handed to the row below (it is read
             // by wave_shr before this step overwrites it, i.e. as H[i][j-1] = H of the row above at
             // the reader's column); before a lane starts it holds the left border H[i][-1], which
@@ -248,13 +281,15 @@ __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_kernel(Intras
 // steps of ~1.4 x the work: scores (and, with LOC, end locations: the same first maximum in column-major order)
 // of forward or reversed jobs of one strip, every border rule and answer region, no stop rule, no direction
 // bytes - the side jobs of one-strip searches and small searches.
-template <bool LOC>
+template <bool LOC, bool PSSM = false>
 __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_wide_kernel(IntraseqArgs a) {
-    __shared__ int smat[kMaxAlphabet * kMatStride];
+    __shared__ int smat[PSSM ? kJobsPerBlock * kPssmWaveInts : kMaxAlphabet * kMatStride];
     const int A = a.alphabet;
-    for (int idx = threadIdx.x; idx < A * A; idx += blockDim.x)
-        smat[(idx / A) * kMatStride + (idx % A)] = a.matrix[idx];
-    __syncthreads();
+    if constexpr (!PSSM) {
+        for (int idx = threadIdx.x; idx < A * A; idx += blockDim.x)
+            smat[(idx / A) * kMatStride + (idx % A)] = a.matrix[idx];
+        __syncthreads();
+    }
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
     const int jobIdx = blockIdx.x * kJobsPerBlock + wave;
@@ -272,8 +307,15 @@ __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_wide_kernel(I
         const uint8_t* tptr = a.residues + job.tOff;
         const int i = lane;
         const bool rowActive = i < Q;
-        const int qres = rowActive ? a.query[job.qOff + (int64_t)i * job.qStep] : 0;
-        const int* srow = smat + qres * kMatStride;
+        const int* srow;
+        if constexpr (PSSM) {
+            int* mine = smat + (wave * kLanes + lane) * kMatStride;
+            stagePssmRow(mine, a.rows, job.qOff + (int64_t)i * job.qStep, A, rowActive);
+            srow = mine;
+        } else {
+            const int qres = rowActive ? a.query[job.qOff + (int64_t)i * job.qStep] : 0;
+            srow = smat + qres * kMatStride;
+        }
         int hLeft = leftGap ? borderGap(i, open, ext) : 0;                               // H[i][-1]
         int eLeft = kNegInf;
         int hDiag = (i == 0) ? 0 : (leftGap ? borderGap(i - 1, open, ext) : 0);          // H[i-1][-1]
@@ -393,12 +435,19 @@ __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_wide_kernel(I
 constexpr int kStripWaitCap = 1 << 22;   // x s_sleep 4: about two seconds, then the unit gives up (a.error)
 
 // (launched as workgroups of 4 wavefronts, or of 16 beside a persistent packed launch: see launchIntraseqStrips)
-__global__ __launch_bounds__(1024) void intraseq_strips_kernel(IntraseqArgs a) {
-    __shared__ int smat[kMaxAlphabet * kMatStride];
+// PSSM_WAVES: 0 = the plain form; else the row-indexed form for workgroups of that many wavefronts (its LDS is
+// sized by them: 33 KB for 4, 132 KB for 16 - a workgroup of 16 has a CU's LDS nearly to itself, as it has its
+// registers' share beside a persistent launch)
+template <int PSSM_WAVES = 0>
+__global__ __launch_bounds__(PSSM_WAVES ? PSSM_WAVES * kLanes : 1024) void intraseq_strips_kernel(IntraseqArgs a) {
+    constexpr bool PSSM = PSSM_WAVES > 0;
+    __shared__ int smat[PSSM ? PSSM_WAVES * kPssmWaveInts : kMaxAlphabet * kMatStride];
     const int A = a.alphabet;
-    for (int idx = threadIdx.x; idx < A * A; idx += blockDim.x)
-        smat[(idx / A) * kMatStride + (idx % A)] = a.matrix[idx];
-    __syncthreads();
+    if constexpr (!PSSM) {
+        for (int idx = threadIdx.x; idx < A * A; idx += blockDim.x)
+            smat[(idx / A) * kMatStride + (idx % A)] = a.matrix[idx];
+        __syncthreads();
+    }
     const int lane = threadIdx.x & 63;
     int unit = 0;
     if (lane == 0) unit = atomicAdd(a.stripCounter, 1);
@@ -432,12 +481,19 @@ __global__ __launch_bounds__(1024) void intraseq_strips_kernel(IntraseqArgs a) {
     const int region = (job.rules >> 4) & 3;
     const int open = a.gapOpen, ext = a.gapExt;
     const uint8_t* tptr = a.residues + job.tOff;
-    const uint8_t* qptr = a.query + job.qOff;
+    [[maybe_unused]] const uint8_t* qptr = a.query + job.qOff;
     const int jobStrips = (Q + kLanes - 1) / kLanes;
     const int i = s * kLanes + lane;
     const bool rowActive = i < Q;
-    const int qres = rowActive ? qptr[(int64_t)i * job.qStep] : 0;
-    const int* srow = smat + qres * kMatStride;
+    const int* srow;
+    if constexpr (PSSM) {
+        int* mine = smat + (int)threadIdx.x * kMatStride;   // (wavefront w, lane l: row w * 64 + l of the staged rows)
+        stagePssmRow(mine, a.rows, job.qOff + (int64_t)i * job.qStep, A, rowActive);
+        srow = mine;
+    } else {
+        const int qres = rowActive ? qptr[(int64_t)i * job.qStep] : 0;
+        srow = smat + qres * kMatStride;
+    }
     int hLeft = leftGap ? borderGap(i, open, ext) : 0;  // H[i][-1]
     int eLeft = kNegInf;
     int hDiag = (i == 0) ? 0 : (leftGap ? borderGap(i - 1, open, ext) : 0);  // H[i-1][-1]
@@ -1256,18 +1312,29 @@ hipError_t launchReverseJobs(int n, const int32_t* score, const int32_t* endQ, c
 hipError_t launchIntraseq(const IntraseqArgs& a, bool trace, hipStream_t stream) {
     if (a.nJobs <= 0) return hipSuccess;
     const int blocks = (a.nJobs + kJobsPerBlock - 1) / kJobsPerBlock;
+    const dim3 grid(blocks), block(kJobsPerBlock * kLanes);
+    const bool pssm = a.rows != nullptr;   // (the row-indexed forms: no [A][A] matrix, a.query is not read)
     if (a.wide && !trace && !a.headWaves) {
         // (the host has checked its jobs: one strip each, no stop rule)
-        if (a.endI || a.endJ)
-            hipLaunchKernelGGL((intraseq_wide_kernel<true>), dim3(blocks), dim3(kJobsPerBlock * kLanes), 0, stream, a);
-        else
-            hipLaunchKernelGGL((intraseq_wide_kernel<false>), dim3(blocks), dim3(kJobsPerBlock * kLanes), 0, stream, a);
+        const bool loc = a.endI || a.endJ;
+        if (pssm) {
+            if (loc) hipLaunchKernelGGL((intraseq_wide_kernel<true, true>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((intraseq_wide_kernel<false, true>), grid, block, 0, stream, a);
+        } else if (loc) {
+            hipLaunchKernelGGL((intraseq_wide_kernel<true>), grid, block, 0, stream, a);
+        } else {
+            hipLaunchKernelGGL((intraseq_wide_kernel<false>), grid, block, 0, stream, a);
+        }
         return hipGetLastError();
     }
-    if (trace)
-        hipLaunchKernelGGL((intraseq_kernel<true>), dim3(blocks), dim3(kJobsPerBlock * kLanes), 0, stream, a);
-    else
-        hipLaunchKernelGGL((intraseq_kernel<false>), dim3(blocks), dim3(kJobsPerBlock * kLanes), 0, stream, a);
+    if (pssm) {
+        if (trace) hipLaunchKernelGGL((intraseq_kernel<true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((intraseq_kernel<false, true>), grid, block, 0, stream, a);
+    } else if (trace) {
+        hipLaunchKernelGGL((intraseq_kernel<true>), grid, block, 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((intraseq_kernel<false>), grid, block, 0, stream, a);
+    }
     return hipGetLastError();
 }
 
@@ -1284,7 +1351,9 @@ hipError_t launchIntraseqStrips(const IntraseqArgs& a, hipStream_t stream) {
     // occupy a quarter of the CUs, the packed workgroups of the others start at once and take the units.
     const int perBlock = a.fatBlocks ? 16 : kJobsPerBlock;
     const int blocks = (int)((units + perBlock - 1) / perBlock);
-    hipLaunchKernelGGL(intraseq_strips_kernel, dim3(blocks), dim3(perBlock * kLanes), 0, stream, a);
+    if (!a.rows) hipLaunchKernelGGL(intraseq_strips_kernel<0>, dim3(blocks), dim3(perBlock * kLanes), 0, stream, a);
+    else if (a.fatBlocks) hipLaunchKernelGGL(intraseq_strips_kernel<16>, dim3(blocks), dim3(perBlock * kLanes), 0, stream, a);
+    else hipLaunchKernelGGL(intraseq_strips_kernel<kJobsPerBlock>, dim3(blocks), dim3(perBlock * kLanes), 0, stream, a);
     hipLaunchKernelGGL(merge_strip_partials_kernel, dim3((a.nJobs + 255) / 256), dim3(256), 0, stream, a);
     return hipGetLastError();
 }

@@ -40,18 +40,34 @@ constexpr int kQueryLds = 4096;  // longest query the kernel stages in LDS
 
 // GLOBALQ (pair lists, miopalAlignPairs): the query buffer - every pair's own query, end to end - is longer than
 // kQueryLds; the lane's rows are read from global memory, once per strip, instead of from an LDS copy
-template <int MODE, bool GLOBALQ = false>  // kAllCells / kLastRow / kLastRowCol: start-location scan; kPerPairTrace: directions
+// PSSM (miopalSearchPssm, a position-specific scoring matrix): the score of a row is the row's own, not the matrix row
+// of a residue. The table in LDS is then [queryLength + 1][A + 1] ints of score + open, pad row / column last - the
+// matrix's layout with the query's POSITIONS where the residues stand - in dynamic LDS (perPairPssmBytes: up to
+// 64 KB, so that a row's byte offset still fits the 16 bits the lanes keep two of per register), filled from a.rows.
+// The cell is the plain form's, instruction for instruction; the plain instantiations are the code they were.
+template <int MODE, bool GLOBALQ = false, bool PSSM = false>  // kAllCells / kLastRow / kLastRowCol: start-location scan; kPerPairTrace: directions
 __global__ __launch_bounds__(kBlock) void perpair_kernel(PerPairArgs a) {
-    __shared__ int smat[kStride * kStride];
-    __shared__ uint8_t qlds[GLOBALQ ? 4 : kQueryLds];
+    __shared__ int smat[PSSM ? 1 : kStride * kStride];
+    __shared__ uint8_t qlds[(GLOBALQ || PSSM) ? 4 : kQueryLds];
+    extern __shared__ __attribute__((aligned(16))) int pssmTable[];
     const int A = a.alphabet;
-    for (int idx = threadIdx.x; idx < kStride * kStride; idx += kBlock) {
-        const int q = idx / kStride, t = idx % kStride;
-        // `open` is folded into the scores: the columns keep H - open (see the cell update)
-        smat[idx] = (q < A && t < A) ? a.matrix[q * A + t] + a.gapOpen : kPadScore;
+    // (PSSM: bytes per row of the table, and its pad row)
+    [[maybe_unused]] const int pssmRowInts = A + 1;
+    [[maybe_unused]] const int pssmPadRow = a.queryLength;
+    if constexpr (PSSM) {
+        for (int idx = threadIdx.x; idx < (a.queryLength + 1) * pssmRowInts; idx += kBlock) {
+            const int q = idx / pssmRowInts, t = idx - q * pssmRowInts;
+            pssmTable[idx] = (q < a.queryLength && t < A) ? a.rows[q * A + t] + a.gapOpen : kPadScore;
+        }
+    } else {
+        for (int idx = threadIdx.x; idx < kStride * kStride; idx += kBlock) {
+            const int q = idx / kStride, t = idx % kStride;
+            // `open` is folded into the scores: the columns keep H - open (see the cell update)
+            smat[idx] = (q < A && t < A) ? a.matrix[q * A + t] + a.gapOpen : kPadScore;
+        }
+        if constexpr (!GLOBALQ)
+            for (int x = threadIdx.x; x < a.queryLength; x += kBlock) qlds[x] = a.query[x];
     }
-    if constexpr (!GLOBALQ)
-        for (int x = threadIdx.x; x < a.queryLength; x += kBlock) qlds[x] = a.query[x];
     __syncthreads();
     auto queryAt = [&](int x) -> int {
         if constexpr (GLOBALQ) return a.query[x];
@@ -101,9 +117,15 @@ __global__ __launch_bounds__(kBlock) void perpair_kernel(PerPairArgs a) {
         uint32_t qo[kLanes / 2];
 #pragma unroll
         for (int i = 0; i < kLanes; i += 2) {
-            const int q0 = row0 + i < Q ? queryAt(job.qOff + (row0 + i) * job.qStep) : A;
-            const int q1 = row0 + i + 1 < Q ? queryAt(job.qOff + (row0 + i + 1) * job.qStep) : A;
-            qo[i >> 1] = (uint32_t)(q0 * kStride * 4) | ((uint32_t)(q1 * kStride * 4) << 16);
+            if constexpr (PSSM) {
+                const int q0 = row0 + i < Q ? job.qOff + (row0 + i) * job.qStep : pssmPadRow;
+                const int q1 = row0 + i + 1 < Q ? job.qOff + (row0 + i + 1) * job.qStep : pssmPadRow;
+                qo[i >> 1] = (uint32_t)(q0 * pssmRowInts * 4) | ((uint32_t)(q1 * pssmRowInts * 4) << 16);
+            } else {
+                const int q0 = row0 + i < Q ? queryAt(job.qOff + (row0 + i) * job.qStep) : A;
+                const int q1 = row0 + i + 1 < Q ? queryAt(job.qOff + (row0 + i + 1) * job.qStep) : A;
+                qo[i >> 1] = (uint32_t)(q0 * kStride * 4) | ((uint32_t)(q1 * kStride * 4) << 16);
+            }
         }
         // Previous column, kept as HM = H - open: the same number opens a gap to the right (E of
         // the next column) and downwards (F of the next row), and the diagonal gets `open` back
@@ -136,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void perpair_kernel(PerPairArgs a) {
                 if (j + 1 < L) t = tptr[(int64_t)(j + 1) * tStep];
                 tcolNext = t * 4;
             }
-            const char* mcol = (const char*)smat + tcol;
+            const char* mcol = (PSSM ? (const char*)pssmTable : (const char*)smat) + tcol;
             int hmUp, fUp;
             if (s == 0) {
                 hmUp = borderGap(j, open, ext) - open;
@@ -276,7 +298,7 @@ __global__ __launch_bounds__(kBlock) void perpair_profile_kernel(PerPairArgs a) 
     for (int idx = threadIdx.x; idx < (A + 1) * pstride; idx += kBlock) {
         const int t = idx / pstride, y = idx - t * pstride;
         int v = kProfilePad;
-        if (t < A && y < Qtot) v = a.matrix[(int)a.query[a.reversed ? Qtot - 1 - y : y] * A + t] + a.gapOpen;
+        if (t < A && y < Qtot) v = scoreAt(a.matrix, a.query, a.rows, A, a.reversed ? Qtot - 1 - y : y, t) + a.gapOpen;
         prof[idx] = (int8_t)v;
     }
     __syncthreads();
@@ -587,7 +609,7 @@ __global__ __launch_bounds__(kBlock) void perpair_scan_refill_kernel(PerPairArgs
     for (int idx = threadIdx.x; idx < (A + 1) * pstride; idx += kBlock) {
         const int t = idx / pstride, y = idx - t * pstride;
         int v = kProfilePad;
-        if (t < A && y < Qtot) v = a.matrix[(int)a.query[a.reversed ? Qtot - 1 - y : y] * A + t] + a.gapOpen;
+        if (t < A && y < Qtot) v = scoreAt(a.matrix, a.query, a.rows, A, a.reversed ? Qtot - 1 - y : y, t) + a.gapOpen;
         prof[idx] = (int8_t)v;
     }
     __syncthreads();
@@ -804,6 +826,15 @@ size_t perPairProfileBytes(int queryLength, int alphabet, int* stride) {
     return bytes <= 64 * 1024 ? bytes : 0;
 }
 
+// LDS bytes of perpair_kernel's row-indexed form for a position-specific scoring matrix of `queryLength` rows
+// (0: the table does not fit the 64 KB a row's 16-bit byte offset can address)
+size_t perPairPssmBytes(int queryLength, int alphabet) {
+    const size_t bytes = (size_t)(queryLength + 1) * (alphabet + 1) * sizeof(int);
+    // (strictly below: the last row's offset fits 16 bits either way, but the PSSM form's few bytes of static LDS -
+    // smat[1], qlds[4] - and anything added to it later must fit the 64 KB of a launch beside the table)
+    return bytes + 256 <= 64 * 1024 ? bytes : 0;
+}
+
 hipError_t launchPerPair(const PerPairArgs& a, int mode, hipStream_t stream) {
     if (a.nJobs <= 0) return hipSuccess;
     const dim3 grid((a.nJobs + kBlock - 1) / kBlock), block(kBlock);
@@ -824,6 +855,19 @@ hipError_t launchPerPair(const PerPairArgs& a, int mode, hipStream_t stream) {
         else if (mode == kLastRow) hipLaunchKernelGGL((perpair_profile_kernel<kLastRow>), grid, block, lds, stream, a);
         else if (mode == kLastRowCol) hipLaunchKernelGGL((perpair_profile_kernel<kLastRowCol>), grid, block, lds, stream, a);
         else hipLaunchKernelGGL((perpair_profile_kernel<kPerPairTrace>), grid, block, lds, stream, a);
+        return hipGetLastError();
+    }
+    if (a.rows) {
+        // position-specific scores: the row-indexed form, when its table fits (the host asks perPairPssmBytes first)
+        const size_t lds = perPairPssmBytes(a.queryLength, a.alphabet);
+        if (lds == 0) return hipErrorInvalidValue;
+        switch (mode) {
+            case kAllCells: hipLaunchKernelGGL((perpair_kernel<kAllCells, false, true>), grid, block, lds, stream, a); break;
+            case kLastRow: hipLaunchKernelGGL((perpair_kernel<kLastRow, false, true>), grid, block, lds, stream, a); break;
+            case kLastRowCol: hipLaunchKernelGGL((perpair_kernel<kLastRowCol, false, true>), grid, block, lds, stream, a); break;
+            case kPerPairTrace: hipLaunchKernelGGL((perpair_kernel<kPerPairTrace, false, true>), grid, block, lds, stream, a); break;
+            default: return hipErrorInvalidValue;
+        }
         return hipGetLastError();
     }
     if (a.queryLength > kQueryLds) {

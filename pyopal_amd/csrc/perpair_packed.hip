@@ -164,7 +164,7 @@ __global__ __launch_bounds__(kPkWaves * kLanes, 2) void perpair_packed_trace_ker
     for (int idx = threadIdx.x; idx < (A + 1) * pstride; idx += kPkBlock) {
         const int t = idx / pstride, y = idx - t * pstride;
         int v = 0;   // padding symbol and rows: the lowest score
-        if (t < A && y < Qtot) v = a.matrix[(int)a.query[y] * A + t] + open + ext + a.packedBias;
+        if (t < A && y < Qtot) v = scoreAt(a.matrix, a.query, a.rows, A, y, t) + open + ext + a.packedBias;
         prof[idx] = (uint8_t)v;
     }
     __syncthreads();
@@ -501,7 +501,7 @@ __global__ __launch_bounds__(kScanBlock, (GROUPS <= 7 && REGION == 0) ? 3 : 2) v
     for (int idx = threadIdx.x; idx < (A + 1) * pstride; idx += kScanBlock) {
         const int t = idx / pstride, y = idx - t * pstride;
         int v = 0;
-        if (t < A && y < Qtot) v = 8 * (a.matrix[(int)a.query[Qtot - 1 - y] * A + t] + open + a.packedBias);
+        if (t < A && y < Qtot) v = 8 * (scoreAt(a.matrix, a.query, a.rows, A, Qtot - 1 - y, t) + open + a.packedBias);
         prof[idx] = (uint8_t)v;
     }
     __syncthreads();

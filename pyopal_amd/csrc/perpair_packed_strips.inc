@@ -22,7 +22,7 @@ __global__ __launch_bounds__(kScanBlock, 2) void perpair_packed_scan_strips_kern
     for (int idx = threadIdx.x; idx < (A + 1) * pstride; idx += kScanBlock) {
         const int t = idx / pstride, y = idx - t * pstride;
         int v = 0;
-        if (t < A && y < Qtot) v = 8 * (a.matrix[(int)a.query[Qtot - 1 - y] * A + t] + open + a.packedBias);
+        if (t < A && y < Qtot) v = 8 * (scoreAt(a.matrix, a.query, a.rows, A, Qtot - 1 - y, t) + open + a.packedBias);
         prof[idx] = (uint8_t)v;
     }
     __syncthreads();

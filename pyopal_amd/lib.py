@@ -691,6 +691,68 @@ class Aligner:
             lengths = np.diff(mirror.offsets[start:end + 1]) if mode == "full" else None
             return ResultArrays(mode, start, len(encoded), lengths, out)
 
+    def align_pssm(self, pssm: "Pssm", database: BaseDatabase, *, mode: str = "score", algorithm: str = "sw",
+                   start: int = 0, end: int = UINT32_MAX, device: int = 0) -> typing.List[ScoreResult]:
+        """Extension: `align` with a position-specific scoring matrix (`Pssm`) in the place of the query and the
+        aligner's matrix: ``pssm.scores[i, t]`` scores query position ``i`` against target residue ``t``. The gap
+        penalties are the aligner's; its scoring matrix is not used. Same result objects as `align`
+        (``FullResult.query_length`` is ``len(pssm)``; a position is a match where the target residue is the
+        consensus'). ``align_pssm(Pssm.from_sequence(q, matrix), db)`` equals ``Aligner(matrix).align(q, db)``."""
+        arrays = self.align_pssm_arrays(pssm, database, mode=mode, algorithm=algorithm, start=start, end=end,
+                                        device=device)
+        if len(arrays) == 0:
+            return []
+        from . import _results
+        scores = np.ascontiguousarray(arrays.score, dtype=np.int32)
+        if mode == "score":
+            return _results.score_results(arrays.start, scores)
+        if mode == "end":
+            return _results.end_results(arrays.start, scores, arrays.query_end, arrays.target_end)
+        with database.lock.read:
+            lengths = database._get_lengths()
+        return _results.full_results(arrays.start, scores, arrays.query_end, arrays.target_end, arrays.query_start,
+                                     arrays.target_start, len(pssm), lengths, arrays.operations,
+                                     arrays.operation_offsets)
+
+    def align_pssm_arrays(self, pssm: "Pssm", database: BaseDatabase, *, mode: str = "score", algorithm: str = "sw",
+                          start: int = 0, end: int = UINT32_MAX, device: int = 0) -> "ResultArrays":
+        """`align_pssm` with the results as arrays (`ResultArrays`, as `align_arrays` returns them)."""
+        if not isinstance(pssm, Pssm):
+            raise TypeError(f"Argument 'pssm' has incorrect type (expected Pssm, got {type(pssm).__name__})")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        if mode not in _OPAL_SEARCH_MODES:
+            raise ValueError(f"invalid search mode: {mode!r}")
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        if start < 0 or end < 0:
+            raise OverflowError("can't convert negative value to uint32_t")
+        if pssm.alphabet != database.alphabet:
+            raise ValueError("database and PSSM have different alphabets")
+        with database.lock.read:
+            size = database._get_size()
+            if end < start:
+                raise IndexError("database slice end is lower than start")
+            end = min(end, size)
+            if start > size:
+                raise IndexError("database slice start is past the end of the database")
+            if end == start:
+                out = {"score": np.zeros(0, dtype=np.int32)}
+                if mode != "score":
+                    out.update(end_q=np.zeros(0, dtype=np.int32), end_t=np.zeros(0, dtype=np.int32))
+                if mode == "full":
+                    out.update(start_q=np.zeros(0, dtype=np.int32), start_t=np.zeros(0, dtype=np.int32),
+                               aln_flat=np.zeros(0, dtype=np.uint8), aln_off=np.zeros(1, dtype=np.int64))
+                return ResultArrays(mode, start, len(pssm), [], out)
+            if _capi.lib().miopalDeviceCount() < 1:
+                raise RuntimeError("no supported SIMD backend available")
+            mirror = database._device_mirror(device)
+            out = mirror.search_pssm(pssm.scores, pssm.consensus, self.gap_open, self.gap_extend, mode, algorithm,
+                                     start, end)
+            lengths = np.diff(mirror.offsets[start:end + 1]) if mode == "full" else None
+            return ResultArrays(mode, start, len(pssm), lengths, out)
+
     def align_many(self, queries, database: BaseDatabase, *, mode: str = "score", algorithm: str = "sw",
                    start: int = 0, end: int = UINT32_MAX, device: int = 0) -> typing.List[typing.List[ScoreResult]]:
         """Extension: align every query of ``queries`` to every target of ``database[start:end]``.
@@ -900,6 +962,91 @@ class Aligner:
                     results.append([EndResult(int(t), int(s), int(qe), int(te)) for t, s, qe, te in
                                     zip(target, row["score"][:c], row["end_q"][:c], row["end_t"][:c])])
             return results
+
+
+class Pssm:
+    """A position-specific scoring matrix: the query of `Aligner.align_pssm`.
+
+    ``scores``: integers of shape ``(Q, len(alphabet))``, ``scores[i, t]`` the score of aligning position ``i`` with
+    residue ``alphabet[t]``; kept as a contiguous, read-only ``int32`` array. ``alphabet``: an `Alphabet` or its
+    letters (default: the protein alphabet). ``consensus``: the residue a position counts as when an alignment tells
+    matches from mismatches - a string over the alphabet or ``Q`` residue codes (255: no residue, never a match);
+    default: each row's best-scoring letter, the lowest index on ties. Kept as a read-only ``uint8`` array of
+    codes; `consensus_sequence` is its text. The numbers are the caller's: nothing here builds a PSSM from an
+    alignment (pseudocounts, background frequencies)."""
+
+    NO_RESIDUE = 255
+    __slots__ = ("scores", "alphabet", "consensus")
+
+    def __init__(self, scores, alphabet=None, consensus=None):
+        if alphabet is None:
+            alphabet = Alphabet()
+        elif isinstance(alphabet, str):
+            alphabet = Alphabet(alphabet)
+        elif not isinstance(alphabet, Alphabet):
+            raise TypeError(f"expected str or Alphabet, found {type(alphabet).__name__}")
+        raw = np.asarray(scores)
+        if raw.dtype == object or not (np.issubdtype(raw.dtype, np.integer) or
+                                       (np.issubdtype(raw.dtype, np.floating) and np.all(raw == np.rint(raw)))):
+            raise ValueError("Integer scores are expected")
+        if raw.ndim != 2 or raw.shape[1] != len(alphabet):
+            raise ValueError(f"scores must have shape (positions, {len(alphabet)}), found {raw.shape}")
+        if raw.size and (raw.min() < -(2 ** 31) or raw.max() >= 2 ** 31):
+            raise OverflowError("scores do not fit 32-bit integers")
+        rows = np.array(raw, dtype=np.int32, order="C")
+        rows.setflags(write=False)
+        if consensus is None:
+            codes = rows.argmax(axis=1).astype(np.uint8) if len(rows) else np.zeros(0, dtype=np.uint8)
+        elif isinstance(consensus, str):
+            codes = np.frombuffer(alphabet.encode(consensus), dtype=np.uint8).copy()
+        else:
+            wide = np.asarray(consensus)
+            if wide.ndim != 1 or (wide.size and not np.issubdtype(wide.dtype, np.integer)):
+                raise ValueError("consensus must be a string or a sequence of residue codes")
+            if wide.size and np.any(((wide < 0) | (wide >= len(alphabet))) & (wide != self.NO_RESIDUE)):
+                raise ValueError(f"consensus residues must be below {len(alphabet)}, or {self.NO_RESIDUE}")
+            codes = wide.astype(np.uint8)
+        if len(codes) != len(rows):
+            raise ValueError(f"consensus has {len(codes)} residues for {len(rows)} positions")
+        codes.setflags(write=False)
+        self.scores = rows
+        self.alphabet = alphabet
+        self.consensus = codes
+
+    @classmethod
+    def from_sequence(cls, sequence, scoring_matrix="BLOSUM62") -> "Pssm":
+        """The PSSM of an ordinary query: row ``i`` is the matrix row of ``sequence[i]``, the consensus the
+        sequence itself. Searching with it gives what the sequence gives under that matrix."""
+        matrix = resolve_scoring_matrix(scoring_matrix, "found")
+        if not matrix.is_integer():
+            raise ValueError("Integer scoring matrix is expected")
+        alphabet = Alphabet(matrix.alphabet)
+        codes = np.frombuffer(alphabet.encode(sequence), dtype=np.uint8)
+        table = _int_matrix_array(matrix.int_array()).reshape(len(alphabet), len(alphabet))
+        return cls(table[codes], alphabet, codes)
+
+    @property
+    def consensus_sequence(self) -> str:
+        """The consensus as text; ``-`` where a position has no residue."""
+        letters = np.frombuffer((self.alphabet.letters + "-" * (256 - len(self.alphabet))).encode("ascii"), dtype=np.uint8)
+        return letters[self.consensus].tobytes().decode("ascii")
+
+    def __len__(self) -> int:
+        return len(self.scores)
+
+    def __eq__(self, other):
+        if not isinstance(other, Pssm):
+            return NotImplemented
+        return (self.alphabet == other.alphabet and np.array_equal(self.scores, other.scores) and
+                np.array_equal(self.consensus, other.consensus))
+
+    __hash__ = None
+
+    def __reduce__(self):
+        return type(self), (np.array(self.scores), self.alphabet.letters, np.array(self.consensus))
+
+    def __repr__(self):
+        return f"{type(self).__name__}(<{len(self)} x {len(self.alphabet)}>, consensus={self.consensus_sequence!r})"
 
 
 class BatchResultArrays:
