@@ -64,6 +64,13 @@ struct InterseqArgs {
     int32_t* directEndJ;
     const int32_t* directIds;  // view position -> database index
     int directN;               // view positions that hold a target
+    // one-strip biased Smith-Waterman kernel, scores only, column split (interseq_impl.h): every resident wavefront
+    // sweeps an equal interval of the launch's chunks; a group cut by an interval's end is handed on
+    int splitMode;             // 0 = off (groups handed out dynamically), 1 = on, 2 = on, consumers recompute from column 0
+    int splitBlocks;           // workgroups of the launch (the plan below is made for splitBlocks * 12 wavefronts)
+    const int64_t* chunkPrefix;   // [groups of the view + 1] running number of chunks
+    uint4* splitState;         // [wavefront][splitStateQuads(rows)][64]: H, E and best at the cut that starts its interval
+    int* splitFlags;           // [wavefronts + 1], zeroed before the launch: 1 = the state is there
     int stripSpinCap;          // strips kernels: polls (x s_sleep) before a unit gives up on the strip above; 0 = the default
     int faultUnit1;            // strips kernels, test hook: unit (this - 1) behaves as if it had died; 0 = none
     unsigned long long* stripTiming;   // diagnostic builds (-DMIOPAL_STRIP_TIMING=1, interseq_impl.h): six counters; else null
@@ -314,6 +321,8 @@ enum PairFlavour : int {
 // limits of the biased flavour (host-side range checks; the kernel's constants are in interseq_impl.h)
 constexpr int kPairStripsMaxRows = 52, kPairStripsMaxRowsLoc = 48;   // tallest strips of the multi-strip pair-table kernel
 constexpr int kPairStripsMaxRowsKnown = 40;   // ... of an `end` search in two sweeps (scores, then the cell that holds them)
+constexpr int kPairWavesPerGroup = 12;     // = kPairWaves: wavefronts of a workgroup of the one-strip pair-table kernels
+inline size_t splitStateBytes(int rows) { return (size_t)((2 * rows + 1 + 3) / 4) * kLanes * 16; }   // per wavefront
 constexpr int kBiasedScoreLimit = 25600;   // = kBiasedLimit: a best at or above it is recomputed
 constexpr int kBiasedMaxMagnitude = 1024;  // |score|, open - ext, ext - open
 constexpr int kBiasedMaxExt = 512;

@@ -1106,10 +1106,7 @@ struct Search {
                 else if (locate)
                     HIP_TRY(launchDecodeStripKeys(ia.stripKeys, view->nGroups * kGroupTargets, ia.score, ia.endI, ia.endJ, stream));
             } else if (usePair || globalPair) {
-                void* wc;
-                RC_TRY(ws->get(kWorkCounter, sizeof(int), &wc));
-                HIP_TRY(hipMemsetAsync(wc, 0, sizeof(int), stream));
-                ia.workCounter = (int*)wc;
+                void* wc = nullptr;   // (taken and zeroed below, with the column split's flags behind it)
                 // The persistent workgroups fill every CU (LDS and registers): a kernel of another
                 // stream - the collective that gathers the previous search's scores - would wait for
                 // them to leave. MIOPAL_RESERVE_CUS keeps a few CUs out of the launch for it.
@@ -1123,12 +1120,11 @@ struct Search {
                     // 2.07 ms; with CUs kept out of the persistent launch 1.66 ms). One CU per 256 pairs.
                     pairUnits = std::max(1, pairUnits - (int)std::min<int64_t>(pairUnits / 4, std::max<int64_t>(8, (g_lastRouting[0] + 255) / 256)));
                 // groups of similar length: every SIMD takes the same share of them (interseq_impl.h)
+                const int longest = view->groupChunksHost[firstGroup];
+                const bool uniform = (int64_t)view->groupChunksHost[view->nGroups - 1] * 5 >= (int64_t)longest * 4;
                 {
                     const int blocks = std::max(1, std::min(pairUnits, ia.nGroups));
-                    const int longest = view->groupChunksHost[firstGroup];
-                    const int shortest = view->groupChunksHost[view->nGroups - 1];
                     const char* tt = tuned(Tune::TAIL_THROTTLE);
-                    const bool uniform = (int64_t)shortest * 5 >= (int64_t)longest * 4;
                     ia.tailThrottle = (tt ? tt[0] == '1' : uniform) ? (ia.nGroups + blocks * 4 - 1) / (blocks * 4) : 0;
                 }
                 // Headline fast path: one strip, Smith-Waterman scores, no lane can leave its range, nothing
@@ -1157,6 +1153,35 @@ struct Search {
                     directScatter = true;
                 }
                 const PairFlavour pf = globalPair ? kPairGlobalBiased : biased ? kPairSwBiased : halfFloat ? kPairSwHalf : kPairSwInt16;
+                // Column split (interseq_impl.h): groups of similar length, Smith-Waterman scores of one strip on the
+                // biased flavour, and at least a longest group's chunks for every resident wavefront - no group is cut
+                // twice - or the launch keeps the dynamic hand-out. The plan follows the CUs the launch may use.
+                // MIOPAL_COLUMN_SPLIT: 0 = off, n = forced on n workgroups, "recompute" = forced, nothing handed on.
+                size_t splitFlags = 0;
+                if (pf == kPairSwBiased && !locate) {
+                    const char* cs = tuned(Tune::COLUMN_SPLIT);
+                    const bool recompute = cs && !strcmp(cs, "recompute");
+                    const int forced = cs && !recompute ? std::max(0, atoi(cs)) : 0;
+                    int64_t chunks = view->totalChunks;
+                    for (int g = 0; g < firstGroup; ++g) chunks -= view->groupChunksHost[g];
+                    // (no empty interval, forced or not: the state of a cut is left for the NEXT wavefront)
+                    const int blocks = (int)std::min<int64_t>(forced > 0 ? std::min(forced, pairUnits) : std::max(1, std::min(pairUnits, ia.nGroups)),
+                                                              chunks / kPairWavesPerGroup);
+                    const int64_t wavefronts = (int64_t)blocks * kPairWavesPerGroup;
+                    if (blocks >= 1 && (recompute || forced > 0 || (!cs && uniform && chunks / wavefronts >= longest))) {
+                        void* st;
+                        RC_TRY(ws->get(kSplitState, (size_t)(wavefronts + 1) * splitStateBytes(pairRows), &st));
+                        ia.splitMode = recompute ? 2 : 1;
+                        ia.splitBlocks = blocks;
+                        ia.chunkPrefix = view->d_chunkPrefix;
+                        ia.splitState = (uint4*)st;
+                        splitFlags = (size_t)wavefronts + 1;
+                    }
+                }
+                RC_TRY(ws->get(kWorkCounter, (1 + splitFlags) * sizeof(int), &wc));
+                HIP_TRY(hipMemsetAsync(wc, 0, (1 + splitFlags) * sizeof(int), stream));
+                ia.workCounter = (int*)wc;
+                if (splitFlags) ia.splitFlags = (int*)wc + 1;
                 // (diagnostic builds of the Smith-Waterman kernel, -DMIOPAL_HEADLINE_TIMING=1: the SIMDs' finish times)
                 unsigned long long* simdFinish = nullptr;
                 const int finishSlots = 1 + 4 * pairUnits;
@@ -1167,7 +1192,7 @@ struct Search {
                     HIP_TRY(hipMemsetAsync(tb, 0xff, sizeof(unsigned long long), stream));
                     ia.stripTiming = simdFinish = (unsigned long long*)tb;
                 }
-                g_lastRouting[1] = 2 + (int)pf;
+                g_lastRouting[1] = 2 + (int)pf + (ia.splitMode ? 64 : 0);   // (64: the column split)
                 // the biased kernels exist for every number of rows (NW / HW / OV: every even number): no padding rows to 8
                 // (test switch: the launch behaves as if the runtime had refused it, e.g. its 150 KB of dynamic LDS)
                 const hipError_t pe = tuned(Tune::TEST_REFUSE_PAIR_LAUNCH)

@@ -20,6 +20,7 @@ struct View {
     int64_t* d_groupOff = nullptr;
     int* d_groupChunks = nullptr;
     int64_t* d_boundaryOff = nullptr;
+    int64_t* d_chunkPrefix = nullptr;  // [nGroups + 1] running number of chunks (the pack kernel, the column split)
     size_t deviceBytes = 0;
     void* d_meta = nullptr;          // one allocation behind d_ids .. d_boundaryOff (and the pack kernel's prefix)
     bool packPending = false;        // lists built and uploaded, residues not packed yet (prefetched view)

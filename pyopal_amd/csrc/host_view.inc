@@ -240,6 +240,7 @@ int buildView(MiopalDb* db, int64_t start, int64_t end, int overlap, std::shared
         v->d_groupOff = (int64_t*)(meta + parts[3].at);
         v->d_groupChunks = (int*)(meta + parts[4].at);
         v->d_boundaryOff = (int64_t*)(meta + parts[5].at);
+        v->d_chunkPrefix = (int64_t*)(meta + parts[6].at);
         UploadLease up(db);
         RC_TRY(up.acquire(metaBytes));
         for (const Part& p : parts)
@@ -254,7 +255,7 @@ int buildView(MiopalDb* db, int64_t start, int64_t end, int overlap, std::shared
         pa.nTargets = v->nPacked;
         pa.groupOff = v->d_groupOff;
         pa.groupChunks = v->d_groupChunks;
-        pa.chunkPrefix = (const int64_t*)(meta + parts[6].at);
+        pa.chunkPrefix = v->d_chunkPrefix;
         pa.nGroups = v->nGroups;
         pa.padSymbol = db->alphabet;
         pa.pack = v->d_pack;

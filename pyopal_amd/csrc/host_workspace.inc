@@ -13,6 +13,7 @@ enum Slot {
     kPairListQ, kPairListT, kPairListTOff, kPairListQBase, kPairListQOff, kPairListBoundary,
     kTopScratch,   // miopalSearchTop / miopalSearchBatchTop: the selection's outputs and scratch (rows x (bins + blocks + k))
     kPssmRows,     // miopalSearchPssm: the rows, [Q][A] ints
+    kSplitState,   // column split of the one-strip Smith-Waterman kernel: a wavefront's DP state at the cut that starts its interval
     kSlots
 };
 

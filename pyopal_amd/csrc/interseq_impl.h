@@ -889,6 +889,7 @@ static hipError_t launchFlavour(const InterseqArgs& a, int rowsPerStrip, int wav
 // is built once per workgroup, so workgroups are persistent: kPairWaves wavefronts
 // each pull groups from a shared counter until none is left.
 constexpr int kPairWaves = 12;  // 3 per SIMD at <= 168 VGPRs
+static_assert(kPairWaves == kPairWavesPerGroup, "common.h mirrors this");
 
 template <int R>
 struct PairLayout {
@@ -1228,8 +1229,46 @@ struct SimdPace {
 #define MIOPAL_HEADLINE_TIMING 0
 #endif
 
-template <int R, bool LOC>
+// Column split (SPLIT; scores only). The dynamic hand-out's unit is a whole group, so a launch of G groups on S
+// SIMDs lasts ceil(G / S) group-times whatever G is. With SPLIT the chunk sequence of all the launch's groups is
+// cut into W = gridDim.x * kPairWaves equal intervals, one per resident wavefront: wavefront w owns the chunks
+// [w C / W, (w + 1) C / W) of a.chunkPrefix. A group cut by an interval's end is BEGUN by that wavefront (the
+// producer, first thing it does) and FINISHED by the next one (the consumer, last thing it does); between the two
+// the whole groups of the interval. At the cut the producer leaves H[R], E[R] and the running best - rebased to
+// shift 0, so that no scalar state travels - in a.splitState (slot w + 1: [quad][lane] x 16 bytes, the sc1 buffer
+// stores of StripRows) and publishes a.splitFlags[w + 1] (stripPublish / stripPoll, common.h); only the wavefront
+// that reaches the group's last chunk writes its scores. The host takes this mode when an interval is at least as
+// long as the longest group (no group is cut twice, and a consumer arrives nearly a whole interval after its
+// producer has left); forced on smaller launches (MIOPAL_COLUMN_SPLIT) an interval may lie inside one group, whose
+// wavefront then consumes and produces. A consumer polls kSplitPolls times at most, then - or at once with
+// a.splitMode == 2 - sweeps the group from column 0 itself: always correct, no launch can hang on a flag.
+// The wavefronts of a SIMD are paced by what is left of their INTERVALS: equal shares that end together.
+// (the state's quads: StripRows' accesses with the quad in the scalar offset - one lane offset for all of them, where
+// a vector offset per quad is hoisted out of the group loop into as many registers)
+struct SplitState {
+    __amdgpu_buffer_rsrc_t rsrc;
+    __device__ __forceinline__ explicit SplitState(void* base)
+        : rsrc(__builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7ffffff0, 0x00020000)) {}
+    // (the offset made where it is used: as a constant it would be hoisted out of the group loop too, into a scalar
+    // register per quad)
+    static __device__ __forceinline__ int at(int quad) {
+        int offset = quad * (kLanes * 16);
+        asm volatile("" : "+s"(offset));
+        return offset;
+    }
+    __device__ __forceinline__ StripU4 load(int quad, int lane) const {
+        return __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, at(quad), 16 /* sc1 */);
+    }
+    __device__ __forceinline__ void store(int quad, int lane, StripU4 v) const {
+        __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, lane * 16, at(quad), 16 /* sc1 */);
+    }
+};
+constexpr int kSplitPolls = 256;
+__host__ __device__ constexpr int splitStateQuads(int rows) { return (2 * rows + 1 + 3) / 4; }   // = splitStateBytes / 1024
+
+template <int R, bool LOC, bool SPLIT = false>
 __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kernel(InterseqArgs a) {
+    static_assert(!(SPLIT && LOC), "the column split carries no end locations");
     constexpr int SLOTS = PairLayout<R>::kRowSlots;
     constexpr int NB4 = (R + 3) / 4;   // R need not be a multiple of 4: the last read is partly used
     constexpr int kBits = LOC ? locRowBits(R) : 0;
@@ -1277,9 +1316,74 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
     // HW_REG_HW_ID (4), SIMD_ID = bits 5:4
     const int simd = (int)__builtin_amdgcn_s_getreg(4 | (4 << 6) | ((2 - 1) << 11)) & 3;
     bool firstRound = true;
+    // SPLIT: this wavefront's interval [lo, hi) of the launch's chunks, the groups gLo / gHi that hold its two ends
+    // and how far into them the ends lie (0: not cut); phase 0 = the piece that begins gHi, 1 = the whole groups,
+    // 2 = the piece that finishes gLo
+    int splitW = 0, gLo = 0, gHi = 0, cutLo = 0, cutHi = 0, gWhole = 0, phase = 0, paceAfter = 0;
+    if constexpr (SPLIT) {
+        const int64_t* pre = a.chunkPrefix + a.groupBase;
+        // (the launch's chunks are fewer than 2^31 and its wavefronts fewer than 2^15: 32-bit arithmetic throughout)
+        const uint32_t C = (uint32_t)(pre[a.nGroups] - pre[0]);
+        const uint32_t W = kPairWaves * gridDim.x, each = C / W, rest = C % W;
+        splitW = kPairWaves * (int)blockIdx.x + wave;
+        const uint32_t lo = splitW * each + splitW * rest / W, hi = (splitW + 1) * each + (splitW + 1) * rest / W;
+        // (groups of similar length: the proportional guess is a step or two off at most)
+        const float groupsPerChunk = (float)a.nGroups / (float)(C > 0 ? C : 1);
+        auto groupOf = [&](uint32_t x) {
+            int k = (int)((float)x * groupsPerChunk);
+            k = k < 0 ? 0 : k > a.nGroups ? a.nGroups : k;
+            while (k > 0 && (uint32_t)(pre[k] - pre[0]) > x) --k;
+            while (k < a.nGroups && (uint32_t)(pre[k + 1] - pre[0]) <= x) ++k;
+            return k;
+        };
+        // (wave-uniform, and said so: what a vector load returns would keep all that follows in VGPRs)
+        gLo = __builtin_amdgcn_readfirstlane(groupOf(lo));
+        gHi = __builtin_amdgcn_readfirstlane(groupOf(hi));
+        cutLo = __builtin_amdgcn_readfirstlane((int)(lo - (uint32_t)(pre[gLo] - pre[0])));
+        cutHi = __builtin_amdgcn_readfirstlane((int)(hi - (uint32_t)(pre[gHi] - pre[0])));
+        gWhole = cutLo > 0 ? gLo + 1 : gLo;
+        paceAfter = __builtin_amdgcn_readfirstlane((int)(hi - lo));
+        if (lo == hi) phase = 3;
+    }
     for (;;) {
         int g;
-        if (firstRound) {
+        int cBegin = 0, cEnd = 0;               // SPLIT: the piece's chunks of group g (cEnd = 0: to the group's end)
+        bool consume = false, produce = false;  // SPLIT: the piece starts from / leaves the state of a cut
+        if constexpr (SPLIT) {
+            if (phase == 0) {
+                phase = 1;
+                if (gLo == gHi) {               // the interval lies inside one group (forced launches only)
+                    phase = 3;
+                    g = gLo;
+                    cBegin = cutLo;
+                    cEnd = cutHi;
+                    consume = cutLo > 0;
+                    produce = true;
+                } else if (cutHi > 0) {
+                    g = gHi;
+                    cEnd = cutHi;
+                    produce = true;
+                } else {
+                    continue;
+                }
+            } else if (phase == 1) {
+                if (gWhole < gHi) {
+                    g = gWhole++;
+                } else {
+                    phase = 2;
+                    continue;
+                }
+            } else if (phase == 2) {
+                phase = 3;
+                if (cutLo == 0) break;
+                g = gLo;
+                cBegin = cutLo;
+                consume = true;
+            } else {
+                break;
+            }
+            g += a.groupBase;
+        } else if (firstRound) {
             g = tier * gridDim.x + ((tier & 1) ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x);
             firstRound = false;
             if (lane == 0 && a.tailThrottle > 0) atomicAdd(&simdTaken[simd], 1);
@@ -1311,12 +1415,51 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
         uint32_t fl = zero2 - ext2;         // zero of column -1
         int shift = -ext;                   // fl = zero2 + both(shift); wave-uniform
         uint32_t H[R], E[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            H[r] = fl;                      // H[r][-1] = 0 on column -1's scale
-            E[r] = zero2;                   // E[r][0]  = 0 on column 0's scale
+        if constexpr (SPLIT) {
+            if (cEnd == 0) cEnd = nChunks;
+            paceAfter -= cEnd - cBegin;     // (a piece swept again from column 0 counts as what it was)
+            if (consume) {
+                bool there = false;
+                if (a.splitMode != 2) {
+                    for (int poll = 0; poll < kSplitPolls && !there; ++poll) {
+                        there = stripPoll(a.splitFlags + splitW) != 0;
+                        if (!there) __builtin_amdgcn_s_sleep(16);
+                    }
+                }
+                if (!there) {
+                    consume = false;
+                    cBegin = 0;
+                }
+            }
         }
-        uint2 cur = pack[lane];
+        if (SPLIT && consume) {
+            // the producer's state at shift 0: H on the last column's scale, E on the next one's, fl = zero2
+            fl = zero2;
+            shift = 0;
+            const SplitState mine(a.splitState + (size_t)splitW * splitStateQuads(R) * kLanes);
+            // (seven loads in flight at a time: each lands in four registers of its own before it moves into H / E)
+#pragma unroll
+            for (int q = 0; q < splitStateQuads(R); ++q) {
+                if (q % 7 == 0 && q > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                const StripU4 v = mine.load(q, lane);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int i = 4 * q + k;
+                    const uint32_t x = k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w;
+                    if (i < R) H[i] = x;
+                    else if (i < 2 * R) E[i - R] = x;
+                    else if (i == 2 * R) best = x;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                H[r] = fl;                      // H[r][-1] = 0 on column -1's scale
+                E[r] = zero2;                   // E[r][0]  = 0 on column 0's scale
+            }
+        }
+        const int cFirst = SPLIT ? cBegin : 0, cLast = SPLIT ? cEnd : nChunks;
+        uint2 cur = pack[(size_t)cFirst * kLanes + lane];
         // LDS row of a residue pair (24-bit multiplies: v_mul_lo_u32 is a quarter-rate instruction)
         auto rowOf = [&](uint32_t tA, uint32_t tB) -> const uint4* {
             const uint32_t rowIdx = __umul24(tA, (uint32_t)nSym) + tB;
@@ -1343,10 +1486,11 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
 #pragma unroll
             for (int k = 0; k < kAhead; ++k) vn[k] = prowNext[k];
         }
-        for (int c = 0; c < nChunks; ++c) {
+        for (int c = cFirst; c < cLast; ++c) {
             uint2 nxt = {0, 0};
             if (c + 1 < nChunks) nxt = pack[(size_t)(c + 1) * kLanes + lane];
-            if (MIOPAL_HEADLINE_PACE) pace.step(c - nChunks, lane, nChunks > a.priorityChunks);
+            // (SPLIT: by what is left of the interval)
+            if (MIOPAL_HEADLINE_PACE) pace.step(c - cLast - (SPLIT ? paceAfter : 0), lane, nChunks > a.priorityChunks);
             uint32_t ra = cur.x, rb = cur.y;
 #pragma unroll 1
             for (int cc = 0; cc < 4; ++cc) {
@@ -1429,6 +1573,24 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
                 shift = 0;
             }
         }
+        if constexpr (SPLIT) {
+            if (produce) {
+                // the cut: the state leaves at shift 0 (the rebase above, whatever the shift has come to)
+                const uint32_t d = both(shift);
+                const SplitState next(a.splitState + (size_t)(splitW + 1) * splitStateQuads(R) * kLanes);
+#pragma unroll
+                for (int q = 0; q < splitStateQuads(R); ++q) {
+                    auto word = [&](int i) -> uint32_t {
+                        if (i < R) return H[i] - d;
+                        if (i < 2 * R) return E[i - R] - d;
+                        return i == 2 * R ? best : 0u;
+                    };
+                    next.store(q, lane, StripU4{word(4 * q), word(4 * q + 1), word(4 * q + 2), word(4 * q + 3)});
+                }
+                stripPublish(a.splitFlags + splitW + 1, 1, lane);
+                continue;                   // (the consumer writes the group's scores)
+            }
+        }
         const int lo = (int)(best & 0xffffu) >> kBits, hi = (int)(best >> 16) >> kBits;
         const size_t base = (size_t)g * kGroupTargets;
         if (a.directOut) {
@@ -1498,11 +1660,47 @@ static hipError_t launchPairBiasedR(const InterseqArgs& a, int computeUnits, hip
     return hipGetLastError();
 }
 
+// the column-split form (a.splitMode != 0; scores only): a.splitBlocks workgroups, whose wavefronts the host's plan
+// (flags, state slots, the interval's length) was made for
+template <int R>
+static hipError_t launchPairBiasedSplitR(const InterseqArgs& a, hipStream_t stream) {
+    const size_t lds = PairLayout<R>::bytes(a.nSymbols) + 16 + kPaceInts * sizeof(int);
+    static uint64_t configured = 0;
+    if (firstUseOnThisDevice(&configured)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&interseq_pair_biased_kernel<R, false, true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) {
+            int dev = 0;
+            (void)hipGetDevice(&dev);
+            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
+            return e;
+        }
+    }
+    if (a.splitBlocks < 1 || !a.chunkPrefix || !a.splitState || !a.splitFlags) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((interseq_pair_biased_kernel<R, false, true>), dim3(a.splitBlocks), dim3(kPairWaves * kLanes), lds, stream, a);
+    return hipGetLastError();
+}
+
 template <int kLo, bool LOC>
 static hipError_t launchPairBiased(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
     if (a.nStrips != 1) return hipErrorInvalidValue;
     // rows: kLo, kLo + 2, ..., kLo + 14; the translation units interseq_swb16_{a,b,c,d}[_loc].hip share the
     // even counts 2..64, interseq_swb16_{a,b,c,d}[_loc]_odd.hip the odd ones 1..63
+    if constexpr (!LOC) {
+        if (a.splitMode != 0) {
+            switch (rowsPerStrip - kLo) {
+                case 0: return launchPairBiasedSplitR<kLo>(a, stream);
+                case 2: return launchPairBiasedSplitR<kLo + 2>(a, stream);
+                case 4: return launchPairBiasedSplitR<kLo + 4>(a, stream);
+                case 6: return launchPairBiasedSplitR<kLo + 6>(a, stream);
+                case 8: return launchPairBiasedSplitR<kLo + 8>(a, stream);
+                case 10: return launchPairBiasedSplitR<kLo + 10>(a, stream);
+                case 12: return launchPairBiasedSplitR<kLo + 12>(a, stream);
+                case 14: return launchPairBiasedSplitR<kLo + 14>(a, stream);
+            }
+            return hipErrorInvalidValue;
+        }
+    }
     switch (rowsPerStrip - kLo) {
         case 0: return launchPairBiasedR<kLo, LOC>(a, computeUnits, stream);
         case 2: return launchPairBiasedR<kLo + 2, LOC>(a, computeUnits, stream);
