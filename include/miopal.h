@@ -140,9 +140,10 @@ int miopalSearchFlat(MiopalDb* db, const unsigned char* query, int queryLength, 
  * with nothing launched. Thread safety as miopalSearch.
  * Where the scores leave the ranges of the profile-driven kernels, the 32-bit kernels stage the rows of
  * the strip at hand in LDS instead of the matrix ("Position-specific scoring matrices").
- * Out of scope: PSSM forms of miopalSearchBatch, miopalSearchTop, miopalSearchBatchTop and
- * miopalAlignPairs, of opalSearchDatabase and of the multi-GPU shard driver; and building a PSSM from
- * an alignment (pseudocounts, background frequencies) - the caller brings the numbers.
+ * The k best hits and pair lists take a PSSM too: miopalSearchPssmTop and miopalAlignPairsPssm, below.
+ * Out of scope: PSSM forms of miopalSearchBatch and miopalSearchBatchTop (their kernels take queries of at
+ * most 64 rows, which few PSSMs are), of opalSearchDatabase and of the multi-GPU shard driver; and building
+ * a PSSM from an alignment (pseudocounts, background frequencies) - the caller brings the numbers.
  */
 int miopalSearchPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
                      int gapOpen, int gapExt, int alphabetLength, int searchType, int mode,
@@ -251,6 +252,25 @@ int miopalSearchTop(MiopalDb* db, const unsigned char* query, int queryLength, i
                     int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery);
 
 /*
+ * miopalSearchTop with a position-specific scoring matrix in the place of (query, scoreMatrix): rowScores
+ * ([queryLength][alphabetLength], as in miopalSearchPssm) and no consensus - the call produces no alignments.
+ * miopalSearchTop's contract holds to the letter: the order (score descending, then target index ascending),
+ * minScore, count = min(k, hits), -1 in the slots past count, k in [0, MIOPAL_MAX_TOP], k = 0 or an empty slice
+ * checked and answered with nothing launched. Entry i equals what miopalSearchPssm returns for targetIndex[i], the
+ * score pass takes the kernels miopalSearchPssm takes (miopalLastRouting reports the same), and the selection is
+ * miopalSearchTop's.
+ * Checked before any device call, with miopalSearchPssm's codes and in its order - first what needs no handle (mode
+ * and search type, queryLength < 0, NULL rowScores with queryLength > 0, the alphabet length's range,
+ * OPAL_SEARCH_ALIGNMENT: OPAL_ERR_INVALID_MODE, k outside its range), then the handle, the alphabet length against
+ * it, the slice, the outputs (miopalSearchTop's), and the 32-bit range check with the extreme entries of the rows
+ * (OPAL_ERR_OVERFLOW). Thread safety as miopalSearch.
+ */
+int miopalSearchPssmTop(MiopalDb* db, const int* rowScores, int queryLength,
+                        int gapOpen, int gapExt, int alphabetLength, int searchType, int mode,
+                        int64_t start, int64_t end, int k, int minScore,
+                        int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery);
+
+/*
  * miopalSearchTop of every query of a batch (queries and queryOffsets as in miopalSearchBatch), in one call through
  * miopalSearchBatch's chunks: each chunk's [queries][targets] rows are selected on the device before they leave.
  * count has nQueries entries; the other outputs are [nQueries][k], row-major. Row i equals miopalSearchTop of query i
@@ -287,7 +307,36 @@ int miopalAlignPairs(MiopalDb* db, const unsigned char* queries, const int64_t* 
                      unsigned char** operations, int64_t* operationOffsets);
 
 /*
- * How the calling thread's most recent miopalAlignPairs ran (diagnostics for tests):
+ * miopalAlignPairs with a list of position-specific scoring matrices in the place of (queries, scoreMatrix): PSSM m
+ * holds the rows rowOffsets[m] .. rowOffsets[m + 1] of rowScores (nPssms + 1 offsets, alphabetLength ints per row),
+ * and consensus is indexed in the same row coordinates (entries: a residue or 255; required for
+ * OPAL_SEARCH_ALIGNMENT, may be NULL otherwise). Pair p aligns PSSM pairPssm[p] with target pairTarget[p], and entry p
+ * of every output equals what miopalSearchPssm returns for that PSSM against the slice [pairTarget[p],
+ * pairTarget[p] + 1) - the -1 locations and empty operations of an empty alignment, empty PSSMs and empty targets
+ * included. Outputs, the nPairs = 0 behaviour, chunking and thread safety as miopalAlignPairs; any order, repeats
+ * allowed, all three search types and four modes. miopalLastPairRouting reports the call like a plain pair list.
+ * Checked before any work, with the existing codes: mode and search type; the offsets (non-negative, non-decreasing,
+ * at most INT32_MAX - 64 rows in total); NULL rowScores; the alphabet length's range; the consensus (NULL for an
+ * alignment search, an entry that is neither a residue nor 255); pairPssm[p] in [0, nPssms) (the message names the
+ * first bad pair); null outputs; then the handle, the alphabet length against it, pairTarget[p] in
+ * [0, miopalDbCount); and the 32-bit range check with the extreme entries of the rows, the tallest PSSM and the
+ * longest target the list names (OPAL_ERR_OVERFLOW).
+ * One lane per pair - the forward pass as well as the start-cell scan and the direction pass of
+ * OPAL_SEARCH_ALIGNMENT - keeps the rows of ALL the list's PSSMs in LDS: it is taken when
+ * (total rows + 1) * (alphabetLength + 1) * 4 bytes fit 64 KB less 256 (493 rows at 32 letters, 651 at 24), under
+ * miopalAlignPairs' cost estimates. A list with more rows runs one wavefront per pair throughout (counts[0] of
+ * miopalLastPairRouting is 0): the same results, more slowly for large lists.
+ * Out of scope: a table per workgroup for lists whose rows do not fit.
+ */
+int miopalAlignPairsPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus,
+                         const int64_t* rowOffsets, int nPssms,
+                         const int32_t* pairPssm, const int64_t* pairTarget, int64_t nPairs,
+                         int gapOpen, int gapExt, int alphabetLength, int searchType, int mode,
+                         int* score, int* endTarget, int* endQuery, int* startTarget, int* startQuery,
+                         unsigned char** operations, int64_t* operationOffsets);
+
+/*
+ * How the calling thread's most recent miopalAlignPairs / miopalAlignPairsPssm ran (diagnostics for tests):
  *   counts[0] pairs whose forward pass ran in the lane-per-pair kernel (pairlist_forward_kernel)
  *   counts[1] pairs whose forward pass ran in the wavefront-per-pair kernel
  *   counts[2] pairs answered without a DP (empty query or target)

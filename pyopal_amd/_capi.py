@@ -50,7 +50,7 @@ EXPORTS = [
     "miopalSearch", "miopalSearchFlat", "miopalSearchFlatInto", "miopalSearchPssm", "miopalSearchDeviceScores", "miopalSetProfiling", "miopalLastKernelTime",
     "miopalLastRouting", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
     "miopalSearchBatch", "miopalLastBatchRouting", "miopalSearchTop", "miopalSearchBatchTop",
-    "miopalAlignPairs", "miopalLastPairRouting",
+    "miopalAlignPairs", "miopalLastPairRouting", "miopalSearchPssmTop", "miopalAlignPairsPssm",
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
     # test hooks
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
@@ -137,6 +137,12 @@ def lib() -> ctypes.CDLL:
         L.miopalAlignPairs.restype = c_int
         L.miopalAlignPairs.argtypes = [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_int,
                                        c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp]
+        L.miopalSearchPssmTop.restype = c_int
+        L.miopalSearchPssmTop.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.miopalAlignPairsPssm.restype = c_int
+        L.miopalAlignPairsPssm.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_int,
+                                           c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp]
         L.miopalLastPairRouting.restype = None
         L.miopalLastPairRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
         L.miopalLastBatchRouting.restype = None
@@ -543,6 +549,26 @@ class DeviceDatabase:
         out["count"] = int(out["count"][0])
         return out
 
+    def search_pssm_top(self, row_scores: np.ndarray, gap_open: int = 3, gap_extend: int = 1, mode: str = "score",
+                        algorithm: str = "sw", start: int = 0, end: typing.Optional[int] = None, k: int = 10,
+                        min_score: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+        """miopalSearchPssmTop: `search_top` with a position-specific scoring matrix (``row_scores`` as in
+        `search_pssm`) in the place of (query, matrix). Returns `search_top`'s dict; entry i equals what
+        `search_pssm` gives for ``target[i]``."""
+        end = self.count if end is None else min(end, self.count)
+        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
+        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
+            raise ValueError(f"row_scores must have shape (query length, {self.alphabet_length})")
+        out = self._top_outputs(None, k, mode)
+        rc = lib().miopalSearchPssmTop(self._h, _ptr(rows) if len(rows) else None, len(rows), gap_open, gap_extend,
+                                       self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end, k,
+                                       -(2 ** 31) if min_score is None else min_score, _ptr(out["count"]),
+                                       _ptr(out["target"]), _ptr(out["score"]), _ptr(out.get("end_t")),
+                                       _ptr(out.get("end_q")))
+        raise_for(rc)
+        out["count"] = int(out["count"][0])
+        return out
+
     def search_batch_top(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
                          gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
                          end: typing.Optional[int] = None, k: int = 10,
@@ -581,12 +607,54 @@ class DeviceDatabase:
         flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
         if flat.size == 0:
             flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+
+        def call(st, pq, pt, n, score, et, eq, s_t, s_q, ops_ptr, aoff):
+            return lib().miopalAlignPairs(self._h, _ptr(flat), _ptr(offsets), len(qs), pq, pt, n, gap_open, gap_extend,
+                                          _ptr(S), self.alphabet_length, st, MODE[algorithm], score, et, eq, s_t, s_q,
+                                          ctypes.byref(ops_ptr), aoff)
+        return self._pair_list(call, pair_query, pair_target, mode)
+
+    def align_pairs_pssm(self, pssm_rows: typing.Sequence[np.ndarray],
+                         consensus: typing.Optional[typing.Sequence[np.ndarray]], pair_pssm, pair_target,
+                         gap_open: int = 3, gap_extend: int = 1, mode: str = "score",
+                         algorithm: str = "sw") -> typing.Dict[str, typing.Any]:
+        """miopalAlignPairsPssm: `align_pairs` with a list of position-specific scoring matrices in the place of
+        (queries, matrix). ``pssm_rows[m]``: integers of shape (rows of PSSM m, alphabet length); ``consensus[m]``:
+        one residue (or 255) per row of PSSM m - required for mode "full", may be None otherwise. Pair p aligns PSSM
+        ``pair_pssm[p]`` with target ``pair_target[p]``; returns `align_pairs`' dict, entry p equal to
+        ``search_pssm(pssm_rows[i], consensus[i], ..., start=j, end=j + 1)``."""
+        rows = [np.ascontiguousarray(r, dtype=np.int32) for r in pssm_rows]
+        for r in rows:
+            if r.ndim != 2 or r.shape[1] != self.alphabet_length:
+                raise ValueError(f"every PSSM must have shape (rows, {self.alphabet_length})")
+        offsets = np.zeros(len(rows) + 1, dtype=np.int64)
+        if rows:
+            np.cumsum([len(r) for r in rows], out=offsets[1:])
+        total = int(offsets[-1])
+        flat = np.concatenate(rows) if total else None
+        cons = None
+        if consensus is not None:
+            cs = [np.ascontiguousarray(c, dtype=np.uint8).ravel() for c in consensus]
+            if [len(c) for c in cs] != [len(r) for r in rows]:
+                raise ValueError("consensus must have one entry per row of every PSSM")
+            cons = np.concatenate(cs) if total else None
+
+        def call(st, pq, pt, n, score, et, eq, s_t, s_q, ops_ptr, aoff):
+            return lib().miopalAlignPairsPssm(self._h, _ptr(flat), _ptr(cons), _ptr(offsets), len(rows), pq, pt, n,
+                                              gap_open, gap_extend, self.alphabet_length, st, MODE[algorithm], score,
+                                              et, eq, s_t, s_q, ctypes.byref(ops_ptr), aoff)
+        return self._pair_list(call, pair_pssm, pair_target, mode)
+
+    def _pair_list(self, call, pair_query, pair_target, mode) -> typing.Dict[str, typing.Any]:
+        """The outputs of one pair-list call (`align_pairs`, `align_pairs_pssm`): ``call(search type, pair queries,
+        pair targets, pairs, score, end_t, end_q, start_t, start_q, ops_ptr, offsets)`` makes the C call with these
+        pointers and returns its code."""
         pq = np.ascontiguousarray(pair_query, dtype=np.int32).ravel()
         pt = np.ascontiguousarray(pair_target, dtype=np.int64).ravel()
         if len(pq) != len(pt):
             raise ValueError("pair_query and pair_target differ in length")
         n = len(pq)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
         st = SEARCH[mode]
         out = {"score": np.empty(n, dtype=np.int32)}
         et = eq = s_t = s_q = aoff = None
@@ -598,10 +666,8 @@ class DeviceDatabase:
             s_t = np.empty(n, dtype=np.int32)
             s_q = np.empty(n, dtype=np.int32)
             aoff = np.zeros(n + 1, dtype=np.int64)
-        rc = lib().miopalAlignPairs(self._h, _ptr(flat), _ptr(offsets), len(qs), _ptr(pq) if n else None,
-                                    _ptr(pt) if n else None, n, gap_open, gap_extend, _ptr(S), self.alphabet_length,
-                                    st, MODE[algorithm], _ptr(out["score"]), _ptr(et), _ptr(eq), _ptr(s_t), _ptr(s_q),
-                                    ctypes.byref(ops_ptr), _ptr(aoff))
+        rc = call(st, _ptr(pq) if n else None, _ptr(pt) if n else None, n, _ptr(out["score"]), _ptr(et), _ptr(eq),
+                  _ptr(s_t), _ptr(s_q), ops_ptr, _ptr(aoff))
         raise_for(rc)
         if st >= 1:
             out.update(end_t=et, end_q=eq)
@@ -617,7 +683,7 @@ class DeviceDatabase:
     @staticmethod
     def last_pair_routing() -> typing.Tuple[int, int, int, int]:
         """(pairs on the lane-per-pair forward kernel, pairs on the wavefront-per-pair kernel, pairs answered without
-        a DP, chunks) for the calling thread's most recent align_pairs."""
+        a DP, chunks) for the calling thread's most recent align_pairs / align_pairs_pssm."""
         counts = (ctypes.c_int64 * 4)()
         lib().miopalLastPairRouting(counts)
         return tuple(int(c) for c in counts)

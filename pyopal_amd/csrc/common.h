@@ -423,6 +423,9 @@ hipError_t launchPairListJobs(int n, const int32_t* pairQuery, const int64_t* pa
                               const int64_t* dbOffsets, int rules, int64_t wsStride, PairJob* jobs,
                               int64_t* targetOff, int32_t* queryBase, hipStream_t stream);
 hipError_t launchPairListForward(const PerPairArgs& a, int region, bool locate, hipStream_t stream);
+// ... its row-indexed form (a.rows: the rows of all the list's PSSMs, a.queryLength of them; pairlist_pssm.hip), which
+// launchPairListForward calls; hipErrorInvalidValue when perPairPssmBytes(a.queryLength, a.alphabet) is 0
+hipError_t launchPairListForwardPssm(const PerPairArgs& a, int region, bool locate, hipStream_t stream);
 hipError_t launchPack(const PackArgs& a, int64_t totalChunks, hipStream_t stream);
 // segmented views with end locations (pack.hip): keyed atomicMax per window, then unpack
 hipError_t launchScatterKeyed(const int32_t* viewScore, const int32_t* viewEndI, const int32_t* viewEndJ,

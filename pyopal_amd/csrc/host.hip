@@ -807,6 +807,85 @@ int miopalSearchPssm(MiopalDb* db, const int* rowScores, const unsigned char* co
     });
 }
 
+// miopalSearchTop with a position-specific scoring matrix as the score source: miopalSearchPssm's checks in its
+// order (no consensus: nothing is aligned), with the two refusals of the selection that need no handle - alignments,
+// k - among the first; then searchTopImpl with the rows where the matrix stands.
+int miopalSearchPssmTop(MiopalDb* db, const int* rowScores, int queryLength, int gapOpen, int gapExt,
+                        int alphabetLength, int searchType, int mode, int64_t start, int64_t end, int k, int minScore,
+                        int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery) {
+    return guarded([&]() -> int {
+    const int Q = queryLength, A = alphabetLength;
+    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
+    if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
+    if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
+    if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
+    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    if (searchType == OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "miopalSearchPssmTop: alignments are not selected on the device");
+    if (k < 0 || k > MIOPAL_MAX_TOP) return fail(MIOPAL_ERR_BAD_ARGUMENT, "k = %d outside [0, %d]", k, MIOPAL_MAX_TOP);
+    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
+    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
+    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
+    // (no rows: an empty query has no scores; the score source still says "position-specific")
+    static const int kNoRows[1] = {0};
+    // (no consensus: every position is "no residue" - the int32 kernels upload it with the rows and never read it)
+    const std::vector<unsigned char> none((size_t)std::max(Q, 1), 255);
+    return searchTopImpl(db, none.data(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, k, minScore, 0, count,
+                         targetIndex, score, endTarget, endQuery, Q > 0 ? rowScores : kNoRows);
+    });
+}
+
+// miopalAlignPairs with a list of position-specific scoring matrices as the score source: what needs no handle is
+// checked here, in miopalSearchPssm's order, then alignPairsImpl with the rows where the matrix stands, the
+// consensus where the queries stand and the row offsets where the query offsets stand.
+int miopalAlignPairsPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, const int64_t* rowOffsets,
+                         int nPssms, const int32_t* pairPssm, const int64_t* pairTarget, int64_t nPairs, int gapOpen,
+                         int gapExt, int alphabetLength, int searchType, int mode, int* score, int* endTarget,
+                         int* endQuery, int* startTarget, int* startQuery, unsigned char** operations,
+                         int64_t* operationOffsets) {
+    return guarded([&]() -> int {
+    const int A = alphabetLength;
+    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
+    if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
+    if (nPssms < 0 || (nPssms > 0 && !rowOffsets)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad PSSM list");
+    for (int m = 0; m < nPssms; ++m)
+        if (rowOffsets[m] < 0 || rowOffsets[m + 1] < rowOffsets[m])
+            return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad row offsets at %d", m);
+    const int64_t first = nPssms > 0 ? rowOffsets[0] : 0, totalRows = nPssms > 0 ? rowOffsets[nPssms] - first : 0;
+    if (totalRows > INT32_MAX - 64) return fail(MIOPAL_ERR_BAD_ARGUMENT, "the PSSMs of a pair list hold 2^31 - 65 rows at most");
+    if (totalRows > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
+    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    const bool full = searchType == OPAL_SEARCH_ALIGNMENT;
+    if (full && totalRows > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
+    if (consensus)
+        for (int64_t i = first; i < first + totalRows; ++i)
+            if (consensus[i] >= A && consensus[i] != 255)
+                return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %lld", consensus[i], (long long)i);
+    // (without a consensus - score and end lists - every position is "no residue": the kernels never read it)
+    std::vector<unsigned char> none;
+    if (!consensus) {
+        none.assign((size_t)(first + std::max<int64_t>(totalRows, 1)), 255);   // (indexed in the offsets' coordinates)
+        consensus = none.data();
+    }
+    static const int kNoRows[1] = {0};
+    HostBytes ops;
+    RC_TRY(alignPairsImpl(db, consensus, rowOffsets, nPssms, pairPssm, pairTarget, nPairs, gapOpen, gapExt, nullptr, A,
+                          searchType, mode, score, endTarget, endQuery, startTarget, startQuery,
+                          full && operations ? &ops : nullptr, operationOffsets,
+                          totalRows > 0 ? rowScores + (size_t)first * A : kNoRows));
+    if (full) {
+        *operations = nullptr;
+        if (nPairs > 0) {
+            if (!ops.data && !ops.resize(0)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+            *operations = ops.release();
+        }
+    }
+    return 0;
+    });
+}
+
 int miopalSearchFlatInto(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                          const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                          int64_t end, int* score, int* endTarget, int* endQuery, int* startTarget,

@@ -14,6 +14,14 @@
 // host_full.inc. Scan and direction pass: perpair_kernel / intraseq_kernel, as in a one-query `full` search, with the
 // pair's query origin added to its jobs. Pairs with an empty query or target are answered here (closed forms of the
 // border, oracle/opal_oracle.c).
+//
+// miopalAlignPairsPssm is the same function with another score source: a list of position-specific scoring matrices
+// (pssmRows: their rows end to end, [total rows][A]; `queries` / `queryOffsets` then hold the consensus and the row
+// offsets, `matrix` is null; the entry point has made the checks that need no handle). The jobs' query origin is the
+// PSSM's first row, which the row-indexed kernels add to the row they look up. One lane per pair - the forward pass
+// (pairlist_forward_kernel<., ., true>) as well as the scan and the direction pass of `full` (perpair_kernel<., false,
+// true>) - needs the whole list's table in LDS (perPairPssmBytes of the total rows: 493 rows at 32 letters, 651 at
+// 24); a list with more rows runs one wavefront per pair throughout.
 namespace {
 
 constexpr int64_t kPairChunkMax = int64_t(1) << 22;   // pairs per chunk at most (56-byte jobs, twice)
@@ -45,16 +53,18 @@ int64_t pairChunkCapacity(int64_t maxQ, int64_t maxL, bool full) {
 static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
                           const int32_t* pairQuery, const int64_t* pairTarget, int64_t nPairs, int open, int ext,
                           const int* matrix, int A, int searchType, int mode, int* score, int* endTarget,
-                          int* endQuery, int* startTarget, int* startQuery, HostBytes* outOps, int64_t* opsOff) {
+                          int* endQuery, int* startTarget, int* startQuery, HostBytes* outOps, int64_t* opsOff,
+                          const int* pssmRows = nullptr) {
     for (int k = 0; k < 4; ++k) g_lastPairRouting[k] = 0;
+    const bool pssm = pssmRows != nullptr;
     // what can be said without the handle first (a caller's mistake is reported whatever the handle's state): the search,
     // the queries and their residues, the pair list's query side, the outputs
     if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
     if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
         return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
     if (nQueries < 0 || (nQueries > 0 && (!queryOffsets || !queries))) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query list");
-    if (!matrix || A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad score matrix / alphabet length %d", A);
-    for (int i = 0; i < nQueries; ++i) {
+    if ((!pssm && !matrix) || A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad score matrix / alphabet length %d", A);
+    for (int i = 0; i < nQueries && !pssm; ++i) {
         const int64_t len = queryOffsets[i + 1] - queryOffsets[i];
         if (queryOffsets[i] < 0 || len < 0 || len > INT32_MAX) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query offsets at %d", i);
         for (int64_t x = 0; x < len; ++x)
@@ -64,7 +74,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
     if (nPairs < 0 || (nPairs > 0 && (!pairQuery || !pairTarget))) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad pair list");
     for (int64_t p = 0; p < nPairs; ++p)
         if (pairQuery[p] < 0 || pairQuery[p] >= nQueries)
-            return fail(MIOPAL_ERR_BAD_ARGUMENT, "pair %lld: query index %d outside [0, %d)", (long long)p, pairQuery[p], nQueries);
+            return fail(MIOPAL_ERR_BAD_ARGUMENT, "pair %lld: %s index %d outside [0, %d)", (long long)p, pssm ? "PSSM" : "query", pairQuery[p], nQueries);
     const bool locate = searchType >= OPAL_SEARCH_SCORE_END, full = searchType == OPAL_SEARCH_ALIGNMENT;
     if (full && (!outOps || !opsOff)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null alignment outputs");
     if (nPairs > 0) {
@@ -73,7 +83,12 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
         if (full && (!startTarget || !startQuery)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null alignment outputs");
     }
     // ... and with it: miopalSearch's own checks query by query, the pair list's target side
-    RC_TRY(validateBatch(db, queries, queryOffsets, nQueries, matrix, A, searchType, mode, 0, 0));
+    if (pssm) {
+        if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
+        if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
+    } else {
+        RC_TRY(validateBatch(db, queries, queryOffsets, nQueries, matrix, A, searchType, mode, 0, 0));
+    }
     int64_t maxQ = 0, maxL = 0;
     for (int64_t p = 0; p < nPairs; ++p) {
         if (pairTarget[p] < 0 || pairTarget[p] >= db->count)
@@ -84,7 +99,11 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
     }
     {
         // miopalSearch's range check for its 32-bit kernels, for the longest query and the longest target of the list
-        const int maxScore = *std::max_element(matrix, matrix + A * A), minScore = *std::min_element(matrix, matrix + A * A);
+        // (position-specific scores: the extreme entries of the rows where the matrix's stand)
+        const int* const entries = pssm ? pssmRows : matrix;
+        const size_t nEntries = pssm ? (size_t)(nQueries > 0 ? queryOffsets[nQueries] - queryOffsets[0] : 0) * A : (size_t)A * A;
+        const int maxScore = nEntries ? *std::max_element(entries, entries + nEntries) : 0;
+        const int minScore = nEntries ? *std::min_element(entries, entries + nEntries) : 0;
         const int64_t mag = std::max<int64_t>(std::llabs((long long)maxScore), std::llabs((long long)minScore));
         const int64_t bound = 2 * (int64_t)std::llabs((long long)open) + (maxQ + maxL) * std::llabs((long long)ext) +
                               std::min(maxQ, maxL) * mag + mag;
@@ -194,6 +213,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
         Workspace* ws = lease.ws;
         hipStream_t stream = ws->stream;
         Search s{db, ws, stream, concat.data(), (int)concat.size(), open, ext, A, searchType, mode, matrix, 0, db->count, nLive};
+        s.pssmRows = pssmRows;
         RC_TRY(s.prepare());
         RC_TRY(s.ensurePairInputs());
         void* pqoff;
@@ -201,6 +221,8 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
         RC_TRY(ws->stageUpload(pqoff, qOff.data(), qOff.size() * sizeof(int32_t), stream));
         const int totalQuery = (int)concat.size();
         const bool forceLane = tuned(Tune::FORCE_LANE_PER_PAIR) != nullptr;
+        // (position-specific scores: the lane-per-pair kernels hold the rows of the whole list in LDS)
+        const bool tableFits = !pssm || perPairPssmBytes(totalQuery, A) != 0;
         const int rules = packRules(fr);
         std::vector<int32_t> cq, hs, hi, hj, hsq, hst, hlen, hts;
         std::vector<int64_t> ct;
@@ -226,7 +248,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
             }
             // one lane per pair: ~14 instructions per cell, but a wavefront lasts as long as its longest lane; one
             // wavefront per pair: ~225 instructions per 64-row column step, a chain of L + 63 steps (host_full.inc; ms)
-            const bool lanePossible = !ch.waveOnly && !tuned(Tune::NO_PERPAIR) && (nc > kSmallSearch || !smallSearchAllowed(db));
+            const bool lanePossible = !ch.waveOnly && tableFits && !tuned(Tune::NO_PERPAIR) && (nc > kSmallSearch || !smallSearchAllowed(db));
             const double perLane = std::max(laneCols * (14 * 4.5) / (1024 * 2.4e6), laneChain * (64 * 14 * 4.5) / 2.4e6);
             const double perWave = std::max(waveCols * 225.0 / (1024 * 2.4e6), waveChain * 250.0 / 2.4e6);
             const bool lane = lanePossible && (forceLane || perLane <= perWave);
@@ -252,6 +274,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
             perPair.query = s.d_query;
             perPair.queryLength = totalQuery;
             perPair.matrix = s.d_matrix;
+            perPair.rows = s.d_rows;
             perPair.alphabet = A;
             perPair.gapOpen = open;
             perPair.gapExt = ext;

@@ -114,14 +114,25 @@ static int selectTopRows(Workspace* ws, Search* s, const int32_t* d_score, const
 // miopalSearchTop: searchImpl's score / end pass with the results left in the workspace's device slots, then the
 // selection on the same stream (the score pass has joined its side-stream jobs and flagged lanes into it).
 // Writes row `outRow` of the outputs.
+// (pssmRows, miopalSearchPssmTop: the score source is [queryLength][alphabetLength] rows, as in searchImpl; scoreMatrix
+// is null, `query` a consensus of 255s - no alignment reads it - and the caller has made miopalSearchPssm's checks)
 static int searchTopImpl(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                          const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                          int64_t end, int k, int minScore, int64_t outRow, int* count, int64_t* targetIndex, int* score,
-                         int* endTarget, int* endQuery) {
-    RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, searchType, mode, start, end));
+                         int* endTarget, int* endQuery, const int* pssmRows = nullptr) {
+    if (!pssmRows) RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, searchType, mode, start, end));
     RC_TRY(checkTopArgs(searchType, k, count, targetIndex, score, endTarget, endQuery));
     const bool locate = searchType == OPAL_SEARCH_SCORE_END;
     const int64_t n = end - start;
+    if (pssmRows && n > 0) {
+        // miopalSearch's range check for its 32-bit kernels, with the extreme entries of the rows (validate()'s place)
+        Search probe{db, nullptr, nullptr, nullptr, queryLength, gapOpen, gapExt, alphabetLength, searchType, mode, nullptr, start, end, n};
+        if (queryLength > 0) {
+            probe.maxScore = *std::max_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
+            probe.minScore = *std::min_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
+        }
+        RC_TRY(probe.checkInt32(db->maxLen));
+    }
     if (k == 0 || n == 0) {
         emptyTopRows((int)outRow, (int)outRow + 1, k, count, targetIndex, score, locate ? endTarget : nullptr,
                      locate ? endQuery : nullptr);
@@ -133,6 +144,7 @@ static int searchTopImpl(MiopalDb* db, const unsigned char* query, int queryLeng
     Workspace* ws = lease.ws;
     Search s{db, ws, ws->stream, query, queryLength, gapOpen, gapExt, alphabetLength, searchType, mode,
              scoreMatrix, start, end, n};
+    s.pssmRows = pssmRows;
     RC_TRY(s.prepare());
     void *ps, *pi = nullptr, *pj = nullptr;
     RC_TRY(ws->get(kScore, (size_t)n * sizeof(int32_t), &ps));

@@ -10,6 +10,17 @@
 //   * the lane's query rows come from the call's concatenated queries in GLOBAL memory, once per strip: no LDS copy
 //     of the queries, so their total length is unbounded;
 //   * score-only instantiations (LOC = false) carry no location bookkeeping.
+// PSSM (miopalAlignPairsPssm, a list of position-specific scoring matrices): the score of a row is the row's own. The
+// call's PSSMs, end to end, are ONE table in dynamic LDS - perpair_kernel's row-indexed layout: [a.queryLength + 1]
+// [A + 1] ints of score + open, pad column and pad row last (perPairPssmBytes: within 64 KB, so that a row's byte
+// offset fits the 16 bits the lanes keep two of per register) - filled once per workgroup from a.rows; job.qOff is
+// the first row of the lane's PSSM in it and a.query is not read. The column loop is the plain one, instruction
+// for instruction, and the plain instantiations are the code they were. Lists whose rows do not fit keep the
+// wavefront-per-pair kernel (host_pairs.inc).
+// Two translation units are made of this file, as of interseq_impl.h: pairlist.o holds the eight plain instantiations
+// and the job builder (pairlist.rpt: the eight entries tests/test_pairs_cpu.py counts), pairlist_pssm.o
+// (pairlist_pssm.hip defines MIOPAL_PAIRLIST_PSSM and includes this file) the eight row-indexed ones, with
+// resource remarks of their own in pairlist_pssm.rpt.
 // Candidates in column-major order, a candidate replaces the best only when strictly greater, Smith-Waterman
 // starts from best = 0 with no location; across strips the higher score wins, then the smaller column, then the
 // upper strip. intraseq_kernel (intraseq.hip) is the other in-tree statement of this pass and the one this kernel
@@ -28,15 +39,32 @@ constexpr int kNegInf = INT32_MIN / 4;
 constexpr int kPadScore = -(1 << 28);
 constexpr int kStride = kMaxAlphabet + 1;  // matrix rows in LDS, in ints (pad column included)
 constexpr int kBlock = 256;
+#ifdef MIOPAL_PAIRLIST_PSSM
+constexpr bool kPssmUnit = true;
+#else
+constexpr bool kPssmUnit = false;
+#endif
 
-template <int REGION, bool LOC>
+template <int REGION, bool LOC, bool PSSM = false>
 __global__ __launch_bounds__(kBlock) void pairlist_forward_kernel(PerPairArgs a) {
-    __shared__ int smat[kStride * kStride];
+    __shared__ int smat[PSSM ? 1 : kStride * kStride];
+    extern __shared__ __attribute__((aligned(16))) int pssmTable[];
     const int A = a.alphabet;
-    for (int idx = threadIdx.x; idx < kStride * kStride; idx += kBlock) {
-        const int q = idx / kStride, t = idx % kStride;
-        // `open` is folded into the scores: the columns keep H - open (perpair_kernel)
-        smat[idx] = (q < A && t < A) ? a.matrix[q * A + t] + a.gapOpen : kPadScore;
+    // (PSSM: ints per row of the table, and its pad row)
+    [[maybe_unused]] const int pssmRowInts = A + 1;
+    [[maybe_unused]] const int pssmPadRow = a.queryLength;
+    if constexpr (PSSM) {
+        // (consecutive threads read consecutive ints of a.rows but for the pad column's gaps)
+        for (int idx = threadIdx.x; idx < (a.queryLength + 1) * pssmRowInts; idx += kBlock) {
+            const int q = idx / pssmRowInts, t = idx - q * pssmRowInts;
+            pssmTable[idx] = (q < a.queryLength && t < A) ? a.rows[q * A + t] + a.gapOpen : kPadScore;
+        }
+    } else {
+        for (int idx = threadIdx.x; idx < kStride * kStride; idx += kBlock) {
+            const int q = idx / kStride, t = idx % kStride;
+            // `open` is folded into the scores: the columns keep H - open (perpair_kernel)
+            smat[idx] = (q < A && t < A) ? a.matrix[q * A + t] + a.gapOpen : kPadScore;
+        }
     }
     __syncthreads();
 
@@ -64,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void pairlist_forward_kernel(PerPairArgs a)
     // running answer over the strips
     int best = floor0 ? 0 : INT32_MIN, brow = -1, bcol = -1;
     const uint8_t* tptr = a.residues + job.tOff;
-    const uint8_t* qptr = a.query + job.qOff;
+    [[maybe_unused]] const uint8_t* qptr = PSSM ? nullptr : a.query + job.qOff;
     // strip boundaries of the wavefront: (H - open, F) of the strip's last row, per column
     int2* bnd = a.boundary ? a.boundary + (int64_t)(idx >> 6) * a.boundaryStride * kLanes + lane : nullptr;
 
@@ -76,9 +104,15 @@ __global__ __launch_bounds__(kBlock) void pairlist_forward_kernel(PerPairArgs a)
         uint32_t qo[kLanes / 2];
 #pragma unroll
         for (int i = 0; i < kLanes; i += 2) {
-            const int q0 = row0 + i < Q ? qptr[row0 + i] : A;
-            const int q1 = row0 + i + 1 < Q ? qptr[row0 + i + 1] : A;
-            qo[i >> 1] = (uint32_t)(q0 * kStride * 4) | ((uint32_t)(q1 * kStride * 4) << 16);
+            if constexpr (PSSM) {
+                const int q0 = row0 + i < Q ? job.qOff + row0 + i : pssmPadRow;
+                const int q1 = row0 + i + 1 < Q ? job.qOff + row0 + i + 1 : pssmPadRow;
+                qo[i >> 1] = (uint32_t)(q0 * pssmRowInts * 4) | ((uint32_t)(q1 * pssmRowInts * 4) << 16);
+            } else {
+                const int q0 = row0 + i < Q ? qptr[row0 + i] : A;
+                const int q1 = row0 + i + 1 < Q ? qptr[row0 + i + 1] : A;
+                qo[i >> 1] = (uint32_t)(q0 * kStride * 4) | ((uint32_t)(q1 * kStride * 4) << 16);
+            }
         }
         int HM[kLanes], E[kLanes];
 #pragma unroll
@@ -99,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void pairlist_forward_kernel(PerPairArgs a)
                 if (j + 1 < L) t = tptr[j + 1];
                 tcolNext = t * 4;
             }
-            const char* mcol = (const char*)smat + tcol;
+            const char* mcol = (PSSM ? (const char*)pssmTable : (const char*)smat) + tcol;
             int hmUp, fUp;
             if (s == 0) {
                 hmUp = (topGap ? borderGap(j, open, ext) : 0) - open;
@@ -157,6 +191,7 @@ __global__ __launch_bounds__(kBlock) void pairlist_forward_kernel(PerPairArgs a)
     }
 }
 
+#ifndef MIOPAL_PAIRLIST_PSSM
 // Jobs of a chunk of the pair list, built where the kernels read them: pair p aligns the whole of query
 // pairQuery[p] with the whole of target pairTarget[p]. targetOff / queryBase: the pair's target and query origin,
 // what launchReverseJobs / launchTraceJobs take as `offsets` and `queryBase`.
@@ -181,9 +216,11 @@ __global__ void pairlist_jobs_kernel(int n, const int32_t* pairQuery, const int6
     targetOff[k] = j.tOff;
     queryBase[k] = j.qOff;
 }
+#endif
 
 }  // namespace
 
+#ifndef MIOPAL_PAIRLIST_PSSM
 hipError_t launchPairListJobs(int n, const int32_t* pairQuery, const int64_t* pairTarget, const int32_t* queryOff,
                               const int64_t* dbOffsets, int rules, int64_t wsStride, PairJob* jobs,
                               int64_t* targetOff, int32_t* queryBase, hipStream_t stream) {
@@ -193,14 +230,29 @@ hipError_t launchPairListJobs(int n, const int32_t* pairQuery, const int64_t* pa
     return hipGetLastError();
 }
 
+#endif
+
+// (pairlist.o: launchPairListForward, which hands a list with position-specific scores to launchPairListForwardPssm
+// of pairlist_pssm.o: the row-indexed form, when the list's table fits - the host asks perPairPssmBytes first)
+#ifdef MIOPAL_PAIRLIST_PSSM
+hipError_t launchPairListForwardPssm(const PerPairArgs& a, int region, bool locate, hipStream_t stream) {
+#else
 hipError_t launchPairListForward(const PerPairArgs& a, int region, bool locate, hipStream_t stream) {
+#endif
     if (a.nJobs <= 0) return hipSuccess;
     if (!a.score || (locate && (!a.endI || !a.endJ))) return hipErrorInvalidValue;
     const dim3 grid((a.nJobs + kBlock - 1) / kBlock), block(kBlock);
-#define MIOPAL_PAIRLIST_GO(R)                                                                               \
-    do {                                                                                                    \
-        if (locate) hipLaunchKernelGGL((pairlist_forward_kernel<R, true>), grid, block, 0, stream, a);      \
-        else hipLaunchKernelGGL((pairlist_forward_kernel<R, false>), grid, block, 0, stream, a);            \
+#ifdef MIOPAL_PAIRLIST_PSSM
+    const size_t lds = a.rows ? perPairPssmBytes(a.queryLength, a.alphabet) : 0;
+    if (lds == 0) return hipErrorInvalidValue;
+#else
+    if (a.rows) return launchPairListForwardPssm(a, region, locate, stream);
+    const size_t lds = 0;
+#endif
+#define MIOPAL_PAIRLIST_GO(R)                                                                                        \
+    do {                                                                                                             \
+        if (locate) hipLaunchKernelGGL((pairlist_forward_kernel<R, true, kPssmUnit>), grid, block, lds, stream, a);  \
+        else hipLaunchKernelGGL((pairlist_forward_kernel<R, false, kPssmUnit>), grid, block, lds, stream, a);        \
     } while (0)
     switch (region) {
         case kAllCells: MIOPAL_PAIRLIST_GO(kAllCells); break;

@@ -861,6 +861,11 @@ class Aligner:
         """One `align_pairs` call on the mirror; its arrays as result objects, in pair order."""
         out = mirror.align_pairs(arrays, pair_query, pair_target, matrix, self.gap_open, self.gap_extend, mode,
                                  algorithm)
+        return self._pair_objects(out, mirror, [len(a) for a in arrays], pair_query, pair_target, mode)
+
+    @staticmethod
+    def _pair_objects(out, mirror, query_lengths, pair_query, pair_target, mode):
+        """The arrays of a pair-list call (`align_pairs`, `align_pairs_pssm`) as result objects, in pair order."""
         score = out["score"].tolist()
         target = np.asarray(pair_target).tolist()
         if mode == "score":
@@ -872,9 +877,107 @@ class Aligner:
         off = out["aln_off"].tolist()
         text = out["aln_flat"].tobytes().translate(_OPS_TO_TEXT).decode("ascii")
         lengths = np.diff(mirror.offsets)
-        return [FullResult(t, score[p], end_q[p], end_t[p], start_q[p], start_t[p], len(arrays[q]), int(lengths[t]),
+        return [FullResult(t, score[p], end_q[p], end_t[p], start_q[p], start_t[p], query_lengths[q], int(lengths[t]),
                            text[off[p]:off[p + 1]])
                 for p, (q, t) in enumerate(zip(np.asarray(pair_query).tolist(), target))]
+
+    def align_pairs_pssm(self, pssms, database: BaseDatabase, pairs, *, mode: str = "score", algorithm: str = "sw",
+                         device: int = 0) -> typing.List[ScoreResult]:
+        """Extension: `align_pairs` with a list of `Pssm` in the place of the queries (include/miopal.h,
+        miopalAlignPairsPssm): ``pairs`` holds ``(pssm_index, target_index)``. Returns one result per pair, in pair
+        order, each equal to ``self.align_pssm(pssms[i], database, mode=mode, algorithm=algorithm, start=j,
+        end=j + 1)[0]`` (``FullResult.query_length`` is ``len(pssms[i])``): a library of PSSMs against the
+        survivors of a prefilter, the hits of a family scan. The gap penalties are the aligner's."""
+        if mode not in _OPAL_SEARCH_MODES:
+            raise ValueError(f"invalid search mode: {mode!r}")
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        pssms = list(pssms)
+        for pssm in pssms:
+            if not isinstance(pssm, Pssm):
+                raise TypeError(f"Argument 'pssms' has an item of incorrect type (expected Pssm, got {type(pssm).__name__})")
+            if pssm.alphabet != database.alphabet:
+                raise ValueError("database and PSSM have different alphabets")
+        pairs = np.asarray(pairs if len(pairs) else np.zeros((0, 2), dtype=np.int64))
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
+            raise ValueError("pairs must be a sequence of (pssm_index, target_index) integers")
+        pairs = pairs.astype(np.int64, copy=False)
+        with database.lock.read:
+            size = database._get_size()
+            if len(pairs):
+                if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= len(pssms):
+                    raise IndexError("PSSM index of a pair outside the PSSMs")
+                if pairs[:, 1].min() < 0 or pairs[:, 1].max() >= size:
+                    raise IndexError("target index of a pair outside the database")
+            if len(pairs) == 0:
+                return []
+            if _capi.lib().miopalDeviceCount() < 1:
+                raise RuntimeError("no supported SIMD backend available")
+            mirror = database._device_mirror(device)
+            return self._pair_results_pssm(pssms, mirror, pairs[:, 0], pairs[:, 1], mode, algorithm)
+
+    def _pair_results_pssm(self, pssms, mirror, pair_pssm, pair_target, mode, algorithm):
+        """One `align_pairs_pssm` call on the mirror; its arrays as result objects, in pair order."""
+        out = mirror.align_pairs_pssm([p.scores for p in pssms], [p.consensus for p in pssms], pair_pssm, pair_target,
+                                      self.gap_open, self.gap_extend, mode, algorithm)
+        return self._pair_objects(out, mirror, [len(p) for p in pssms], pair_pssm, pair_target, mode)
+
+    def top_hits_pssm(self, pssm: "Pssm", database: BaseDatabase, k: int = 10, *, mode: str = "score",
+                      algorithm: str = "sw", min_score: typing.Optional[int] = None, start: int = 0,
+                      end: int = UINT32_MAX, device: int = 0) -> typing.List[ScoreResult]:
+        """Extension: `top_hits` with a `Pssm` in the place of the query and the aligner's matrix
+        (include/miopal.h, miopalSearchPssmTop): the ``k`` best targets of ``database[start:end]``, best first,
+        selected on the GPU. Equal to ``[r for r in sorted(self.align_pssm(pssm, database, mode=mode, ...),
+        key=lambda r: r.score, reverse=True) if min_score is None or r.score >= min_score][:k]``. ``mode="full"``
+        selects on the scores, then aligns the chosen targets only, in one pair-list call (miopalAlignPairsPssm):
+        the step an iterated profile search repeats."""
+        if not isinstance(pssm, Pssm):
+            raise TypeError(f"Argument 'pssm' has incorrect type (expected Pssm, got {type(pssm).__name__})")
+        if mode not in _OPAL_SEARCH_MODES:
+            raise ValueError(f"invalid search mode: {mode!r}")
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"k must be an integer, not {type(k).__name__}")
+        k = int(k)
+        if k < 0 or k > _capi.MIOPAL_MAX_TOP:
+            raise ValueError(f"k must be between 0 and {_capi.MIOPAL_MAX_TOP} (MIOPAL_MAX_TOP), got {k}")
+        if min_score is not None:
+            min_score = int(min_score)
+        if start < 0 or end < 0:
+            raise OverflowError("can't convert negative value to uint32_t")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        if pssm.alphabet != database.alphabet:
+            raise ValueError("database and PSSM have different alphabets")
+        with database.lock.read:
+            size = database._get_size()
+            if end < start:
+                raise IndexError("database slice end is lower than start")
+            end = min(end, size)
+            if start > size:
+                raise IndexError("database slice start is past the end of the database")
+            if end == start or k == 0:
+                return []
+            if _capi.lib().miopalDeviceCount() < 1:
+                raise RuntimeError("no supported SIMD backend available")
+            mirror = database._device_mirror(device)
+            out = mirror.search_pssm_top(pssm.scores, self.gap_open, self.gap_extend, "score" if mode == "full" else mode,
+                                         algorithm, start, end, k, min_score)
+            c = out["count"]
+            target = out["target"][:c]
+            if mode == "full":
+                if c == 0:
+                    return []
+                return self._pair_results_pssm([pssm], mirror, np.zeros(c, dtype=np.int32), target, "full", algorithm)
+            if mode == "score":
+                return [ScoreResult(int(t), int(s)) for t, s in zip(target, out["score"][:c])]
+            return [EndResult(int(t), int(s), int(qe), int(te)) for t, s, qe, te in
+                    zip(target, out["score"][:c], out["end_q"][:c], out["end_t"][:c])]
 
     def top_hits(self, query, database: BaseDatabase, k: int = 10, *, mode: str = "score", algorithm: str = "sw",
                  min_score: typing.Optional[int] = None, start: int = 0, end: int = UINT32_MAX,
