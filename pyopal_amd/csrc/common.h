@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "launch_layer.h"
 
 namespace miopal {
 
@@ -308,7 +309,13 @@ constexpr int kSwShiftZero = 0x1000;       // = kSwU16Zero
 constexpr int kUnsignedDiagZero = 0x1000;  // = kU16Zero
 hipError_t launchInterseq(const InterseqArgs& a, int rowsPerStrip, int waves, InterseqFlavour flavour,
                           bool locate, hipStream_t stream);
-// pair-indexed LDS profile (single strip, Smith-Waterman); false = table does not fit LDS
+// pair-indexed LDS profile: pairs[tA * nSymbols + tB][r] in 16-byte slots of four rows, an odd number of them per
+// table row so that the rows start on different slots
+__host__ __device__ constexpr int pairRowSlots(int rowsPerStrip) { return ((rowsPerStrip + 3) / 4) | 1; }
+__host__ __device__ constexpr size_t pairLdsBytes(int rowsPerStrip, int nSymbols) {
+    return (size_t)nSymbols * nSymbols * pairRowSlots(rowsPerStrip) * 16;
+}
+// false = the table does not fit LDS
 bool interseqPairFits(int rowsPerStrip, int nSymbols);
 enum PairFlavour : int {
     kPairSwInt16 = 0,   // saturating int16
@@ -319,6 +326,7 @@ enum PairFlavour : int {
     kPairGlobalStrips = 5  // NW / HW / OV of several strips on the same units (scores; end locations through keys)
 };
 // limits of the biased flavour (host-side range checks; the kernel's constants are in interseq_impl.h)
+constexpr int kPairStripsFirst = 32;       // shortest strips of the multi-strip pair-table kernels
 constexpr int kPairStripsMaxRows = 52, kPairStripsMaxRowsLoc = 48;   // tallest strips of the multi-strip pair-table kernel
 constexpr int kPairStripsMaxRowsKnown = 40;   // ... of an `end` search in two sweeps (scores, then the cell that holds them)
 constexpr int kPairWavesPerGroup = 12;     // = kPairWaves: wavefronts of a workgroup of the one-strip pair-table kernels
@@ -335,57 +343,35 @@ constexpr int kLocMaxShift = 4096;         // 5 * (ext << bits) must fit
 inline int locRowBitsHost(int rows) { return rows <= 16 ? 4 : rows <= 32 ? 5 : 6; }
 hipError_t launchInterseqPair(const InterseqArgs& a, int rowsPerStrip, PairFlavour flavour, int computeUnits,
                               hipStream_t stream, bool locate = false);
-hipError_t launchInterseqPairSwBiasedA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedC(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedD(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwStripsA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwStripsB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwStripsLocA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwStripsLocB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-// second pass of an `end` search: the first cell that holds each target's known optimum (a.known)
-hipError_t launchInterseqPairSwStripsKnownA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairGlobalStripsA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairGlobalStripsB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairGlobalStripsLocA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairGlobalStripsLocB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
+// The kernel families behind launchInterseq / launchInterseqPair, one function template each (defined in
+// interseq_impl.h). A translation unit interseq_*.hip is one explicit instantiation: an arithmetic of the general
+// kernel, or kPairUnitCounts row counts of a pair-table kernel from kLo upwards in steps of two (one parity).
+struct ArithSwI16;
+struct ArithSwF16;
+struct ArithI16;
+struct ArithI16Diag;
+struct ArithU16Diag;
+struct ArithSwU16;
+constexpr int kPairUnitCounts = 8, kPairUnitSpan = 2 * kPairUnitCounts;   // a unit's row counts, and from unit to unit
+template <typename Arith, bool TRACK_ALL, bool LOC>   // general kernel: strips of 8, 16, ..., 64 rows
+hipError_t launchFlavour(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
+template <typename Arith>                              // one-strip pair table, int16 / half floats: 8, 16, ..., 64 rows
+hipError_t launchPairFlavour(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream);
+template <int kLo, bool LOC>    // one-strip Smith-Waterman on biased halves: units from 2 (even counts) and from 1 (odd)
+hipError_t launchPairBiased(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream);
+template <int kLo>              // one-strip NW / HW / OV (end locations: a.endI != nullptr): units from 2
+hipError_t launchPairGlobal(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream);
+// several strips: units from kPairStripsFirst up to kPairStripsMaxRows*; KNOWN: second pass of an `end` search, the
+// first cell that holds each target's known optimum (a.known)
+template <int kLo, bool LOC, bool KNOWN = false>
+hipError_t launchPairStrips(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream);
+template <int kLo, bool LOC>    // (end locations leave as keys: launchDecodeGlobalKeys)
+hipError_t launchPairGlobalStrips(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream);
 // keys of the multi-strip NW / HW / OV kernel -> view-order scores and end locations (endI / endJ may be null)
 hipError_t launchDecodeGlobalKeys(const unsigned long long* keys, const int32_t* lens, int n, int queryLength,
                                   int32_t* score, int32_t* endI, int32_t* endJ, hipStream_t stream);
 // (score, column, row) keys of the strips kernel -> view-order scores and end locations
 hipError_t launchDecodeStripKeys(const unsigned long long* keys, int n, int32_t* score, int32_t* endI, int32_t* endJ, hipStream_t stream);
-hipError_t launchInterseqPairGlobalA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairGlobalB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairGlobalC(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairGlobalD(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedLocA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedLocB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedLocC(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedLocD(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-// (odd row counts: the query's own length, no padding row)
-hipError_t launchInterseqPairSwBiasedOddA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedOddB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedOddC(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedOddD(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedLocOddA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedLocOddB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedLocOddC(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwBiasedLocOddD(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwHalf(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqPairSwInt16(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream);
-hipError_t launchInterseqSwHalf(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSwHalfLoc(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSwInt16(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSwInt16Loc(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSigned(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSignedLoc(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSignedAll(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSignedDiag(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSignedDiagLoc(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSwShifted(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqUnsignedDiag(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqUnsignedDiagLoc(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
-hipError_t launchInterseqSignedAllLoc(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream);
 hipError_t launchIntraseq(const IntraseqArgs& a, bool trace, hipStream_t stream);
 hipError_t launchIntraseqStrips(const IntraseqArgs& a, hipStream_t stream);
 hipError_t launchWalk(const WalkArgs& a, hipStream_t stream);

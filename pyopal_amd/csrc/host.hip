@@ -34,6 +34,7 @@
 
 #include "../../include/miopal.h"
 #include "common.h"
+#include "launch_layer_selftest.h"
 #include "select_top.h"
 #include "tuning.h"
 
@@ -545,6 +546,11 @@ int miopalSelfTest(int which) {
             }
             { unpack::Crew unused(3); }   // (a crew that is never run goes away quietly)
             return 0;
+        }
+        if (which == 3) {
+            // the launch layer's once-per-device logic (eight racing first calls, a failing setter, devices without a
+            // bit) and its row dispatcher on every range the kernel units use: launch_layer_selftest.h
+            return launchLayerSelfTest();
         }
         if (which != 1) return -1;
         // (no device call on the way: the handle is never filled, the builders are injected)

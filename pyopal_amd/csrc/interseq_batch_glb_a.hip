@@ -5,13 +5,8 @@
 namespace miopal {
 
 hipError_t launchInterseqBatchGlobalA(const BatchArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    switch (rows) {
-        case 8: return launchBatchGlobalR<8>(a, computeUnits, stream);
-        case 16: return launchBatchGlobalR<16>(a, computeUnits, stream);
-        case 24: return launchBatchGlobalR<24>(a, computeUnits, stream);
-        case 32: return launchBatchGlobalR<32>(a, computeUnits, stream);
-    }
-    return hipErrorInvalidValue;
+    // (the row classes, kBatchRowClasses, are no arithmetic sequence: a list)
+    return dispatchRowList<8, 16, 24, 32>(rows, [&](auto r) { return launchBatchGlobalR<r>(a, computeUnits, stream); });
 }
 
 }  // namespace miopal

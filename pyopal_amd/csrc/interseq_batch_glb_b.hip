@@ -5,14 +5,8 @@
 namespace miopal {
 
 hipError_t launchInterseqBatchGlobalB(const BatchArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    switch (rows) {
-        case 40: return launchBatchGlobalR<40>(a, computeUnits, stream);
-        case 48: return launchBatchGlobalR<48>(a, computeUnits, stream);
-        case 56: return launchBatchGlobalR<56>(a, computeUnits, stream);
-        case 60: return launchBatchGlobalR<60>(a, computeUnits, stream);
-        case 64: return launchBatchGlobalR<64>(a, computeUnits, stream);
-    }
-    return hipErrorInvalidValue;
+    // (the row classes, kBatchRowClasses, are no arithmetic sequence: a list)
+    return dispatchRowList<40, 48, 56, 60, 64>(rows, [&](auto r) { return launchBatchGlobalR<r>(a, computeUnits, stream); });
 }
 
 }  // namespace miopal

@@ -226,17 +226,7 @@ __global__ __launch_bounds__(batchSwWaves(R) * kLanes) void interseq_batch_sw_ke
 template <int R, bool LOC>
 static hipError_t launchBatchSwR(const BatchArgs& a, int computeUnits, hipStream_t stream) {
     const size_t lds = PairLayout<R>::bytes(a.nSymbols) + 16;   // table + unit / group counters
-    static uint64_t configured = 0;
-    if (firstUseOnThisDevice(&configured)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&interseq_batch_sw_kernel<R, LOC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
-            return e;
-        }
-    }
+    if (const hipError_t e = allowFullLds<&interseq_batch_sw_kernel<R, LOC>>(); e != hipSuccess) return e;
     const int blocks = std::max(1, std::min(computeUnits, a.nQueries * a.unitsPerQuery));
     hipLaunchKernelGGL((interseq_batch_sw_kernel<R, LOC>), dim3(blocks), dim3(batchSwWaves(R) * kLanes), lds, stream, a);
     return hipGetLastError();
@@ -444,17 +434,7 @@ __global__ __launch_bounds__(globalWaves(R) * kLanes) void interseq_batch_global
 template <int R>
 static hipError_t launchBatchGlobalR(const BatchArgs& a, int computeUnits, hipStream_t stream) {
     const size_t lds = PairLayout<R>::bytes(a.nSymbols) + 16;
-    static uint64_t configured = 0;
-    if (firstUseOnThisDevice(&configured)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&interseq_batch_global_kernel<R>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
-            return e;
-        }
-    }
+    if (const hipError_t e = allowFullLds<&interseq_batch_global_kernel<R>>(); e != hipSuccess) return e;
     constexpr int kGlobalWaves = globalWaves(R);
     const int blocks = std::max(1, std::min(computeUnits, a.nQueries * a.unitsPerQuery));
     hipLaunchKernelGGL((interseq_batch_global_kernel<R>), dim3(blocks), dim3(kGlobalWaves * kLanes), lds, stream, a);

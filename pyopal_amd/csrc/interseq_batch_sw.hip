@@ -5,18 +5,8 @@
 namespace miopal {
 
 hipError_t launchInterseqBatchSw(const BatchArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    switch (rows) {
-        case 8: return launchBatchSwR<8, false>(a, computeUnits, stream);
-        case 16: return launchBatchSwR<16, false>(a, computeUnits, stream);
-        case 24: return launchBatchSwR<24, false>(a, computeUnits, stream);
-        case 32: return launchBatchSwR<32, false>(a, computeUnits, stream);
-        case 40: return launchBatchSwR<40, false>(a, computeUnits, stream);
-        case 48: return launchBatchSwR<48, false>(a, computeUnits, stream);
-        case 56: return launchBatchSwR<56, false>(a, computeUnits, stream);
-        case 60: return launchBatchSwR<60, false>(a, computeUnits, stream);
-        case 64: return launchBatchSwR<64, false>(a, computeUnits, stream);
-    }
-    return hipErrorInvalidValue;
+    // (the row classes, kBatchRowClasses, are no arithmetic sequence: a list)
+    return dispatchRowList<8, 16, 24, 32, 40, 48, 56, 60, 64>(rows, [&](auto r) { return launchBatchSwR<r, false>(a, computeUnits, stream); });
 }
 
 }  // namespace miopal

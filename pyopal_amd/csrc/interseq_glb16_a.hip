@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairGlobalA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairGlobal<2>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairGlobal<2>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

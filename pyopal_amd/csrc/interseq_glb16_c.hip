@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairGlobalC(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairGlobal<34>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairGlobal<34>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairGlobalD(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairGlobal<50>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairGlobal<50>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairGlobalStripsA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairGlobalStrips<32, false>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairGlobalStrips<32, false>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

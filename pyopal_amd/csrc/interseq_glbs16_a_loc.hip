@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairGlobalStripsLocA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairGlobalStrips<32, true>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairGlobalStrips<32, true>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairGlobalStripsB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairGlobalStrips<48, false>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairGlobalStrips<48, false>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairGlobalStripsLocB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairGlobalStrips<48, true>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairGlobalStrips<48, true>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -3,8 +3,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqSignedAllLoc(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream) {
-    return launchFlavour<ArithI16, true, true>(a, rowsPerStrip, waves, stream);
-}
+template hipError_t launchFlavour<ArithI16, true, true>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -3,8 +3,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqSignedDiag(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream) {
-    return launchFlavour<ArithI16Diag, false, false>(a, rowsPerStrip, waves, stream);
-}
+template hipError_t launchFlavour<ArithI16Diag, false, false>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

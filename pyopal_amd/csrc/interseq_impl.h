@@ -864,18 +864,8 @@ static hipError_t launchW(const InterseqArgs& a, int waves, hipStream_t stream) 
 // Rows per strip are a multiple of 8 (one ds_read_b128 = 8 16-bit scores);
 // `waves` (1, 2, 4 or 8) is the number of strips of a group in flight.
 template <typename Arith, bool TRACK_ALL, bool LOC>
-static hipError_t launchFlavour(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream) {
-    switch (rowsPerStrip) {
-        case 8: return launchW<8, Arith, TRACK_ALL, LOC>(a, waves, stream);
-        case 16: return launchW<16, Arith, TRACK_ALL, LOC>(a, waves, stream);
-        case 24: return launchW<24, Arith, TRACK_ALL, LOC>(a, waves, stream);
-        case 32: return launchW<32, Arith, TRACK_ALL, LOC>(a, waves, stream);
-        case 40: return launchW<40, Arith, TRACK_ALL, LOC>(a, waves, stream);
-        case 48: return launchW<48, Arith, TRACK_ALL, LOC>(a, waves, stream);
-        case 56: return launchW<56, Arith, TRACK_ALL, LOC>(a, waves, stream);
-        case 64: return launchW<64, Arith, TRACK_ALL, LOC>(a, waves, stream);
-    }
-    return hipErrorInvalidValue;
+hipError_t launchFlavour(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream) {
+    return dispatchRows<8, 8, 8>(rowsPerStrip, [&](auto r) { return launchW<r, Arith, TRACK_ALL, LOC>(a, waves, stream); });
 }
 
 
@@ -893,10 +883,8 @@ static_assert(kPairWaves == kPairWavesPerGroup, "common.h mirrors this");
 
 template <int R>
 struct PairLayout {
-    static constexpr int kRowSlots = ((R + 3) / 4) | 1;  // 16-byte slots per row, odd: rows start on different slots
-    static __host__ __device__ constexpr size_t bytes(int nSymbols) {
-        return (size_t)nSymbols * nSymbols * kRowSlots * 16;
-    }
+    static constexpr int kRowSlots = pairRowSlots(R);
+    static __host__ __device__ constexpr size_t bytes(int nSymbols) { return pairLdsBytes(R, nSymbols); }
 };
 
 template <int R, typename Arith>
@@ -1014,29 +1002,10 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_kernel(Inte
     }
 }
 
-// per-device: hipFuncSetAttribute applies to the current device only
-static inline bool firstUseOnThisDevice(uint64_t* seen) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-    const uint64_t bit = 1ull << dev;
-    const uint64_t old = __atomic_fetch_or(seen, bit, __ATOMIC_RELAXED);
-    return !(old & bit);
-}
-
 template <int R, typename Arith>
 static hipError_t launchPairR(const InterseqArgs& a, int computeUnits, hipStream_t stream) {
     const size_t lds = PairLayout<R>::bytes(a.nSymbols);
-    static uint64_t configured = 0;  // one bit per device: the attribute belongs to the device
-    if (firstUseOnThisDevice(&configured)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&interseq_pair_kernel<R, Arith>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
-            return e;
-        }
-    }
+    if (const hipError_t e = allowFullLds<&interseq_pair_kernel<R, Arith>>(); e != hipSuccess) return e;
     // (every CU takes part even when the groups are fewer than its wavefronts: the first round hands
     // out group g to wavefront tier g / blocks of workgroup g % blocks, and a wavefront alone on its
     // SIMD sweeps its group three times faster than one of three)
@@ -1048,19 +1017,9 @@ static hipError_t launchPairR(const InterseqArgs& a, int computeUnits, hipStream
 // Smith-Waterman, one strip, pair-indexed profile. Returns hipErrorInvalidValue when
 // the table does not fit LDS (the caller then uses the v_perm variant).
 template <typename Arith>
-static hipError_t launchPairFlavour(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
+hipError_t launchPairFlavour(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
     if (a.nStrips != 1) return hipErrorInvalidValue;
-    switch (rowsPerStrip) {
-        case 8: return launchPairR<8, Arith>(a, computeUnits, stream);
-        case 16: return launchPairR<16, Arith>(a, computeUnits, stream);
-        case 24: return launchPairR<24, Arith>(a, computeUnits, stream);
-        case 32: return launchPairR<32, Arith>(a, computeUnits, stream);
-        case 40: return launchPairR<40, Arith>(a, computeUnits, stream);
-        case 48: return launchPairR<48, Arith>(a, computeUnits, stream);
-        case 56: return launchPairR<56, Arith>(a, computeUnits, stream);
-        case 64: return launchPairR<64, Arith>(a, computeUnits, stream);
-    }
-    return hipErrorInvalidValue;
+    return dispatchRows<8, 8, 8>(rowsPerStrip, [&](auto r) { return launchPairR<r, Arith>(a, computeUnits, stream); });
 }
 
 // ---- single-strip Smith-Waterman on biased integer halves, column-shifted ---------
@@ -1641,17 +1600,7 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
 template <int R, bool LOC>
 static hipError_t launchPairBiasedR(const InterseqArgs& a, int computeUnits, hipStream_t stream) {
     const size_t lds = PairLayout<R>::bytes(a.nSymbols) + 16 + kPaceInts * sizeof(int);  // table + per-SIMD counters (+ pacing)
-    static uint64_t configured = 0;  // one bit per device; setting the attribute twice is harmless
-    if (firstUseOnThisDevice(&configured)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&interseq_pair_biased_kernel<R, LOC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
-            return e;
-        }
-    }
+    if (const hipError_t e = allowFullLds<&interseq_pair_biased_kernel<R, LOC>>(); e != hipSuccess) return e;
     // (every CU takes part even when the groups are fewer than its wavefronts: the first round hands
     // out group g to wavefront tier g / blocks of workgroup g % blocks, and a wavefront alone on its
     // SIMD sweeps its group three times faster than one of three)
@@ -1665,53 +1614,22 @@ static hipError_t launchPairBiasedR(const InterseqArgs& a, int computeUnits, hip
 template <int R>
 static hipError_t launchPairBiasedSplitR(const InterseqArgs& a, hipStream_t stream) {
     const size_t lds = PairLayout<R>::bytes(a.nSymbols) + 16 + kPaceInts * sizeof(int);
-    static uint64_t configured = 0;
-    if (firstUseOnThisDevice(&configured)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&interseq_pair_biased_kernel<R, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
-            return e;
-        }
-    }
+    if (const hipError_t e = allowFullLds<&interseq_pair_biased_kernel<R, false, true>>(); e != hipSuccess) return e;
     if (a.splitBlocks < 1 || !a.chunkPrefix || !a.splitState || !a.splitFlags) return hipErrorInvalidValue;
     hipLaunchKernelGGL((interseq_pair_biased_kernel<R, false, true>), dim3(a.splitBlocks), dim3(kPairWaves * kLanes), lds, stream, a);
     return hipGetLastError();
 }
 
 template <int kLo, bool LOC>
-static hipError_t launchPairBiased(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
+hipError_t launchPairBiased(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
     if (a.nStrips != 1) return hipErrorInvalidValue;
     // rows: kLo, kLo + 2, ..., kLo + 14; the translation units interseq_swb16_{a,b,c,d}[_loc].hip share the
     // even counts 2..64, interseq_swb16_{a,b,c,d}[_loc]_odd.hip the odd ones 1..63
     if constexpr (!LOC) {
-        if (a.splitMode != 0) {
-            switch (rowsPerStrip - kLo) {
-                case 0: return launchPairBiasedSplitR<kLo>(a, stream);
-                case 2: return launchPairBiasedSplitR<kLo + 2>(a, stream);
-                case 4: return launchPairBiasedSplitR<kLo + 4>(a, stream);
-                case 6: return launchPairBiasedSplitR<kLo + 6>(a, stream);
-                case 8: return launchPairBiasedSplitR<kLo + 8>(a, stream);
-                case 10: return launchPairBiasedSplitR<kLo + 10>(a, stream);
-                case 12: return launchPairBiasedSplitR<kLo + 12>(a, stream);
-                case 14: return launchPairBiasedSplitR<kLo + 14>(a, stream);
-            }
-            return hipErrorInvalidValue;
-        }
+        if (a.splitMode != 0)
+            return dispatchRows<kLo, 2, kPairUnitCounts>(rowsPerStrip, [&](auto r) { return launchPairBiasedSplitR<r>(a, stream); });
     }
-    switch (rowsPerStrip - kLo) {
-        case 0: return launchPairBiasedR<kLo, LOC>(a, computeUnits, stream);
-        case 2: return launchPairBiasedR<kLo + 2, LOC>(a, computeUnits, stream);
-        case 4: return launchPairBiasedR<kLo + 4, LOC>(a, computeUnits, stream);
-        case 6: return launchPairBiasedR<kLo + 6, LOC>(a, computeUnits, stream);
-        case 8: return launchPairBiasedR<kLo + 8, LOC>(a, computeUnits, stream);
-        case 10: return launchPairBiasedR<kLo + 10, LOC>(a, computeUnits, stream);
-        case 12: return launchPairBiasedR<kLo + 12, LOC>(a, computeUnits, stream);
-        case 14: return launchPairBiasedR<kLo + 14, LOC>(a, computeUnits, stream);
-    }
-    return hipErrorInvalidValue;
+    return dispatchRows<kLo, 2, kPairUnitCounts>(rowsPerStrip, [&](auto r) { return launchPairBiasedR<r, LOC>(a, computeUnits, stream); });
 }
 
 // ---- Smith-Waterman scores of SEVERAL strips on the pair table (round 2) -----------
@@ -2122,50 +2040,23 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_strips_kern
 template <int R, bool LOC, bool KNOWN = false>
 static hipError_t launchPairStripsR(const InterseqArgs& a, int computeUnits, hipStream_t stream) {
     const size_t lds = PairLayout<R>::bytes(a.nSymbols) + 16 + kPaceInts * sizeof(int);  // table + the unit in flight + pacing
-    static uint64_t configured = 0;  // one bit per device
-    if (firstUseOnThisDevice(&configured)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&interseq_pair_strips_kernel<R, LOC, KNOWN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
-            return e;
-        }
-    }
+    if (const hipError_t e = allowFullLds<&interseq_pair_strips_kernel<R, LOC, KNOWN>>(); e != hipSuccess) return e;
     const int nBatches = (a.nGroups + a.batchGroups - 1) / a.batchGroups;
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(computeUnits, (int64_t)nBatches * a.nStrips));
     hipLaunchKernelGGL((interseq_pair_strips_kernel<R, LOC, KNOWN>), dim3(blocks), dim3(kPairWaves * kLanes), lds, stream, a);
     return hipGetLastError();
 }
 
-constexpr int kStripsMaxRows = 52;      // taller strips spill (the boundary rows cost 9 registers)
-constexpr int kStripsMaxRowsLoc = 48;   // with end locations
-constexpr int kStripsMaxRowsKnown = 40; // second pass of an `end` search (a row scan inside the column loop)
-static_assert(kStripsMaxRows == kPairStripsMaxRows && kStripsMaxRowsLoc == kPairStripsMaxRowsLoc &&
-              kStripsMaxRowsKnown == kPairStripsMaxRowsKnown, "common.h mirrors these");
-template <int kLo, int kStep, bool LOC, bool KNOWN>
-static hipError_t launchPairStripsCase(const InterseqArgs& a, int computeUnits, hipStream_t stream) {
-    if constexpr (kLo + kStep <= (KNOWN ? kStripsMaxRowsKnown : LOC ? kStripsMaxRowsLoc : kStripsMaxRows))
-        return launchPairStripsR<kLo + kStep, LOC, KNOWN>(a, computeUnits, stream);
-    else return hipErrorInvalidValue;
-}
-template <int kLo, bool LOC, bool KNOWN = false>
-static hipError_t launchPairStrips(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
+// (the tallest strips, kPairStripsMaxRows*: taller ones spill - the boundary rows cost 9 registers, the row scan of
+// the known-optimum pass sits inside the column loop - and are not even instantiated)
+template <int kLo, bool LOC, bool KNOWN>
+hipError_t launchPairStrips(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
     if (a.nStrips < 2 || !a.unitCounter || !a.unitFlags || !a.boundary[0] || !a.boundary[1] || a.batchGroups < 1 ||
         a.batchGroups > kPairWaves || ((LOC || KNOWN) && !a.stripKeys) || (KNOWN && !a.known))
         return hipErrorInvalidValue;
-    switch (rowsPerStrip - kLo) {
-        case 0: return launchPairStripsCase<kLo, 0, LOC, KNOWN>(a, computeUnits, stream);
-        case 2: return launchPairStripsCase<kLo, 2, LOC, KNOWN>(a, computeUnits, stream);
-        case 4: return launchPairStripsCase<kLo, 4, LOC, KNOWN>(a, computeUnits, stream);
-        case 6: return launchPairStripsCase<kLo, 6, LOC, KNOWN>(a, computeUnits, stream);
-        case 8: return launchPairStripsCase<kLo, 8, LOC, KNOWN>(a, computeUnits, stream);
-        case 10: return launchPairStripsCase<kLo, 10, LOC, KNOWN>(a, computeUnits, stream);
-        case 12: return launchPairStripsCase<kLo, 12, LOC, KNOWN>(a, computeUnits, stream);
-        case 14: return launchPairStripsCase<kLo, 14, LOC, KNOWN>(a, computeUnits, stream);
-    }
-    return hipErrorInvalidValue;
+    constexpr int kMax = KNOWN ? kPairStripsMaxRowsKnown : LOC ? kPairStripsMaxRowsLoc : kPairStripsMaxRows;
+    return dispatchRows<kLo, 2, kPairUnitCounts, kMax>(
+        rowsPerStrip, [&](auto r) { return launchPairStripsR<r, LOC, KNOWN>(a, computeUnits, stream); });
 }
 
 // ---- one-strip NW / HW / OV on biased integer halves, column-shifted --------------
@@ -2456,17 +2347,7 @@ __global__ __launch_bounds__(globalWaves(R) * kLanes) void interseq_pair_global_
 template <int R>
 static hipError_t launchPairGlobalR(const InterseqArgs& a, int computeUnits, hipStream_t stream) {
     const size_t lds = PairLayout<R>::bytes(a.nSymbols) + 16 + kPaceInts * sizeof(int);
-    static uint64_t configured = 0;
-    if (firstUseOnThisDevice(&configured)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&interseq_pair_global_kernel<R>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
-            return e;
-        }
-    }
+    if (const hipError_t e = allowFullLds<&interseq_pair_global_kernel<R>>(); e != hipSuccess) return e;
     constexpr int kGlobalWaves = globalWaves(R);
     const int blocks = std::max(1, std::min(computeUnits, a.nGroups));   // (see launchPairBiasedR)
     hipLaunchKernelGGL((interseq_pair_global_kernel<R>), dim3(blocks), dim3(kGlobalWaves * kLanes), lds, stream, a);
@@ -2474,19 +2355,9 @@ static hipError_t launchPairGlobalR(const InterseqArgs& a, int computeUnits, hip
 }
 
 template <int kLo>
-static hipError_t launchPairGlobal(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
+hipError_t launchPairGlobal(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
     if (a.nStrips != 1) return hipErrorInvalidValue;
-    switch (rowsPerStrip - kLo) {
-        case 0: return launchPairGlobalR<kLo>(a, computeUnits, stream);
-        case 2: return launchPairGlobalR<kLo + 2>(a, computeUnits, stream);
-        case 4: return launchPairGlobalR<kLo + 4>(a, computeUnits, stream);
-        case 6: return launchPairGlobalR<kLo + 6>(a, computeUnits, stream);
-        case 8: return launchPairGlobalR<kLo + 8>(a, computeUnits, stream);
-        case 10: return launchPairGlobalR<kLo + 10>(a, computeUnits, stream);
-        case 12: return launchPairGlobalR<kLo + 12>(a, computeUnits, stream);
-        case 14: return launchPairGlobalR<kLo + 14>(a, computeUnits, stream);
-    }
-    return hipErrorInvalidValue;
+    return dispatchRows<kLo, 2, kPairUnitCounts>(rowsPerStrip, [&](auto r) { return launchPairGlobalR<r>(a, computeUnits, stream); });
 }
 
 // H[row] for a wave-uniform, run-time `row` in [LO, HI]: a binary tree of scalar branches (the opaque
@@ -2899,50 +2770,20 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_global_stri
 template <int R, bool LOC>
 static hipError_t launchPairGlobalStripsR(const InterseqArgs& a, int computeUnits, hipStream_t stream) {
     const size_t lds = PairLayout<R>::bytes(a.nSymbols) + 16 + kPaceInts * sizeof(int);  // table + the unit in flight + pacing
-    static uint64_t configured = 0;  // one bit per device
-    if (firstUseOnThisDevice(&configured)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&interseq_pair_global_strips_kernel<R, LOC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
-            return e;
-        }
-    }
+    if (const hipError_t e = allowFullLds<&interseq_pair_global_strips_kernel<R, LOC>>(); e != hipSuccess) return e;
     const int nBatches = (a.nGroups + a.batchGroups - 1) / a.batchGroups;
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(computeUnits, (int64_t)nBatches * a.nStrips));
     hipLaunchKernelGGL((interseq_pair_global_strips_kernel<R, LOC>), dim3(blocks), dim3(kPairWaves * kLanes), lds, stream, a);
     return hipGetLastError();
 }
 
-template <int kLo, int kStep, bool LOC>
-static hipError_t launchPairGlobalStripsCase(const InterseqArgs& a, int computeUnits, hipStream_t stream) {
-    if constexpr (kLo + kStep <= (LOC ? kStripsMaxRowsLoc : kStripsMaxRows))
-        return launchPairGlobalStripsR<kLo + kStep, LOC>(a, computeUnits, stream);
-    else return hipErrorInvalidValue;
-}
 template <int kLo, bool LOC>
-static hipError_t launchPairGlobalStrips(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
+hipError_t launchPairGlobalStrips(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
     if (a.nStrips < 2 || !a.unitCounter || !a.unitFlags || !a.boundary[0] || !a.boundary[1] || a.batchGroups < 1 ||
         a.batchGroups > kPairWaves || (LOC && !a.stripKeys) || a.region == kAllCells)
         return hipErrorInvalidValue;
-    switch (rowsPerStrip - kLo) {
-        case 0: return launchPairGlobalStripsCase<kLo, 0, LOC>(a, computeUnits, stream);
-        case 2: return launchPairGlobalStripsCase<kLo, 2, LOC>(a, computeUnits, stream);
-        case 4: return launchPairGlobalStripsCase<kLo, 4, LOC>(a, computeUnits, stream);
-        case 6: return launchPairGlobalStripsCase<kLo, 6, LOC>(a, computeUnits, stream);
-        case 8: return launchPairGlobalStripsCase<kLo, 8, LOC>(a, computeUnits, stream);
-        case 10: return launchPairGlobalStripsCase<kLo, 10, LOC>(a, computeUnits, stream);
-        case 12: return launchPairGlobalStripsCase<kLo, 12, LOC>(a, computeUnits, stream);
-        case 14: return launchPairGlobalStripsCase<kLo, 14, LOC>(a, computeUnits, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
-// Bytes of LDS the pair table needs for this strip height (host-side sizing).
-static inline size_t pairTableBytes(int rowsPerStrip, int nSymbols) {
-    return (size_t)nSymbols * nSymbols * (size_t)(((rowsPerStrip + 3) / 4) | 1) * 16;
+    return dispatchRows<kLo, 2, kPairUnitCounts, LOC ? kPairStripsMaxRowsLoc : kPairStripsMaxRows>(
+        rowsPerStrip, [&](auto r) { return launchPairGlobalStripsR<r, LOC>(a, computeUnits, stream); });
 }
 
 }  // namespace miopal

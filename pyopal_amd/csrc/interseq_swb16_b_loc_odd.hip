@@ -5,8 +5,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairSwBiasedLocOddB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairBiased<17, true>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairBiased<17, true>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

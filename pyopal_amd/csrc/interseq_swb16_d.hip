@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairSwBiasedD(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairBiased<50, false>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairBiased<50, false>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

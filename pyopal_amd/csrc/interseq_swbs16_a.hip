@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairSwStripsA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairStrips<32, false>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairStrips<32, false>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

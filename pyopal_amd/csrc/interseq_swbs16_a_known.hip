@@ -5,8 +5,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairSwStripsKnownA(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairStrips<32, false, true>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairStrips<32, false, true>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairSwStripsB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairStrips<48, false>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairStrips<48, false>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -5,8 +5,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqPairSwStripsLocB(const InterseqArgs& a, int rows, int computeUnits, hipStream_t stream) {
-    return launchPairStrips<48, true>(a, rows, computeUnits, stream);
-}
+template hipError_t launchPairStrips<48, true>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -3,12 +3,8 @@
 
 namespace miopal {
 
-hipError_t launchInterseqSwHalf(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream) {
-    return launchFlavour<ArithSwF16, true, false>(a, rowsPerStrip, waves, stream);
-}
+template hipError_t launchFlavour<ArithSwF16, true, false>(const InterseqArgs&, int, int, hipStream_t);
 
-hipError_t launchInterseqPairSwHalf(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
-    return launchPairFlavour<ArithSwF16>(a, rowsPerStrip, computeUnits, stream);
-}
+template hipError_t launchPairFlavour<ArithSwF16>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -3,8 +3,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqSwHalfLoc(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream) {
-    return launchFlavour<ArithSwF16, true, true>(a, rowsPerStrip, waves, stream);
-}
+template hipError_t launchFlavour<ArithSwF16, true, true>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

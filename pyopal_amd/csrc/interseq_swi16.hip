@@ -3,12 +3,8 @@
 
 namespace miopal {
 
-hipError_t launchInterseqSwInt16(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream) {
-    return launchFlavour<ArithSwI16, true, false>(a, rowsPerStrip, waves, stream);
-}
+template hipError_t launchFlavour<ArithSwI16, true, false>(const InterseqArgs&, int, int, hipStream_t);
 
-hipError_t launchInterseqPairSwInt16(const InterseqArgs& a, int rowsPerStrip, int computeUnits, hipStream_t stream) {
-    return launchPairFlavour<ArithSwI16>(a, rowsPerStrip, computeUnits, stream);
-}
+template hipError_t launchPairFlavour<ArithSwI16>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

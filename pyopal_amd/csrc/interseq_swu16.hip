@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqSwShifted(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream) {
-    return launchFlavour<ArithSwU16, true, false>(a, rowsPerStrip, waves, stream);
-}
+template hipError_t launchFlavour<ArithSwU16, true, false>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

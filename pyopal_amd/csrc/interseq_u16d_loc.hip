@@ -4,8 +4,6 @@
 
 namespace miopal {
 
-hipError_t launchInterseqUnsignedDiagLoc(const InterseqArgs& a, int rowsPerStrip, int waves, hipStream_t stream) {
-    return launchFlavour<ArithU16Diag, false, true>(a, rowsPerStrip, waves, stream);
-}
+template hipError_t launchFlavour<ArithU16Diag, false, true>(const InterseqArgs&, int, int, hipStream_t);
 
 }  // namespace miopal

@@ -839,27 +839,9 @@ bool packedTraceFits(int queryLength, int alphabet, int open, int ext, int maxSc
     return true;
 }
 
-static inline bool firstUseHere(uint64_t* seen) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-    const uint64_t bit = 1ull << dev;
-    const uint64_t old = __atomic_fetch_or(seen, bit, __ATOMIC_RELAXED);
-    return !(old & bit);
-}
-
 template <bool BIASED, int WAVES, bool MULTI>
 static hipError_t launchPackedTraceAs(const PerPairArgs& a, size_t ldsBytes, hipStream_t stream) {
-    static uint64_t configured = 0;   // one bit per device: the attribute belongs to the device
-    if (firstUseHere(&configured)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&perpair_packed_trace_kernel<BIASED, WAVES, MULTI>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            __atomic_fetch_and(&configured, ~(1ull << dev), __ATOMIC_RELAXED);
-            return e;
-        }
-    }
+    if (const hipError_t e = allowFullLds<&perpair_packed_trace_kernel<BIASED, WAVES, MULTI>>(); e != hipSuccess) return e;
     const int waves = (a.nJobs + 2 * kLanes - 1) / (2 * kLanes);
     hipLaunchKernelGGL((perpair_packed_trace_kernel<BIASED, WAVES, MULTI>), dim3((waves + WAVES - 1) / WAVES), dim3(WAVES * kLanes),
                        ldsBytes, stream, a);

@@ -105,6 +105,16 @@ def test_operations_unpacked_from_two_bits_each(capi):
     assert capi.lib().miopalSelfTest(2) == 0
 
 
+@pytest.mark.timeout(60)
+def test_launch_layer_once_per_device_and_row_dispatch(capi):
+    # launch_layer.h: (a) the dynamic LDS limit is raised once per device, and the device's bit is published only after
+    # the setter has succeeded - eight threads make the first call at once and none returns before a setter call has
+    # completed; a failing setter leaves the bit clear and is tried again; a device outside 0..63 sets every time.
+    # (b) the row dispatcher reaches exactly the instantiation of the requested row count, on every range the kernel
+    # units use, and refuses every other count from -1 to 70. Needs no device: the setter is injected.
+    assert capi.lib().miopalSelfTest(3) == 0
+
+
 def test_tuning_switches_are_arguments_not_environment(capi, monkeypatch):
     """include/miopal.h, miopalSetTuning: the library reads MIOPAL_* from the environment once (tests/conftest.py
     sets MIOPAL_NO_SMALL_SEARCH before the first use); afterwards the environment is not looked at again - a
