@@ -35,6 +35,7 @@
 #include "../../include/miopal.h"
 #include "common.h"
 #include "launch_layer_selftest.h"
+#include "score_ranges_selftest.h"
 #include "select_top.h"
 #include "tuning.h"
 
@@ -118,6 +119,14 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// the range check of the 32-bit kernels (score_ranges.h), as every entry point reports it
+int checkInt32Range(const ScoreModel& m, int64_t Q, int64_t maxLen) {
+    const int64_t bound = int32Bound(m, Q, maxLen);
+    if (!int32Fits(bound))
+        return fail(OPAL_ERR_OVERFLOW, "scores may exceed the 32-bit range (bound %lld)", (long long)bound);
+    return 0;
+}
+
 #define HIP_TRY(expr)                                                                      \
     do {                                                                                   \
         hipError_t _e = (expr);                                                            \
@@ -183,7 +192,6 @@ inline hipError_t createUploadStream(hipStream_t* s) {
 constexpr int kLongTarget = 8192;          // longer targets always take the intra-sequence path
 constexpr int64_t kDirBudgetOneLaunch = 8ll << 30;   // directions of every batch of a `full` search at once (host_full.inc)
 constexpr int64_t kDirBudget = 2ll << 30;  // direction workspace: 2 x this per device-resident traceback batch, 1 x per host-built batch
-constexpr int64_t kInt32Safe = 1ll << 29;
 constexpr int kMaxDirectRecompute = 2048;  // lanes that left their range and are sent straight to int32: at least this many (see directLimit)
 // A lane that owns a whole target walks its columns one after the other (about 0.8 us per
 // column of 56 rows): whatever the number of targets, the lane-per-target kernels need
@@ -552,6 +560,10 @@ int miopalSelfTest(int which) {
             // bit) and its row dispatcher on every range the kernel units use: launch_layer_selftest.h
             return launchLayerSelfTest();
         }
+        if (which == 4) {
+            // the range model of the host router against literals worked out by hand: score_ranges_selftest.h
+            return scoreRangesSelfTest();
+        }
         if (which != 1) return -1;
         // (no device call on the way: the handle is never filled, the builders are injected)
         std::unique_ptr<MiopalDb> db(new MiopalDb());
@@ -786,12 +798,12 @@ int miopalSearchPssm(MiopalDb* db, const int* rowScores, const unsigned char* co
     if (end == start) return 0;
     {
         // miopalSearch's range check for its 32-bit kernels, with the extreme entries of the rows
-        Search probe{db, nullptr, nullptr, nullptr, Q, gapOpen, gapExt, A, searchType, mode, nullptr, start, end, end - start};
+        ScoreModel m{gapOpen, gapExt, 0, 0};
         if (Q > 0) {
-            probe.maxScore = *std::max_element(rowScores, rowScores + (size_t)Q * A);
-            probe.minScore = *std::min_element(rowScores, rowScores + (size_t)Q * A);
+            m.maxScore = *std::max_element(rowScores, rowScores + (size_t)Q * A);
+            m.minScore = *std::min_element(rowScores, rowScores + (size_t)Q * A);
         }
-        RC_TRY(probe.checkInt32(db->maxLen));
+        RC_TRY(checkInt32Range(m, Q, db->maxLen));
     }
     // (without a consensus - score and end searches - every position is "no residue": the kernels never read it)
     std::vector<unsigned char> none;

@@ -28,40 +28,25 @@ void planBatchQuery(const unsigned char* query, int Q, int open, int ext, const 
     BatchPlan& p = *out;
     p = BatchPlan{};
     if (Q < 1 || Q > kMaxStripRows || open < 0 || ext < 0 || maxScore > 16383 || minScore < -16383) return;
+    const ScoreModel m{open, ext, maxScore, minScore};
     // (miopalSearch's range check for its 32-bit kernels: a query that fails it fails there)
-    const int64_t mag = std::max<int64_t>(std::llabs((long long)maxScore), std::llabs((long long)minScore));
-    if (2 * (int64_t)open + ((int64_t)Q + maxLen) * ext + std::min<int64_t>(Q, maxLen) * mag + mag >= kInt32Safe) return;
+    if (!int32Fits(int32Bound(m, Q, maxLen))) return;
     const int R = batchRowClass(Q);
     if (R == 0 || !interseqPairFits(R, A + 1) || minScore <= kBiasedPad) return;
     const bool locate = searchType != OPAL_SEARCH_SCORE;
     if (mode == OPAL_MODE_SW) {
-        const int bits = locate ? locRowBitsHost(R) : 0;
-        const int64_t up = std::max<int64_t>((int64_t)maxScore + ext, (int64_t)ext - open);
-        const int64_t down = std::max<int64_t>(-((int64_t)minScore + ext), (int64_t)open - ext);
-        if ((up << bits) > kBiasedMaxStepUp || (down << bits) > (locate ? kLocGuardBand : kBiasedMaxMagnitude) ||
-            5 * ((int64_t)ext << bits) > kLocMaxShift)
-            return;
-        p.biasedLimit = (int)(((locate ? 0x7C00 - kLocZeroPattern - kLocMaxShift : kBiasedScoreLimit) -
-                               std::max<int64_t>(0, (up << bits) - 0x0400)) >> bits);
+        // (the row keys of the class's R rows)
+        const int bits = rowKeyBits(R, locate);
+        if (!biasedBandFits(m, bits, locate)) return;
+        p.biasedLimit = biasedLimit(m, bits, locate);
         // (every residue aligned at most once, at best with its most favourable partner)
-        int64_t queryBest = 0;
-        for (int i = 0; i < Q; ++i) {
-            int rowMax = 0;
-            for (int t = 0; t < A; ++t) rowMax = std::max(rowMax, matrix[query[i] * A + t]);
-            queryBest += rowMax;
-        }
-        p.mayOverflow = std::min<int64_t>((int64_t)Q * std::max(maxScore, 0), queryBest) >= p.biasedLimit;
+        const int64_t best = queryBest(Q, A, [&](int i, int t) { return matrix[query[i] * A + t]; });
+        p.mayOverflow = std::min<int64_t>((int64_t)Q * std::max(maxScore, 0), best) >= p.biasedLimit;
     } else {
         // the single-query kernel's static bounds with the class's R rows (padding rows included): the padding
         // rows score -2 ext, which the room below zero covers as well
-        const bool topGap = mode == OPAL_MODE_NW;
-        if ((topGap && open < ext) || 5 * (int64_t)ext > kLocMaxShift) return;
-        const int64_t pos = std::max(maxScore, 0);
-        const int64_t zero = 0x0400 + 3 * (int64_t)open + ((int64_t)R + 4) * ext +
-                             std::max<int64_t>({0, -(int64_t)minScore, 2 * (int64_t)ext});
-        if (zero + (int64_t)R * (pos + ext) + kLocMaxShift + 5 * (int64_t)ext + pos + ((int64_t)R + 4) * ext + open >= 0x7C00)
-            return;
-        p.biasedZero = (int)zero;
+        if (!globalOneStripFits(m, R, mode == OPAL_MODE_NW, true)) return;
+        p.biasedZero = (int)globalZeroPattern(m, R, true);
     }
     p.rows = R;
 }
@@ -124,12 +109,7 @@ static int batchImpl(MiopalDb* db, const unsigned char* queries, const int64_t* 
         Workspace* ws = lease.ws;
         hipStream_t stream = ws->stream;
         DpRules r{};
-        switch (mode) {
-            case OPAL_MODE_NW: r = {1, 1, 0, kLastCell}; break;
-            case OPAL_MODE_HW: r = {0, 1, 0, kLastRow}; break;
-            case OPAL_MODE_OV: r = {0, 0, 0, kLastRowCol}; break;
-            default: r = {0, 0, 1, kAllCells}; break;
-        }
+        rulesForMode(mode, &r);   // (validateBatch has seen the mode)
         const int rules = packRules(r);
         const bool sw = mode == OPAL_MODE_SW;
         // small searches: the wavefront-per-pair kernel for every pair (what miopalSearch does for one query)

@@ -241,14 +241,8 @@ static int searchImpl(MiopalDb* db, const unsigned char* query, int queryLength,
                                           (mode == OPAL_MODE_OV && fr.region == kLastRowCol && !tuned(Tune::NO_PACKED_HW_SCAN));
                 if (scanLanePerPair && profileStride > 0 && packedRegion && !tuned(Tune::NO_PACKED_SCAN)) {
                     // (no cell of a prefix scan beats the query's own best: every residue against its best partner)
-                    int64_t queryBest = 0;
-                    for (int y = 0; y < queryLength; ++y) {
-                        int rowMax = 0;
-                        for (int t = 0; t < alphabetLength; ++t)
-                            rowMax = std::max(rowMax, s.at(y, t));
-                        queryBest += rowMax;
-                    }
-                    const int64_t best = std::min<int64_t>(queryBest, std::min<int64_t>(queryLength, db->maxLen) * std::max(s.maxScore, 0));
+                    const int64_t ownBest = queryBest(queryLength, alphabetLength, [&](int y, int t) { return s.at(y, t); });
+                    const int64_t best = std::min<int64_t>(ownBest, std::min<int64_t>(queryLength, db->maxLen) * std::max(s.maxScore, 0));
                     packedScan = packedScanFits(queryLength, alphabetLength, gapOpen, gapExt, s.maxScore, s.minScore,
                                                 db->maxLen, best, &scanBias, &scanZero, &scanStride, &scanLds) &&
                                  (oneStrip || ((n + 127) / 128) * kLanes * db->maxLen * (int64_t)sizeof(int2) <= (8ll << 30));

@@ -104,11 +104,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
         const size_t nEntries = pssm ? (size_t)(nQueries > 0 ? queryOffsets[nQueries] - queryOffsets[0] : 0) * A : (size_t)A * A;
         const int maxScore = nEntries ? *std::max_element(entries, entries + nEntries) : 0;
         const int minScore = nEntries ? *std::min_element(entries, entries + nEntries) : 0;
-        const int64_t mag = std::max<int64_t>(std::llabs((long long)maxScore), std::llabs((long long)minScore));
-        const int64_t bound = 2 * (int64_t)std::llabs((long long)open) + (maxQ + maxL) * std::llabs((long long)ext) +
-                              std::min(maxQ, maxL) * mag + mag;
-        if (nPairs > 0 && bound >= kInt32Safe)
-            return fail(OPAL_ERR_OVERFLOW, "scores may exceed the 32-bit range (bound %lld)", (long long)bound);
+        if (nPairs > 0) RC_TRY(checkInt32Range({open, ext, maxScore, minScore}, maxQ, maxL));
     }
     if (full) opsOff[0] = 0;
     if (nPairs == 0) return 0;
@@ -129,12 +125,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
     auto qLenOf = [&](int64_t p) { return (int)(qOff[(size_t)pairQuery[p] + 1] - qOff[(size_t)pairQuery[p]]); };
 
     DpRules fr{};
-    switch (mode) {
-        case OPAL_MODE_NW: fr = {1, 1, 0, kLastCell}; break;
-        case OPAL_MODE_HW: fr = {0, 1, 0, kLastRow}; break;
-        case OPAL_MODE_OV: fr = {0, 0, 0, kLastRowCol}; break;
-        default: fr = {0, 0, 1, kAllCells}; break;
-    }
+    rulesForMode(mode, &fr);   // (the mode was checked above)
     // pairs without a DP: the closed forms of the border, no cell and no operations
     std::vector<int64_t> order;   // the other pairs, in the order they are processed
     order.reserve((size_t)nPairs);

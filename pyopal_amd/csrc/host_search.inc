@@ -63,13 +63,13 @@ struct Search {
     int32_t* d_matrix = nullptr;
     int32_t* d_rows = nullptr;         // pssmRows on the device ([Q][A]); null for a plain search
 
-    int rulesFor(int m, DpRules* r) const {
-        switch (m) {
-            case OPAL_MODE_NW: *r = {1, 1, 0, kLastCell}; return 0;
-            case OPAL_MODE_HW: *r = {0, 1, 0, kLastRow}; return 0;
-            case OPAL_MODE_OV: *r = {0, 0, 0, kLastRowCol}; return 0;
-            case OPAL_MODE_SW: *r = {0, 0, 1, kAllCells}; return 0;
-        }
+    // the border / answer rules of `mode`: set by scorePassImpl, read by its steps
+    DpRules r{};
+    int rules = 0;
+    ScoreModel model() const { return {open, ext, maxScore, minScore}; }
+
+    int rulesFor(int m, DpRules* out) const {
+        if (rulesForMode(m, out)) return 0;
         return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", m);
     }
 
@@ -108,18 +108,6 @@ struct Search {
         RC_TRY(ws->get(kMatrix, (size_t)A * A * sizeof(int32_t), &p));
         d_matrix = (int32_t*)p;
         RC_TRY(ws->stageUpload(d_matrix, matrix, (size_t)A * A * sizeof(int32_t), stream));
-        return 0;
-    }
-
-    // Conservative range check for the 32-bit kernels (the reference returns
-    // OPAL_ERR_OVERFLOW when its widest lanes overflow, pyx.in:104-105).
-    int checkInt32(int64_t maxLen) const {
-        const int64_t mag = std::max<int64_t>(std::llabs((long long)maxScore), std::llabs((long long)minScore));
-        const int64_t bound = 2 * (int64_t)std::llabs((long long)open) +
-                              ((int64_t)Q + maxLen) * std::llabs((long long)ext) +
-                              std::min<int64_t>(Q, maxLen) * mag + mag;
-        if (bound >= kInt32Safe)
-            return fail(OPAL_ERR_OVERFLOW, "scores may exceed the 32-bit range (bound %lld)", (long long)bound);
         return 0;
     }
 
@@ -269,22 +257,53 @@ struct Search {
         return j;
     }
 
-    // Score pass (all search types). d_score/d_endI/d_endJ are in database order.
-    int scorePass(int32_t* d_score, int32_t* d_endI, int32_t* d_endJ) {
-        return scorePassImpl(d_score, d_endI, d_endJ, true);
+    // ---- the score pass ------------------------------------------------------------------------------------------
+    // scorePassImpl (at the end) is a sequence of steps: a plan (planWindows .. planLanes: no device call, no
+    // workspace - they read this search's scalars, the handle's sizes, the tuning switches and the view's host
+    // fields), then the profile, the side jobs, the kernel arguments, one of three launches, the scatter.
+    // What one pass through the routing decided: rebuilt by every pass. What has to survive a pass that starts over
+    // (refused launches, the declined probe, two sweeps, what is on the side stream, the cut) is on Search, above.
+    struct ScorePlan {
+        bool sw = false, locate = false;   // Smith-Waterman; end locations wanted
+        // planWindows: long targets as overlapping windows
+        int64_t queryBest = 0;
+        int overlap = 0, stride = 0;
+        int keyBias = 0;                   // HW in windows: scores above -2^22 in the merge keys
+        bool keyed = false;                // windows with end locations: merged by key
+        // planGeneralStrips / planSwPairStrips / planGlobalPairStrips
+        int nStrips = 1, waves = 1;
+        int stripRows = 0;                 // > 0: a multi-strip pair-table kernel, strips of that many rows
+        bool globalStrips = false;         // ... the NW / HW / OV one
+        // planSideCut: the leading groups that leave for the side kernel
+        int firstGroup = 0, firstPos = 0;
+        // planLanes: the lane arithmetic, its limits, and which targets the int32 kernel takes
+        bool pairStrips = false;
+        int rows = 0, qPad = 0, nSym = 0, pairRows = 0;
+        int packedSkip = 0;                // first view position whose packed result is scattered
+        int capGroups = 0, capChunks = 0;
+        bool twoPass = false, rowKeys = false;
+        bool usePair = false, biased = false, globalPair = false;
+        bool swShifted = false, halfFloat = false;
+        int biasedLimit = 0, swBias = 0, swLimit = 0, profileShift = 0;
+        int64_t globalZero = 0;
+        InterseqFlavour flavour = kSwInt16;
+        bool mayOverflow = false;
+        int64_t directLimit = 0;           // flagged lanes redone one by one before the view takes the next rung
+        bool probeEnds = false;            // the strips kernel with row keys: probe the longest groups' scores first
+    };
+    // device buffers of a pass that several steps use
+    struct PassBuffers {
+        void* keys = nullptr;   // merge keys of a windowed search with end locations
+        void* vo = nullptr;     // view-order overflow flags
+        void* ct = nullptr;     // count of flagged lanes
+    };
+    // (a target whose windows are neighbours in the view is queued once)
+    void queueWhole(std::vector<PairJob>& list, int32_t id) const {
+        if (list.empty() || list.back().out != (int32_t)(id - start)) list.push_back(forwardJob(id, rules));
     }
 
-    int scorePassImpl(int32_t* d_score, int32_t* d_endI, int32_t* d_endJ, bool useHalf) {
-        DpRules r;
-        RC_TRY(rulesFor(mode, &r));
-        const int rules = packRules(r);
-        std::vector<PairJob> jobs;
-        RC_TRY(checkInt32(db->maxLen));
-        // a pass that starts over (refused launch, declined probe, next rung) writes the device arrays:
-        // whatever an earlier attempt put into the host-visible buffer is not the result
-        wroteHost = false;
-
-        g_lastRouting[0] = g_lastRouting[1] = g_lastRouting[2] = g_lastRouting[3] = 0;
+    // step 1: the small-search route
+    bool smallSearch() const {
         // Small searches: the wavefront-per-pair kernel has the shorter start-up (0.08-0.1 ms for a handful of targets
         // against 0.26-1.3 ms for the packed kernels' views, tables and persistent launch). Queries of one strip: up to
         // kSmallSearch targets. Longer ones: when an estimate of its time is below one of the packed kernels' - both
@@ -306,14 +325,11 @@ struct Search {
             const double packed = 0.26 + 0.0006 * (double)Q + (Q <= 512 ? 0.0003 * (double)db->maxLen : 0.0);
             small = perPair < packed;
         }
-        if (!interseqUsable() || (small && smallSearchAllowed(db))) {
-            g_lastRouting[0] = n;
-            jobs.reserve((size_t)n);
-            for (int64_t k = start; k < end; ++k) jobs.push_back(forwardJob(k, rules));
-            return runPairs(jobs, false, d_score, d_endI, d_endJ, nullptr);
-        }
+        return small;
+    }
 
-        PhaseTimer spt;
+    // step 2: the window plan
+    void planWindows(ScorePlan& p) const {
         // Smith-Waterman: long targets can be searched as overlapping windows. A
         // local alignment with a positive score has at most Q aligned pairs and, each gap
         // column costing at least min(open, ext), at most Q * max(S) / min(open, ext) gap
@@ -324,14 +340,9 @@ struct Search {
         // (The aligned pairs are bounded by the query itself: every residue is aligned at most once, at best with
         // its most favourable partner - 280 for the 53-aa README query under BLOSUM62, where Q * max(S) says 583:
         // windows that overlap by 384 columns instead of 640.)
-        int64_t queryBest = 0;
-        for (int i = 0; i < Q; ++i) {
-            int rowMax = 0;
-            for (int t = 0; t < A; ++t) rowMax = std::max(rowMax, at(i, t));
-            queryBest += rowMax;
-        }
-        const int64_t pairsBest = std::min<int64_t>((int64_t)Q * std::max(maxScore, 0), queryBest);
-        int overlap = 0;
+        p.queryBest = queryBest(Q, A, [this](int i, int t) { return at(i, t); });
+        const int64_t pairsBest = std::min<int64_t>((int64_t)Q * std::max(maxScore, 0), p.queryBest);
+        p.overlap = 0;
         if (mode == OPAL_MODE_SW && std::min(open, ext) > 0 && maxScore > 0 && (int64_t)Q * maxScore < (1 << 23) &&
             Q < 65536 && db->maxLen < (1 << 24) && !tuned(Tune::NO_SEGMENTS)) {
             const int64_t reach = Q + pairsBest / std::min(open, ext) + 1;
@@ -348,7 +359,7 @@ struct Search {
             const int64_t looseReach = Q + (int64_t)Q * maxScore / std::min(open, ext) + 1;
             const int64_t looseRounded = (looseReach + 127) / 128 * 128;
             const bool cut = looseRounded <= 2048 && db->maxLen > segmentStride((int)looseRounded) + looseRounded;
-            if (cut && rounded <= 2048 && db->maxLen > segmentStride((int)rounded) + rounded) overlap = (int)rounded;
+            if (cut && rounded <= 2048 && db->maxLen > segmentStride((int)rounded) + rounded) p.overlap = (int)rounded;
         }
         // HW (the whole query, free ends in the target) can be cut the same way. Its optimum is at least
         // -(open + (Q - 1) ext) (the query gapped against nothing) and at most Q max(S) minus what its
@@ -357,7 +368,7 @@ struct Search {
         // alignments (the query's head gapped from the free top border), so no window exceeds the whole
         // target and the one that holds the optimal alignment reaches it. NW spans the whole target by
         // definition; OV's last-column candidates only exist in a target's last window: both stay whole.
-        int keyBias = 0;
+        p.keyBias = 0;
         if (mode == OPAL_MODE_HW && std::min(open, ext) > 0 && Q < 4096 && db->maxLen < (1 << 24) &&
             !tuned(Tune::NO_SEGMENTS)) {
             const int64_t gaps = (pairsBest + open + ((int64_t)Q - 1) * ext) / std::min(open, ext);
@@ -367,8 +378,8 @@ struct Search {
             const int64_t looseRounded = (Q + looseGaps + 1 + 127) / 128 * 128;
             const bool cut = looseRounded <= 2048 && db->maxLen > segmentStride((int)looseRounded) + looseRounded;
             if (cut && rounded <= 2048 && db->maxLen > segmentStride((int)rounded) + rounded && lowest < (1 << 21)) {
-                overlap = (int)rounded;
-                keyBias = 1 << 22;   // scores above -2^22 in the key's 24-bit score field
+                p.overlap = (int)rounded;
+                p.keyBias = 1 << 22;   // scores above -2^22 in the key's 24-bit score field
             }
         }
         // Window stride. The overlap is what correctness needs; the stride only trades the length of a window
@@ -377,37 +388,17 @@ struct Search {
         // its cells). When long targets are the bulk of the database rather than its tail - a tenth of 2M
         // targets thirty times as long as the rest: 5.3 TCUPS for Smith-Waterman at Q = 53 where NW, which
         // cannot cut them, ran at 9.6 - a window may be as long as 1.5 balanced shares of a wavefront slot.
-        int stride = overlap > 0 ? segmentStride(overlap) : 0;
-        if (overlap > 0) {
+        p.stride = p.overlap > 0 ? segmentStride(p.overlap) : 0;
+        if (p.overlap > 0) {
             const double share = db->count > 0 ? (double)n / (double)db->count : 1.0;
             const double balancedColumns = (double)db->total * share / ((double)kGroupTargets * 12.0 * db->computeUnits);
-            const int64_t want = (int64_t)(1.5 * balancedColumns) - overlap;
-            if (want > stride) stride = (int)std::min<int64_t>((want + 255) / 256 * 256, 8192);
+            const int64_t want = (int64_t)(1.5 * balancedColumns) - p.overlap;
+            if (want > p.stride) p.stride = (int)std::min<int64_t>((want + 255) / 256 * 256, 8192);
         }
-        std::shared_ptr<View> view;
-        RC_TRY(getView(db, start, end, overlap, &view, stride));
-        spt.mark("    view lookup");
-        // not handled by the packed kernel: can be recomputed beside it
-        std::vector<PairJob> sideJobs;
-        for (int32_t id : view->longIds) sideJobs.push_back(forwardJob(id, rules));
-        // windows of one target are merged with atomicMax: start from 0 (Smith-Waterman scores
-        // are never negative); whole-target results of the int32 kernel are plain stores of the
-        // final value, in either order the maximum is that value
-        const bool keyed = overlap > 0 && searchType != OPAL_SEARCH_SCORE;  // with end locations
-        void* keys = nullptr;
-        if (keyed) {
-            RC_TRY(ws->get(kKeys, (size_t)n * sizeof(unsigned long long), &keys));
-            HIP_TRY(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream));
-        } else if (overlap > 0) {
-            // (Smith-Waterman scores start from 0, HW scores from "minus infinity")
-            if (keyBias) HIP_TRY(launchFillInt32(d_score, (int)n, INT32_MIN, stream));
-            else HIP_TRY(hipMemsetAsync(d_score, 0, (size_t)n * sizeof(int32_t), stream));
-        }
-        // (a target whose windows are neighbours in the view is queued once)
-        auto queueWhole = [&](std::vector<PairJob>& list, int32_t id) {
-            if (list.empty() || list.back().out != (int32_t)(id - start)) list.push_back(forwardJob(id, rules));
-        };
+    }
 
+    // step 3: the strip plan - the general kernel's strips, then either pair-table strips kernel where it pays
+    void planGeneralStrips(const View* view, ScorePlan& p) const {
         // Strips and wavefronts per workgroup for queries of more than 64 rows. A workgroup of W
         // wavefronts pipelines W strips of one group; a round with fewer strips than W leaves
         // wavefronts (and their registers and LDS) idle, so the number of strips is a multiple
@@ -417,8 +408,8 @@ struct Search {
         // pipeline per cell, W = 8 pays off when there are too few groups to fill the chip
         // (Q=2000 vs 100k x 2000: 782 groups), W = 1 (strips in turn through HBM) only with
         // thousands of groups.
-        int nStrips = std::max(1, (Q + kMaxStripRows - 1) / kMaxStripRows);
-        int waves = nStrips >= 8 ? 8 : nStrips >= 4 ? 4 : nStrips >= 2 ? 2 : 1;
+        p.nStrips = std::max(1, (Q + kMaxStripRows - 1) / kMaxStripRows);
+        p.waves = p.nStrips >= 8 ? 8 : p.nStrips >= 4 ? 4 : p.nStrips >= 2 ? 2 : 1;
         if (Q > kMaxStripRows) {
             const double need = 24.0 * db->computeUnits;  // wavefronts that fill the chip
             const double groups = std::max(1, view->nGroups);
@@ -434,8 +425,8 @@ struct Search {
                 if (parallel < need) cost *= need / parallel;
                 if (bestCost == 0 || cost < bestCost) {
                     bestCost = cost;
-                    nStrips = strips;
-                    waves = w;
+                    p.nStrips = strips;
+                    p.waves = w;
                 }
             }
         }
@@ -444,34 +435,31 @@ struct Search {
             const int least = std::max(1, (Q + kMaxStripRows - 1) / kMaxStripRows);
             if (sscanf(o, "%d,%d", &a, &b) == 2 && a >= least && (b == 1 || b == 2 || b == 4 || b == 8) &&
                 (a - 1) * (((Q + a - 1) / a + 7) / 8 * 8) < Q) {
-                nStrips = a;
-                waves = b;
+                p.nStrips = a;
+                p.waves = b;
             }
         }
+    }
+
+    // (sets twoPassEnds where MIOPAL_TWO_PASS_ENDS asks for two sweeps)
+    void planSwPairStrips(const View* view, bool useHalf, ScorePlan& p) {
         // Smith-Waterman scores of more rows than one pair table holds: the pair-table kernel strip by
         // strip (interseq_pair_strips_kernel: units of (batch of 12 groups, strip), boundary rows
         // through HBM), when the scores and gap costs fit the biased halves' guard band. Strips of at
         // most 52 rows (the kernel's register budget), all of the same even height.
-        int stripRows = 0;
+        p.stripRows = 0;
         {
             const char* noPair = tuned(Tune::NO_PAIR_TABLE);
-            const int64_t up = std::max<int64_t>((int64_t)maxScore + ext, (int64_t)ext - open);
-            const int64_t down = std::max<int64_t>(-((int64_t)minScore + ext), (int64_t)open - ext);
             // (with end locations every value is scaled by 2^bits: the row inside a strip of 32 .. 48 rows)
             const bool wantEnds = searchType != OPAL_SEARCH_SCORE;
             // (two sweeps: unscaled values like a score search, strips of at most 40 rows; MIOPAL_TWO_PASS_ENDS=1
             // asks for them whatever the scores - tests)
             if (wantEnds && mode == OPAL_MODE_SW && tuned(Tune::TWO_PASS_ENDS)) twoPassEnds = true;
             const bool rowKeyEnds = wantEnds && !twoPassEnds;
-            auto band = [&](int rowsP) {
-                const int sbits = rowKeyEnds ? locRowBitsHost(rowsP) : 0;
-                return (up << sbits) <= kBiasedMaxStepUp && (down << sbits) <= (rowKeyEnds ? kLocGuardBand : kBiasedMaxMagnitude) &&
-                       5 * ((int64_t)ext << sbits) <= kLocMaxShift && minScore > kBiasedPad;
-            };
-            const int single = std::max(2, (Q + 1) / 2 * 2);
-            const bool oneStrip = Q <= kLanes && interseqPairFits(single, A + 1);
-            int maxRows = !wantEnds ? kPairStripsMaxRows : twoPassEnds ? kPairStripsMaxRowsKnown : kPairStripsMaxRowsLoc;
-            while (maxRows >= 32 && !interseqPairFits(maxRows, A + 1)) maxRows -= 2;
+            auto band = [&](int rowsP) { return biasedBandFits(model(), rowKeyBits(rowsP, rowKeyEnds), rowKeyEnds); };
+            const bool oneStrip = oneStripFits(Q, A + 1, interseqPairFits);
+            const int maxRows = tallestStrip(!wantEnds ? kPairStripsMaxRows : twoPassEnds ? kPairStripsMaxRowsKnown : kPairStripsMaxRowsLoc,
+                                             A + 1, interseqPairFits);
             if (mode == OPAL_MODE_SW && Q < (1 << 20) && useHalf && !oneStrip && maxRows >= 32 &&
                 !pairStripsRefused && !(wantEnds && stripsEndsDeclined && !twoPassEnds) && !(noPair && noPair[0] == '1') && !tuned(Tune::NO_BIASED) &&
                 !tuned(Tune::NO_PAIR_STRIPS) && !tuned(Tune::STRIPS)) {
@@ -488,9 +476,7 @@ struct Search {
                 // at a third of that. The longest group must therefore be short against the launch, or
                 // it IS the launch: log-normal lengths, 500k targets at Q = 150, windows of 3072 columns:
                 // 5.3 ms against the general kernel's 2.9 ms.
-                int64_t totalChunks = 0;
-                for (int c : view->groupChunksHost) totalChunks += c;
-                const int64_t balanced = totalChunks * ns / ((int64_t)db->computeUnits * 12);
+                const int64_t balanced = view->totalChunks * ns / ((int64_t)db->computeUnits * 12);
                 // (Round 3, with the wavefronts of a SIMD paced: measured again over 20k .. 2M targets, uniform,
                 // log-normal and bimodal lengths - tools/quick_routing_ab.py, profiles/r03_routing_ab.txt. The
                 // strips kernel wins from 1.5 units per CU on; its longest group may be as long as 1.2 balanced
@@ -502,12 +488,15 @@ struct Search {
                 // targets, a tenth of them thirty times as long as the rest - loses 15 %: profiles/r03c_routing_table.txt)
                 const bool enough = (ns >= 16 || (2 * units >= 3 * (int64_t)db->computeUnits && hidden)) || tuned(Tune::PAIR_STRIPS);
                 if (enough && rowsP >= 32 && rowsP <= maxRows && band(rowsP) && (int64_t)(ns - 1) * rowsP < Q && ns <= 4096) {
-                    stripRows = rowsP;
-                    nStrips = ns;
-                    waves = 1;   // (strips of a group in turn, each in its own unit)
+                    p.stripRows = rowsP;
+                    p.nStrips = ns;
+                    p.waves = 1;   // (strips of a group in turn, each in its own unit)
                 }
             }
         }
+    }
+
+    void planGlobalPairStrips(const View* view, bool useHalf, ScorePlan& p) const {
         // NW / HW / OV of more rows than one pair table holds: the same units with the one-strip global
         // kernel's cell (interseq_pair_global_strips_kernel, round 3: 3 integer adds + 3 max per cell pair
         // and no v_perm, against 5 + 1 v_perm and a barrier per chunk on the general kernel's cheapest
@@ -517,24 +506,14 @@ struct Search {
         //           above: NW Q (max S + ext), HW / OV Q max S + the rebase shift.
         // A 2000-residue query under BLOSUM62 3 / 1 (BASELINE configs[3]) fits; from about 2200 (HW / OV)
         // and 2350 residues (NW) on the general kernel takes over.
-        bool globalStrips = false;
+        p.globalStrips = false;
         if (mode != OPAL_MODE_SW && useHalf && !globalStripsRefused && !tuned(Tune::NO_BIASED) &&
             !tuned(Tune::NO_GLOBAL_STRIPS) && !tuned(Tune::STRIPS)) {
             const char* noPair = tuned(Tune::NO_PAIR_TABLE);
-            const int single = std::max(2, (Q + 1) / 2 * 2);
-            const bool oneStrip = Q <= kLanes && interseqPairFits(single, A + 1);
+            const bool oneStrip = oneStripFits(Q, A + 1, interseqPairFits);
             // (with end locations the row / column bookkeeping costs registers: shorter strips)
-            int maxRows = searchType != OPAL_SEARCH_SCORE ? kPairStripsMaxRowsLoc : kPairStripsMaxRows;
-            while (maxRows >= 32 && !interseqPairFits(maxRows, A + 1)) maxRows -= 2;
-            const int64_t pos = std::max(maxScore, 0);
-            const int64_t zeroG = 0x0400 + 3 * (int64_t)open + ((int64_t)Q + 4) * ext + std::max(0, -minScore);
-            // (the cells of a strip are on anti-diagonally shifted scales - row r carries r ext more - and H is
-            // kept open - ext below its plain form: one strip's rows and an opening more on either side; the
-            // kernel's zero is the one-strip kernel's, which has this room below it: 3 open cover 2)
-            const int64_t above = (r.topGap ? (int64_t)Q * (pos + ext) : (int64_t)Q * pos + kLocMaxShift) +
-                                  ((int64_t)kPairStripsMaxRows + 4) * ext + open;
-            const bool inRange = zeroG + above + 5 * (int64_t)ext + pos < 0x7C00 && 5 * (int64_t)ext <= kLocMaxShift &&
-                                 minScore > kBiasedPad && (r.topGap ? open >= ext : true);
+            const int maxRows = tallestStrip(searchType != OPAL_SEARCH_SCORE ? kPairStripsMaxRowsLoc : kPairStripsMaxRows, A + 1, interseqPairFits);
+            const bool inRange = globalStripsFit(model(), Q, r.topGap != 0);
             if (!oneStrip && maxRows >= 32 && Q > 32 && inRange && !(noPair && noPair[0] == '1')) {
                 // strip height: even, at most maxRows; every strip costs about four rows' worth of per-column
                 // work on top of its cells (row above in, last row out, answers), and a last query row that
@@ -553,9 +532,7 @@ struct Search {
                 }
                 if (bestRows > 0 && bestNs <= 4096) {
                     const int64_t units = (int64_t)((view->nGroups + 11) / 12) * bestNs;
-                    int64_t totalChunks = 0;
-                    for (int c : view->groupChunksHost) totalChunks += c;
-                    const int64_t balanced = totalChunks * bestNs / ((int64_t)db->computeUnits * 12);
+                    const int64_t balanced = view->totalChunks * bestNs / ((int64_t)db->computeUnits * 12);
                     // (the general kernel's lanes are a third slower for these modes than this kernel's: a longest
                     // group of up to 1.5 balanced shares still pays, and so does one unit per CU)
                     const bool hidden = view->nGroups > 0 && 2 * (int64_t)view->groupChunksHost[0] <= 3 * balanced;
@@ -563,26 +540,30 @@ struct Search {
                     // CU on one strip for a while, the longest group short against the launch)
                     const bool enough = (bestNs >= 16 || (units >= (int64_t)db->computeUnits && hidden)) || tuned(Tune::PAIR_STRIPS);
                     if (enough) {
-                        stripRows = bestRows;
-                        nStrips = bestNs;
-                        waves = 1;
-                        globalStrips = true;
+                        p.stripRows = bestRows;
+                        p.nStrips = bestNs;
+                        p.waves = 1;
+                        p.globalStrips = true;
                     }
                 }
             }
         }
+    }
+
+    // step 4: the side cut - the ladder of cuts and its estimate; what leaves is queued in sideJobs
+    // (keeps the cut for a pass that starts over - cutView, cutFirstGroup -, sets balancedChunks, reports in g_lastRouting)
+    void planSideCut(const View* view, ScorePlan& p, std::vector<PairJob>& sideJobs) {
         // A group keeps its wavefronts busy for (columns of its longest target) x (rounds of strips).
         // Groups far above the balanced share of a workgroup slot would stretch the kernel to
         // their own length (one lane per target cannot split a target), so the leading
         // (longest) groups are skipped and their targets go to the intra-sequence kernel,
         // which spreads each pair over 64 lanes.
-        int firstGroup = 0;
+        p.firstGroup = 0;
         if (view->nGroups > 0) {
-            int64_t total = 0;
-            for (int c : view->groupChunksHost) total += c;
+            const int64_t total = view->totalChunks;   // (= the sum of the groups' chunks)
             // (the strips kernel: 12 wavefronts per CU, a group's strips side by side in different ones)
-            const int64_t slots = stripRows ? std::max<int64_t>(1, (int64_t)db->computeUnits * 12 / nStrips)
-                                            : (int64_t)db->computeUnits * std::max(1, 12 / waves);
+            const int64_t slots = p.stripRows ? std::max<int64_t>(1, (int64_t)db->computeUnits * 12 / p.nStrips)
+                                            : (int64_t)db->computeUnits * std::max(1, 12 / p.waves);
             // Which leading groups leave the packed launch for the wavefront-per-pair kernel on the side stream.
             // Round 3 cut at 2.5 balanced shares of a wavefront slot and compared that one cut with keeping
             // everything. Round 4: ONE estimate over a ladder of cuts (the multiples below, and "none"), the
@@ -595,29 +576,29 @@ struct Search {
             // int32 kernel fills about 1e12 cells a second with the chip to itself, and its longest pair is a chain
             // of (L + 128 per strip) anti-diagonal steps of 0.15 us. Both launches share the chip: their work adds
             // up, their chains run side by side.
-            const int rowsNow = stripRows ? stripRows : std::min(Q, kMaxStripRows);
-            const double rounds = stripRows ? 1.0 : (double)((nStrips + waves - 1) / waves);
+            const int rowsNow = p.stripRows ? p.stripRows : std::min(Q, kMaxStripRows);
+            const double rounds = p.stripRows ? 1.0 : (double)((p.nStrips + p.waves - 1) / p.waves);
             // (the general kernel of several strips: a workgroup pipelines a group's strips with a barrier
             // per chunk step, about 7.5 us per step and round whoever else is on the CU - no faster alone)
-            const bool pipelined = !stripRows && nStrips > 1;
+            const bool pipelined = !p.stripRows && p.nStrips > 1;
             const double tau = pipelined ? 7.5e-6 * rounds : 7e-6 * rowsNow / 54.0;
             // (... but the long groups at the head of the hand-out still end with the CU to themselves: log-normal
             // 500k at Q = 150 with nothing on the side, 5.2 ms for a longest group of 2000 chunks)
             // (not on the strips kernels: the twelve wavefronts of a unit are neighbours of the length-sorted view - all
             // long - and share their CU to the end; bimodal 20k at Q = 1000, `end`: 16 ms packed where the estimate
             // with the factor said 4)
-            const double alone = stripRows ? 1.0 : 2.5;
+            const double alone = p.stripRows ? 1.0 : 2.5;
             // (end locations in two sweeps of the strips kernel: the packed side twice)
             // (... known after the probe of the longest groups; before it, expected where the probe is made at all: scores of
             // long queries against long targets leave the row keys' 384, the cut is kept across the restart)
-            const double sweeps = (stripRows && mode == OPAL_MODE_SW && searchType != OPAL_SEARCH_SCORE &&
+            const double sweeps = (p.stripRows && mode == OPAL_MODE_SW && searchType != OPAL_SEARCH_SCORE &&
                                    (twoPassEnds || std::min(Q, view->maxPackedLen) >= 512)) ? 2.0 : 1.0;
             // (a slot = the wavefronts that sweep one group: all its strips side by side on the strips kernels; round 3
             // multiplied the balanced share by the number of strips once more - the same factor on both sides of its one
             // comparison, but twenty times too much of a packed launch against the side kernel at Q = 1000)
             const double perSlot = 1.0 / (double)std::max<int64_t>(slots, 1);
             const int64_t balancedNow = total / std::max<int64_t>(slots, 1);
-            const int64_t floorLimit = overlap > 0 ? (stride + overlap + 3) / 4 : 0;   // windows are as short as long targets get
+            const int64_t floorLimit = p.overlap > 0 ? (p.stride + p.overlap + 3) / 4 : 0;   // windows are as short as long targets get
             const int qStrips = (Q + kLanes - 1) / kLanes;
             auto cutAt = [&](double shares) {
                 int64_t limit = std::max<int64_t>((int64_t)(shares * (double)balancedNow), 128);
@@ -647,11 +628,11 @@ struct Search {
                 }
                 return std::max({packedChain, sideChain, packedWork + sideWork});
             };
-            if (cutView == view.get()) {
-                firstGroup = cutFirstGroup;
+            if (cutView == view) {
+                p.firstGroup = cutFirstGroup;
             } else {
                 double bestCost = estimate(0);
-                firstGroup = 0;
+                p.firstGroup = 0;
                 int lastTried = 0;
                 for (double shares : {8.0, 6.0, 5.0, 4.0, 3.5, 3.0, 2.5, 2.0, 1.5}) {
                     const int fg = cutAt(shares);
@@ -660,350 +641,625 @@ struct Search {
                     const double cost = estimate(fg);
                     if (cost < 0.97 * bestCost) {   // (a cut has to pay for itself: fewer targets on the side at equal cost)
                         bestCost = cost;
-                        firstGroup = fg;
+                        p.firstGroup = fg;
                     }
                 }
             }
-            cutView = view.get();
-            cutFirstGroup = firstGroup;
-            const int skipped = std::min(firstGroup * kGroupTargets, view->nPacked);
+            cutView = view;
+            cutFirstGroup = p.firstGroup;
+            const int skipped = std::min(p.firstGroup * kGroupTargets, view->nPacked);
             for (int k = 0; k < skipped; ++k) queueWhole(sideJobs, view->ids[k]);
             balancedChunks = total / std::max<int64_t>(slots, 1);
         }
-        const int firstPos = std::min(firstGroup * kGroupTargets, view->nPacked);
+        p.firstPos = std::min(p.firstGroup * kGroupTargets, view->nPacked);
         g_lastRouting[0] = (int64_t)sideJobs.size();
-        g_lastRouting[2] = view->nGroups - firstGroup;
+        g_lastRouting[2] = view->nGroups - p.firstGroup;
+    }
 
-        if (view->nGroups > firstGroup) {
-            const bool pairStrips = stripRows > 0;
-            const int rows = pairStrips ? stripRows : (((Q + nStrips - 1) / nStrips) + 7) / 8 * 8;
-            const int qPad = nStrips * rows;
-            const int nSym = A + 1;
-            // Lane arithmetic. Smith-Waterman: packed half floats are exact for integers
-            // below 2048 and cost fewer instructions per cell (interseq_impl.h); saturating
-            // int16 is the second rung, the int32 intra-sequence kernel the last. The other
-            // modes use signed int16 lanes; whether a target fits is known from its length:
-            //   every true H, E, F >= -(3*open + (Q + L)*ext)   and   H <= min(Q, L)*maxScore
-            const bool sw = mode == OPAL_MODE_SW;
-            const bool locate = searchType != OPAL_SEARCH_SCORE;  // end locations wanted
-            int packedSkip = firstPos;   // first view position whose packed result is scattered
-            int capGroups = 0, capChunks = 0;
-            // Smith-Waterman with several strips and no windows (long queries): a few targets far longer
-            // than the rest of the first group set that group's - on the strips kernel the launch's - length
-            // (cfg4 with its tail: 4000 .. 8000 residues among 2000-residue targets, 56 instead of 47 ms).
-            // With a pair's strips side by side the int32 kernel takes them in a few milliseconds beside the
-            // packed launch: up to 64 leading targets more than a quarter longer than the longest of the next
-            // group go there, and the first group stops at the longest target that stays.
-            if ((sw || globalStrips) && overlap == 0 && Q > kLanes && view->nPacked - firstPos > 2 * kGroupTargets &&
-                !tuned(Tune::NO_SIDE_STREAM)) {
-                const int ref = dbLen(db, view->ids[firstPos + kGroupTargets]);
-                int k = 0;
-                while (k < 64 && (int64_t)dbLen(db, view->ids[firstPos + k]) * 4 > (int64_t)ref * 5 + 1024) ++k;
-                if (k > 0) {
-                    for (int x = 0; x < k; ++x) sideJobs.push_back(forwardJob(view->ids[firstPos + x], rules));
-                    g_lastRouting[0] = (int64_t)sideJobs.size();
-                    packedSkip = firstPos + k;
-                    capGroups = 1;
-                    capChunks = std::max(1, (dbLen(db, view->ids[firstPos + k]) + 3) / 4);
-                }
+    // step 5: the lane arithmetic - flavour, limits, caps, which targets go to the int32 kernel (jobs: after the
+    // packed launch; sideJobs: beside it)
+    void planLanes(const View* view, bool useHalf, ScorePlan& p, std::vector<PairJob>& jobs, std::vector<PairJob>& sideJobs) const {
+        p.pairStrips = p.stripRows > 0;
+        p.rows = p.pairStrips ? p.stripRows : (((Q + p.nStrips - 1) / p.nStrips) + 7) / 8 * 8;
+        p.qPad = p.nStrips * p.rows;
+        p.nSym = A + 1;
+        // Lane arithmetic. Smith-Waterman: packed half floats are exact for integers
+        // below 2048 and cost fewer instructions per cell (interseq_impl.h); saturating
+        // int16 is the second rung, the int32 intra-sequence kernel the last. The other
+        // modes use signed int16 lanes; whether a target fits is known from its length:
+        //   every true H, E, F >= -(3*open + (Q + L)*ext)   and   H <= min(Q, L)*maxScore
+        p.sw = mode == OPAL_MODE_SW;
+        p.locate = searchType != OPAL_SEARCH_SCORE;  // end locations wanted
+        p.packedSkip = p.firstPos;   // first view position whose packed result is scattered
+        // Smith-Waterman with several strips and no windows (long queries): a few targets far longer
+        // than the rest of the first group set that group's - on the strips kernel the launch's - length
+        // (cfg4 with its tail: 4000 .. 8000 residues among 2000-residue targets, 56 instead of 47 ms).
+        // With a pair's strips side by side the int32 kernel takes them in a few milliseconds beside the
+        // packed launch: up to 64 leading targets more than a quarter longer than the longest of the next
+        // group go there, and the first group stops at the longest target that stays.
+        if ((p.sw || p.globalStrips) && p.overlap == 0 && Q > kLanes && view->nPacked - p.firstPos > 2 * kGroupTargets &&
+            !tuned(Tune::NO_SIDE_STREAM)) {
+            const int ref = dbLen(db, view->ids[p.firstPos + kGroupTargets]);
+            int k = 0;
+            while (k < 64 && (int64_t)dbLen(db, view->ids[p.firstPos + k]) * 4 > (int64_t)ref * 5 + 1024) ++k;
+            if (k > 0) {
+                for (int x = 0; x < k; ++x) sideJobs.push_back(forwardJob(view->ids[p.firstPos + x], rules));
+                g_lastRouting[0] = (int64_t)sideJobs.size();
+                p.packedSkip = p.firstPos + k;
+                p.capGroups = 1;
+                p.capChunks = std::max(1, (dbLen(db, view->ids[p.firstPos + k]) + 3) / 4);
             }
-            // one strip + Smith-Waterman scores: the pair-indexed LDS profile saves the v_perm per cell
-            const char* noPair = tuned(Tune::NO_PAIR_TABLE);
-            // first rung of the pair-table kernel: biased integer halves (exact below 25600,
-            // interseq_impl.h) when the scores and gap costs leave its guard band alone: a step up
-            // (score + ext, or ext - open) of at most 0x0400 so that a finite half cannot jump over
-            // the NaN patterns, a step down (score + ext, open - ext) within the room below zero.
-            // With end locations every value is scaled by 2^bits (row keys in the low bits).
-            // (Smith-Waterman: the query's own rows, the biased kernel exists for odd counts too; the NW / HW / OV
-            // kernel sweeps rows in pairs)
-            const int pairRows = sw ? std::max(1, Q) : std::max(2, (Q + 1) / 2 * 2);
-            // (row keys in the low bits of every value - unless the end locations come from a second sweep)
-            const bool twoPass = pairStrips && sw && locate && twoPassEnds;
-            const bool rowKeys = locate && !twoPass;
-            const int bits = rowKeys ? locRowBitsHost(pairStrips ? stripRows : pairRows) : 0;
-            const int64_t up = std::max<int64_t>((int64_t)maxScore + ext, (int64_t)ext - open);
-            const int64_t down = std::max<int64_t>(-((int64_t)minScore + ext), (int64_t)open - ext);
-            // (A step up of more than 0x0400 could carry a finite half past the NaN patterns, 0x7C00 to
-            // 0x7FFF, into the negative ones, where the max would drop it: the limit is then lowered
-            // by the excess, so that the cell it would jump from is itself flagged.)
-            const bool biasedFits = nStrips == 1 && useHalf && !tuned(Tune::NO_BIASED) &&
-                                    (up << bits) <= kBiasedMaxStepUp &&
-                                    (down << bits) <= (rowKeys ? kLocGuardBand : kBiasedMaxMagnitude) &&
-                                    5 * ((int64_t)ext << bits) <= kLocMaxShift && minScore > kBiasedPad;
-            const int biasedLimit =
-                (int)(((rowKeys ? 0x7C00 - kLocZeroPattern - kLocMaxShift : kBiasedScoreLimit) -
-                       std::max<int64_t>(0, (up << bits) - 0x0400)) >> bits);
-            const bool usePair = sw && nStrips == 1 && !(noPair && noPair[0] == '1') &&
-                                 interseqPairFits(biasedFits ? pairRows : rows, nSym) && (!locate || biasedFits);
-            const bool biased = usePair && biasedFits;
-            // Smith-Waterman scores in the general kernel (several strips, or a pair table that does not
-            // fit LDS): column-shifted unsigned patterns (ArithSwU16) when the longest packed target
-            // leaves a range worth having - zero + ext x columns + score below 0x7C00.
-            int swBias = 0, swLimit = 0;
-            bool swShifted = false;
-            if (sw && !locate && !usePair && !pairStrips && useHalf && !tuned(Tune::NO_SW_SHIFT)) {
-                swBias = std::max(0, -(minScore + ext));                       // profile entries s + ext + K >= 0
-                const int64_t stepUp = std::max<int64_t>((int64_t)maxScore + ext, (int64_t)ext - open);
-                const int64_t lim = 0x7C00 - kSwShiftZero - (int64_t)ext * (view->maxPackedLen + 8) -
-                                    std::max<int64_t>(0, stepUp - 0x0400);
-                if (lim >= 4096 && swBias + ext <= 0x0800 && open - ext <= 0x0800 && stepUp <= 0x1000 &&
-                    (int64_t)maxScore + ext + swBias < 0x4000) {
-                    swShifted = true;
-                    swLimit = (int)lim;
-                }
-            }
-            // Half floats turn a sum above 65504 into +inf, and inf + (-inf padding) into NaN, which
-            // the flag `best >= 2048` would miss (NaN converts to 0): only matrices whose best
-            // possible score stays finite take the half-float rung.
-            const bool halfFloat = sw && useHalf && !biased && !swShifted && !pairStrips && maxScore <= 1024 && minScore >= -1024 &&
-                                   (int64_t)std::min<int64_t>(Q, db->maxLen) * std::max(maxScore, 0) < 60000;
-            InterseqFlavour flavour = sw ? (swShifted ? kSwShifted : halfFloat ? kSwHalf : kSwInt16) : kSignedInt16;
-            int profileShift = swShifted ? ext + swBias : 0;
-            // One-strip NW / HW / OV: the pair-table kernel on biased integer halves (interseq_impl.h).
-            // The true values around a pattern's zero are bounded by the query, not by the targets'
-            // lengths, so no target is redone at 32 bit; the bounds are static:
-            //   below zero: 3 open + (Q + 4) ext + |min S|,   above: Q (max S + ext) + the rebase shift
-            const int64_t globalZero = 0x0400 + 3 * (int64_t)open + ((int64_t)Q + 4) * ext + std::max(0, -minScore);
-            const bool globalPair =
-                !sw && nStrips == 1 && !globalPairRefused && !(noPair && noPair[0] == '1') && !tuned(Tune::NO_BIASED) &&
-                interseqPairFits(pairRows, nSym) && minScore > kBiasedPad && (r.topGap ? open >= ext : true) &&
-                5 * (int64_t)ext <= kLocMaxShift &&
-                // (+ the strip's rows and an opening: the cells are on anti-diagonally shifted scales, round 3)
-                globalZero + (int64_t)Q * (std::max(maxScore, 0) + ext) + kLocMaxShift + 5 * (int64_t)ext +
-                        std::max(maxScore, 0) + ((int64_t)Q + 4) * ext + open < 0x7C00;
-            if (globalPair || globalStrips) {
-                // only empty targets (closed forms of the border) are left to the int32 kernel
-                for (int e = view->nPacked - 1; e >= firstPos && dbLen(db, view->ids[e]) == 0; --e)
-                    jobs.push_back(forwardJob(view->ids[e], rules));
-            } else if (!sw) {
-                const int64_t pos = std::max(maxScore, 0);
-                auto fitsPlain = [&](int64_t L) {
-                    return L > 0 && 3 * (int64_t)open + (Q + L) * ext < 32000 && std::min<int64_t>(Q, L) * pos < 32000;
-                };
-                // the shifted flavour stores X + (i + j) * ext: (Q + L) * ext more head-room
-                auto fitsDiag = [&](int64_t L) {
-                    return L > 0 && 3 * (int64_t)open + (Q + L + 2) * ext < 32000 &&
-                           std::min<int64_t>(Q, L) * pos + (Q + L) * ext < 32000;
-                };
-                // longest packed target that the plain flavour can take (view order: longest first)
-                int firstFit = firstPos;
-                while (firstFit < view->nPacked && !fitsPlain(dbLen(db, view->ids[firstFit]))) ++firstFit;
-                // The shifted flavours need more head-room, i.e. shorter targets. A few targets too long
-                // for them would put the WHOLE view on the plain int16 lanes (8 operations per cell pair
-                // instead of 5: cfg4 with the reference's 1000 .. 35000 tail, NW: 78 ms instead of 48); the
-                // int32 kernel takes a long pair in a few milliseconds now (one wavefront per strip), so up
-                // to 1024 of the longest targets are handed to it when that buys the view a cheaper flavour.
-                auto firstThat = [&](int from, auto&& fits) {
-                    int p = from;
-                    while (p < view->nPacked && p - from <= 1024 && !fits(dbLen(db, view->ids[p]))) ++p;
-                    return (p < view->nPacked && p - from <= 1024 && dbLen(db, view->ids[p]) > 0) ? p : -1;
-                };
-                const int firstDiag = tuned(Tune::NO_DIAG_SHIFT) ? -1 : firstThat(firstFit, fitsDiag);
-                if (firstDiag >= 0) {
-                    firstFit = firstDiag;
-                    flavour = kSignedInt16Diag;
-                    profileShift = 2 * ext;
-                    // The same shift on unsigned patterns compared as half floats (ArithU16Diag: integer
-                    // adds, one max3 for h): scores after the shift must not be negative
-                    // (s + ext + open >= 0), open >= ext, and every pattern
-                    // zero + x + (i + j) ext within [0, 0x7BFF] for the longest target that stays packed.
-                    const int64_t c = (int64_t)open - ext;
-                    const int64_t below = 3 * (int64_t)open + 2 * (int64_t)ext + std::max(0, -minScore) + c;
-                    auto fitsUnsigned = [&](int64_t L) {
-                        return L > 0 && kUnsignedDiagZero + std::min<int64_t>(Q, L) * pos + (Q + L + 2) * (int64_t)ext + pos +
-                                                2 * (int64_t)ext + c < 0x7C00;
-                    };
-                    if (c >= 0 && (int64_t)minScore + ext + open >= 0 &&
-                        0x0400 + below + 64 <= kUnsignedDiagZero) {   // real cells stay above the padding cells' floor
-                        const int firstU = firstThat(firstFit, fitsUnsigned);
-                        if (firstU >= 0) {
-                            firstFit = firstU;
-                            flavour = kUnsignedDiag;
-                            profileShift = 2 * ext + (int)c;
-                        }
-                    }
-                }
-                // The targets that do not fit form a prefix of the view: they go to the int32 kernel BESIDE
-                // the packed launch, and the scatter starts behind them (their lanes of the packed kernel hold
-                // nothing). Empty targets (closed forms of the border) form a suffix, redone after the scatter.
-                // (windows of a segmented view are merged by key afterwards: there the whole targets are redone after)
-                if (overlap > 0) {
-                    for (int k = firstPos; k < firstFit; ++k) queueWhole(jobs, view->ids[k]);
-                } else {
-                    for (int k = firstPos; k < firstFit; ++k) sideJobs.push_back(forwardJob(view->ids[k], rules));
-                    packedSkip = firstFit;
-                    g_lastRouting[0] = (int64_t)sideJobs.size();
-                    // ... and the groups they sit in sweep no further than the longest target that stays (cfg4
-                    // with its tail: five targets of 4000 .. 8000 residues kept the first group, and with it
-                    // the launch, at 8000 columns: 57 instead of 48 ms)
-                    if (firstFit > firstPos && firstFit < view->nPacked) {
-                        capGroups = (firstFit - firstPos + kGroupTargets - 1) / kGroupTargets;
-                        capChunks = std::max(1, (dbLen(db, view->ids[firstFit]) + 3) / 4);
-                    }
-                }
-                for (int e = view->nPacked - 1; e >= firstFit && dbLen(db, view->ids[e]) == 0; --e)
-                    jobs.push_back(forwardJob(view->ids[e], rules));
-            }
-            // query profile: profile[t][i] = S[q_i][t]; padding symbol and padding rows can
-            // never win a max: -32768 (int16) or -inf (half)
-            auto enc = [&](int v) -> int16_t {
-                if (!halfFloat) return (int16_t)v;
-                const _Float16 h = (_Float16)(float)v;
-                int16_t bits;
-                memcpy(&bits, &h, sizeof bits);
-                return bits;
+        }
+        // one strip + Smith-Waterman scores: the pair-indexed LDS profile saves the v_perm per cell
+        const char* noPair = tuned(Tune::NO_PAIR_TABLE);
+        // first rung of the pair-table kernel: biased integer halves (exact below 25600,
+        // interseq_impl.h) when the scores and gap costs leave its guard band alone (score_ranges.h).
+        // With end locations every value is scaled by 2^bits (row keys in the low bits).
+        // (Smith-Waterman: the query's own rows, the biased kernel exists for odd counts too; the NW / HW / OV
+        // kernel sweeps rows in pairs)
+        p.pairRows = p.sw ? std::max(1, Q) : pairTableRows(Q);
+        // (row keys in the low bits of every value - unless the end locations come from a second sweep)
+        p.twoPass = p.pairStrips && p.sw && p.locate && twoPassEnds;
+        p.rowKeys = p.locate && !p.twoPass;
+        const int bits = rowKeyBits(p.pairStrips ? p.stripRows : p.pairRows, p.rowKeys);
+        const bool biasedFits = p.nStrips == 1 && useHalf && !tuned(Tune::NO_BIASED) && biasedBandFits(model(), bits, p.rowKeys);
+        p.biasedLimit = biasedLimit(model(), bits, p.rowKeys);
+        p.usePair = p.sw && p.nStrips == 1 && !(noPair && noPair[0] == '1') &&
+                    interseqPairFits(biasedFits ? p.pairRows : p.rows, p.nSym) && (!p.locate || biasedFits);
+        p.biased = p.usePair && biasedFits;
+        // Smith-Waterman scores in the general kernel (several strips, or a pair table that does not
+        // fit LDS): column-shifted unsigned patterns (ArithSwU16) when the longest packed target
+        // leaves a range worth having.
+        if (p.sw && !p.locate && !p.usePair && !p.pairStrips && useHalf && !tuned(Tune::NO_SW_SHIFT)) {
+            const SwShiftPlan shift = swShiftPlan(model(), view->maxPackedLen);
+            p.swBias = shift.bias;   // (the kernel arguments carry it whether the flavour is used or not)
+            p.swShifted = shift.usable;
+            p.swLimit = shift.limit;
+        }
+        // only matrices whose best possible score stays finite take the half-float rung
+        p.halfFloat = p.sw && useHalf && !p.biased && !p.swShifted && !p.pairStrips && halfFloatFits(model(), Q, db->maxLen);
+        p.flavour = p.sw ? (p.swShifted ? kSwShifted : p.halfFloat ? kSwHalf : kSwInt16) : kSignedInt16;
+        p.profileShift = p.swShifted ? ext + p.swBias : 0;
+        // One-strip NW / HW / OV: the pair-table kernel on biased integer halves (interseq_impl.h), its static
+        // bounds in score_ranges.h; the multi-strip kernel shares its zero.
+        p.globalZero = globalZeroPattern(model(), Q, false);
+        p.globalPair = !p.sw && p.nStrips == 1 && !globalPairRefused && !(noPair && noPair[0] == '1') && !tuned(Tune::NO_BIASED) &&
+                       interseqPairFits(p.pairRows, p.nSym) && globalOneStripFits(model(), Q, r.topGap != 0, false);
+        if (p.globalPair || p.globalStrips) {
+            // only empty targets (closed forms of the border) are left to the int32 kernel
+            for (int e = view->nPacked - 1; e >= p.firstPos && dbLen(db, view->ids[e]) == 0; --e)
+                jobs.push_back(forwardJob(view->ids[e], rules));
+        } else if (!p.sw) {
+            const ScoreModel m = model();
+            auto plain = [&](int64_t L) { return fitsPlain(m, Q, L); };
+            auto diag = [&](int64_t L) { return fitsDiag(m, Q, L); };
+            auto unsignedDiag = [&](int64_t L) { return fitsUnsigned(m, Q, L); };
+            // longest packed target that the plain flavour can take (view order: longest first)
+            int firstFit = p.firstPos;
+            while (firstFit < view->nPacked && !plain(dbLen(db, view->ids[firstFit]))) ++firstFit;
+            // The shifted flavours need more head-room, i.e. shorter targets. A few targets too long
+            // for them would put the WHOLE view on the plain int16 lanes (8 operations per cell pair
+            // instead of 5: cfg4 with the reference's 1000 .. 35000 tail, NW: 78 ms instead of 48); the
+            // int32 kernel takes a long pair in a few milliseconds now (one wavefront per strip), so up
+            // to 1024 of the longest targets are handed to it when that buys the view a cheaper flavour.
+            auto firstThat = [&](int from, auto&& fits) {
+                int k = from;
+                while (k < view->nPacked && k - from <= 1024 && !fits(dbLen(db, view->ids[k]))) ++k;
+                return (k < view->nPacked && k - from <= 1024 && dbLen(db, view->ids[k]) > 0) ? k : -1;
             };
-            // (the unsigned shifted flavour: padding scores open - ext after the shift, see ArithU16Diag)
-            const int16_t padValue = (biased || globalPair || pairStrips) ? (int16_t)kBiasedPad
-                                     : swShifted ? (int16_t)0   // s + ext + K = 0: a true score of -(ext + K) <= 0
-                                     : flavour == kUnsignedDiag ? (int16_t)(open - ext)
-                                     : halfFloat ? (int16_t)0xFC00 : (int16_t)-32768;
-            std::vector<int16_t> prof((size_t)nSym * qPad, padValue);
-            for (int t = 0; t < A; ++t)
-                for (int i = 0; i < Q; ++i) prof[(size_t)t * qPad + i] = enc(at(i, t) + profileShift);
-            // targets kept out of the packed view (too long for one lane each) are computed by the
-            // int32 kernel on a side stream BESIDE the packed kernel; packed targets that need
-            // the int32 kernel are redone after it, because both write the same result slots
+            const int firstDiag = tuned(Tune::NO_DIAG_SHIFT) ? -1 : firstThat(firstFit, diag);
+            if (firstDiag >= 0) {
+                firstFit = firstDiag;
+                p.flavour = kSignedInt16Diag;
+                p.profileShift = 2 * ext;
+                // The same shift on unsigned patterns compared as half floats (ArithU16Diag), where the model allows it
+                if (unsignedDiagUsable(m)) {
+                    const int firstU = firstThat(firstFit, unsignedDiag);
+                    if (firstU >= 0) {
+                        firstFit = firstU;
+                        p.flavour = kUnsignedDiag;
+                        p.profileShift = 2 * ext + (open - ext);
+                    }
+                }
+            }
+            // The targets that do not fit form a prefix of the view: they go to the int32 kernel BESIDE
+            // the packed launch, and the scatter starts behind them (their lanes of the packed kernel hold
+            // nothing). Empty targets (closed forms of the border) form a suffix, redone after the scatter.
+            // (windows of a segmented view are merged by key afterwards: there the whole targets are redone after)
+            if (p.overlap > 0) {
+                for (int k = p.firstPos; k < firstFit; ++k) queueWhole(jobs, view->ids[k]);
+            } else {
+                for (int k = p.firstPos; k < firstFit; ++k) sideJobs.push_back(forwardJob(view->ids[k], rules));
+                p.packedSkip = firstFit;
+                g_lastRouting[0] = (int64_t)sideJobs.size();
+                // ... and the groups they sit in sweep no further than the longest target that stays (cfg4
+                // with its tail: five targets of 4000 .. 8000 residues kept the first group, and with it
+                // the launch, at 8000 columns: 57 instead of 48 ms)
+                if (firstFit > p.firstPos && firstFit < view->nPacked) {
+                    p.capGroups = (firstFit - p.firstPos + kGroupTargets - 1) / kGroupTargets;
+                    p.capChunks = std::max(1, (dbLen(db, view->ids[firstFit]) + 3) / 4);
+                }
+            }
+            for (int e = view->nPacked - 1; e >= firstFit && dbLen(db, view->ids[e]) == 0; --e)
+                jobs.push_back(forwardJob(view->ids[e], rules));
+        }
+        // lanes can only leave the exact range when min(Q, L) * maxScore reaches the limit
+        // (also bounded by the query itself: every residue is aligned at most once, at best with
+        // its most favourable partner - 280 for the 53-aa README query under BLOSUM62, where
+        // Q * max(S) says 583)
+        const int64_t reach = std::min<int64_t>((int64_t)std::min(Q, view->maxPackedLen) * std::max(maxScore, 0), p.queryBest);
+        const int64_t limit = (p.biased || p.pairStrips) ? p.biasedLimit : p.swShifted ? p.swLimit : p.halfFloat ? 2048 : 32767;
+        // (the multi-strip NW / HW / OV kernel flags nothing for its range; the count brings back the
+        // lanes of units that gave up on the strip above - never seen outside the fault-injection test)
+        // (the strips kernels: always - the count also brings back the lanes of a unit that gave up on
+        // the strip above it; searches of several strips take milliseconds, the 4-byte download is free)
+        p.mayOverflow = p.sw ? (reach >= limit || p.pairStrips) : p.globalStrips;
+        // How many flagged lanes are redone one by one before the whole view takes the next rung: the int32
+        // kernel fills about 1e12 cells a second, the next rung 5e12 .. 8e12 over the WHOLE view - an eighth
+        // of the view's targets costs the same either way (round 3; it was 2048 whatever the size: 0.3 % of
+        // 1M x 300 beyond the row keys' 384 at Q = 1000 sent the other 99.7 % through a second launch)
+        p.directLimit = std::max<int64_t>(kMaxDirectRecompute, (view->nPacked - p.packedSkip) / 8);
+        // (random pairs only get there in the linear regime of the scoring system, and then score
+        // about half a unit per aligned residue: nothing to probe for under ~500 residues)
+        p.probeEnds = p.pairStrips && p.sw && p.rowKeys && p.mayOverflow && std::min(Q, view->maxPackedLen) >= 512 && !tuned(Tune::PAIR_STRIPS);
+    }
+
+    // step 6: the query profile of the packed kernels
+    std::vector<int16_t> buildProfile(const ScorePlan& p) const {
+        // query profile: profile[t][i] = S[q_i][t]; padding symbol and padding rows can
+        // never win a max: -32768 (int16) or -inf (half)
+        auto enc = [&](int v) -> int16_t {
+            if (!p.halfFloat) return (int16_t)v;
+            const _Float16 h = (_Float16)(float)v;
+            int16_t bits;
+            memcpy(&bits, &h, sizeof bits);
+            return bits;
+        };
+        // (the unsigned shifted flavour: padding scores open - ext after the shift, see ArithU16Diag)
+        const int16_t padValue = (p.biased || p.globalPair || p.pairStrips) ? (int16_t)kBiasedPad
+                                 : p.swShifted ? (int16_t)0   // s + ext + K = 0: a true score of -(ext + K) <= 0
+                                 : p.flavour == kUnsignedDiag ? (int16_t)(open - ext)
+                                 : p.halfFloat ? (int16_t)0xFC00 : (int16_t)-32768;
+        std::vector<int16_t> prof((size_t)p.nSym * p.qPad, padValue);
+        for (int t = 0; t < A; ++t)
+            for (int i = 0; i < Q; ++i) prof[(size_t)t * p.qPad + i] = enc(at(i, t) + p.profileShift);
+        return prof;
+    }
+
+    // step 7: the side jobs go to the side stream (*forked: the pass has something to join)
+    int forkSideJobs(const ScorePlan& p, std::vector<PairJob>& sideJobs, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ,
+                     bool* forked, PhaseTimer& spt) {
+        // targets kept out of the packed view (too long for one lane each) are computed by the
+        // int32 kernel on a side stream BESIDE the packed kernel; packed targets that need
+        // the int32 kernel are redone after it, because both write the same result slots
+        if (!sideDone.empty()) {
+            sideJobs.erase(std::remove_if(sideJobs.begin(), sideJobs.end(), [&](const PairJob& j) {
+                               return std::binary_search(sideDone.begin(), sideDone.end(), j.out);
+                           }), sideJobs.end());
+        }
+        // The side kernel is handed to its stream BEFORE the packed launch: its wavefronts are dispatched
+        // first, over the whole chip, and the persistent packed workgroups (one per CU, every register of
+        // it) start on a CU when its side wavefronts are done. (Handed over after the packed launch the
+        // side kernel only finds the CUs the launch left out: cfg4 with its tail, 8 CUs: 54 against 44 ms.)
+        // Beside a strips kernel the side units come in workgroups of 16 wavefronts,
+        // so that they hold few CUs (launchIntraseqStrips), and the packed launch takes EVERY CU: the
+        // workgroups that start late simply take fewer units.
+        if (!sideJobs.empty() && !tuned(Tune::NO_SIDE_STREAM)) {
+            RC_TRY(ws->ensureAux());
+            RC_TRY(ensurePairInputs());
+            HIP_TRY(hipEventRecord(ws->evFork, stream));
+            HIP_TRY(hipStreamWaitEvent(ws->aux, ws->evFork, 0));
+            *forked = true;
+            besidePersistent = p.pairStrips;
+            RC_TRY(runPairs(sideJobs, false, d_score, d_endI, d_endJ, nullptr, ws->aux, kAuxJobs - kJobs));
+            HIP_TRY(hipEventRecord(ws->evJoin, ws->aux));
+            for (const PairJob& j : sideJobs) sideDone.push_back(j.out);
+            std::sort(sideDone.begin(), sideDone.end());
+            sideJobs.clear();
+            sideForked = true;   // (a score pass that starts over still joins what is on the side stream)
+            spt.mark("    side jobs enqueued");
+        }
+        return 0;
+    }
+
+    // step 8: the packed kernels' arguments, and the unit / boundary buffers of the launch that was planned
+    int prepareLaunch(const View* view, const ScorePlan& p, const std::vector<int16_t>& prof, PassBuffers& b, InterseqArgs& ia) {
+        void *pp, *vs;
+        RC_TRY(ws->get(kProfile, prof.size() * sizeof(int16_t), &pp));
+        RC_TRY(ws->get(kViewScore, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), &vs));
+        RC_TRY(ws->get(kViewOvf, (size_t)view->nGroups * kGroupTargets, &b.vo));
+        RC_TRY(ws->get(kCounter, sizeof(int32_t), &b.ct));
+        RC_TRY(ws->stageUpload(pp, prof.data(), prof.size() * sizeof(prof[0]), stream));
+        if (p.mayOverflow) HIP_TRY(hipMemsetAsync(b.ct, 0, sizeof(int32_t), stream));
+        ia.pack = view->d_pack;
+        ia.groupOff = view->d_groupOff;
+        ia.groupChunks = view->d_groupChunks;
+        ia.nGroups = view->nGroups - p.firstGroup;
+        ia.groupBase = p.firstGroup;
+        ia.profile = (const int16_t*)pp;
+        ia.nSymbols = p.nSym;
+        ia.qPad = p.qPad;
+        ia.nStrips = p.nStrips;
+        ia.qLen = Q;
+        ia.gapOpen = std::min(open, 32767);
+        ia.gapExt = std::min(ext, 32767);
+        ia.topGap = r.topGap;
+        ia.leftGap = r.leftGap;
+        ia.region = r.region;
+        ia.lens = view->d_lens;
+        ia.score = (int32_t*)vs;
+        if (p.locate) {
+            void *vi, *vj;
+            RC_TRY(ws->get(kViewEndI, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), &vi));
+            RC_TRY(ws->get(kViewEndJ, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), &vj));
+            ia.endI = (int32_t*)vi;
+            ia.endJ = (int32_t*)vj;
+        }
+        ia.overflow = (p.sw || p.globalStrips) ? (uint8_t*)b.vo : nullptr;
+        ia.stripSpinCap = faultSpinCap;
+        ia.faultUnit1 = faultKind == 1 ? faultUnit + 1 : 0;
+        ia.biasedLimit = p.swShifted ? p.swLimit : p.biasedLimit;
+        ia.scoreBias = p.swBias;
+        ia.biasedZero = (int)p.globalZero;
+        ia.boundaryOff = view->d_boundaryOff;
+        ia.capGroups = p.capGroups;
+        ia.capChunks = p.capChunks;
+        ia.priorityChunks = (int)std::min<int64_t>(std::max<int64_t>(balancedChunks, 16), INT32_MAX);
+        if ((p.nStrips + p.waves - 1) / p.waves > 1) {
+            void *b0, *b1;
+            const size_t bytes = (size_t)view->totalChunks * 4 * kLanes * sizeof(uint2);
+            RC_TRY(ws->get(kBoundary0, bytes, &b0));
+            RC_TRY(ws->get(kBoundary1, bytes, &b1));
+            ia.boundary[0] = (uint2*)b0;
+            ia.boundary[1] = (uint2*)b1;
+        }
+        // several rounds of strips per group, scores only: (group, round) units instead of one
+        // workgroup per group (interseq_impl.h, "unit mode")
+        // Only when the groups are few for the chip (under six workgroup-lifetimes): the rounds of
+        // a group are then far apart in time and its boundary rows come back from HBM, not from
+        // the caches (500k x 300 at Q = 300, 7.6 lifetimes: 6.6 ms classic, 7.0 ms in units;
+        // 100k x 2000 at Q = 2000, 3.05 lifetimes: 66 ms classic, 55 ms in units).
+        const int64_t unitSlots = (int64_t)db->computeUnits * std::max(1, 8 / p.waves);
+        const char* um = tuned(Tune::UNITS);
+        const bool wantUnits = um ? um[0] == '1' : (int64_t)(view->nGroups - p.firstGroup) < 6 * unitSlots;
+        if (p.pairStrips) {
+            // unit counter + chunks published per (group, strip); scores and flags start from zero
+            // (a group's answer is the maximum over its strips' units)
+            void* us;
+            const size_t ints = (size_t)ia.nGroups * p.nStrips + 2;
+            RC_TRY(ws->get(kUnitState, ints * sizeof(int), &us));
+            HIP_TRY(hipMemsetAsync(us, 0, ints * sizeof(int), stream));
+            if (p.mayOverflow && p.sw) {
+                // more flagged lanes than are redone one by one: the launch stops, the view takes the next rung
+                ia.stripAbort = (int*)us + ints - 1;
+                ia.stripAbortAt = (int)std::min<int64_t>(2 * p.directLimit, INT32_MAX / 2);
+                ia.stripGaveUp = (int*)b.ct;
+            }
+            // (the scores-only form of the NW / HW / OV kernel folds OV's candidates into the view scores,
+            // and what a unit that gave up leaves behind is "minus infinity" in every mode)
+            if (p.globalStrips) HIP_TRY(launchFillInt32((int32_t*)vs, view->nGroups * kGroupTargets, INT32_MIN, stream));
+            else HIP_TRY(hipMemsetAsync(vs, 0, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), stream));
+            HIP_TRY(hipMemsetAsync(b.vo, 0, (size_t)view->nGroups * kGroupTargets, stream));
+            ia.unitCounter = (int*)us;
+            ia.unitFlags = (int*)us + 1;
+            if (p.locate) {
+                void* sk;
+                RC_TRY(ws->get(kStripKeys, (size_t)view->nGroups * kGroupTargets * sizeof(unsigned long long), &sk));
+                HIP_TRY(hipMemsetAsync(sk, 0, (size_t)view->nGroups * kGroupTargets * sizeof(unsigned long long), stream));
+                ia.stripKeys = (unsigned long long*)sk;
+            }
+        } else if ((p.nStrips + p.waves - 1) / p.waves > 1 && !p.locate && !p.usePair && !p.globalPair && wantUnits) {
+            void *us, *up;
+            const size_t ints = (size_t)ia.nGroups + 1;
+            RC_TRY(ws->get(kUnitState, ints * sizeof(int), &us));
+            RC_TRY(ws->get(kUnitPartial, (size_t)ia.nGroups * p.waves * kLanes * sizeof(uint2), &up));
+            HIP_TRY(hipMemsetAsync(us, 0, ints * sizeof(int), stream));
+            ia.unitCounter = (int*)us;
+            ia.unitFlags = (int*)us + 1;
+            ia.unitPartial = (uint2*)up;
+        }
+        return 0;
+    }
+
+    // step 9, the multi-strip pair-table kernels: the launch's size and flavour, ...
+    struct StripsLaunch {
+        int pairUnits = 0;
+        PairFlavour flavour = kPairSwStrips;
+        unsigned long long* timing = nullptr;
+    };
+    int prepareStripsLaunch(const ScorePlan& p, InterseqArgs& ia, StripsLaunch* sl) {
+        int pairUnits = db->computeUnits;
+        if (const int keep = reservedCus(db); keep >= 0)
+            pairUnits = std::max(1, pairUnits - keep);
+        // (no CUs are kept out of the launch for the side kernel, as round 2 did: the units are taken
+        // dynamically, so a workgroup whose CU is busy with side wavefronts at first just starts later
+        // and takes fewer)
+        const PairFlavour stripsFlavour = p.globalStrips ? kPairGlobalStrips : kPairSwStrips;
+        g_lastRouting[1] = 2 + (int)stripsFlavour;
+        sl->pairUnits = pairUnits;
+        sl->flavour = stripsFlavour;
+        // few (group, strip) units: fewer groups per workgroup, so that every CU gets a unit and a
+        // wavefront shares its SIMD with fewer others
+        ia.batchGroups = (int)std::max<int64_t>(1, std::min<int64_t>(12, (int64_t)ia.nGroups * p.nStrips / std::max(1, pairUnits)));
+        // (diagnostic builds of the kernels, -DMIOPAL_STRIP_TIMING=1: their six counters, printed below)
+        if (tuned(Tune::STRIP_TIMING)) {
+            void* tb;
+            RC_TRY(ws->get(kStripTiming, 8 * sizeof(unsigned long long), &tb));
+            HIP_TRY(hipMemsetAsync(tb, 0, 8 * sizeof(unsigned long long), stream));
+            ia.stripTiming = sl->timing = (unsigned long long*)tb;
+        }
+        return 0;
+    }
+
+    // ... the probe of the longest groups (p.probeEnds): how many of their scores are beyond the row keys' range, ...
+    struct StripsProbe {
+        hipError_t launch = hipSuccess;   // what the probe's launch said; nothing is counted when it was refused
+        int beyond = 0, lanes = 0;        // scores at or beyond the row keys' limit, of that many
+    };
+    int probeStripsEnds(const ScorePlan& p, const InterseqArgs& ia, const StripsLaunch& sl, StripsProbe* seenOut) {
+        // With end locations a lane is exact below 384 (768 for strips of 32 rows). Scores of
+        // long queries against long targets under cheap gaps are in the thousands - every lane
+        // would be redone, and a launch that gives up half-way has cost half its time. The
+        // twelve longest groups (the highest scores) go through the scores-only kernel first:
+        // 1536 targets, a unit's time; when half of them are beyond the range the general
+        // kernel takes the search.
+        InterseqArgs probe = ia;
+        probe.nGroups = std::min(12, ia.nGroups);
+        probe.batchGroups = 1;
+        probe.overflow = nullptr;
+        probe.stripKeys = nullptr;
+        probe.stripAbort = nullptr;
+        seenOut->launch = launchInterseqPair(probe, p.rows, kPairSwStrips, sl.pairUnits, stream, false);
+        if (seenOut->launch == hipSuccess) {
+            seenOut->lanes = probe.nGroups * kGroupTargets;
+            std::vector<int32_t> seen((size_t)seenOut->lanes);
+            RC_TRY(ws->stageDownload(seen.data(), ia.score + (size_t)p.firstGroup * kGroupTargets, seen.size() * sizeof(int32_t)));
+            RC_TRY(ws->finishDownloads());
+            for (int32_t v : seen) seenOut->beyond += v >= p.biasedLimit;
+        }
+        return 0;
+    }
+
+    // ... and the launch itself, with its second sweep where the end locations come from one (*pe: refused)
+    int launchStripsSweeps(const View* view, const ScorePlan& p, const InterseqArgs& ia, const StripsLaunch& sl, hipError_t* refused) {
+        hipError_t pe = hipSuccess;
+        if (p.probeEnds) {
+            // (the probe's units and scores are wiped: the real launch starts from zero)
+            HIP_TRY(hipMemsetAsync(ia.unitCounter, 0, ((size_t)ia.nGroups * p.nStrips + 2) * sizeof(int), stream));
+            HIP_TRY(hipMemsetAsync(ia.score, 0, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), stream));
+        }
+        pe = tuned(Tune::TEST_REFUSE_PAIR_LAUNCH) ? hipErrorInvalidValue
+                                                  : launchInterseqPair(ia, p.rows, sl.flavour, sl.pairUnits, stream, p.rowKeys);
+        if (pe == hipSuccess && sl.timing) {
+            unsigned long long t[8] = {};
+            HIP_TRY(hipMemcpyAsync(t, sl.timing, sizeof t, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            const double life = (double)std::max<unsigned long long>(t[4], 1);
+            fprintf(stderr, "[miopal] strip timing (%llu wavefronts, s_memtime ticks): unit %.3f  poll %.3f  publish %.3f  sweeps %.3f "
+                            "of the wavefronts' life (%.0f ticks each)\n",
+                    t[5], t[0] / life, t[1] / life, t[2] / life, t[3] / life, life / (double)std::max<unsigned long long>(t[5], 1));
+        }
+        if (pe == hipSuccess && p.twoPass) {
+            // second sweep: the first cell (column-major) that holds each target's score, as keys
+            InterseqArgs second = ia;
+            second.known = ia.score;
+            second.overflow = nullptr;
+            second.stripAbort = nullptr;
+            second.faultUnit1 = 0;
+            HIP_TRY(hipMemsetAsync(ia.unitCounter, 0, ((size_t)ia.nGroups * p.nStrips + 1) * sizeof(int), stream));
+            pe = launchInterseqPair(second, p.rows, sl.flavour, sl.pairUnits, stream, false);
+        }
+        *refused = pe;
+        return 0;
+    }
+
+    // step 9, the one-strip pair-table kernels, with the direct scatter and the column split
+    struct OneStripLaunch {
+        hipError_t launch = hipSuccess;   // what the launch said
+        bool directScatter = false;       // the kernel writes database order itself
+    };
+    int launchOneStripPair(const View* view, const ScorePlan& p, InterseqArgs& ia, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ,
+                           bool forked, bool nothingElseWrites, OneStripLaunch* done) {
+        bool directScatter = false;
+        void* wc = nullptr;   // (taken and zeroed below, with the column split's flags behind it)
+        // The persistent workgroups fill every CU (LDS and registers): a kernel of another
+        // stream - the collective that gathers the previous search's scores - would wait for
+        // them to leave. MIOPAL_RESERVE_CUS keeps a few CUs out of the launch for it.
+        int pairUnits = db->computeUnits;
+        if (const int keep = reservedCus(db); keep >= 0)
+            pairUnits = std::max(1, pairUnits - keep);
+        else if (forked)
+            // The persistent workgroups hold their CU's registers for the whole launch: the
+            // wavefront-per-pair kernel on the side stream only finds room as they leave, i.e. it
+            // runs AFTER the packed kernel (log-normal lengths, NW at Q = 53, 6400 pairs on the side:
+            // 2.07 ms; with CUs kept out of the persistent launch 1.66 ms). One CU per 256 pairs.
+            pairUnits = std::max(1, pairUnits - (int)std::min<int64_t>(pairUnits / 4, std::max<int64_t>(8, (g_lastRouting[0] + 255) / 256)));
+        // groups of similar length: every SIMD takes the same share of them (interseq_impl.h)
+        const int longest = view->groupChunksHost[p.firstGroup];
+        const bool uniform = (int64_t)view->groupChunksHost[view->nGroups - 1] * 5 >= (int64_t)longest * 4;
+        {
+            const int blocks = std::max(1, std::min(pairUnits, ia.nGroups));
+            const char* tt = tuned(Tune::TAIL_THROTTLE);
+            ia.tailThrottle = (tt ? tt[0] == '1' : uniform) ? (ia.nGroups + blocks * 4 - 1) / (blocks * 4) : 0;
+        }
+        // Headline fast path: one strip, Smith-Waterman scores, no lane can leave its range, nothing
+        // else writes the results (no side jobs, no skipped groups, no windows): the kernel writes
+        // database order itself - into the caller's device buffer, or for miopalSearch into the
+        // pinned host buffer the results leave from (no scatter kernel, no device-to-host copy).
+        // (round 3, later: with end locations too - three arrays instead of one)
+        if ((p.biased || p.globalPair) && !p.mayOverflow && p.overlap == 0 && !forked && nothingElseWrites &&
+            p.firstGroup == 0 && p.packedSkip == 0 && !tuned(Tune::NO_DIRECT_SCATTER)) {
+            int32_t *target = d_score, *targetI = d_endI, *targetJ = d_endJ;
+            if (hostScoreOut && (hostScoreIsCallers || hostScoreGeneration == ws->stagingGeneration) &&
+                (!p.locate || (hostEndIOut && hostEndJOut)) && !tuned(Tune::NO_HOST_SCATTER)) {
+                target = hostScoreOut;
+                targetI = hostEndIOut;
+                targetJ = hostEndJOut;
+                wroteHost = true;
+            }
+            ia.directOut = target - start;
+            if (p.locate) {
+                ia.directEndI = targetI - start;
+                ia.directEndJ = targetJ - start;
+            }
+            ia.directIds = view->d_ids;
+            ia.directN = view->nPacked;
+            ia.overflow = nullptr;
+            directScatter = true;
+        }
+        const PairFlavour pf = p.globalPair ? kPairGlobalBiased : p.biased ? kPairSwBiased : p.halfFloat ? kPairSwHalf : kPairSwInt16;
+        // Column split (interseq_impl.h): groups of similar length, Smith-Waterman scores of one strip on the
+        // biased flavour, and at least a longest group's chunks for every resident wavefront - no group is cut
+        // twice - or the launch keeps the dynamic hand-out. The plan follows the CUs the launch may use.
+        // MIOPAL_COLUMN_SPLIT: 0 = off, n = forced on n workgroups, "recompute" = forced, nothing handed on.
+        size_t splitFlags = 0;
+        if (pf == kPairSwBiased && !p.locate) {
+            const char* cs = tuned(Tune::COLUMN_SPLIT);
+            const bool recompute = cs && !strcmp(cs, "recompute");
+            const int forced = cs && !recompute ? std::max(0, atoi(cs)) : 0;
+            int64_t chunks = view->totalChunks;
+            for (int g = 0; g < p.firstGroup; ++g) chunks -= view->groupChunksHost[g];
+            // (no empty interval, forced or not: the state of a cut is left for the NEXT wavefront)
+            const int blocks = (int)std::min<int64_t>(forced > 0 ? std::min(forced, pairUnits) : std::max(1, std::min(pairUnits, ia.nGroups)),
+                                                      chunks / kPairWavesPerGroup);
+            const int64_t wavefronts = (int64_t)blocks * kPairWavesPerGroup;
+            if (blocks >= 1 && (recompute || forced > 0 || (!cs && uniform && chunks / wavefronts >= longest))) {
+                void* st;
+                RC_TRY(ws->get(kSplitState, (size_t)(wavefronts + 1) * splitStateBytes(p.pairRows), &st));
+                ia.splitMode = recompute ? 2 : 1;
+                ia.splitBlocks = blocks;
+                ia.chunkPrefix = view->d_chunkPrefix;
+                ia.splitState = (uint4*)st;
+                splitFlags = (size_t)wavefronts + 1;
+            }
+        }
+        RC_TRY(ws->get(kWorkCounter, (1 + splitFlags) * sizeof(int), &wc));
+        HIP_TRY(hipMemsetAsync(wc, 0, (1 + splitFlags) * sizeof(int), stream));
+        ia.workCounter = (int*)wc;
+        if (splitFlags) ia.splitFlags = (int*)wc + 1;
+        // (diagnostic builds of the Smith-Waterman kernel, -DMIOPAL_HEADLINE_TIMING=1: the SIMDs' finish times)
+        unsigned long long* simdFinish = nullptr;
+        const int finishSlots = 1 + 4 * pairUnits;
+        if (pf == kPairSwBiased && tuned(Tune::STRIP_TIMING)) {
+            void* tb;
+            RC_TRY(ws->get(kStripTiming, finishSlots * sizeof(unsigned long long), &tb));
+            HIP_TRY(hipMemsetAsync(tb, 0, finishSlots * sizeof(unsigned long long), stream));
+            HIP_TRY(hipMemsetAsync(tb, 0xff, sizeof(unsigned long long), stream));
+            ia.stripTiming = simdFinish = (unsigned long long*)tb;
+        }
+        g_lastRouting[1] = 2 + (int)pf + (ia.splitMode ? 64 : 0);   // (64: the column split)
+        // the biased kernels exist for every number of rows (NW / HW / OV: every even number): no padding rows to 8
+        // (test switch: the launch behaves as if the runtime had refused it, e.g. its 150 KB of dynamic LDS)
+        const hipError_t pe = tuned(Tune::TEST_REFUSE_PAIR_LAUNCH)
+                                  ? hipErrorInvalidValue
+                                  : launchInterseqPair(ia, (p.biased || p.globalPair) ? p.pairRows : p.rows, pf, pairUnits, stream, p.locate);
+        if (pe == hipSuccess && simdFinish) {
+            std::vector<unsigned long long> t((size_t)finishSlots);
+            HIP_TRY(hipMemcpyAsync(t.data(), simdFinish, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            double sum = 0, last = 0, first = 1e30;
+            int n = 0;
+            for (int i = 1; i < finishSlots; ++i) {
+                if (t[i] == 0) continue;   // (a build without stamps, or a SIMD the launch left alone)
+                const double us = (double)(t[i] - t[0]) / 100.0;   // 100 MHz ticks -> us
+                sum += us;
+                last = std::max(last, us);
+                first = std::min(first, us);
+                ++n;
+            }
+            if (n > 0)
+                fprintf(stderr, "[miopal] headline timing (%d SIMDs, %d groups, %d rows): finish mean %.1f us  first %.1f  last %.1f  "
+                                "last - mean %.1f us\n",
+                        n, ia.nGroups, p.pairRows, sum / n, first, last, last - sum / n);
+        }
+        done->directScatter = directScatter;
+        done->launch = pe;
+        return 0;
+    }
+
+    // step 10: view order -> database order (windows: merged by key)
+    int scatterResults(const View* view, const ScorePlan& p, const InterseqArgs& ia, const PassBuffers& b, bool sideEmpty, bool forked,
+                       bool directScatter, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ) {
+        const int nScatter = view->nPacked - p.packedSkip;
+        if (p.keyed) {
+            // nothing else writes the results of a segmented search before this point: no
+            // target is kept out of the view, no group is skipped (limit >= one window)
+            if (p.firstPos != 0 || !sideEmpty || forked)
+                return fail(MIOPAL_ERR_INTERNAL, "segmented view with side jobs");
+            HIP_TRY(launchScatterKeyed(ia.score, ia.endI, ia.endJ, (const uint8_t*)b.vo, view->d_ids,
+                                       view->d_segStart, nScatter, start, (unsigned long long*)b.keys,
+                                       p.mayOverflow ? (int32_t*)b.ct : nullptr, stream, p.keyBias));
+            HIP_TRY(launchDecodeKeys((const unsigned long long*)b.keys, (int)n, d_score, d_endI, d_endJ, stream, p.keyBias));
+        } else if (!directScatter) {
+            HIP_TRY(launchScatter(ia.score + p.packedSkip, (const uint8_t*)b.vo + p.packedSkip, view->d_ids + p.packedSkip,
+                                  nScatter, start, d_score, p.mayOverflow ? (int32_t*)b.ct : nullptr, p.overlap > 0,
+                                  stream));
+            if (p.locate)
+                HIP_TRY(launchScatterEnds(ia.endI + p.packedSkip, ia.endJ + p.packedSkip, view->d_ids + p.packedSkip,
+                                          nScatter, start, d_endI, d_endJ, stream));
+        }
+        return 0;
+    }
+
+    // Score pass (all search types). d_score/d_endI/d_endJ are in database order.
+    int scorePass(int32_t* d_score, int32_t* d_endI, int32_t* d_endJ) {
+        return scorePassImpl(d_score, d_endI, d_endJ, true);
+    }
+
+    // The steps in order. A pass that has to start over calls itself: every such condition is in this function.
+    int scorePassImpl(int32_t* d_score, int32_t* d_endI, int32_t* d_endJ, bool useHalf) {
+        RC_TRY(rulesFor(mode, &r));
+        rules = packRules(r);
+        std::vector<PairJob> jobs;
+        RC_TRY(checkInt32Range(model(), Q, db->maxLen));
+        // a pass that starts over (refused launch, declined probe, next rung) writes the device arrays:
+        // whatever an earlier attempt put into the host-visible buffer is not the result
+        wroteHost = false;
+
+        g_lastRouting[0] = g_lastRouting[1] = g_lastRouting[2] = g_lastRouting[3] = 0;
+        if (!interseqUsable() || (smallSearch() && smallSearchAllowed(db))) {
+            g_lastRouting[0] = n;
+            jobs.reserve((size_t)n);
+            for (int64_t k = start; k < end; ++k) jobs.push_back(forwardJob(k, rules));
+            return runPairs(jobs, false, d_score, d_endI, d_endJ, nullptr);
+        }
+
+        PhaseTimer spt;
+        ScorePlan p;
+        PassBuffers b;
+        planWindows(p);
+        std::shared_ptr<View> view;
+        RC_TRY(getView(db, start, end, p.overlap, &view, p.stride));
+        spt.mark("    view lookup");
+        // not handled by the packed kernel: can be recomputed beside it
+        std::vector<PairJob> sideJobs;
+        for (int32_t id : view->longIds) sideJobs.push_back(forwardJob(id, rules));
+        // windows of one target are merged with atomicMax: start from 0 (Smith-Waterman scores
+        // are never negative); whole-target results of the int32 kernel are plain stores of the
+        // final value, in either order the maximum is that value
+        p.keyed = p.overlap > 0 && searchType != OPAL_SEARCH_SCORE;  // with end locations
+        if (p.keyed) {
+            RC_TRY(ws->get(kKeys, (size_t)n * sizeof(unsigned long long), &b.keys));
+            HIP_TRY(hipMemsetAsync(b.keys, 0, (size_t)n * sizeof(unsigned long long), stream));
+        } else if (p.overlap > 0) {
+            // (Smith-Waterman scores start from 0, HW scores from "minus infinity")
+            if (p.keyBias) HIP_TRY(launchFillInt32(d_score, (int)n, INT32_MIN, stream));
+            else HIP_TRY(hipMemsetAsync(d_score, 0, (size_t)n * sizeof(int32_t), stream));
+        }
+        planGeneralStrips(view.get(), p);
+        planSwPairStrips(view.get(), useHalf, p);
+        planGlobalPairStrips(view.get(), useHalf, p);
+        planSideCut(view.get(), p, sideJobs);
+
+        if (view->nGroups > p.firstGroup) {
+            planLanes(view.get(), useHalf, p, jobs, sideJobs);
+            const std::vector<int16_t> prof = buildProfile(p);
+            // (a score pass that started over has its side jobs on the side stream already: they are still joined)
             bool forked = sideForked;
             bool directScatter = false;   // the packed kernel wrote database order itself
-            if (!sideDone.empty()) {
-                sideJobs.erase(std::remove_if(sideJobs.begin(), sideJobs.end(), [&](const PairJob& j) {
-                                   return std::binary_search(sideDone.begin(), sideDone.end(), j.out);
-                               }), sideJobs.end());
-            }
-            // The side kernel is handed to its stream BEFORE the packed launch: its wavefronts are dispatched
-            // first, over the whole chip, and the persistent packed workgroups (one per CU, every register of
-            // it) start on a CU when its side wavefronts are done. (Handed over after the packed launch the
-            // side kernel only finds the CUs the launch left out: cfg4 with its tail, 8 CUs: 54 against 44 ms.)
-            // Beside a strips kernel the side units come in workgroups of 16 wavefronts,
-            // so that they hold few CUs (launchIntraseqStrips), and the packed launch takes EVERY CU: the
-            // workgroups that start late simply take fewer units.
-            if (!sideJobs.empty() && !tuned(Tune::NO_SIDE_STREAM)) {
-                RC_TRY(ws->ensureAux());
-                RC_TRY(ensurePairInputs());
-                HIP_TRY(hipEventRecord(ws->evFork, stream));
-                HIP_TRY(hipStreamWaitEvent(ws->aux, ws->evFork, 0));
-                forked = true;
-                besidePersistent = pairStrips;
-                RC_TRY(runPairs(sideJobs, false, d_score, d_endI, d_endJ, nullptr, ws->aux, kAuxJobs - kJobs));
-                HIP_TRY(hipEventRecord(ws->evJoin, ws->aux));
-                for (const PairJob& j : sideJobs) sideDone.push_back(j.out);
-                std::sort(sideDone.begin(), sideDone.end());
-                sideJobs.clear();
-                sideForked = true;   // (a score pass that starts over still joins what is on the side stream)
-                spt.mark("    side jobs enqueued");
-            }
-            void *pp, *vs, *vo, *ct;
-            RC_TRY(ws->get(kProfile, prof.size() * sizeof(int16_t), &pp));
-            RC_TRY(ws->get(kViewScore, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), &vs));
-            RC_TRY(ws->get(kViewOvf, (size_t)view->nGroups * kGroupTargets, &vo));
-            RC_TRY(ws->get(kCounter, sizeof(int32_t), &ct));
-            RC_TRY(ws->stageUpload(pp, prof.data(), prof.size() * sizeof(prof[0]), stream));
-            // lanes can only leave the exact range when min(Q, L) * maxScore reaches the limit
-            // (also bounded by the query itself: every residue is aligned at most once, at best with
-            // its most favourable partner - 280 for the 53-aa README query under BLOSUM62, where
-            // Q * max(S) says 583)
-            const int64_t reach = std::min<int64_t>((int64_t)std::min(Q, view->maxPackedLen) * std::max(maxScore, 0), queryBest);
-            const int64_t limit = (biased || pairStrips) ? biasedLimit : swShifted ? swLimit : halfFloat ? 2048 : 32767;
-            // (the multi-strip NW / HW / OV kernel flags nothing for its range; the count brings back the
-            // lanes of units that gave up on the strip above - never seen outside the fault-injection test)
-            // (the strips kernels: always - the count also brings back the lanes of a unit that gave up on
-            // the strip above it; searches of several strips take milliseconds, the 4-byte download is free)
-            const bool mayOverflow = sw ? (reach >= limit || pairStrips) : globalStrips;
-            // How many flagged lanes are redone one by one before the whole view takes the next rung: the int32
-            // kernel fills about 1e12 cells a second, the next rung 5e12 .. 8e12 over the WHOLE view - an eighth
-            // of the view's targets costs the same either way (round 3; it was 2048 whatever the size: 0.3 % of
-            // 1M x 300 beyond the row keys' 384 at Q = 1000 sent the other 99.7 % through a second launch)
-            const int64_t directLimit = std::max<int64_t>(kMaxDirectRecompute, (view->nPacked - packedSkip) / 8);
-            if (mayOverflow) HIP_TRY(hipMemsetAsync(ct, 0, sizeof(int32_t), stream));
+            RC_TRY(forkSideJobs(p, sideJobs, d_score, d_endI, d_endJ, &forked, spt));
             InterseqArgs ia{};
-            ia.pack = view->d_pack;
-            ia.groupOff = view->d_groupOff;
-            ia.groupChunks = view->d_groupChunks;
-            ia.nGroups = view->nGroups - firstGroup;
-            ia.groupBase = firstGroup;
-            ia.profile = (const int16_t*)pp;
-            ia.nSymbols = nSym;
-            ia.qPad = qPad;
-            ia.nStrips = nStrips;
-            ia.qLen = Q;
-            ia.gapOpen = std::min(open, 32767);
-            ia.gapExt = std::min(ext, 32767);
-            ia.topGap = r.topGap;
-            ia.leftGap = r.leftGap;
-            ia.region = r.region;
-            ia.lens = view->d_lens;
-            ia.score = (int32_t*)vs;
-            if (locate) {
-                void *vi, *vj;
-                RC_TRY(ws->get(kViewEndI, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), &vi));
-                RC_TRY(ws->get(kViewEndJ, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), &vj));
-                ia.endI = (int32_t*)vi;
-                ia.endJ = (int32_t*)vj;
-            }
-            ia.overflow = (sw || globalStrips) ? (uint8_t*)vo : nullptr;
-            ia.stripSpinCap = faultSpinCap;
-            ia.faultUnit1 = faultKind == 1 ? faultUnit + 1 : 0;
-            ia.biasedLimit = swShifted ? swLimit : biasedLimit;
-            ia.scoreBias = swBias;
-            ia.biasedZero = (int)globalZero;
-            ia.boundaryOff = view->d_boundaryOff;
-            ia.capGroups = capGroups;
-            ia.capChunks = capChunks;
-            ia.priorityChunks = (int)std::min<int64_t>(std::max<int64_t>(balancedChunks, 16), INT32_MAX);
-            if ((nStrips + waves - 1) / waves > 1) {
-                void *b0, *b1;
-                const size_t bytes = (size_t)view->totalChunks * 4 * kLanes * sizeof(uint2);
-                RC_TRY(ws->get(kBoundary0, bytes, &b0));
-                RC_TRY(ws->get(kBoundary1, bytes, &b1));
-                ia.boundary[0] = (uint2*)b0;
-                ia.boundary[1] = (uint2*)b1;
-            }
-            // several rounds of strips per group, scores only: (group, round) units instead of one
-            // workgroup per group (interseq_impl.h, "unit mode")
-            // Only when the groups are few for the chip (under six workgroup-lifetimes): the rounds of
-            // a group are then far apart in time and its boundary rows come back from HBM, not from
-            // the caches (500k x 300 at Q = 300, 7.6 lifetimes: 6.6 ms classic, 7.0 ms in units;
-            // 100k x 2000 at Q = 2000, 3.05 lifetimes: 66 ms classic, 55 ms in units).
-            const int64_t unitSlots = (int64_t)db->computeUnits * std::max(1, 8 / waves);
-            const char* um = tuned(Tune::UNITS);
-            const bool wantUnits = um ? um[0] == '1' : (int64_t)(view->nGroups - firstGroup) < 6 * unitSlots;
-            if (pairStrips) {
-                // unit counter + chunks published per (group, strip); scores and flags start from zero
-                // (a group's answer is the maximum over its strips' units)
-                void* us;
-                const size_t ints = (size_t)ia.nGroups * nStrips + 2;
-                RC_TRY(ws->get(kUnitState, ints * sizeof(int), &us));
-                HIP_TRY(hipMemsetAsync(us, 0, ints * sizeof(int), stream));
-                if (mayOverflow && sw) {
-                    // more flagged lanes than are redone one by one: the launch stops, the view takes the next rung
-                    ia.stripAbort = (int*)us + ints - 1;
-                    ia.stripAbortAt = (int)std::min<int64_t>(2 * directLimit, INT32_MAX / 2);
-                    ia.stripGaveUp = (int*)ct;
-                }
-                // (the scores-only form of the NW / HW / OV kernel folds OV's candidates into the view scores,
-                // and what a unit that gave up leaves behind is "minus infinity" in every mode)
-                if (globalStrips) HIP_TRY(launchFillInt32((int32_t*)vs, view->nGroups * kGroupTargets, INT32_MIN, stream));
-                else HIP_TRY(hipMemsetAsync(vs, 0, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), stream));
-                HIP_TRY(hipMemsetAsync(vo, 0, (size_t)view->nGroups * kGroupTargets, stream));
-                ia.unitCounter = (int*)us;
-                ia.unitFlags = (int*)us + 1;
-                if (locate) {
-                    void* sk;
-                    RC_TRY(ws->get(kStripKeys, (size_t)view->nGroups * kGroupTargets * sizeof(unsigned long long), &sk));
-                    HIP_TRY(hipMemsetAsync(sk, 0, (size_t)view->nGroups * kGroupTargets * sizeof(unsigned long long), stream));
-                    ia.stripKeys = (unsigned long long*)sk;
-                }
-            } else if ((nStrips + waves - 1) / waves > 1 && !locate && !usePair && !globalPair && wantUnits) {
-                void *us, *up;
-                const size_t ints = (size_t)ia.nGroups + 1;
-                RC_TRY(ws->get(kUnitState, ints * sizeof(int), &us));
-                RC_TRY(ws->get(kUnitPartial, (size_t)ia.nGroups * waves * kLanes * sizeof(uint2), &up));
-                HIP_TRY(hipMemsetAsync(us, 0, ints * sizeof(int), stream));
-                ia.unitCounter = (int*)us;
-                ia.unitFlags = (int*)us + 1;
-                ia.unitPartial = (uint2*)up;
-            }
+            RC_TRY(prepareLaunch(view.get(), p, prof, b, ia));
             const bool timed = db->profiling.load() != 0;
             EventPair ev;
             if (timed) {
@@ -1011,218 +1267,50 @@ struct Search {
                 HIP_TRY(hipEventCreate(&ev.e1));
                 HIP_TRY(hipEventRecord(ev.e0, stream));
             }
-            g_lastRouting[1] = 1 + 32 * (int)flavour;  // general kernel and its lane arithmetic
-            if (pairStrips) {
-                int pairUnits = db->computeUnits;
-                if (const int keep = reservedCus(db); keep >= 0)
-                    pairUnits = std::max(1, pairUnits - keep);
-                // (no CUs are kept out of the launch for the side kernel, as round 2 did: the units are taken
-                // dynamically, so a workgroup whose CU is busy with side wavefronts at first just starts later
-                // and takes fewer)
-                const PairFlavour stripsFlavour = globalStrips ? kPairGlobalStrips : kPairSwStrips;
-                g_lastRouting[1] = 2 + (int)stripsFlavour;
-                // few (group, strip) units: fewer groups per workgroup, so that every CU gets a unit and a
-                // wavefront shares its SIMD with fewer others
-                ia.batchGroups = (int)std::max<int64_t>(1, std::min<int64_t>(12, (int64_t)ia.nGroups * nStrips / std::max(1, pairUnits)));
-                // (diagnostic builds of the kernels, -DMIOPAL_STRIP_TIMING=1: their six counters, printed below)
-                unsigned long long* stripTiming = nullptr;
-                if (tuned(Tune::STRIP_TIMING)) {
-                    void* tb;
-                    RC_TRY(ws->get(kStripTiming, 8 * sizeof(unsigned long long), &tb));
-                    HIP_TRY(hipMemsetAsync(tb, 0, 8 * sizeof(unsigned long long), stream));
-                    ia.stripTiming = stripTiming = (unsigned long long*)tb;
-                }
+            g_lastRouting[1] = 1 + 32 * (int)p.flavour;  // general kernel and its lane arithmetic
+            if (p.pairStrips) {
+                StripsLaunch sl;
+                RC_TRY(prepareStripsLaunch(p, ia, &sl));
                 hipError_t pe = hipSuccess;
-                // (random pairs only get there in the linear regime of the scoring system, and then score
-                // about half a unit per aligned residue: nothing to probe for under ~500 residues)
-                if (sw && rowKeys && mayOverflow && std::min(Q, view->maxPackedLen) >= 512 && !tuned(Tune::PAIR_STRIPS)) {
-                    // With end locations a lane is exact below 384 (768 for strips of 32 rows). Scores of
-                    // long queries against long targets under cheap gaps are in the thousands - every lane
-                    // would be redone, and a launch that gives up half-way has cost half its time. The
-                    // twelve longest groups (the highest scores) go through the scores-only kernel first:
-                    // 1536 targets, a unit's time; when half of them are beyond the range the general
-                    // kernel takes the search.
-                    InterseqArgs probe = ia;
-                    probe.nGroups = std::min(12, ia.nGroups);
-                    probe.batchGroups = 1;
-                    probe.overflow = nullptr;
-                    probe.stripKeys = nullptr;
-                    probe.stripAbort = nullptr;
-                    pe = launchInterseqPair(probe, rows, kPairSwStrips, pairUnits, stream, false);
-                    if (pe == hipSuccess) {
-                        const int lanes = probe.nGroups * kGroupTargets;
-                        std::vector<int32_t> seen((size_t)lanes);
-                        RC_TRY(ws->stageDownload(seen.data(), ia.score + (size_t)firstGroup * kGroupTargets, (size_t)lanes * sizeof(int32_t)));
-                        RC_TRY(ws->finishDownloads());
-                        int beyond = 0;
-                        for (int32_t v : seen) beyond += v >= biasedLimit;
-                        if (2 * beyond >= lanes) {
-                            // (round 3: two sweeps of this kernel instead of the general kernel's row scans;
-                            // MIOPAL_NO_TWO_PASS_ENDS restores round 2)
-                            stripsEndsDeclined = true;
-                            twoPassEnds = !tuned(Tune::NO_TWO_PASS_ENDS);
-                            return scorePassImpl(d_score, d_endI, d_endJ, useHalf);
-                        }
-                        // (the probe's units and scores are wiped: the real launch starts from zero)
-                        HIP_TRY(hipMemsetAsync(ia.unitCounter, 0, ((size_t)ia.nGroups * nStrips + 2) * sizeof(int), stream));
-                        HIP_TRY(hipMemsetAsync(ia.score, 0, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), stream));
+                if (p.probeEnds) {
+                    StripsProbe probe;
+                    RC_TRY(probeStripsEnds(p, ia, sl, &probe));
+                    pe = probe.launch;
+                    if (pe == hipSuccess && 2 * probe.beyond >= probe.lanes) {
+                        // (round 3: two sweeps of this kernel instead of the general kernel's row scans;
+                        // MIOPAL_NO_TWO_PASS_ENDS restores round 2)
+                        stripsEndsDeclined = true;
+                        twoPassEnds = !tuned(Tune::NO_TWO_PASS_ENDS);
+                        return scorePassImpl(d_score, d_endI, d_endJ, useHalf);
                     }
                 }
-                if (pe == hipSuccess)
-                    pe = tuned(Tune::TEST_REFUSE_PAIR_LAUNCH) ? hipErrorInvalidValue
-                                                              : launchInterseqPair(ia, rows, stripsFlavour, pairUnits, stream, rowKeys);
-                if (pe == hipSuccess && stripTiming) {
-                    unsigned long long t[8] = {};
-                    HIP_TRY(hipMemcpyAsync(t, stripTiming, sizeof t, hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    const double life = (double)std::max<unsigned long long>(t[4], 1);
-                    fprintf(stderr, "[miopal] strip timing (%llu wavefronts, s_memtime ticks): unit %.3f  poll %.3f  publish %.3f  sweeps %.3f "
-                                    "of the wavefronts' life (%.0f ticks each)\n",
-                            t[5], t[0] / life, t[1] / life, t[2] / life, t[3] / life, life / (double)std::max<unsigned long long>(t[5], 1));
-                }
-                if (pe == hipSuccess && twoPass) {
-                    // second sweep: the first cell (column-major) that holds each target's score, as keys
-                    InterseqArgs second = ia;
-                    second.known = ia.score;
-                    second.overflow = nullptr;
-                    second.stripAbort = nullptr;
-                    second.faultUnit1 = 0;
-                    HIP_TRY(hipMemsetAsync(ia.unitCounter, 0, ((size_t)ia.nGroups * nStrips + 1) * sizeof(int), stream));
-                    pe = launchInterseqPair(second, rows, stripsFlavour, pairUnits, stream, false);
-                }
+                if (pe == hipSuccess) RC_TRY(launchStripsSweeps(view.get(), p, ia, sl, &pe));
                 if (pe != hipSuccess) {
                     // (e.g. the runtime refuses 150 KB of dynamic LDS: start over on the general kernel)
                     (void)hipGetLastError();
-                    (globalStrips ? globalStripsRefused : pairStripsRefused) = true;
+                    (p.globalStrips ? globalStripsRefused : pairStripsRefused) = true;
                     if (tuned(Tune::VERBOSE))
                         fprintf(stderr, "miopal: multi-strip pair-table kernel refused (%s), using the general kernel\n",
                                 hipGetErrorString(pe));
                     return scorePassImpl(d_score, d_endI, d_endJ, useHalf);
                 }
                 // (score, column, row) keys merged over the strips -> view-order scores and end locations
-                if (globalStrips && locate)
+                if (p.globalStrips && p.locate)
                     HIP_TRY(launchDecodeGlobalKeys(ia.stripKeys, view->d_lens, view->nGroups * kGroupTargets, Q, ia.score,
                                                    ia.endI, ia.endJ, stream));
-                else if (locate)
+                else if (p.locate)
                     HIP_TRY(launchDecodeStripKeys(ia.stripKeys, view->nGroups * kGroupTargets, ia.score, ia.endI, ia.endJ, stream));
-            } else if (usePair || globalPair) {
-                void* wc = nullptr;   // (taken and zeroed below, with the column split's flags behind it)
-                // The persistent workgroups fill every CU (LDS and registers): a kernel of another
-                // stream - the collective that gathers the previous search's scores - would wait for
-                // them to leave. MIOPAL_RESERVE_CUS keeps a few CUs out of the launch for it.
-                int pairUnits = db->computeUnits;
-                if (const int keep = reservedCus(db); keep >= 0)
-                    pairUnits = std::max(1, pairUnits - keep);
-                else if (forked)
-                    // The persistent workgroups hold their CU's registers for the whole launch: the
-                    // wavefront-per-pair kernel on the side stream only finds room as they leave, i.e. it
-                    // runs AFTER the packed kernel (log-normal lengths, NW at Q = 53, 6400 pairs on the side:
-                    // 2.07 ms; with CUs kept out of the persistent launch 1.66 ms). One CU per 256 pairs.
-                    pairUnits = std::max(1, pairUnits - (int)std::min<int64_t>(pairUnits / 4, std::max<int64_t>(8, (g_lastRouting[0] + 255) / 256)));
-                // groups of similar length: every SIMD takes the same share of them (interseq_impl.h)
-                const int longest = view->groupChunksHost[firstGroup];
-                const bool uniform = (int64_t)view->groupChunksHost[view->nGroups - 1] * 5 >= (int64_t)longest * 4;
-                {
-                    const int blocks = std::max(1, std::min(pairUnits, ia.nGroups));
-                    const char* tt = tuned(Tune::TAIL_THROTTLE);
-                    ia.tailThrottle = (tt ? tt[0] == '1' : uniform) ? (ia.nGroups + blocks * 4 - 1) / (blocks * 4) : 0;
-                }
-                // Headline fast path: one strip, Smith-Waterman scores, no lane can leave its range, nothing
-                // else writes the results (no side jobs, no skipped groups, no windows): the kernel writes
-                // database order itself - into the caller's device buffer, or for miopalSearch into the
-                // pinned host buffer the results leave from (no scatter kernel, no device-to-host copy).
-                // (round 3, later: with end locations too - three arrays instead of one)
-                if ((biased || globalPair) && !mayOverflow && overlap == 0 && !forked && sideJobs.empty() && jobs.empty() &&
-                    firstGroup == 0 && packedSkip == 0 && !tuned(Tune::NO_DIRECT_SCATTER)) {
-                    int32_t *target = d_score, *targetI = d_endI, *targetJ = d_endJ;
-                    if (hostScoreOut && (hostScoreIsCallers || hostScoreGeneration == ws->stagingGeneration) &&
-                        (!locate || (hostEndIOut && hostEndJOut)) && !tuned(Tune::NO_HOST_SCATTER)) {
-                        target = hostScoreOut;
-                        targetI = hostEndIOut;
-                        targetJ = hostEndJOut;
-                        wroteHost = true;
-                    }
-                    ia.directOut = target - start;
-                    if (locate) {
-                        ia.directEndI = targetI - start;
-                        ia.directEndJ = targetJ - start;
-                    }
-                    ia.directIds = view->d_ids;
-                    ia.directN = view->nPacked;
-                    ia.overflow = nullptr;
-                    directScatter = true;
-                }
-                const PairFlavour pf = globalPair ? kPairGlobalBiased : biased ? kPairSwBiased : halfFloat ? kPairSwHalf : kPairSwInt16;
-                // Column split (interseq_impl.h): groups of similar length, Smith-Waterman scores of one strip on the
-                // biased flavour, and at least a longest group's chunks for every resident wavefront - no group is cut
-                // twice - or the launch keeps the dynamic hand-out. The plan follows the CUs the launch may use.
-                // MIOPAL_COLUMN_SPLIT: 0 = off, n = forced on n workgroups, "recompute" = forced, nothing handed on.
-                size_t splitFlags = 0;
-                if (pf == kPairSwBiased && !locate) {
-                    const char* cs = tuned(Tune::COLUMN_SPLIT);
-                    const bool recompute = cs && !strcmp(cs, "recompute");
-                    const int forced = cs && !recompute ? std::max(0, atoi(cs)) : 0;
-                    int64_t chunks = view->totalChunks;
-                    for (int g = 0; g < firstGroup; ++g) chunks -= view->groupChunksHost[g];
-                    // (no empty interval, forced or not: the state of a cut is left for the NEXT wavefront)
-                    const int blocks = (int)std::min<int64_t>(forced > 0 ? std::min(forced, pairUnits) : std::max(1, std::min(pairUnits, ia.nGroups)),
-                                                              chunks / kPairWavesPerGroup);
-                    const int64_t wavefronts = (int64_t)blocks * kPairWavesPerGroup;
-                    if (blocks >= 1 && (recompute || forced > 0 || (!cs && uniform && chunks / wavefronts >= longest))) {
-                        void* st;
-                        RC_TRY(ws->get(kSplitState, (size_t)(wavefronts + 1) * splitStateBytes(pairRows), &st));
-                        ia.splitMode = recompute ? 2 : 1;
-                        ia.splitBlocks = blocks;
-                        ia.chunkPrefix = view->d_chunkPrefix;
-                        ia.splitState = (uint4*)st;
-                        splitFlags = (size_t)wavefronts + 1;
-                    }
-                }
-                RC_TRY(ws->get(kWorkCounter, (1 + splitFlags) * sizeof(int), &wc));
-                HIP_TRY(hipMemsetAsync(wc, 0, (1 + splitFlags) * sizeof(int), stream));
-                ia.workCounter = (int*)wc;
-                if (splitFlags) ia.splitFlags = (int*)wc + 1;
-                // (diagnostic builds of the Smith-Waterman kernel, -DMIOPAL_HEADLINE_TIMING=1: the SIMDs' finish times)
-                unsigned long long* simdFinish = nullptr;
-                const int finishSlots = 1 + 4 * pairUnits;
-                if (pf == kPairSwBiased && tuned(Tune::STRIP_TIMING)) {
-                    void* tb;
-                    RC_TRY(ws->get(kStripTiming, finishSlots * sizeof(unsigned long long), &tb));
-                    HIP_TRY(hipMemsetAsync(tb, 0, finishSlots * sizeof(unsigned long long), stream));
-                    HIP_TRY(hipMemsetAsync(tb, 0xff, sizeof(unsigned long long), stream));
-                    ia.stripTiming = simdFinish = (unsigned long long*)tb;
-                }
-                g_lastRouting[1] = 2 + (int)pf + (ia.splitMode ? 64 : 0);   // (64: the column split)
-                // the biased kernels exist for every number of rows (NW / HW / OV: every even number): no padding rows to 8
-                // (test switch: the launch behaves as if the runtime had refused it, e.g. its 150 KB of dynamic LDS)
-                const hipError_t pe = tuned(Tune::TEST_REFUSE_PAIR_LAUNCH)
-                                          ? hipErrorInvalidValue
-                                          : launchInterseqPair(ia, (biased || globalPair) ? pairRows : rows, pf, pairUnits, stream, locate);
-                if (pe == hipSuccess && simdFinish) {
-                    std::vector<unsigned long long> t((size_t)finishSlots);
-                    HIP_TRY(hipMemcpyAsync(t.data(), simdFinish, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    double sum = 0, last = 0, first = 1e30;
-                    int n = 0;
-                    for (int i = 1; i < finishSlots; ++i) {
-                        if (t[i] == 0) continue;   // (a build without stamps, or a SIMD the launch left alone)
-                        const double us = (double)(t[i] - t[0]) / 100.0;   // 100 MHz ticks -> us
-                        sum += us;
-                        last = std::max(last, us);
-                        first = std::min(first, us);
-                        ++n;
-                    }
-                    if (n > 0)
-                        fprintf(stderr, "[miopal] headline timing (%d SIMDs, %d groups, %d rows): finish mean %.1f us  first %.1f  last %.1f  "
-                                        "last - mean %.1f us\n",
-                                n, ia.nGroups, pairRows, sum / n, first, last, last - sum / n);
-                }
+            } else if (p.usePair || p.globalPair) {
+                OneStripLaunch done;
+                RC_TRY(launchOneStripPair(view.get(), p, ia, d_score, d_endI, d_endJ, forked, sideJobs.empty() && jobs.empty(), &done));
+                directScatter = done.directScatter;
+                const hipError_t pe = done.launch;
                 if (pe != hipSuccess) {
                     // e.g. the runtime refuses 150 KB of dynamic LDS: use the v_perm variant (the
                     // biased profile is a plain int16 profile whose padding score, -1024, cannot raise
                     // a Smith-Waterman maximum either)
                     (void)hipGetLastError();
-                    if (globalPair) {
+                    if (p.globalPair) {
                         // (its profile and its routing of long targets do not suit the general kernel:
                         // start over without it)
                         globalPairRefused = true;
@@ -1235,12 +1323,12 @@ struct Search {
                     if (directScatter) {   // (the general kernel writes view order)
                         directScatter = wroteHost = false;
                         ia.directOut = nullptr;
-                        ia.overflow = (uint8_t*)vo;
+                        ia.overflow = (uint8_t*)b.vo;
                     }
-                    HIP_TRY(launchInterseq(ia, rows, waves, flavour, locate, stream));
+                    HIP_TRY(launchInterseq(ia, p.rows, p.waves, p.flavour, p.locate, stream));
                 }
             } else {
-                HIP_TRY(launchInterseq(ia, rows, waves, flavour, locate, stream));
+                HIP_TRY(launchInterseq(ia, p.rows, p.waves, p.flavour, p.locate, stream));
             }
             if (timed) {
                 HIP_TRY(hipEventRecord(ev.e1, stream));
@@ -1248,50 +1336,33 @@ struct Search {
                 ws->timings.emplace_back(ev.release());
                 db->lastTimed = ws;
             }
-            const int nScatter = view->nPacked - packedSkip;
-            if (keyed) {
-                // nothing else writes the results of a segmented search before this point: no
-                // target is kept out of the view, no group is skipped (limit >= one window)
-                if (firstPos != 0 || !sideJobs.empty() || forked)
-                    return fail(MIOPAL_ERR_INTERNAL, "segmented view with side jobs");
-                HIP_TRY(launchScatterKeyed(ia.score, ia.endI, ia.endJ, (const uint8_t*)vo, view->d_ids,
-                                           view->d_segStart, nScatter, start, (unsigned long long*)keys,
-                                           mayOverflow ? (int32_t*)ct : nullptr, stream, keyBias));
-                HIP_TRY(launchDecodeKeys((const unsigned long long*)keys, (int)n, d_score, d_endI, d_endJ, stream, keyBias));
-            } else if (!directScatter) {
-                HIP_TRY(launchScatter(ia.score + packedSkip, (const uint8_t*)vo + packedSkip, view->d_ids + packedSkip,
-                                      nScatter, start, d_score, mayOverflow ? (int32_t*)ct : nullptr, overlap > 0,
-                                      stream));
-                if (locate)
-                    HIP_TRY(launchScatterEnds(ia.endI + packedSkip, ia.endJ + packedSkip, view->d_ids + packedSkip,
-                                              nScatter, start, d_endI, d_endJ, stream));
-            }
+            RC_TRY(scatterResults(view.get(), p, ia, b, sideJobs.empty(), forked, directScatter, d_score, d_endI, d_endJ));
             if (forked) HIP_TRY(hipStreamWaitEvent(stream, ws->evJoin, 0));
             spt.mark("    packed kernel enqueued");
             if (spt.on) {
                 HIP_TRY(hipStreamSynchronize(stream));
                 spt.mark("    packed + side kernels done");
             }
-            if (mayOverflow) {
+            if (p.mayOverflow) {
                 int32_t count = 0;
-                RC_TRY(ws->stageDownload(&count, ct, sizeof(int32_t)));
+                RC_TRY(ws->stageDownload(&count, b.ct, sizeof(int32_t)));
                 RC_TRY(ws->finishDownloads());
-                if (pairStrips && sw && rowKeys && count > directLimit && !twoPassEnds && !tuned(Tune::NO_TWO_PASS_ENDS)) {
+                if (p.pairStrips && p.sw && p.rowKeys && count > p.directLimit && !twoPassEnds && !tuned(Tune::NO_TWO_PASS_ENDS)) {
                     // many lanes left the row keys' range (384 .. 768): the scores' own range is 25600 -
                     // two sweeps of the strips kernel before the int16 rung
                     twoPassEnds = true;
                     return scorePassImpl(d_score, d_endI, d_endJ, useHalf);
                 }
-                if ((halfFloat || biased || swShifted || pairStrips) && count > directLimit) {
+                if ((p.halfFloat || p.biased || p.swShifted || p.pairStrips) && count > p.directLimit) {
                     // many targets left the half-float range: second rung, int16 lanes,
                     // over the whole view (its results overwrite the first pass)
                     return scorePassImpl(d_score, d_endI, d_endJ, false);
                 }
                 if (count > 0) {
                     std::vector<uint8_t> flags((size_t)view->nPacked);
-                    RC_TRY(ws->stageDownload(flags.data(), vo, flags.size()));
+                    RC_TRY(ws->stageDownload(flags.data(), b.vo, flags.size()));
                     RC_TRY(ws->finishDownloads());
-                    for (int k = packedSkip; k < view->nPacked; ++k)
+                    for (int k = p.packedSkip; k < view->nPacked; ++k)
                         if (flags[k]) queueWhole(jobs, view->ids[k]);
                     g_lastRouting[3] = count;
                 }
@@ -1301,4 +1372,3 @@ struct Search {
         return runPairs(jobs, false, d_score, d_endI, d_endJ, nullptr);
     }
 };
-

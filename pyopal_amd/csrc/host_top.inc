@@ -126,12 +126,12 @@ static int searchTopImpl(MiopalDb* db, const unsigned char* query, int queryLeng
     const int64_t n = end - start;
     if (pssmRows && n > 0) {
         // miopalSearch's range check for its 32-bit kernels, with the extreme entries of the rows (validate()'s place)
-        Search probe{db, nullptr, nullptr, nullptr, queryLength, gapOpen, gapExt, alphabetLength, searchType, mode, nullptr, start, end, n};
+        ScoreModel m{gapOpen, gapExt, 0, 0};
         if (queryLength > 0) {
-            probe.maxScore = *std::max_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
-            probe.minScore = *std::min_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
+            m.maxScore = *std::max_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
+            m.minScore = *std::min_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
         }
-        RC_TRY(probe.checkInt32(db->maxLen));
+        RC_TRY(checkInt32Range(m, queryLength, db->maxLen));
     }
     if (k == 0 || n == 0) {
         emptyTopRows((int)outRow, (int)outRow + 1, k, count, targetIndex, score, locate ? endTarget : nullptr,

@@ -115,6 +115,15 @@ def test_launch_layer_once_per_device_and_row_dispatch(capi):
     assert capi.lib().miopalSelfTest(3) == 0
 
 
+def test_score_ranges_against_hand_worked_literals(capi):
+    # score_ranges.h, the one copy of the host router's range rules, under BLOSUM62 3 / 1: the biased band and its limits
+    # (25600; 1536 / 768 / 384 with row keys; lowered by a step up's excess over 0x0400; each of its four conditions at
+    # its boundary), the longest query of the multi-strip NW / HW / OV kernels (2355 / 2210), the one-strip zero (1105,
+    # the batch form's 2 ext floor), the 32-bit bound around 2^29, the longest targets of the int16 lane flavours at
+    # Q = 53 (31937 / 31363 / 26994). The number of the first failing check comes back. Needs no device.
+    assert capi.lib().miopalSelfTest(4) == 0
+
+
 def test_tuning_switches_are_arguments_not_environment(capi, monkeypatch):
     """include/miopal.h, miopalSetTuning: the library reads MIOPAL_* from the environment once (tests/conftest.py
     sets MIOPAL_NO_SMALL_SEARCH before the first use); afterwards the environment is not looked at again - a

@@ -1,5 +1,6 @@
 """Two routing tables (tools/routing_table.py) cell by cell: usage compare_routing_tables.py OLD.txt NEW.txt [threshold]
-Prints the cells whose time changed by more than the threshold (default 10 %) and a summary."""
+Prints the cells whose time changed by more than the threshold (default 10 %), every cell whose routing differs between the
+two tables (all of them: the time plays no part), and a summary."""
 import sys
 def load(path):
     rows = {}
@@ -10,9 +11,12 @@ def load(path):
     return rows
 old, new = load(sys.argv[1]), load(sys.argv[2])
 thr = float(sys.argv[3]) if len(sys.argv) > 3 else 0.10
-faster = slower = same = 0
+faster = slower = same = rerouted = 0
 for key in sorted(set(old) & set(new)):
     o, n = old[key], new[key]
+    if o[2] != n[2]:
+        rerouted += 1
+        print(f"ROUTING {key[0]:16s} {key[1]} {key[2]:5s} N={key[3]:8d} Q={key[4]:5d}: {o[2]} -> {n[2]}")
     if o[0] < 0.15 and n[0] < 0.15:     # (searches of a handful of targets: launch latencies, box to box)
         continue
     ratio = n[0] / o[0]
@@ -26,4 +30,5 @@ for key in sorted(set(old) & set(new)):
         same += 1
         continue
     print(f"{tag} {key[0]:16s} {key[1]} {key[2]:5s} N={key[3]:8d} Q={key[4]:5d}: {o[0]:9.3f} -> {n[0]:9.3f} ms ({o[1]:6.2f} -> {n[1]:6.2f} TCUPS) routing {o[2]} -> {n[2]}")
-print(f"# {faster} cells more than {thr:.0%} faster, {slower} slower, {same} within, of {len(set(old) & set(new))} common cells")
+print(f"# {faster} cells more than {thr:.0%} faster, {slower} slower, {same} within, {rerouted} routed differently, "
+      f"of {len(set(old) & set(new))} common cells")
