@@ -747,6 +747,7 @@ struct Search {
                 while (k < view->nPacked && k - from <= 1024 && !fits(dbLen(db, view->ids[k]))) ++k;
                 return (k < view->nPacked && k - from <= 1024 && dbLen(db, view->ids[k]) > 0) ? k : -1;
             };
+            const int firstPlain = firstFit;
             const int firstDiag = tuned(Tune::NO_DIAG_SHIFT) ? -1 : firstThat(firstFit, diag);
             if (firstDiag >= 0) {
                 firstFit = firstDiag;
@@ -760,6 +761,15 @@ struct Search {
                         p.flavour = kUnsignedDiag;
                         p.profileShift = 2 * ext + (open - ext);
                     }
+                }
+                // Windows: every entry stays in the launch, and a lane sweeps its group's columns to the end. Beyond
+                // the signed shifted flavour's range the shift (i + j) ext of a column no longer fits 16 bits, and HW's
+                // last-row maximum, which that flavour takes over every swept column, would read it: plain lanes then
+                // (the unsigned flavour masks the columns beyond its own target)
+                if (p.flavour == kSignedInt16Diag && p.overlap > 0 && !diag(view->maxPackedLen)) {
+                    firstFit = firstPlain;
+                    p.flavour = kSignedInt16;
+                    p.profileShift = 0;
                 }
             }
             // The targets that do not fit form a prefix of the view: they go to the int32 kernel BESIDE
