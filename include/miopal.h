@@ -363,6 +363,7 @@ void miopalLastBatchRouting(int64_t counts[4]);
  *      (perpair_scan_refill_kernel: queries of one 64-row strip)
  *  64  directions: two pairs per lane on 16-bit halves (perpair_packed.hip)
  * 128  start cells: two pairs per lane on 16-bit halves
+ * 256  directions: one launch of the packed kernel per group of traceback batches
  * 0: no such search yet, or one whose traceback batches were built on the host.
  */
 int miopalLastFullRouting(void);

@@ -34,6 +34,7 @@
 
 #include "../../include/miopal.h"
 #include "common.h"
+#include "full_plan_selftest.h"
 #include "launch_layer_selftest.h"
 #include "score_ranges_selftest.h"
 #include "select_top.h"
@@ -190,8 +191,7 @@ inline hipError_t createUploadStream(hipStream_t* s) {
 }
 
 constexpr int kLongTarget = 8192;          // longer targets always take the intra-sequence path
-constexpr int64_t kDirBudgetOneLaunch = 8ll << 30;   // directions of every batch of a `full` search at once (host_full.inc)
-constexpr int64_t kDirBudget = 2ll << 30;  // direction workspace: 2 x this per device-resident traceback batch, 1 x per host-built batch
+static_assert(kPlanLanes == kLanes, "full_plan.h counts in wavefronts of kLanes");   // (kDirBudget, kDirBudgetOneLaunch: full_plan.h)
 constexpr int kMaxDirectRecompute = 2048;  // lanes that left their range and are sent straight to int32: at least this many (see directLimit)
 // A lane that owns a whole target walks its columns one after the other (about 0.8 us per
 // column of 56 rows): whatever the number of targets, the lane-per-target kernels need
@@ -563,6 +563,11 @@ int miopalSelfTest(int which) {
         if (which == 4) {
             // the range model of the host router against literals worked out by hand: score_ranges_selftest.h
             return scoreRangesSelfTest();
+        }
+        if (which == 5) {
+            // the plan of the later passes of a `full` search and of a pair list - routing bits, cost model, slot geometry,
+            // traceback batches - against literals worked out from the expressions it replaced: full_plan_selftest.h
+            return fullPlanSelfTest();
         }
         if (which != 1) return -1;
         // (no device call on the way: the handle is never filled, the builders are injected)

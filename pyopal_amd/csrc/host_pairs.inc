@@ -11,7 +11,7 @@
 // Forward pass: one lane per pair (pairlist_forward_kernel; the jobs sorted by length, the outlier head of the sort
 // on the wavefront-per-pair kernel) or one wavefront per pair (intraseq_kernel) for chunks too small to fill the
 // chip, for queries of more than 4096 residues and under NO_PERPAIR - decided by the per-cell cost estimates of
-// host_full.inc. Scan and direction pass: perpair_kernel / intraseq_kernel, as in a one-query `full` search, with the
+// full_plan.h. Scan and direction pass: perpair_kernel / intraseq_kernel, as in a one-query `full` search, with the
 // pair's query origin added to its jobs. Pairs with an empty query or target are answered here (closed forms of the
 // border, oracle/opal_oracle.c).
 //
@@ -42,8 +42,8 @@ int64_t pairChunkCapacity(int64_t maxQ, int64_t maxL, bool full) {
     const int64_t strips = pairStrips(maxQ);
     if (strips > 1) cap = std::min<int64_t>(cap, (4ll << 30) / (16 * std::max<int64_t>(maxL, 1)));
     if (full) {
-        cap = std::min<int64_t>(cap, 2 * kDirBudget / (strips * (maxL + kLanes - 1) * kLanes));
-        cap = std::min<int64_t>(cap, (2ll << 30) / (maxQ + maxL + 16));
+        cap = std::min<int64_t>(cap, 2 * kDirBudget / slotDir(strips, maxL));
+        cap = std::min<int64_t>(cap, (2ll << 30) / slotOpsMost(maxQ, maxL));
     }
     return std::max<int64_t>(cap, 1);
 }
@@ -221,11 +221,11 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
 
         for (const PairChunkPlan& ch : chunks) {
             const int nc = (int)ch.count;
-            const int64_t nc64 = ((int64_t)nc + kLanes - 1) / kLanes * kLanes;
+            const int64_t nc64 = roundLanes(nc);
             const bool oneStrip = ch.maxQ <= kLanes;
             cq.resize((size_t)nc);
             ct.resize((size_t)nc);
-            // the chunk's cells, in 64-row column steps: what either kind of kernel sweeps (host_full.inc's estimates)
+            // the chunk's cells, in 64-row column steps: what either kind of kernel sweeps (full_plan.h's estimates)
             double laneCols = 0, waveCols = 0, laneChain = 0, waveChain = 0;
             for (int k = 0; k < nc; ++k) {
                 const int64_t p = order[(size_t)(ch.first + k)];
@@ -237,12 +237,10 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                 laneChain = std::max(laneChain, strips * L);
                 waveChain = std::max(waveChain, strips * (L + 63));
             }
-            // one lane per pair: ~14 instructions per cell, but a wavefront lasts as long as its longest lane; one
-            // wavefront per pair: ~225 instructions per 64-row column step, a chain of L + 63 steps (host_full.inc; ms)
+            // one lane per pair, where a wavefront lasts as long as its longest lane, or one wavefront per pair, a chain
+            // of L + 63 steps (full_plan.h; ms)
             const bool lanePossible = !ch.waveOnly && tableFits && !tuned(Tune::NO_PERPAIR) && (nc > kSmallSearch || !smallSearchAllowed(db));
-            const double perLane = std::max(laneCols * (14 * 4.5) / (1024 * 2.4e6), laneChain * (64 * 14 * 4.5) / 2.4e6);
-            const double perWave = std::max(waveCols * 225.0 / (1024 * 2.4e6), waveChain * 250.0 / 2.4e6);
-            const bool lane = lanePossible && (forceLane || perLane <= perWave);
+            const bool lane = lanePossible && (forceLane || scanLaneMs(laneCols, laneChain) <= scanWaveMs(waveCols, waveChain));
 
             void *pcq, *pct, *ptoff, *pqbase, *pjobs, *ps, *pi = nullptr, *pj = nullptr;
             RC_TRY(ws->get(kPairListQ, (size_t)nc * sizeof(int32_t), &pcq));
@@ -260,16 +258,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
             const int64_t fwdWsStride = oneStrip ? 0 : ch.maxL;
             HIP_TRY(launchPairListJobs(nc, (const int32_t*)pcq, (const int64_t*)pct, (const int32_t*)pqoff, db->d_offsets, rules,
                                        lane ? 0 : fwdWsStride, (PairJob*)pjobs, (int64_t*)ptoff, (int32_t*)pqbase, stream));
-            PerPairArgs perPair{};
-            perPair.residues = db->d_residues;
-            perPair.query = s.d_query;
-            perPair.queryLength = totalQuery;
-            perPair.matrix = s.d_matrix;
-            perPair.rows = s.d_rows;
-            perPair.alphabet = A;
-            perPair.gapOpen = open;
-            perPair.gapExt = ext;
-            perPair.residueCount = db->total;
+            const PerPairArgs perPair = perPairCommon(db, s, totalQuery, A, open, ext);
             void *pbins = nullptr, *psorted = nullptr, *phead = nullptr;
             int headWaves = 0;
             if (lanePossible) {
@@ -295,7 +284,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                 pa.skipWaves = (const int*)phead;
                 if (!oneStrip) {
                     void* pb;
-                    RC_TRY(ws->get(kPairListBoundary, (size_t)nc64 * ch.maxL * sizeof(int2), &pb));
+                    RC_TRY(ws->get(kPairListBoundary, boundaryBytes(nc, ch.maxL), &pb));
                     pa.boundary = (int2*)pb;
                     pa.boundaryStride = ch.maxL;
                 }
@@ -343,7 +332,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                             HIP_TRY(launchSortJobsByLength((const PairJob*)pjobs, nc, ch.maxL, (int*)pbins, (PairJob*)psorted, stream));
                             pa.jobs = (const PairJob*)psorted;
                             void* pb;
-                            RC_TRY(ws->get(kPairListBoundary, (size_t)nc64 * ch.maxL * sizeof(int2), &pb));
+                            RC_TRY(ws->get(kPairListBoundary, boundaryBytes(nc, ch.maxL), &pb));
                             pa.boundary = (int2*)pb;
                             pa.boundaryStride = ch.maxL;
                         }
@@ -371,17 +360,12 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                                 (long long)order[(size_t)(ch.first + checks[0] - 1)]);
                 const int64_t maxWindow = std::max(checks[1], 1), windowRows = std::max(checks[2], 1);
                 const int64_t windowStrips = (windowRows + kLanes - 1) / kLanes;
-                const int64_t slotDir = windowStrips * (maxWindow + kLanes - 1) * kLanes;
-                const int64_t slotOps = (windowRows + maxWindow + 15) & ~(int64_t)15;
+                const int64_t slotDir = miopal::slotDir(windowStrips, maxWindow);
+                const int64_t slotOps = miopal::slotOps(windowRows, maxWindow);
                 const int64_t traceWsStride = windowStrips > 1 ? maxWindow : 0;
-                // ---- directions: ~21 instructions per cell and lane, or a wavefront per pair (host_full.inc; ms) ------
-                bool traceLane = lanePossible;
-                if (lanePossible && !forceLane) {
-                    const double cells = (double)windowStrips * (double)(maxWindow + kLanes - 1);
-                    const double tl = std::ceil((double)nc / kLanes / 2048.0) * cells * (64 * 21 * 4.5) / 2.4e6;
-                    const double tw = std::max((double)nc * cells * 225.0 / (1024 * 2.4e6), cells * 250.0 / 2.4e6);
-                    traceLane = tl <= tw;
-                }
+                // ---- directions: one lane or one wavefront per pair (full_plan.h; ms; the chunk is one batch) ------
+                const double cells = traceCells(windowStrips, maxWindow);
+                const bool traceLane = lanePossible && (forceLane || traceLaneMs(1, (double)nc, cells) <= traceWaveMs(1, (double)nc, cells));
                 void *pd, *pslots, *pcompact, *pblock, *ptotals;
                 RC_TRY(ws->get(kOps, (size_t)(nc * slotOps), &pslots));
                 RC_TRY(ws->get(kCompactOps, (size_t)(nc * slotOps), &pcompact));
@@ -393,7 +377,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                                         (PairJob*)pjobs, stream, (const int32_t*)pqbase));
                 WalkArgs wa{};
                 if (traceLane) {
-                    const int64_t slotDirUsed = slotDir / 2;   // two rows per byte
+                    const int64_t slotDirUsed = miopal::slotDirUsed(kDirLane, windowStrips, maxWindow);   // two rows per byte
                     if (!ws->tryGet(kDirs, (size_t)(nc64 * slotDirUsed), &pd))
                         return fail(MIOPAL_ERR_HIP, "out of device memory for the traceback workspace");
                     int64_t maxHead = std::min<int64_t>((1ll << 30) / slotDir / kLanes, nc64 / kLanes);
@@ -418,15 +402,14 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                     pa.dirs = (uint8_t*)pd;
                     pa.score = (int32_t*)pts;
                     pa.dirWaveStride = slotDirUsed * kLanes;
-                    pa.dirStripColumns = maxWindow + kLanes - 1;
+                    pa.dirStripColumns = dirStripColumns(false, maxWindow);
                     if (windowStrips > 1) {
                         void* pb;
-                        RC_TRY(ws->get(kPairListBoundary, (size_t)nc64 * maxWindow * sizeof(int2), &pb));
+                        RC_TRY(ws->get(kPairListBoundary, boundaryBytes(nc, maxWindow), &pb));
                         pa.boundary = (int2*)pb;
                         pa.boundaryStride = maxWindow;
                     }
                     HIP_TRY(launchPerPair(pa, kPerPairTrace, stream));
-                    wa.jobs = (const PairJob*)psorted;
                     wa.slotByOut = 1;
                     wa.dirWaveStride = pa.dirWaveStride;
                     wa.dirStripColumns = pa.dirStripColumns;
@@ -434,16 +417,8 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                     if (!ws->tryGet(kDirs, (size_t)(nc * slotDir), &pd))
                         return fail(MIOPAL_ERR_HIP, "out of device memory for the traceback workspace");
                     RC_TRY(s.runDeviceJobs((const PairJob*)pjobs, nc, (int32_t*)pts, nullptr, nullptr, true, (uint8_t*)pd, traceWsStride));
-                    wa.jobs = (const PairJob*)pjobs;
                 }
-                wa.nJobs = nc;
-                wa.residues = db->d_residues;
-                wa.query = s.d_query;
-                wa.dirs = (const uint8_t*)pd;
-                wa.ops = (uint8_t*)pslots;
-                wa.opsSlot = slotOps;
-                wa.queryLength = totalQuery;
-                wa.opsLen = (int32_t*)plen;
+                fillWalk(&wa, (const PairJob*)(traceLane ? psorted : pjobs), nc, db, s, totalQuery, pd, pslots, slotOps, plen);
                 HIP_TRY(launchWalk(wa, stream));
                 HIP_TRY(launchGatherOps(nc, (const uint8_t*)pslots, slotOps, (const int32_t*)plen, (int64_t*)pblock,
                                         (const int64_t*)ptotals, (int64_t*)ptotals + 1, (uint8_t*)pcompact, stream));

@@ -124,6 +124,15 @@ def test_score_ranges_against_hand_worked_literals(capi):
     assert capi.lib().miopalSelfTest(4) == 0
 
 
+def test_full_plan_against_literals_of_the_expressions_it_replaced(capi):
+    # full_plan.h, the one copy of what the later passes of a `full` search and of a pair list decide without the
+    # device: the bits of the routing word, the lane-against-wavefront cost estimates, the slots' geometry and the
+    # traceback batch plan - cfg3 (53 residues against 1M x 300 on 256 CUs: four batches of 285760, two launches),
+    # Q = 300 (one round of 262144 per batch, packed or not), one- and two-strip windows, n = 1 / 64 / 65 / 270 000,
+    # windows of 35 000 columns (the wavefront route), every switch. The number of the first failing check comes back.
+    assert capi.lib().miopalSelfTest(5) == 0
+
+
 def test_tuning_switches_are_arguments_not_environment(capi, monkeypatch):
     """include/miopal.h, miopalSetTuning: the library reads MIOPAL_* from the environment once (tests/conftest.py
     sets MIOPAL_NO_SMALL_SEARCH before the first use); afterwards the environment is not looked at again - a

@@ -2,7 +2,8 @@
     targets N  x  query length Q  x  length distribution  x  algorithm  x  search type,
 and every cell whose throughput is below 0.6 x the better of its neighbours along N or Q (same
 distribution, algorithm and search type) flagged as a cliff. Times the product path only (wall time
-of miopalSearch with host results, best of 3 after a warm-up; no CPU checker).
+of miopalSearch with host results, best of 3 after a warm-up; no CPU checker). RT_MODES=full selects the `full` search
+type: its rows also carry the routing word of the passes behind the score pass (miopalLastFullRouting).
 
 usage: routing_table.py OUT.txt [quick]
 """
@@ -28,7 +29,7 @@ if quick:
 DISTS = ("uniform300", "lognormal", "bimodal100_3000")
 ALGOS = ("sw", "nw", "hw", "ov")
 MODES = ("score", "end")
-# (a part of the table: RT_NS=20000,100000 RT_QS=64,150 RT_DISTS=lognormal RT_ALGOS=sw,hw RT_MODES=score)
+# (a part of the table: RT_NS=20000,100000 RT_QS=64,150 RT_DISTS=lognormal RT_ALGOS=sw,hw RT_MODES=score; RT_MODES=full)
 if os.environ.get("RT_NS"):
     NS = [int(x) for x in os.environ["RT_NS"].split(",")]
 if os.environ.get("RT_QS"):
@@ -60,7 +61,7 @@ def say(line):
     log.flush()
 
 
-say("# dist algo mode N Q ms TCUPS routing(int32 targets, kernel code, groups, redone)")
+say("# dist algo mode N Q ms TCUPS routing(int32 targets, kernel code, groups, redone) [full: + the routing word of the later passes]")
 for dist in DISTS:
     for n in NS:
         rng = np.random.default_rng(1000 + n)
@@ -83,6 +84,8 @@ for dist in DISTS:
                         db.search(q, m, 3, 1, mode, algo)
                         best = min(best, time.perf_counter() - t0)
                     routing = _capi.DeviceDatabase.last_routing()
+                    if mode == "full":
+                        routing = f"{routing} full={_capi.DeviceDatabase.last_full_routing()}"
                     rows[(dist, algo, mode, n, qlen)] = (cells / best / 1e12, best * 1e3, routing)
                     say(f"{dist:16s} {algo} {mode:5s} {n:8d} {qlen:5d} {best * 1e3:10.3f} {cells / best / 1e12:8.3f} {routing}")
         db.close()
