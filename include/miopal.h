@@ -283,6 +283,58 @@ int miopalSearchBatchTop(MiopalDb* db, const unsigned char* queries, const int64
                          int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery);
 
 /*
+ * Every target of the slice that scores at least minScore, compacted on the device: the hits of a query are the
+ * targets of [start, end) with score >= minScore, in index order (database order), and each carries what miopalSearch
+ * returns for it - *targetIndex (absolute indices), *score and, for OPAL_SEARCH_SCORE_END, *endTarget / *endQuery,
+ * *count entries each. minScore = INT_MIN: every target. No bound on the number of hits (miopalSearchTop stops at
+ * MIOPAL_MAX_TOP); only the hits cross PCIe, in two host round trips - the counts, then arrays sized to them.
+ * Every output array is malloc'ed by the library and freed by the caller (like *operations of miopalSearchFlat); a
+ * pointer is NULL when there are no hits or when the search type does not produce that array (endTarget / endQuery
+ * may themselves be NULL for OPAL_SEARCH_SCORE).
+ * maxHits < 0: no bound. With more than maxHits hits the call returns MIOPAL_ERR_TOO_MANY_HITS: *count is filled - the
+ * caller knows what it would take - nothing is allocated, the array pointers are as they were and the handle stays
+ * usable. On any other error every output is as it was.
+ * Checks, codes, their order and thread safety: miopalSearchTop's - miopalSearch's checks (the handle first), then
+ * OPAL_SEARCH_ALIGNMENT refused with OPAL_ERR_INVALID_MODE, then null outputs; OPAL_ERR_OVERFLOW as miopalSearch. An
+ * empty slice is checked and answered with *count = 0 and NULL arrays, nothing launched. The score pass takes the
+ * kernels miopalSearch takes (miopalLastRouting reports the same).
+ */
+int miopalSearchHits(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                     const int* scoreMatrix, int alphabetLength, int searchType, int mode,
+                     int64_t start, int64_t end, int minScore, int64_t maxHits,
+                     int64_t* count, int64_t** targetIndex, int** score, int** endTarget, int** endQuery);
+
+/*
+ * miopalSearchHits with a position-specific scoring matrix in the place of (query, scoreMatrix): rowScores as in
+ * miopalSearchPssm, no consensus. miopalSearchHits' contract holds to the letter, and hit i equals what
+ * miopalSearchPssm returns for (*targetIndex)[i]. Checked before any device call, with miopalSearchPssmTop's codes and
+ * in its order - first what needs no handle (mode and search type, queryLength < 0, NULL rowScores with
+ * queryLength > 0, the alphabet length's range, OPAL_SEARCH_ALIGNMENT: OPAL_ERR_INVALID_MODE, null outputs), then the
+ * handle, the alphabet length against it, the slice, and the 32-bit range check with the extreme entries of the rows
+ * (OPAL_ERR_OVERFLOW).
+ */
+int miopalSearchPssmHits(MiopalDb* db, const int* rowScores, int queryLength,
+                         int gapOpen, int gapExt, int alphabetLength, int searchType, int mode,
+                         int64_t start, int64_t end, int minScore, int64_t maxHits,
+                         int64_t* count, int64_t** targetIndex, int** score, int** endTarget, int** endQuery);
+
+/*
+ * miopalSearchHits of every query of a batch (queries and queryOffsets as in miopalSearchBatch) with one threshold per
+ * query (minScore[nQueries]), in one call through miopalSearchBatch's chunks: each chunk's [queries][targets] rows are
+ * compacted on the device before they leave. The answer is a CSR: hitOffsets (nQueries + 1 entries, the CALLER's
+ * array; hitOffsets[0] = 0) and the malloc'ed arrays of hitOffsets[nQueries] entries; entries hitOffsets[i] ..
+ * hitOffsets[i + 1] equal miopalSearchHits of query i alone. maxHits bounds the total over all queries; with more,
+ * MIOPAL_ERR_TOO_MANY_HITS with hitOffsets filled and nothing allocated. miopalLastBatchRouting reports what
+ * miopalSearchBatch reports for the same inputs. Checks and their order: miopalSearchBatchTop's (OPAL_SEARCH_ALIGNMENT
+ * refused first, then the query list, then every query with miopalSearch's checks), then null outputs and a NULL
+ * minScore with nQueries > 0. nQueries = 0 or an empty slice: checked, hitOffsets all 0, NULL arrays, 0.
+ */
+int miopalSearchBatchHits(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                          int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType,
+                          int mode, int64_t start, int64_t end, const int* minScore, int64_t maxHits,
+                          int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery);
+
+/*
  * A list of (query, target) pairs in one call: pair p aligns query pairQuery[p] (queries / queryOffsets as in
  * miopalSearchBatch) with target pairTarget[p] (absolute index into the handle). Any order, repeats allowed; all three
  * search types and all four modes. No reference counterpart (its callers loop over queries); an extension of the
@@ -441,6 +493,21 @@ int miopalTestSelectTop(const int* score, const int* endTarget, const int* endQu
                         int rows, int64_t stride, int k, int minScore, int64_t start,
                         int* count, int64_t* targetIndex, int* outScore, int* outEndTarget, int* outEndQuery,
                         int* gaveUp);
+
+/*
+ * Test hook: the device compaction of miopalSearchHits and its forms alone, on rows of int32 scores the caller
+ * supplies (any int32 values), with no search and no handle in front of it. score, and endTarget / endQuery (both or
+ * neither), are host arrays [rows][stride]; entry i of a row has the index start + i; row r keeps its entries >=
+ * minScore[r]. The rows are uploaded to device 0 and compacted by the production kernels exactly as a search's rows
+ * are; the answer is miopalSearchBatchHits' CSR: hitOffsets[rows + 1] (the caller's) and malloc'ed arrays (NULL
+ * without hits; outEndTarget / outEndQuery may be NULL without end arrays).
+ * MIOPAL_ERR_BAD_ARGUMENT, before any device call: rows < 1, stride < 1, a null input or output, one end array
+ * without the other, rows x stride above 2^27.
+ */
+int miopalTestSelectHits(const int* score, const int* endTarget, const int* endQuery,
+                         int rows, int64_t stride, const int* minScore, int64_t start,
+                         int64_t* hitOffsets, int64_t** targetIndex, int** outScore, int** outEndTarget,
+                         int** outEndQuery);
 
 #ifdef __cplusplus
 }

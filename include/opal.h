@@ -32,6 +32,8 @@ extern "C" {
 #define MIOPAL_ERR_HIP 100
 #define MIOPAL_ERR_BAD_ARGUMENT 101
 #define MIOPAL_ERR_INTERNAL 102
+/* miopalSearchHits and its forms: more hits than the caller's maxHits; the counts are filled, nothing is allocated. */
+#define MIOPAL_ERR_TOO_MANY_HITS 103
 
 /* Alignment modes (src/pyopal/opal.pxd:7-10). */
 #define OPAL_MODE_NW 0

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("MIOPAL_LIBRARY") or os.path.join(_HERE, "libmiopal.so
 OPAL_ERR_OVERFLOW = 1
 OPAL_ERR_NO_SIMD_SUPPORT = 2
 OPAL_ERR_INVALID_MODE = 3
+MIOPAL_ERR_TOO_MANY_HITS = 103   # include/opal.h: more hits than max_hits (search_hits and its forms)
 MIOPAL_MAX_TOP = 4096   # include/miopal.h: the largest k of miopalSearchTop / miopalSearchBatchTop
 
 SEARCH = {"score": 0, "end": 1, "full": 2}
@@ -51,9 +52,11 @@ EXPORTS = [
     "miopalLastRouting", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
     "miopalSearchBatch", "miopalLastBatchRouting", "miopalSearchTop", "miopalSearchBatchTop",
     "miopalAlignPairs", "miopalLastPairRouting", "miopalSearchPssmTop", "miopalAlignPairsPssm",
+    "miopalSearchHits", "miopalSearchPssmHits", "miopalSearchBatchHits",
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
     # test hooks
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
+    "miopalTestSelectHits",
 ]
 
 
@@ -134,6 +137,18 @@ def lib() -> ctypes.CDLL:
         L.miopalTestSelectTop.restype = c_int
         L.miopalTestSelectTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_i64,
                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+        pp = ctypes.POINTER(c_vp)
+        L.miopalSearchHits.restype = c_int
+        L.miopalSearchHits.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                       c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_i64), pp, pp, pp, pp]
+        L.miopalSearchPssmHits.restype = c_int
+        L.miopalSearchPssmHits.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_i64), pp, pp, pp, pp]
+        L.miopalSearchBatchHits.restype = c_int
+        L.miopalSearchBatchHits.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                            c_i64, c_i64, c_vp, c_i64, c_vp, pp, pp, pp, pp]
+        L.miopalTestSelectHits.restype = c_int
+        L.miopalTestSelectHits.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp, pp, pp, pp, pp]
         L.miopalAlignPairs.restype = c_int
         L.miopalAlignPairs.argtypes = [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_int,
                                        c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp]
@@ -190,10 +205,22 @@ def last_error() -> str:
     return msg.decode("utf-8", "replace") if msg else ""
 
 
+class TooManyHits(RuntimeError):
+    """MIOPAL_ERR_TOO_MANY_HITS: a hit search found more than ``max_hits``. ``counts``: what it would take - the
+    number of hits (search_hits, search_pssm_hits) or the CSR offsets, one entry per query plus one
+    (search_batch_hits). Nothing was allocated and the handle stays usable."""
+
+    def __init__(self, message: str, counts=None):
+        super().__init__(message)
+        self.counts = counts
+
+
 def raise_for(rc: int) -> None:
     """Error mapping of the reference plugin (src/pyopal/platform/pyx.in:102-107)."""
     if rc == 0:
         return
+    if rc == MIOPAL_ERR_TOO_MANY_HITS:
+        raise TooManyHits(f"more hits than max_hits (code={rc}): {last_error()}")
     if rc == OPAL_ERR_NO_SIMD_SUPPORT:
         raise RuntimeError("no supported SIMD backend available")
     if rc == OPAL_ERR_OVERFLOW:
@@ -299,6 +326,63 @@ class _MallocView:
         self._owner = owner
         self.__array_interface__ = {"data": (owner._address, False), "shape": (size,), "typestr": "|u1",
                                     "version": 3}
+
+
+def _take_malloced(pointer: ctypes.c_void_p, length: int, dtype) -> np.ndarray:
+    """The ``length`` entries of ``dtype`` at a malloc'ed address the C ABI returned, as an array that takes the buffer
+    over without a copy (freed with the array); NULL: an empty array."""
+    if not pointer.value or length == 0:
+        if pointer.value:
+            _libc.free(pointer)
+        return np.zeros(0, dtype=dtype)
+    return np.asarray(_MallocBytes(pointer.value, length * np.dtype(dtype).itemsize)).view(dtype)
+
+
+class _HitPointers:
+    """The four output pointers of a hit search and the arrays made from them."""
+
+    def __init__(self):
+        self.target, self.score, self.end_t, self.end_q = (ctypes.c_void_p() for _ in range(4))
+
+    def refs(self):
+        return tuple(ctypes.byref(p) for p in (self.target, self.score, self.end_t, self.end_q))
+
+    def arrays(self, total: int, ends: bool) -> typing.Dict[str, np.ndarray]:
+        out = {"target": _take_malloced(self.target, total, np.int64), "score": _take_malloced(self.score, total, np.int32)}
+        if ends:
+            out.update(end_t=_take_malloced(self.end_t, total, np.int32), end_q=_take_malloced(self.end_q, total, np.int32))
+        return out
+
+
+def select_hits_rows(score: np.ndarray, min_score, end_q: typing.Optional[np.ndarray] = None,
+                     end_t: typing.Optional[np.ndarray] = None, start: int = 0) -> typing.Dict[str, np.ndarray]:
+    """miopalTestSelectHits (test hook): the device compaction alone on the rows of ``score`` (int32, (rows, stride); a
+    1-D array is one row), with ``end_q`` / ``end_t`` of the same shape beside them (both or neither). ``min_score``:
+    an integer or one per row. Returns search_batch_hits' dict: "offsets" (rows + 1,), "target" (int64, ``start`` +
+    index), "score" and, with end arrays, "end_t" / "end_q", row after row, index ascending inside a row. The C side
+    checks the arguments."""
+    score = np.ascontiguousarray(score, dtype=np.int32)
+    if score.ndim == 1:
+        score = score[None, :]
+    if score.ndim != 2:
+        raise ValueError("score must have shape (rows, stride)")
+    rows, stride = score.shape
+    ends = []
+    for e in (end_q, end_t):
+        if e is not None:
+            e = np.ascontiguousarray(e, dtype=np.int32).reshape(-1, e.shape[-1])
+            if e.shape != score.shape:
+                raise ValueError("end arrays must have the shape of score")
+        ends.append(e)
+    thresholds = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, dtype=np.int32), (rows,)))
+    offsets = np.zeros(rows + 1, dtype=np.int64)
+    ptrs = _HitPointers()
+    rc = lib().miopalTestSelectHits(_ptr(score), _ptr(ends[1]), _ptr(ends[0]), rows, stride, _ptr(thresholds), start,
+                                    _ptr(offsets), *ptrs.refs())
+    raise_for(rc)
+    out = {"offsets": offsets}
+    out.update(ptrs.arrays(int(offsets[-1]), ends[0] is not None))
+    return out
 
 
 class _LazyAlignments:
@@ -592,6 +676,88 @@ class DeviceDatabase:
                                         _ptr(out.get("end_q")))
         raise_for(rc)
         return out
+
+    def search_hits(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
+                    mode: str = "score", algorithm: str = "sw", start: int = 0, end: typing.Optional[int] = None,
+                    min_score: typing.Optional[int] = None,
+                    max_hits: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+        """miopalSearchHits: every target of the slice scoring at least ``min_score`` (None: every target), compacted
+        on the device. Returns "count" (an int), "target" (int64, absolute indices, ascending), "score" and for mode
+        "end" "end_t" / "end_q", arrays of count entries that own the buffers the library allocated. With more than
+        ``max_hits`` hits (None: no bound): TooManyHits, its ``counts`` the number of hits. Mode "full" is refused
+        (OPAL_ERR_INVALID_MODE)."""
+        end = self.count if end is None else min(end, self.count)
+        q = np.ascontiguousarray(query, dtype=np.uint8)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        count = ctypes.c_int64(-1)
+        ptrs = _HitPointers()
+        rc = lib().miopalSearchHits(self._h, _ptr(q), len(q), gap_open, gap_extend, _ptr(S), self.alphabet_length,
+                                    SEARCH[mode], MODE[algorithm], start, end,
+                                    -(2 ** 31) if min_score is None else min_score, -1 if max_hits is None else max_hits,
+                                    ctypes.byref(count), *ptrs.refs())
+        return self._hits_result(rc, int(count.value), ptrs, mode)
+
+    @staticmethod
+    def _hits_result(rc, count, ptrs, mode):
+        if rc == MIOPAL_ERR_TOO_MANY_HITS:
+            raise TooManyHits(f"more hits than max_hits (code={rc}): {last_error()}", count)
+        raise_for(rc)
+        out = {"count": count}
+        out.update(ptrs.arrays(count, mode == "end"))
+        return out
+
+    def search_pssm_hits(self, row_scores: np.ndarray, gap_open: int = 3, gap_extend: int = 1, mode: str = "score",
+                         algorithm: str = "sw", start: int = 0, end: typing.Optional[int] = None,
+                         min_score: typing.Optional[int] = None,
+                         max_hits: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+        """miopalSearchPssmHits: `search_hits` with a position-specific scoring matrix (``row_scores`` as in
+        `search_pssm`) in the place of (query, matrix). Returns `search_hits`' dict; hit i equals what `search_pssm`
+        gives for ``target[i]``."""
+        end = self.count if end is None else min(end, self.count)
+        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
+        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
+            raise ValueError(f"row_scores must have shape (query length, {self.alphabet_length})")
+        count = ctypes.c_int64(-1)
+        ptrs = _HitPointers()
+        rc = lib().miopalSearchPssmHits(self._h, _ptr(rows) if len(rows) else None, len(rows), gap_open, gap_extend,
+                                        self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end,
+                                        -(2 ** 31) if min_score is None else min_score,
+                                        -1 if max_hits is None else max_hits, ctypes.byref(count), *ptrs.refs())
+        return self._hits_result(rc, int(count.value), ptrs, mode)
+
+    def search_batch_hits(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
+                          gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
+                          end: typing.Optional[int] = None, min_score=None,
+                          max_hits: typing.Optional[int] = None) -> typing.Dict[str, np.ndarray]:
+        """miopalSearchBatchHits: search_hits of every query in one batched call. ``min_score``: an integer, one per
+        query, or None. Returns a CSR: "offsets" (len(queries) + 1,) and "target", "score" (and "end_t" / "end_q") of
+        offsets[-1] entries; entries offsets[i]:offsets[i + 1] equal search_hits(queries[i], ...). ``max_hits`` bounds
+        the total; TooManyHits carries the offsets in ``counts``."""
+        end = self.count if end is None else min(end, self.count)
+        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
+        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            np.cumsum([len(q) for q in qs], out=offsets[1:])
+        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
+        if flat.size == 0:
+            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        thresholds = np.ascontiguousarray(np.broadcast_to(
+            np.asarray(-(2 ** 31) if min_score is None else min_score, dtype=np.int32), (len(qs),)))
+        hit_offsets = np.zeros(len(qs) + 1, dtype=np.int64)
+        ptrs = _HitPointers()
+        rc = lib().miopalSearchBatchHits(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
+                                         self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end,
+                                         _ptr(thresholds) if len(qs) else None, -1 if max_hits is None else max_hits,
+                                         _ptr(hit_offsets), *ptrs.refs())
+        if rc == MIOPAL_ERR_TOO_MANY_HITS:
+            raise TooManyHits(f"more hits than max_hits (code={rc}): {last_error()}", hit_offsets)
+        raise_for(rc)
+        out = {"offsets": hit_offsets}
+        out.update(ptrs.arrays(int(hit_offsets[-1]), mode == "end"))
+        return out
+
+    select_hits_rows = staticmethod(select_hits_rows)
 
     def align_pairs(self, queries: typing.Sequence[np.ndarray], pair_query, pair_target, matrix: np.ndarray,
                     gap_open: int = 3, gap_extend: int = 1, mode: str = "score",

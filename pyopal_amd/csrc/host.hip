@@ -37,6 +37,7 @@
 #include "full_plan_selftest.h"
 #include "launch_layer_selftest.h"
 #include "score_ranges_selftest.h"
+#include "select_hits.h"
 #include "select_top.h"
 #include "tuning.h"
 
@@ -676,6 +677,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_full.inc"
 #include "host_batch.inc"
 #include "host_top.inc"
+#include "host_hits.inc"
 #include "host_pairs.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
@@ -856,6 +858,74 @@ int miopalSearchPssmTop(MiopalDb* db, const int* rowScores, int queryLength, int
     const std::vector<unsigned char> none((size_t)std::max(Q, 1), 255);
     return searchTopImpl(db, none.data(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, k, minScore, 0, count,
                          targetIndex, score, endTarget, endQuery, Q > 0 ? rowScores : kNoRows);
+    });
+}
+
+// miopalSearchHits: miopalSearchTop's checks in its order (the handle, the query and the matrix, the slice; alignments;
+// the outputs), then the score pass and the compaction
+int miopalSearchHits(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                     const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start, int64_t end,
+                     int minScore, int64_t maxHits, int64_t* count, int64_t** targetIndex, int** score, int** endTarget,
+                     int** endQuery) {
+    return guarded([&]() -> int {
+    RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, searchType, mode, start, end));
+    if (searchType == OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "miopalSearchHits: alignments are not selected on the device");
+    RC_TRY(checkHitsOutputs(searchType, count, targetIndex, score, endTarget, endQuery));
+    HitRows rows;
+    RC_TRY(searchHitsImpl(db, query, queryLength, gapOpen, gapExt, scoreMatrix, alphabetLength, searchType, mode, start, end,
+                          minScore, maxHits, &rows));
+    return finishHits(rows, searchType, maxHits, count, targetIndex, score, endTarget, endQuery);
+    });
+}
+
+// miopalSearchPssmHits: miopalSearchPssmTop's checks in its order - what needs no handle first, the refusal of
+// alignments and the outputs (where the top form checks k) among it - then searchHitsImpl with the rows where the
+// matrix stands
+int miopalSearchPssmHits(MiopalDb* db, const int* rowScores, int queryLength, int gapOpen, int gapExt, int alphabetLength,
+                         int searchType, int mode, int64_t start, int64_t end, int minScore, int64_t maxHits,
+                         int64_t* count, int64_t** targetIndex, int** score, int** endTarget, int** endQuery) {
+    return guarded([&]() -> int {
+    const int Q = queryLength, A = alphabetLength;
+    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
+    if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
+    if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
+    if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
+    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    if (searchType == OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "miopalSearchPssmHits: alignments are not selected on the device");
+    RC_TRY(checkHitsOutputs(searchType, count, targetIndex, score, endTarget, endQuery));
+    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
+    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
+    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
+    // (no rows: an empty query has no scores; the score source still says "position-specific")
+    static const int kNoRows[1] = {0};
+    // (no consensus: every position is "no residue" - the int32 kernels upload it with the rows and never read it)
+    const std::vector<unsigned char> none((size_t)std::max(Q, 1), 255);
+    HitRows rows;
+    RC_TRY(searchHitsImpl(db, none.data(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, minScore, maxHits,
+                          &rows, Q > 0 ? rowScores : kNoRows));
+    return finishHits(rows, searchType, maxHits, count, targetIndex, score, endTarget, endQuery);
+    });
+}
+
+int miopalSearchBatchHits(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                          int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType, int mode,
+                          int64_t start, int64_t end, const int* minScore, int64_t maxHits, int64_t* hitOffsets,
+                          int64_t** targetIndex, int** score, int** endTarget, int** endQuery) {
+    return guarded([&]() -> int {
+    return searchBatchHitsImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength, searchType,
+                               mode, start, end, minScore, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery);
+    });
+}
+
+int miopalTestSelectHits(const int* score, const int* endTarget, const int* endQuery, int rows, int64_t stride,
+                         const int* minScore, int64_t start, int64_t* hitOffsets, int64_t** targetIndex, int** outScore,
+                         int** outEndTarget, int** outEndQuery) {
+    return guarded([&]() -> int {
+    return testSelectHitsImpl(score, endTarget, endQuery, rows, stride, minScore, start, hitOffsets, targetIndex, outScore,
+                              outEndTarget, outEndQuery);
     });
 }
 

@@ -12,6 +12,9 @@ enum Slot {
     // and the lane-per-pair kernels' strip boundaries
     kPairListQ, kPairListT, kPairListTOff, kPairListQBase, kPairListQOff, kPairListBoundary,
     kTopScratch,   // miopalSearchTop / miopalSearchBatchTop: the selection's outputs and scratch (rows x (bins + blocks + k))
+    // miopalSearchHits and its PSSM and batch forms (host_hits.inc): the compaction's thresholds, counts and offsets
+    // (a few bytes per block of 4096 scores), and the written hits, sized to their number
+    kHitsScratch, kHitsOut,
     kPssmRows,     // miopalSearchPssm: the rows, [Q][A] ints
     kSplitState,   // column split of the one-strip Smith-Waterman kernel: a wavefront's DP state at the cut that starts its interval
     kSlots

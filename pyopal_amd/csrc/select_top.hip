@@ -17,6 +17,7 @@
 // first read them again only for rows whose range spans 4096 or more.
 #include <climits>
 
+#include "select_rows.h"
 #include "select_top.h"
 
 namespace miopal {
@@ -53,11 +54,6 @@ struct Scratch {
     unsigned long long* cand;       // [rows][k]
     size_t zeroBytes;               // rows, hist and status: zeroed before every sequence
 };
-__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-__host__ __device__ inline int blocksPerRow(int64_t stride) {
-    const int64_t slots = (stride + 3) / 4 + 1;   // (a row that starts mid-slot touches one slot more)
-    return (int)((slots + kTopBlockSlots - 1) / kTopBlockSlots);
-}
 inline size_t histOffset(int rows) { return align256(sizeof(TopRow) * (size_t)rows); }
 inline size_t statusOffset(int rows) { return histOffset(rows) + align256(sizeof(unsigned) * (size_t)rows * kTopBins); }
 inline size_t candOffset(int rows, int64_t stride) {
@@ -74,38 +70,6 @@ inline Scratch scratchLayout(void* base, int rows, int64_t stride) {
     return s;
 }
 
-// The 16-byte slots of a row: slot s holds buffer entries [a0 + 4 s, a0 + 4 s + 4); entries outside
-// [first, last) belong to other rows (or lie past the buffer) and are neither read nor counted.
-struct RowSpan {
-    int64_t first, last, a0, slots;
-};
-__device__ inline RowSpan rowSpan(int64_t stride, int r) {
-    RowSpan rs;
-    rs.first = (int64_t)r * stride;
-    rs.last = rs.first + stride;
-    rs.a0 = rs.first & ~(int64_t)3;
-    rs.slots = (rs.last - rs.a0 + 3) >> 2;
-    return rs;
-}
-// slot s of the row (s < rs.slots); `mask` bit c: entry c belongs to the row
-__device__ inline int4 loadSlot(const int32_t* buf, const RowSpan& rs, int64_t s, unsigned& mask) {
-    const int64_t e = rs.a0 + 4 * s;
-    if (e >= rs.first && e + 4 <= rs.last) {
-        mask = 0xF;
-        return *(const int4*)(buf + e);
-    }
-    int v[4];
-    mask = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const bool in = e + c >= rs.first && e + c < rs.last;
-        v[c] = in ? buf[e + c] : 0;
-        mask |= in ? 1u << c : 0u;
-    }
-    return make_int4(v[0], v[1], v[2], v[3]);
-}
-__device__ inline int lane(const int4& v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
-
 // the range round `round` counts; false: nothing to count (round 0: no entry reaches minScore)
 __device__ inline bool roundRange(const TopRow& t, int round, int minScore, int& lo, int& hi, int& sh) {
     if (round == 0) {
@@ -120,19 +84,6 @@ __device__ inline bool roundRange(const TopRow& t, int round, int minScore, int&
     hi = t.hi;
     sh = t.shift;
     return true;
-}
-
-// exclusive prefix and total over the wavefront of per-lane counts (two 16-bit halves at once)
-__device__ inline void wavePrefix(unsigned c, unsigned& prefix, unsigned& total) {
-    const int lane = threadIdx.x % 64;
-    unsigned x = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned y = __shfl_up(x, d);
-        x += lane >= d ? y : 0u;
-    }
-    prefix = x - c;
-    total = __shfl(x, 63);
 }
 
 // ---- A: range --------------------------------------------------------------------------------------------

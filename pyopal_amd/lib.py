@@ -1067,6 +1067,192 @@ class Aligner:
             return results
 
 
+    def hits(self, query, database: BaseDatabase, min_score: int, *, mode: str = "score", algorithm: str = "sw",
+             start: int = 0, end: int = UINT32_MAX, device: int = 0, max_hits: typing.Optional[int] = None,
+             sort: bool = False) -> typing.List[ScoreResult]:
+        """Extension: every target of ``database[start:end]`` that scores at least ``min_score``, compacted on the
+        GPU (include/miopal.h, miopalSearchHits): only the hits leave the device, however many there are (`top_hits`
+        stops at 4096). Equal to ``[r for r in self.align(query, database, mode=mode, ...) if r.score >= min_score]``,
+        in database order; ``sort=True`` orders best first (score descending, index ascending: `top_hits`' order) on
+        the host. ``mode="full"`` selects on the scores, then aligns the hits only, in one pair-list call
+        (miopalAlignPairs). With more than ``max_hits`` hits: `_capi.TooManyHits`, its ``counts`` the number."""
+        return self._hit_objects(*self._hit_arrays([query], None, database, min_score, mode, algorithm, start, end,
+                                                   device, max_hits, sort, False), mode)[0]
+
+    def hits_arrays(self, query, database: BaseDatabase, min_score: int, *, mode: str = "score", algorithm: str = "sw",
+                    start: int = 0, end: int = UINT32_MAX, device: int = 0, max_hits: typing.Optional[int] = None,
+                    sort: bool = False) -> typing.Dict[str, np.ndarray]:
+        """`hits` without result objects: "target" (int64) and "score" - for "end" and "full" also "end_q" / "end_t",
+        for "full" also "start_q" / "start_t", "aln_flat" / "aln_off" - one entry per hit (and "offsets": [0, hits])."""
+        return self._hit_arrays([query], None, database, min_score, mode, algorithm, start, end, device, max_hits, sort,
+                                False)[0]
+
+    def hits_many(self, queries, database: BaseDatabase, min_score, *, mode: str = "score", algorithm: str = "sw",
+                  start: int = 0, end: int = UINT32_MAX, device: int = 0, max_hits: typing.Optional[int] = None,
+                  sort: bool = False) -> typing.List[typing.List[ScoreResult]]:
+        """Extension: `hits` of every query of ``queries`` in one batched search (miopalSearchBatchHits); returns one
+        list per query. ``min_score``: an integer, or one per query. ``max_hits`` bounds the total over all queries.
+        ``mode="full"`` aligns all (query, hit) pairs in ONE pair-list call."""
+        return self._hit_objects(*self._hit_arrays(queries, None, database, min_score, mode, algorithm, start, end,
+                                                   device, max_hits, sort, True), mode)
+
+    def hits_many_arrays(self, queries, database: BaseDatabase, min_score, *, mode: str = "score",
+                         algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                         max_hits: typing.Optional[int] = None, sort: bool = False) -> typing.Dict[str, np.ndarray]:
+        """`hits_many` as a CSR, for callers that want no objects (the edge list of an all-against-all comparison):
+        "offsets" (len(queries) + 1,), and `hits_arrays`' arrays with entries offsets[i]:offsets[i + 1] the hits of
+        query i."""
+        return self._hit_arrays(queries, None, database, min_score, mode, algorithm, start, end, device, max_hits, sort,
+                                True)[0]
+
+    def hits_pssm(self, pssm: "Pssm", database: BaseDatabase, min_score: int, *, mode: str = "score",
+                  algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                  max_hits: typing.Optional[int] = None, sort: bool = False) -> typing.List[ScoreResult]:
+        """Extension: `hits` with a `Pssm` in the place of the query and the aligner's matrix (miopalSearchPssmHits):
+        equal to ``[r for r in self.align_pssm(pssm, database, mode=mode, ...) if r.score >= min_score]``.
+        ``mode="full"`` aligns the hits in one pair-list call (miopalAlignPairsPssm): all targets above the inclusion
+        threshold, the step an iterated profile search repeats."""
+        return self._hit_objects(*self._hit_arrays(None, pssm, database, min_score, mode, algorithm, start, end, device,
+                                                   max_hits, sort, False), mode)[0]
+
+    def hits_pssm_arrays(self, pssm: "Pssm", database: BaseDatabase, min_score: int, *, mode: str = "score",
+                         algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                         max_hits: typing.Optional[int] = None, sort: bool = False) -> typing.Dict[str, np.ndarray]:
+        """`hits_pssm` without result objects (`hits_arrays`' dict)."""
+        return self._hit_arrays(None, pssm, database, min_score, mode, algorithm, start, end, device, max_hits, sort,
+                                False)[0]
+
+    @staticmethod
+    def _hit_thresholds(min_score, count, many):
+        """``min_score`` as one int32 per query: an integer, or (hits_many) a sequence of ``count`` integers."""
+        per_query = many and not isinstance(min_score, (int, np.integer, str)) and np.ndim(min_score) == 1
+        values = list(min_score) if per_query else [min_score]
+        for v in values:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"min_score must be an integer, not {type(v).__name__}")
+            if not -(2 ** 31) <= int(v) < 2 ** 31:
+                raise OverflowError("min_score does not fit a 32-bit integer")
+        if per_query and len(values) != count:
+            raise ValueError(f"min_score must be an integer or hold one per query ({count}), got {len(values)}")
+        return np.array([int(v) for v in values] if per_query else [int(min_score)] * count, dtype=np.int32)
+
+    def _hit_arrays(self, queries, pssm, database, min_score, mode, algorithm, start, end, device, max_hits, sort, many):
+        """The CSR of `hits`, `hits_many` (queries) and `hits_pssm` (pssm): the checks of `_top` / `top_hits_pssm`, the
+        device selection, the host sort, and for "full" the pair list behind them. Returns (arrays, (query lengths,
+        target lengths or None)): what `_hit_objects` needs beside the arrays."""
+        if pssm is not None or queries is None:
+            if not isinstance(pssm, Pssm):
+                raise TypeError(f"Argument 'pssm' has incorrect type (expected Pssm, got {type(pssm).__name__})")
+        if mode not in _OPAL_SEARCH_MODES:
+            raise ValueError(f"invalid search mode: {mode!r}")
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        if max_hits is not None:
+            if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
+                raise TypeError(f"max_hits must be an integer or None, not {type(max_hits).__name__}")
+            if max_hits < 0:
+                raise ValueError("max_hits must not be negative")
+            max_hits = int(max_hits)
+        if start < 0 or end < 0:
+            raise OverflowError("can't convert negative value to uint32_t")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        if pssm is not None:
+            if pssm.alphabet != database.alphabet:
+                raise ValueError("database and PSSM have different alphabets")
+            count, encoded = 1, None
+        else:
+            if database.alphabet != self.alphabet:
+                raise ValueError("database and score matrix have different alphabets")
+            queries = list(queries)
+            for q in queries:
+                if q is None:
+                    raise TypeError("Argument 'query' must not be None")
+            encoded = [database.alphabet.encode(q) for q in queries]
+            count = len(encoded)
+        thresholds = self._hit_thresholds(min_score, count, many)
+        query_lengths = [len(pssm)] if pssm is not None else [len(e) for e in encoded]
+        ends = mode != "score"
+        with database.lock.read:
+            size = database._get_size()
+            if end < start:
+                raise IndexError("database slice end is lower than start")
+            end = min(end, size)
+            if start > size:
+                raise IndexError("database slice start is past the end of the database")
+            if end == start or count == 0:
+                out = {"offsets": np.zeros(count + 1, dtype=np.int64), "target": np.zeros(0, dtype=np.int64),
+                       "score": np.zeros(0, dtype=np.int32)}
+                if ends:
+                    out.update(end_q=np.zeros(0, dtype=np.int32), end_t=np.zeros(0, dtype=np.int32))
+                if mode == "full":
+                    out.update(start_q=np.zeros(0, dtype=np.int32), start_t=np.zeros(0, dtype=np.int32),
+                               aln_flat=np.zeros(0, dtype=np.uint8), aln_off=np.zeros(1, dtype=np.int64))
+                return out, (query_lengths, None)
+            if _capi.lib().miopalDeviceCount() < 1:
+                raise RuntimeError("no supported SIMD backend available")
+            mirror = database._device_mirror(device)
+            search_mode = "score" if mode == "full" else mode
+            if pssm is not None:
+                got = mirror.search_pssm_hits(pssm.scores, self.gap_open, self.gap_extend, search_mode, algorithm, start,
+                                              end, int(thresholds[0]), max_hits)
+                got["offsets"] = np.array([0, got.pop("count")], dtype=np.int64)
+                arrays, matrix = None, None
+            else:
+                matrix = _int_matrix_array(self._int_matrix)
+                arrays = [np.frombuffer(e, dtype=np.uint8) for e in encoded]
+                if many:
+                    got = mirror.search_batch_hits(arrays, matrix, self.gap_open, self.gap_extend, search_mode, algorithm,
+                                                   start, end, thresholds, max_hits)
+                else:
+                    got = mirror.search_hits(arrays[0], matrix, self.gap_open, self.gap_extend, search_mode, algorithm,
+                                             start, end, int(thresholds[0]), max_hits)
+                    got["offsets"] = np.array([0, got.pop("count")], dtype=np.int64)
+            offsets = got["offsets"]
+            owner = np.repeat(np.arange(count, dtype=np.int32), np.diff(offsets))
+            if sort and len(owner):
+                # best first inside every query: score descending, then index ascending (`top_hits`' order)
+                order = np.lexsort((got["target"], -got["score"].astype(np.int64), owner))
+                for key in ("target", "score", "end_q", "end_t"):
+                    if key in got:
+                        got[key] = got[key][order]
+            if mode == "full":
+                # every (query, hit) pair in one pair-list call, in the order chosen above
+                target = got["target"]
+                if pssm is not None:
+                    got = mirror.align_pairs_pssm([pssm.scores], [pssm.consensus], owner, target, self.gap_open,
+                                                  self.gap_extend, "full", algorithm)
+                else:
+                    got = mirror.align_pairs(arrays, owner, target, matrix, self.gap_open, self.gap_extend, "full",
+                                             algorithm)
+                got.pop("aln", None)
+                got.update(offsets=offsets, target=target)
+            return got, (query_lengths, np.diff(mirror.offsets) if mode == "full" else None)
+
+    @staticmethod
+    def _hit_objects(out, lengths, mode):
+        """The CSR of `_hit_arrays` as one list of result objects per query."""
+        offsets = out["offsets"].tolist()
+        owner = np.repeat(np.arange(len(offsets) - 1), np.diff(out["offsets"])).tolist()
+        score, target = out["score"].tolist(), out["target"].tolist()
+        if mode == "score":
+            flat = [ScoreResult(t, s) for t, s in zip(target, score)]
+        else:
+            end_q, end_t = out["end_q"].tolist(), out["end_t"].tolist()
+            if mode == "end":
+                flat = [EndResult(t, s, qe, te) for t, s, qe, te in zip(target, score, end_q, end_t)]
+            else:
+                start_q, start_t = out["start_q"].tolist(), out["start_t"].tolist()
+                off = out["aln_off"].tolist()
+                text = out["aln_flat"].tobytes().translate(_OPS_TO_TEXT).decode("ascii")
+                qlen, tlen = lengths
+                flat = [FullResult(t, score[p], end_q[p], end_t[p], start_q[p], start_t[p], qlen[q], int(tlen[t]),
+                                   text[off[p]:off[p + 1]])
+                        for p, (q, t) in enumerate(zip(owner, target))]
+        return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+
+
 class Pssm:
     """A position-specific scoring matrix: the query of `Aligner.align_pssm`.
 
