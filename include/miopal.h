@@ -335,6 +335,32 @@ int miopalSearchBatchHits(MiopalDb* db, const unsigned char* queries, const int6
                           int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery);
 
 /*
+ * The m best QUERIES of every target of the slice, selected on the device: the selection of miopalSearchBatchTop turned
+ * round - which barcode, adapter, primer or motif of a batch matches each read best, and by what margin over the
+ * runner-up. queries and queryOffsets as in miopalSearchBatch; all four modes; OPAL_SEARCH_SCORE and
+ * OPAL_SEARCH_SCORE_END. For target t of [start, end) the candidates are the queries q with score(q, t) >= minScore
+ * (INT_MIN: no bound), score(q, t) being what miopalSearch returns for query q alone; they are ordered by score
+ * descending, then query index ascending - a total order: the answer does not depend on how the batch is cut into
+ * chunks. count[t - start] = min(m, candidates); queryIndex, score and - for OPAL_SEARCH_SCORE_END - endTarget /
+ * endQuery are [end - start][m] row-major, best first, -1 in the slots count .. m - 1 of every array. queryIndex is
+ * int32_t: with the target indices it goes straight into miopalAlignPairs as pairQuery. 1 <= m <=
+ * MIOPAL_MAX_TARGET_TOP; m > nQueries is allowed. The batch runs through miopalSearchBatch's chunks and single-query
+ * path (miopalLastBatchRouting reports what miopalSearchBatch reports for the same inputs); every chunk's
+ * [queries][targets] rows are folded into m x (end - start) running entries on the device, and only count and the
+ * [end - start][m] arrays cross PCIe.
+ * Checks, in this order: OPAL_SEARCH_ALIGNMENT refused with OPAL_ERR_INVALID_MODE; the query list and every query with
+ * miopalSearchBatch's checks and codes (OPAL_ERR_OVERFLOW as miopalSearch); m outside its range and null outputs
+ * (endTarget / endQuery only for OPAL_SEARCH_SCORE_END): MIOPAL_ERR_BAD_ARGUMENT. An empty slice: checked, 0, nothing
+ * written, nothing launched. nQueries = 0 on a slice that is not empty: count all 0, every slot -1, nothing launched.
+ * On an error every output is as it was. Thread-safe like miopalSearch: the running state belongs to the call.
+ */
+#define MIOPAL_MAX_TARGET_TOP 8
+int miopalSearchBatchTargetTop(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                               int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType,
+                               int mode, int64_t start, int64_t end, int m, int minScore,
+                               int* count, int32_t* queryIndex, int* score, int* endTarget, int* endQuery);
+
+/*
  * A list of (query, target) pairs in one call: pair p aligns query pairQuery[p] (queries / queryOffsets as in
  * miopalSearchBatch) with target pairTarget[p] (absolute index into the handle). Any order, repeats allowed; all three
  * search types and all four modes. No reference counterpart (its callers loop over queries); an extension of the
@@ -508,6 +534,23 @@ int miopalTestSelectHits(const int* score, const int* endTarget, const int* endQ
                          int rows, int64_t stride, const int* minScore, int64_t start,
                          int64_t* hitOffsets, int64_t** targetIndex, int** outScore, int** outEndTarget,
                          int** outEndQuery);
+
+/*
+ * Test hook: the device selection of miopalSearchBatchTargetTop alone - the m best rows of every column - on rows of
+ * int32 scores the caller supplies (any int32 values), with no search and no handle in front of it. score, and
+ * endTarget / endQuery (both or neither), are host arrays [rows][stride]. The rows are uploaded to device 0 and folded
+ * by the production kernels, piece by piece in the order of the list: piece p is rows pieceFirst[p] .. pieceFirst[p] +
+ * pieceCount[p] - 1 (at least one row), with base query index pieceFirst[p]; a row may appear in at most one piece, and
+ * rows in no piece are not part of the answer. skip (one byte per row, or NULL): skip[r] != 0 - row r is never read.
+ * The answer is miopalSearchBatchTargetTop's: count[stride], the others [stride][m] (outEndTarget / outEndQuery may be
+ * NULL without end arrays), best first (score descending, row ascending), -1 past the count.
+ * MIOPAL_ERR_BAD_ARGUMENT, before any device call: rows < 1, stride < 1, m outside [1, MIOPAL_MAX_TARGET_TOP], a null
+ * input or output, one end array without the other, a piece outside [0, rows), rows x stride above 2^27.
+ */
+int miopalTestSelectColumns(const int* score, const int* endTarget, const int* endQuery, int rows, int64_t stride,
+                            const int32_t* pieceFirst, const int32_t* pieceCount, int pieces,
+                            const unsigned char* skip, int m, int minScore,
+                            int* count, int32_t* queryIndex, int* outScore, int* outEndTarget, int* outEndQuery);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@ OPAL_ERR_NO_SIMD_SUPPORT = 2
 OPAL_ERR_INVALID_MODE = 3
 MIOPAL_ERR_TOO_MANY_HITS = 103   # include/opal.h: more hits than max_hits (search_hits and its forms)
 MIOPAL_MAX_TOP = 4096   # include/miopal.h: the largest k of miopalSearchTop / miopalSearchBatchTop
+MIOPAL_MAX_TARGET_TOP = 8   # include/miopal.h: the largest m of miopalSearchBatchTargetTop
 
 SEARCH = {"score": 0, "end": 1, "full": 2}
 MODE = {"nw": 0, "hw": 1, "ov": 2, "sw": 3}
@@ -52,11 +53,11 @@ EXPORTS = [
     "miopalLastRouting", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
     "miopalSearchBatch", "miopalLastBatchRouting", "miopalSearchTop", "miopalSearchBatchTop",
     "miopalAlignPairs", "miopalLastPairRouting", "miopalSearchPssmTop", "miopalAlignPairsPssm",
-    "miopalSearchHits", "miopalSearchPssmHits", "miopalSearchBatchHits",
+    "miopalSearchHits", "miopalSearchPssmHits", "miopalSearchBatchHits", "miopalSearchBatchTargetTop",
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
     # test hooks
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
-    "miopalTestSelectHits",
+    "miopalTestSelectHits", "miopalTestSelectColumns",
 ]
 
 
@@ -149,6 +150,12 @@ def lib() -> ctypes.CDLL:
                                             c_i64, c_i64, c_vp, c_i64, c_vp, pp, pp, pp, pp]
         L.miopalTestSelectHits.restype = c_int
         L.miopalTestSelectHits.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp, pp, pp, pp, pp]
+        L.miopalSearchBatchTargetTop.restype = c_int
+        L.miopalSearchBatchTargetTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                                 c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.miopalTestSelectColumns.restype = c_int
+        L.miopalTestSelectColumns.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_vp, c_int, c_int,
+                                              c_vp, c_vp, c_vp, c_vp, c_vp]
         L.miopalAlignPairs.restype = c_int
         L.miopalAlignPairs.argtypes = [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_int,
                                        c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp]
@@ -382,6 +389,47 @@ def select_hits_rows(score: np.ndarray, min_score, end_q: typing.Optional[np.nda
     raise_for(rc)
     out = {"offsets": offsets}
     out.update(ptrs.arrays(int(offsets[-1]), ends[0] is not None))
+    return out
+
+
+def select_columns_rows(score: np.ndarray, m: int, min_score: typing.Optional[int] = None,
+                        end_q: typing.Optional[np.ndarray] = None, end_t: typing.Optional[np.ndarray] = None,
+                        pieces: typing.Optional[typing.Sequence[typing.Tuple[int, int]]] = None,
+                        skip: typing.Optional[np.ndarray] = None) -> typing.Dict[str, np.ndarray]:
+    """miopalTestSelectColumns (test hook): the device selection of search_batch_target_top alone - the ``m`` best
+    rows of every column - on the rows of ``score`` (int32, (rows, stride); a 1-D array is one row), with ``end_q`` /
+    ``end_t`` of the same shape beside them (both or neither). ``pieces``: (first row, rows) of every piece, folded in
+    this order (None: all rows in one piece); ``skip``: one flag per row, non-zero - the row is never read. Returns
+    search_batch_target_top's dict: "count" (stride,), "query" (the row), "score" and, with end arrays, "end_t" /
+    "end_q", of shape (stride, m), best first, -1 past the count. The C side checks the arguments."""
+    score = np.ascontiguousarray(score, dtype=np.int32)
+    if score.ndim == 1:
+        score = score[None, :]
+    if score.ndim != 2:
+        raise ValueError("score must have shape (rows, stride)")
+    rows, stride = score.shape
+    ends = []
+    for e in (end_q, end_t):
+        if e is not None:
+            e = np.ascontiguousarray(e, dtype=np.int32).reshape(-1, e.shape[-1])
+            if e.shape != score.shape:
+                raise ValueError("end arrays must have the shape of score")
+        ends.append(e)
+    pieces = np.ascontiguousarray([(0, rows)] if pieces is None else pieces, dtype=np.int32).reshape(-1, 2)
+    first, counts = np.ascontiguousarray(pieces[:, 0]), np.ascontiguousarray(pieces[:, 1])
+    flags = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
+    if flags is not None and flags.shape != (rows,):
+        raise ValueError("skip must hold one flag per row")
+    shape = (stride, max(m, 0))
+    out = {"count": np.zeros(stride, dtype=np.int32), "query": np.empty(shape, dtype=np.int32),
+           "score": np.empty(shape, dtype=np.int32)}
+    if ends[0] is not None or ends[1] is not None:
+        out.update(end_t=np.empty(shape, dtype=np.int32), end_q=np.empty(shape, dtype=np.int32))
+    rc = lib().miopalTestSelectColumns(_ptr(score), _ptr(ends[1]), _ptr(ends[0]), rows, stride, _ptr(first), _ptr(counts),
+                                       len(pieces), _ptr(flags), m, -(2 ** 31) if min_score is None else min_score,
+                                       _ptr(out["count"]), _ptr(out["query"]), _ptr(out["score"]), _ptr(out.get("end_t")),
+                                       _ptr(out.get("end_q")))
+    raise_for(rc)
     return out
 
 
@@ -758,6 +806,40 @@ class DeviceDatabase:
         return out
 
     select_hits_rows = staticmethod(select_hits_rows)
+
+    def search_batch_target_top(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
+                                gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
+                                end: typing.Optional[int] = None, m: int = 1,
+                                min_score: typing.Optional[int] = None) -> typing.Dict[str, np.ndarray]:
+        """miopalSearchBatchTargetTop: the ``m`` best queries of every target of the slice, selected on the device.
+        Returns "count" (end - start,), "query" (int32, indices into ``queries``), "score" and for mode "end" "end_t" /
+        "end_q", arrays of shape (end - start, m): best first (score descending, query index ascending), -1 past the
+        count. ``min_score``: only queries scoring at least that many count (None: no bound). Row t equals the
+        reduction of column t of `search_batch`. Mode "full" is refused (OPAL_ERR_INVALID_MODE)."""
+        end = self.count if end is None else min(end, self.count)
+        n = max(end - start, 0)
+        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
+        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            np.cumsum([len(q) for q in qs], out=offsets[1:])
+        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
+        if flat.size == 0:
+            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        shape = (n, max(m, 0))
+        out = {"count": np.zeros(n, dtype=np.int32), "query": np.empty(shape, dtype=np.int32),
+               "score": np.empty(shape, dtype=np.int32)}
+        if mode == "end":
+            out.update(end_t=np.empty(shape, dtype=np.int32), end_q=np.empty(shape, dtype=np.int32))
+        rc = lib().miopalSearchBatchTargetTop(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
+                                              self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end, m,
+                                              -(2 ** 31) if min_score is None else min_score, _ptr(out["count"]),
+                                              _ptr(out["query"]), _ptr(out["score"]), _ptr(out.get("end_t")),
+                                              _ptr(out.get("end_q")))
+        raise_for(rc)
+        return out
+
+    select_columns_rows = staticmethod(select_columns_rows)
 
     def align_pairs(self, queries: typing.Sequence[np.ndarray], pair_query, pair_target, matrix: np.ndarray,
                     gap_open: int = 3, gap_extend: int = 1, mode: str = "score",

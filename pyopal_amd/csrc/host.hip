@@ -37,6 +37,7 @@
 #include "full_plan_selftest.h"
 #include "launch_layer_selftest.h"
 #include "score_ranges_selftest.h"
+#include "select_columns.h"
 #include "select_hits.h"
 #include "select_top.h"
 #include "tuning.h"
@@ -678,6 +679,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_batch.inc"
 #include "host_top.inc"
 #include "host_hits.inc"
+#include "host_columns.inc"
 #include "host_pairs.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
@@ -926,6 +928,26 @@ int miopalTestSelectHits(const int* score, const int* endTarget, const int* endQ
     return guarded([&]() -> int {
     return testSelectHitsImpl(score, endTarget, endQuery, rows, stride, minScore, start, hitOffsets, targetIndex, outScore,
                               outEndTarget, outEndQuery);
+    });
+}
+
+int miopalSearchBatchTargetTop(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                               int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType,
+                               int mode, int64_t start, int64_t end, int m, int minScore,
+                               int* count, int32_t* queryIndex, int* score, int* endTarget, int* endQuery) {
+    return guarded([&]() -> int {
+    return searchBatchTargetTopImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength,
+                                    searchType, mode, start, end, m, minScore, count, queryIndex, score, endTarget, endQuery);
+    });
+}
+
+int miopalTestSelectColumns(const int* score, const int* endTarget, const int* endQuery, int rows, int64_t stride,
+                            const int32_t* pieceFirst, const int32_t* pieceCount, int pieces,
+                            const unsigned char* skip, int m, int minScore,
+                            int* count, int32_t* queryIndex, int* outScore, int* outEndTarget, int* outEndQuery) {
+    return guarded([&]() -> int {
+    return testSelectColumnsImpl(score, endTarget, endQuery, rows, stride, pieceFirst, pieceCount, pieces, skip, m, minScore,
+                                 count, queryIndex, outScore, outEndTarget, outEndQuery);
     });
 }
 

@@ -15,6 +15,9 @@ enum Slot {
     // miopalSearchHits and its PSSM and batch forms (host_hits.inc): the compaction's thresholds, counts and offsets
     // (a few bytes per block of 4096 scores), and the written hits, sized to their number
     kHitsScratch, kHitsOut,
+    // miopalSearchBatchTargetTop (host_columns.inc): the running state and the answer, in the workspace the call holds
+    // throughout; a chunk's skip flags, in the workspace that produced the chunk
+    kColumnsState, kColumnsOut, kColumnsSkip,
     kPssmRows,     // miopalSearchPssm: the rows, [Q][A] ints
     kSplitState,   // column split of the one-strip Smith-Waterman kernel: a wavefront's DP state at the cut that starts its interval
     kSlots

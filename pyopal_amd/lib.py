@@ -1066,6 +1066,109 @@ class Aligner:
                                     zip(target, row["score"][:c], row["end_q"][:c], row["end_t"][:c])])
             return results
 
+    def best_queries(self, queries, database: BaseDatabase, m: int = 1, *, mode: str = "score", algorithm: str = "sw",
+                     min_score: typing.Optional[int] = None, start: int = 0, end: int = UINT32_MAX,
+                     device: int = 0) -> typing.List[typing.List[typing.Tuple[int, ScoreResult]]]:
+        """Extension: the ``m`` best queries of every target of ``database[start:end]``, selected on the GPU
+        (include/miopal.h, miopalSearchBatchTargetTop): which barcode, adapter or motif of ``queries`` matches each
+        read best, and the runner-up for the margin. Returns one list per target of ``(query_index, result)``, best
+        first (score descending, query index ascending), at most ``m`` long; ``result`` equals
+        ``self.align(queries[query_index], database, mode=mode, ...)[target]``. ``min_score``: only queries scoring at
+        least that many count. ``mode="full"`` selects on the scores, then aligns all chosen (query, target) pairs in
+        ONE pair-list call (miopalAlignPairs)."""
+        out, query_lengths, mirror = self._best_queries(queries, database, m, mode, algorithm, min_score, start, end,
+                                                        device)
+        counts = out["count"].tolist()
+        chosen = np.arange(out["query"].shape[1])[None, :] < out["count"][:, None]
+        index = out["query"][chosen].tolist()
+        target = np.repeat(np.arange(start, start + len(counts), dtype=np.int64), counts)
+        if mode == "full":
+            flat = self._pair_objects(out["pairs"], mirror, query_lengths, index, target, mode) if index else []
+        elif mode == "score":
+            flat = [ScoreResult(t, s) for t, s in zip(target.tolist(), out["score"][chosen].tolist())]
+        else:
+            flat = [EndResult(t, s, qe, te) for t, s, qe, te in
+                    zip(target.tolist(), out["score"][chosen].tolist(), out["end_q"][chosen].tolist(),
+                        out["end_t"][chosen].tolist())]
+        bounds = np.concatenate(([0], np.cumsum(counts))).tolist()
+        return [list(zip(index[bounds[t]:bounds[t + 1]], flat[bounds[t]:bounds[t + 1]])) for t in range(len(counts))]
+
+    def best_queries_arrays(self, queries, database: BaseDatabase, m: int = 1, *, mode: str = "score",
+                            algorithm: str = "sw", min_score: typing.Optional[int] = None, start: int = 0,
+                            end: int = UINT32_MAX, device: int = 0) -> typing.Dict[str, typing.Any]:
+        """`best_queries` without result objects: "count" (one per target), and "query" (int32), "score" - for "end"
+        also "end_q" / "end_t" - of shape (targets, m), best first, -1 past the count. For "full" also "pairs": the
+        arrays of the one `align_pairs` call on all chosen pairs - "query", "target", "score", "end_q" / "end_t",
+        "start_q" / "start_t", "aln_flat" / "aln_off" - row-major over (target, rank) for rank < count."""
+        return self._best_queries(queries, database, m, mode, algorithm, min_score, start, end, device)[0]
+
+    def _best_queries(self, queries, database, m, mode, algorithm, min_score, start, end, device):
+        """The arrays of `best_queries_arrays`, the query lengths and the device mirror (None where none was needed):
+        `_top`'s checks, the device selection, and for "full" the pair list behind it."""
+        if mode not in _OPAL_SEARCH_MODES:
+            raise ValueError(f"invalid search mode: {mode!r}")
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+            raise TypeError(f"m must be an integer, not {type(m).__name__}")
+        m = int(m)
+        if m < 1 or m > _capi.MIOPAL_MAX_TARGET_TOP:
+            raise ValueError(f"m must be between 1 and {_capi.MIOPAL_MAX_TARGET_TOP} (MIOPAL_MAX_TARGET_TOP), got {m}")
+        if min_score is not None:
+            min_score = int(min_score)
+        if start < 0 or end < 0:
+            raise OverflowError("can't convert negative value to uint32_t")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        if database.alphabet != self.alphabet:
+            raise ValueError("database and score matrix have different alphabets")
+        queries = list(queries)
+        for q in queries:
+            if q is None:
+                raise TypeError("Argument 'query' must not be None")
+        encoded = [database.alphabet.encode(q) for q in queries]
+        query_lengths = [len(e) for e in encoded]
+        with database.lock.read:
+            size = database._get_size()
+            if end < start:
+                raise IndexError("database slice end is lower than start")
+            end = min(end, size)
+            if start > size:
+                raise IndexError("database slice start is past the end of the database")
+            n = end - start
+            mirror = None
+            if n == 0 or not encoded:
+                out = {"count": np.zeros(n, dtype=np.int32), "query": np.full((n, m), -1, dtype=np.int32),
+                       "score": np.full((n, m), -1, dtype=np.int32)}
+                if mode == "end":
+                    out.update(end_q=np.full((n, m), -1, dtype=np.int32), end_t=np.full((n, m), -1, dtype=np.int32))
+            else:
+                if _capi.lib().miopalDeviceCount() < 1:
+                    raise RuntimeError("no supported SIMD backend available")
+                mirror = database._device_mirror(device)
+                matrix = _int_matrix_array(self._int_matrix)
+                arrays = [np.frombuffer(e, dtype=np.uint8) for e in encoded]
+                out = mirror.search_batch_target_top(arrays, matrix, self.gap_open, self.gap_extend,
+                                                     "score" if mode == "full" else mode, algorithm, start, end, m,
+                                                     min_score)
+            if mode == "full":
+                # every chosen (query, target) pair in one pair-list call, row-major over (target, rank)
+                chosen = np.arange(m)[None, :] < out["count"][:, None]
+                pair_query = out["query"][chosen]
+                pair_target = np.repeat(np.arange(start, end, dtype=np.int64), out["count"])
+                if len(pair_query):
+                    pairs = mirror.align_pairs(arrays, pair_query, pair_target, matrix, self.gap_open, self.gap_extend,
+                                               "full", algorithm)
+                    pairs.pop("aln", None)
+                else:
+                    zeros = lambda: np.zeros(0, dtype=np.int32)   # noqa: E731
+                    pairs = {"score": zeros(), "end_q": zeros(), "end_t": zeros(), "start_q": zeros(), "start_t": zeros(),
+                             "aln_flat": np.zeros(0, dtype=np.uint8), "aln_off": np.zeros(1, dtype=np.int64)}
+                pairs.update(query=pair_query, target=pair_target)
+                out["pairs"] = pairs
+            return out, query_lengths, mirror
+
 
     def hits(self, query, database: BaseDatabase, min_score: int, *, mode: str = "score", algorithm: str = "sw",
              start: int = 0, end: int = UINT32_MAX, device: int = 0, max_hits: typing.Optional[int] = None,
