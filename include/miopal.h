@@ -335,6 +335,87 @@ int miopalSearchBatchHits(MiopalDb* db, const unsigned char* queries, const int6
                           int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery);
 
 /*
+ * The significant hits of a query: miopalSearchHits with the cut stated as an E-value, the statistics gathered on the
+ * device from the search's own scores (almost all targets of a database search are unrelated to the query: the search
+ * is its own calibration sample). No table of Karlin-Altschul parameters is involved.
+ *   Length bins: a target of length L falls into bin 0 for L = 0, otherwise into bin 1 + 4 e + m with e = floor(log2 L)
+ *     and m the two bits below the leading one of L (quarter octaves; at most 124 for 32-bit lengths).
+ *   Statistics: per bin the device sums n, score and score^2 of the slice's targets as 64-bit integers (exact, the
+ *     same in any order), and the targets and the sum of their lengths (binTargets, binLength).
+ *   Fit (host, doubles), over the bins 1 .. 127 that hold targets: x_b = ln(binLength[b] / binTargets[b]); the weighted
+ *     least-squares line mean_b = intercept + slope x_b through the scores (slope 0 and intercept the mean when all
+ *     targets share one bin); sigma^2 = sum_b (sum s^2 - 2 mean_b sum s + n_b mean_b^2) / (used - 2).
+ *   Refits: with excludeZ > 0 the statistics are taken again leaving out every target with score > ceiling[b] =
+ *     floor(mean_b + excludeZ sigma) - related sequences inflate the spread; only the upper tail is cut - and the fit
+ *     repeated, until the ceilings repeat or MIOPAL_FIT_MAX_REFITS refits are done. The ceilings of a refit apply to
+ *     all targets and replace the ones before. excludeZ <= 0: one pass.
+ *   Tail: z = (score - mean_b) / sigma; P = 1 - exp(-exp(-(pi / sqrt 6) z - gamma)), the tail of a Gumbel variable with
+ *     mean 0 and variance 1; E = targets x P, targets the non-empty targets of the slice. The z-score holds for any
+ *     mode; the Gumbel tail is the one of local (OPAL_MODE_SW) scores - for the other modes E is a ranking on the same
+ *     scale, not a calibrated expectation.
+ *   Hits: with P* = maxEvalue / targets, zCut = -(ln(-log1p(-P*)) + gamma) sqrt 6 / pi and threshold[b] =
+ *     ceil(mean_b + zCut sigma), clamped to int32; a target of bin b is a hit iff score >= threshold[b]. P* >= 1:
+ *     threshold[b] = INT_MIN for the bins that hold targets (every non-empty target; zCut = -infinity). Bin 0 (empty
+ *     targets) and bins without targets: INT_MAX, never a hit.
+ *   Degenerate: fewer than 3 targets in the fit, a residual sum that is not positive, or a value that is not finite -
+ *     degenerate = 1, every threshold INT_MAX, no hits, and the call returns 0.
+ * The outputs are miopalSearchHits' (database order, malloc'ed arrays, maxHits and MIOPAL_ERR_TOO_MANY_HITS - *fit is
+ * filled then, too) with *evalue beside them: the E-value of hit i, malloc'ed, NULL without hits. The score rows stay
+ * in HBM: per pass 3 KB of sums come back, the 512-byte table goes up, and only the hits cross PCIe.
+ * Checks: miopalSearchHits' in their order, then a NULL fit or evalue, a maxEvalue that is not finite and positive, an
+ * excludeZ that is NaN: MIOPAL_ERR_BAD_ARGUMENT. An empty slice is checked and answered with *count = 0, NULL arrays and
+ * a zeroed fit with degenerate = 1 (no ceilings, every threshold INT_MAX), nothing launched. The score pass takes the
+ * kernels miopalSearch takes (miopalLastRouting reports the same). Thread-safe like miopalSearch; the handle builds its
+ * bin per target on the device at its first call of this family.
+ */
+#define MIOPAL_STAT_BINS 128
+#define MIOPAL_FIT_MAX_REFITS 3
+typedef struct MiopalScoreFit {
+    int64_t targets, used;            /* non-empty targets of the slice; targets the last fit rests on */
+    int32_t passes, degenerate;       /* 1 + refits done */
+    double  intercept, slope, sigma, zCut;
+    int64_t binTargets[MIOPAL_STAT_BINS], binLength[MIOPAL_STAT_BINS];   /* n_b, sum of lengths */
+    int64_t all[MIOPAL_STAT_BINS][3];    /* n, sum, sum of squares: every target */
+    int64_t kept[MIOPAL_STAT_BINS][3];   /* the same under `ceiling` (= all when no refit ran) */
+    int32_t ceiling[MIOPAL_STAT_BINS];   /* of the last pass; INT_MAX: none */
+    int32_t threshold[MIOPAL_STAT_BINS]; /* a target of bin b is a hit iff score >= threshold[b] */
+} MiopalScoreFit;
+int miopalSearchSignificant(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                            const int* scoreMatrix, int alphabetLength, int searchType, int mode,
+                            int64_t start, int64_t end, double maxEvalue, double excludeZ, int64_t maxHits,
+                            MiopalScoreFit* fit, int64_t* count, int64_t** targetIndex, int** score,
+                            int** endTarget, int** endQuery, double** evalue);
+
+/*
+ * miopalSearchSignificant with a position-specific scoring matrix in the place of (query, scoreMatrix): rowScores as in
+ * miopalSearchPssm, no consensus - the inclusion step of an iterated profile search, stated as "E below 1e-3".
+ * miopalSearchSignificant's contract holds to the letter. Checked before any device call in miopalSearchPssmHits' order:
+ * what needs no handle first (the fit and evalue outputs, maxEvalue and excludeZ behind the null outputs), then the
+ * handle, the alphabet length against it, the slice, and the 32-bit range check (OPAL_ERR_OVERFLOW).
+ */
+int miopalSearchPssmSignificant(MiopalDb* db, const int* rowScores, int queryLength,
+                                int gapOpen, int gapExt, int alphabetLength, int searchType, int mode,
+                                int64_t start, int64_t end, double maxEvalue, double excludeZ, int64_t maxHits,
+                                MiopalScoreFit* fit, int64_t* count, int64_t** targetIndex, int** score,
+                                int** endTarget, int** endQuery, double** evalue);
+
+/*
+ * miopalSearchSignificant of every query of a batch, with one cut per query (maxEvalue[nQueries]) and one fit per query
+ * (fits[nQueries], the caller's): miopalSearchBatchHits' chunks, each chunk's statistics taken for all its rows in one
+ * launch, the fits made, the tables uploaded and the rows compacted before they leave. The answer is
+ * miopalSearchBatchHits' CSR with *evalue beside the arrays; entries hitOffsets[i] .. hitOffsets[i + 1] and fits[i]
+ * equal miopalSearchSignificant of query i alone. maxHits bounds the total; with more, MIOPAL_ERR_TOO_MANY_HITS with
+ * hitOffsets and fits filled and nothing allocated. Checks: miopalSearchBatchHits' in their order, then a NULL evalue,
+ * a NULL maxEvalue or fits with nQueries > 0, every maxEvalue[i] and excludeZ as in miopalSearchSignificant. nQueries =
+ * 0 or an empty slice: checked, hitOffsets all 0, NULL arrays, every fit as for an empty slice, 0.
+ */
+int miopalSearchBatchSignificant(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                                 int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType,
+                                 int mode, int64_t start, int64_t end, const double* maxEvalue, double excludeZ,
+                                 int64_t maxHits, MiopalScoreFit* fits, int64_t* hitOffsets, int64_t** targetIndex,
+                                 int** score, int** endTarget, int** endQuery, double** evalue);
+
+/*
  * The m best QUERIES of every target of the slice, selected on the device: the selection of miopalSearchBatchTop turned
  * round - which barcode, adapter, primer or motif of a batch matches each read best, and by what margin over the
  * runner-up. queries and queryOffsets as in miopalSearchBatch; all four modes; OPAL_SEARCH_SCORE and
@@ -534,6 +615,30 @@ int miopalTestSelectHits(const int* score, const int* endTarget, const int* endQ
                          int rows, int64_t stride, const int* minScore, int64_t start,
                          int64_t* hitOffsets, int64_t** targetIndex, int** outScore, int** outEndTarget,
                          int** outEndQuery);
+
+/*
+ * Test hook: the statistics kernels of miopalSearchSignificant alone, on rows of int32 scores the caller supplies (any
+ * int32 values), with no search and no handle in front of them. score is a host array [rows][stride]; column i belongs
+ * to a target of length[i] (>= 0). The device turns the lengths into bins and sums, per (row, bin), n, score and
+ * score^2 of the entries with score <= ceiling[row][bin] (ceiling [rows][MIOPAL_STAT_BINS], or NULL: every entry) as
+ * 64-bit two's-complement integers that wrap; rows with skip[row] != 0 (skip may be NULL) are not read and stay 0.
+ * Outputs: stats [rows][MIOPAL_STAT_BINS][3] and the device's bin[stride]. Device 0.
+ * MIOPAL_ERR_BAD_ARGUMENT, before any device call: rows < 1, stride < 1, a null input or output, a negative length,
+ * rows x stride above 2^27.
+ */
+int miopalTestRowStats(const int* score, int rows, int64_t stride, const int32_t* length, const int32_t* ceiling,
+                       const int* skip, int64_t* stats, unsigned char* bin);
+
+/*
+ * Test hook: miopalTestSelectHits with length[stride] (>= 0) and threshold[rows][MIOPAL_STAT_BINS] in the place of
+ * minScore: entry i of row r is kept iff score >= threshold[r][bin of length[i]] - the binned compaction of
+ * miopalSearchSignificant alone. Everything else, the checks included, as miopalTestSelectHits (a null length or
+ * threshold and a negative length: MIOPAL_ERR_BAD_ARGUMENT).
+ */
+int miopalTestSelectHitsBinned(const int* score, const int* endTarget, const int* endQuery,
+                               int rows, int64_t stride, const int32_t* length, const int32_t* threshold,
+                               int64_t start, int64_t* hitOffsets, int64_t** targetIndex, int** outScore,
+                               int** outEndTarget, int** outEndQuery);
 
 /*
  * Test hook: the device selection of miopalSearchBatchTargetTop alone - the m best rows of every column - on rows of

@@ -20,6 +20,8 @@ OPAL_ERR_INVALID_MODE = 3
 MIOPAL_ERR_TOO_MANY_HITS = 103   # include/opal.h: more hits than max_hits (search_hits and its forms)
 MIOPAL_MAX_TOP = 4096   # include/miopal.h: the largest k of miopalSearchTop / miopalSearchBatchTop
 MIOPAL_MAX_TARGET_TOP = 8   # include/miopal.h: the largest m of miopalSearchBatchTargetTop
+MIOPAL_STAT_BINS = 128   # include/miopal.h: the length bins of miopalSearchSignificant's statistics
+MIOPAL_FIT_MAX_REFITS = 3
 
 SEARCH = {"score": 0, "end": 1, "full": 2}
 MODE = {"nw": 0, "hw": 1, "ov": 2, "sw": 3}
@@ -39,6 +41,32 @@ class OpalSearchResult(ctypes.Structure):
     ]
 
 
+class ScoreFit(ctypes.Structure):
+    """MiopalScoreFit (include/miopal.h): the statistics, the fit and the table of a significance search."""
+    _fields_ = [
+        ("targets", ctypes.c_int64), ("used", ctypes.c_int64),
+        ("passes", ctypes.c_int32), ("degenerate", ctypes.c_int32),
+        ("intercept", ctypes.c_double), ("slope", ctypes.c_double), ("sigma", ctypes.c_double), ("zCut", ctypes.c_double),
+        ("binTargets", ctypes.c_int64 * MIOPAL_STAT_BINS), ("binLength", ctypes.c_int64 * MIOPAL_STAT_BINS),
+        ("all", ctypes.c_int64 * 3 * MIOPAL_STAT_BINS), ("kept", ctypes.c_int64 * 3 * MIOPAL_STAT_BINS),
+        ("ceiling", ctypes.c_int32 * MIOPAL_STAT_BINS), ("threshold", ctypes.c_int32 * MIOPAL_STAT_BINS),
+    ]
+
+
+def length_bins(lengths) -> np.ndarray:
+    """The length bin of include/miopal.h for every entry of ``lengths`` (integers >= 0), in integers: 0 for 0,
+    otherwise 1 + 4 e + m with e = floor(log2 L) and m the two bits below the leading one."""
+    L = np.asarray(lengths, dtype=np.int64)
+    if np.any(L < 0):
+        raise ValueError("lengths must not be negative")
+    e = np.zeros(L.shape, dtype=np.int64)
+    for shift in (32, 16, 8, 4, 2, 1):   # floor(log2 L) by halving, no floating point
+        up = (L >> (e + shift)) > 0
+        e[up] += shift
+    m = np.where(e >= 2, (L >> np.maximum(e - 2, 0)) & 3, (L << np.maximum(2 - e, 0)) & 3)
+    return np.where(L == 0, 0, np.minimum(1 + 4 * e + m, MIOPAL_STAT_BINS - 1)).astype(np.int64)
+
+
 _lib = None
 _libc = None
 
@@ -54,10 +82,11 @@ EXPORTS = [
     "miopalSearchBatch", "miopalLastBatchRouting", "miopalSearchTop", "miopalSearchBatchTop",
     "miopalAlignPairs", "miopalLastPairRouting", "miopalSearchPssmTop", "miopalAlignPairsPssm",
     "miopalSearchHits", "miopalSearchPssmHits", "miopalSearchBatchHits", "miopalSearchBatchTargetTop",
+    "miopalSearchSignificant", "miopalSearchPssmSignificant", "miopalSearchBatchSignificant",
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
     # test hooks
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
-    "miopalTestSelectHits", "miopalTestSelectColumns",
+    "miopalTestSelectHits", "miopalTestSelectColumns", "miopalTestRowStats", "miopalTestSelectHitsBinned",
 ]
 
 
@@ -150,6 +179,20 @@ def lib() -> ctypes.CDLL:
                                             c_i64, c_i64, c_vp, c_i64, c_vp, pp, pp, pp, pp]
         L.miopalTestSelectHits.restype = c_int
         L.miopalTestSelectHits.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp, pp, pp, pp, pp]
+        c_dbl = ctypes.c_double
+        L.miopalSearchSignificant.restype = c_int
+        L.miopalSearchSignificant.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_i64, c_i64,
+                                              c_dbl, c_dbl, c_i64, c_vp, ctypes.POINTER(c_i64), pp, pp, pp, pp, pp]
+        L.miopalSearchPssmSignificant.restype = c_int
+        L.miopalSearchPssmSignificant.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64,
+                                                  c_dbl, c_dbl, c_i64, c_vp, ctypes.POINTER(c_i64), pp, pp, pp, pp, pp]
+        L.miopalSearchBatchSignificant.restype = c_int
+        L.miopalSearchBatchSignificant.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
+                                                   c_i64, c_i64, c_vp, c_dbl, c_i64, c_vp, c_vp, pp, pp, pp, pp, pp]
+        L.miopalTestRowStats.restype = c_int
+        L.miopalTestRowStats.argtypes = [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.miopalTestSelectHitsBinned.restype = c_int
+        L.miopalTestSelectHitsBinned.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_i64, c_vp, pp, pp, pp, pp]
         L.miopalSearchBatchTargetTop.restype = c_int
         L.miopalSearchBatchTargetTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
                                                  c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
@@ -386,6 +429,75 @@ def select_hits_rows(score: np.ndarray, min_score, end_q: typing.Optional[np.nda
     ptrs = _HitPointers()
     rc = lib().miopalTestSelectHits(_ptr(score), _ptr(ends[1]), _ptr(ends[0]), rows, stride, _ptr(thresholds), start,
                                     _ptr(offsets), *ptrs.refs())
+    raise_for(rc)
+    out = {"offsets": offsets}
+    out.update(ptrs.arrays(int(offsets[-1]), ends[0] is not None))
+    return out
+
+
+def _score_rows(score, end_q, end_t):
+    """score as int32 (rows, stride) and the end arrays beside it, as the test hooks take them"""
+    score = np.ascontiguousarray(score, dtype=np.int32)
+    if score.ndim == 1:
+        score = score[None, :]
+    if score.ndim != 2:
+        raise ValueError("score must have shape (rows, stride)")
+    ends = []
+    for e in (end_q, end_t):
+        if e is not None:
+            e = np.ascontiguousarray(e, dtype=np.int32).reshape(-1, e.shape[-1])
+            if e.shape != score.shape:
+                raise ValueError("end arrays must have the shape of score")
+        ends.append(e)
+    return score, ends
+
+
+def _bin_table(table, rows, name):
+    table = np.asarray(table, dtype=np.int32)
+    if table.shape not in ((MIOPAL_STAT_BINS,), (rows, MIOPAL_STAT_BINS)):
+        raise ValueError(f"{name} must hold {MIOPAL_STAT_BINS} entries, or as many per row")
+    return np.ascontiguousarray(np.broadcast_to(table, (rows, MIOPAL_STAT_BINS)))
+
+
+def row_stats_rows(score: np.ndarray, length: np.ndarray, ceiling: typing.Optional[np.ndarray] = None,
+                   skip: typing.Optional[np.ndarray] = None) -> typing.Dict[str, np.ndarray]:
+    """miopalTestRowStats (test hook): the statistics kernels alone on the rows of ``score`` (int32, (rows, stride); a
+    1-D array is one row) whose column i belongs to a target of ``length[i]``. ``ceiling``: (128,) or (rows, 128), the
+    entries above it left out (None: none); ``skip``: one flag per row, non-zero - the row is not read. Returns
+    "stats" (int64, (rows, 128, 3): n, sum, sum of squares per bin, wrapping) and "bin" (uint8, (stride,), the
+    device's bins). The C side checks the arguments."""
+    score, _ = _score_rows(score, None, None)
+    rows, stride = score.shape
+    length = np.ascontiguousarray(length, dtype=np.int32)
+    if length.shape != (stride,):
+        raise ValueError("length must hold one entry per column of score")
+    table = None if ceiling is None else _bin_table(ceiling, rows, "ceiling")
+    flags = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.int32)
+    if flags is not None and flags.shape != (rows,):
+        raise ValueError("skip must hold one flag per row")
+    out = {"stats": np.zeros((rows, MIOPAL_STAT_BINS, 3), dtype=np.int64), "bin": np.zeros(stride, dtype=np.uint8)}
+    rc = lib().miopalTestRowStats(_ptr(score), rows, stride, _ptr(length), _ptr(table), _ptr(flags), _ptr(out["stats"]),
+                                  _ptr(out["bin"]))
+    raise_for(rc)
+    return out
+
+
+def select_hits_binned_rows(score: np.ndarray, length: np.ndarray, threshold: np.ndarray,
+                            end_q: typing.Optional[np.ndarray] = None, end_t: typing.Optional[np.ndarray] = None,
+                            start: int = 0) -> typing.Dict[str, np.ndarray]:
+    """miopalTestSelectHitsBinned (test hook): `select_hits_rows` with ``length`` (one per column) and ``threshold``
+    ((128,) or (rows, 128)) in the place of ``min_score``: entry i of row r is kept iff score >=
+    threshold[r, bin of length[i]]. Returns `select_hits_rows`' dict."""
+    score, ends = _score_rows(score, end_q, end_t)
+    rows, stride = score.shape
+    length = np.ascontiguousarray(length, dtype=np.int32)
+    if length.shape != (stride,):
+        raise ValueError("length must hold one entry per column of score")
+    table = _bin_table(threshold, rows, "threshold")
+    offsets = np.zeros(rows + 1, dtype=np.int64)
+    ptrs = _HitPointers()
+    rc = lib().miopalTestSelectHitsBinned(_ptr(score), _ptr(ends[1]), _ptr(ends[0]), rows, stride, _ptr(length), _ptr(table),
+                                          start, _ptr(offsets), *ptrs.refs())
     raise_for(rc)
     out = {"offsets": offsets}
     out.update(ptrs.arrays(int(offsets[-1]), ends[0] is not None))
@@ -806,6 +918,105 @@ class DeviceDatabase:
         return out
 
     select_hits_rows = staticmethod(select_hits_rows)
+
+    @staticmethod
+    def _check_evalue_cut(max_evalue, exclude_z):
+        """what the C side refuses, refused before it is reached: a cut that is not finite and positive, a NaN"""
+        cuts = np.atleast_1d(np.asarray(max_evalue, dtype=np.float64))
+        if not np.all(np.isfinite(cuts)) or not np.all(cuts > 0):
+            raise ValueError("max_evalue must be finite and positive")
+        if np.isnan(float(exclude_z)):
+            raise ValueError("exclude_z must not be NaN")
+
+    def search_significant(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
+                           mode: str = "score", algorithm: str = "sw", start: int = 0,
+                           end: typing.Optional[int] = None, max_evalue: float = 1e-3, exclude_z: float = 5.0,
+                           max_hits: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+        """miopalSearchSignificant: every target of the slice with an E-value of at most ``max_evalue``, the
+        statistics gathered on the device from the search's own scores. Returns `search_hits`' dict plus "evalue"
+        (float64, one per hit) and "fit" (a `ScoreFit` structure). TooManyHits carries the fit as ``fit``."""
+        self._check_evalue_cut(max_evalue, exclude_z)
+        end = self.count if end is None else min(end, self.count)
+        q = np.ascontiguousarray(query, dtype=np.uint8)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        count = ctypes.c_int64(-1)
+        ptrs, fit, ev = _HitPointers(), ScoreFit(), ctypes.c_void_p()
+        rc = lib().miopalSearchSignificant(self._h, _ptr(q), len(q), gap_open, gap_extend, _ptr(S), self.alphabet_length,
+                                           SEARCH[mode], MODE[algorithm], start, end, float(max_evalue), float(exclude_z),
+                                           -1 if max_hits is None else max_hits, ctypes.addressof(fit),
+                                           ctypes.byref(count), *ptrs.refs(), ctypes.byref(ev))
+        return self._significant_result(rc, int(count.value), ptrs, ev, fit, mode)
+
+    def _significant_result(self, rc, count, ptrs, ev, fit, mode):
+        try:
+            out = self._hits_result(rc, count, ptrs, mode)
+        except TooManyHits as err:
+            err.fit = fit
+            raise
+        out["evalue"] = _take_malloced(ev, count, np.float64)
+        out["fit"] = fit
+        return out
+
+    def search_pssm_significant(self, row_scores: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
+                                mode: str = "score", algorithm: str = "sw", start: int = 0,
+                                end: typing.Optional[int] = None, max_evalue: float = 1e-3, exclude_z: float = 5.0,
+                                max_hits: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+        """miopalSearchPssmSignificant: `search_significant` with a position-specific scoring matrix (``row_scores``
+        as in `search_pssm`) in the place of (query, matrix)."""
+        self._check_evalue_cut(max_evalue, exclude_z)
+        end = self.count if end is None else min(end, self.count)
+        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
+        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
+            raise ValueError(f"row_scores must have shape (query length, {self.alphabet_length})")
+        count = ctypes.c_int64(-1)
+        ptrs, fit, ev = _HitPointers(), ScoreFit(), ctypes.c_void_p()
+        rc = lib().miopalSearchPssmSignificant(self._h, _ptr(rows) if len(rows) else None, len(rows), gap_open, gap_extend,
+                                               self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end,
+                                               float(max_evalue), float(exclude_z), -1 if max_hits is None else max_hits,
+                                               ctypes.addressof(fit), ctypes.byref(count), *ptrs.refs(), ctypes.byref(ev))
+        return self._significant_result(rc, int(count.value), ptrs, ev, fit, mode)
+
+    def search_batch_significant(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
+                                 gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
+                                 end: typing.Optional[int] = None, max_evalue=1e-3, exclude_z: float = 5.0,
+                                 max_hits: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+        """miopalSearchBatchSignificant: search_significant of every query in one batched call. ``max_evalue``: a
+        number or one per query. Returns `search_batch_hits`' CSR plus "evalue" and "fits" (a list of `ScoreFit`
+        structures, one per query). TooManyHits carries the offsets in ``counts`` and the fits in ``fits``."""
+        self._check_evalue_cut(max_evalue, exclude_z)
+        end = self.count if end is None else min(end, self.count)
+        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
+        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            np.cumsum([len(q) for q in qs], out=offsets[1:])
+        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
+        if flat.size == 0:
+            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        cuts = np.ascontiguousarray(np.broadcast_to(np.asarray(max_evalue, dtype=np.float64), (len(qs),)))
+        fits = (ScoreFit * max(len(qs), 1))()
+        hit_offsets = np.zeros(len(qs) + 1, dtype=np.int64)
+        ptrs, ev = _HitPointers(), ctypes.c_void_p()
+        rc = lib().miopalSearchBatchSignificant(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
+                                                self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end,
+                                                _ptr(cuts) if len(qs) else None, float(exclude_z),
+                                                -1 if max_hits is None else max_hits, ctypes.addressof(fits),
+                                                _ptr(hit_offsets), *ptrs.refs(), ctypes.byref(ev))
+        fit_list = [fits[i] for i in range(len(qs))]
+        if rc == MIOPAL_ERR_TOO_MANY_HITS:
+            err = TooManyHits(f"more hits than max_hits (code={rc}): {last_error()}", hit_offsets)
+            err.fits = fit_list
+            raise err
+        raise_for(rc)
+        out = {"offsets": hit_offsets}
+        out.update(ptrs.arrays(int(hit_offsets[-1]), mode == "end"))
+        out["evalue"] = _take_malloced(ev, int(hit_offsets[-1]), np.float64)
+        out["fits"] = fit_list
+        out["_fits_owner"] = fits
+        return out
+
+    row_stats_rows = staticmethod(row_stats_rows)
+    select_hits_binned_rows = staticmethod(select_hits_binned_rows)
 
     def search_batch_target_top(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
                                 gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,

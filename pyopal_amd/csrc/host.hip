@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -39,6 +40,7 @@
 #include "score_ranges_selftest.h"
 #include "select_columns.h"
 #include "select_hits.h"
+#include "select_stats.h"
 #include "select_top.h"
 #include "tuning.h"
 
@@ -679,6 +681,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_batch.inc"
 #include "host_top.inc"
 #include "host_hits.inc"
+#include "host_stats.inc"
 #include "host_columns.inc"
 #include "host_pairs.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
@@ -928,6 +931,90 @@ int miopalTestSelectHits(const int* score, const int* endTarget, const int* endQ
     return guarded([&]() -> int {
     return testSelectHitsImpl(score, endTarget, endQuery, rows, stride, minScore, start, hitOffsets, targetIndex, outScore,
                               outEndTarget, outEndQuery);
+    });
+}
+
+// miopalSearchSignificant: miopalSearchHits' checks in its order, then the fit and E-value outputs and the cut, then the
+// score pass, the statistics, the fit and the binned compaction (host_stats.inc)
+int miopalSearchSignificant(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                            const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
+                            int64_t end, double maxEvalue, double excludeZ, int64_t maxHits, MiopalScoreFit* fit,
+                            int64_t* count, int64_t** targetIndex, int** score, int** endTarget, int** endQuery,
+                            double** evalue) {
+    return guarded([&]() -> int {
+    RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, searchType, mode, start, end));
+    if (searchType == OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "miopalSearchSignificant: alignments are not selected on the device");
+    RC_TRY(checkHitsOutputs(searchType, count, targetIndex, score, endTarget, endQuery));
+    RC_TRY(checkSignificantArgs(fit, evalue));
+    RC_TRY(checkEvalueCut(maxEvalue, excludeZ));
+    HitRows rows;
+    std::vector<double> ev;
+    SliceLengths lengths;
+    RC_TRY(searchSignificantImpl(db, query, queryLength, gapOpen, gapExt, scoreMatrix, alphabetLength, searchType, mode, start,
+                                 end, maxEvalue, excludeZ, maxHits, &lengths, fit, &rows, &ev));
+    return finishSignificant(rows, ev, searchType, maxHits, count, targetIndex, score, endTarget, endQuery, evalue);
+    });
+}
+
+// miopalSearchPssmSignificant: miopalSearchPssmHits' checks in its order - the fit and E-value outputs and the cut among
+// what needs no handle - then searchSignificantImpl with the rows where the matrix stands
+int miopalSearchPssmSignificant(MiopalDb* db, const int* rowScores, int queryLength, int gapOpen, int gapExt,
+                                int alphabetLength, int searchType, int mode, int64_t start, int64_t end, double maxEvalue,
+                                double excludeZ, int64_t maxHits, MiopalScoreFit* fit, int64_t* count,
+                                int64_t** targetIndex, int** score, int** endTarget, int** endQuery, double** evalue) {
+    return guarded([&]() -> int {
+    const int Q = queryLength, A = alphabetLength;
+    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
+    if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
+    if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
+    if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
+    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    if (searchType == OPAL_SEARCH_ALIGNMENT)
+        return fail(OPAL_ERR_INVALID_MODE, "miopalSearchPssmSignificant: alignments are not selected on the device");
+    RC_TRY(checkHitsOutputs(searchType, count, targetIndex, score, endTarget, endQuery));
+    RC_TRY(checkSignificantArgs(fit, evalue));
+    RC_TRY(checkEvalueCut(maxEvalue, excludeZ));
+    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
+    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
+    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
+    // (no rows: an empty query has no scores; the score source still says "position-specific")
+    static const int kNoRows[1] = {0};
+    // (no consensus: every position is "no residue" - the int32 kernels upload it with the rows and never read it)
+    const std::vector<unsigned char> none((size_t)std::max(Q, 1), 255);
+    HitRows rows;
+    std::vector<double> ev;
+    SliceLengths lengths;
+    RC_TRY(searchSignificantImpl(db, none.data(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, maxEvalue,
+                                 excludeZ, maxHits, &lengths, fit, &rows, &ev, Q > 0 ? rowScores : kNoRows));
+    return finishSignificant(rows, ev, searchType, maxHits, count, targetIndex, score, endTarget, endQuery, evalue);
+    });
+}
+
+int miopalSearchBatchSignificant(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                                 int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int searchType,
+                                 int mode, int64_t start, int64_t end, const double* maxEvalue, double excludeZ,
+                                 int64_t maxHits, MiopalScoreFit* fits, int64_t* hitOffsets, int64_t** targetIndex,
+                                 int** score, int** endTarget, int** endQuery, double** evalue) {
+    return guarded([&]() -> int {
+    return searchBatchSignificantImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength,
+                                      searchType, mode, start, end, maxEvalue, excludeZ, maxHits, fits, hitOffsets,
+                                      targetIndex, score, endTarget, endQuery, evalue);
+    });
+}
+
+int miopalTestRowStats(const int* score, int rows, int64_t stride, const int32_t* length, const int32_t* ceiling,
+                       const int* skip, int64_t* stats, unsigned char* bin) {
+    return guarded([&]() -> int { return testRowStatsImpl(score, rows, stride, length, ceiling, skip, stats, bin); });
+}
+
+int miopalTestSelectHitsBinned(const int* score, const int* endTarget, const int* endQuery, int rows, int64_t stride,
+                               const int32_t* length, const int32_t* threshold, int64_t start, int64_t* hitOffsets,
+                               int64_t** targetIndex, int** outScore, int** outEndTarget, int** outEndQuery) {
+    return guarded([&]() -> int {
+    return testSelectHitsImpl(score, endTarget, endQuery, rows, stride, nullptr, start, hitOffsets, targetIndex, outScore,
+                              outEndTarget, outEndQuery, true, length, threshold);
     });
 }
 

@@ -74,6 +74,12 @@ int fillHandle(MiopalDb* db, const ResidueSource& src, std::vector<int64_t>&& of
         db->views.clear();
         db->prefetched.clear();
     }
+    {
+        // (the bins of the filling before this one)
+        std::lock_guard<std::mutex> g(db->binsMutex);
+        if (db->d_bins) HIP_TRY(hipFree(db->d_bins));
+        db->d_bins = nullptr;
+    }
     db->alphabet = alphabetLength;
     db->count = count;
     db->offsets = std::move(offsets);

@@ -64,14 +64,16 @@ struct HitsOutSlot {
 // are not read. First trip: count and offsets, rowOffset comes back (with the strip error of `s`, the search that
 // made the rows, or null). `room` < 0: no bound; a total above it is counted and not written. Second trip: the
 // outputs are sized to the total, the write enqueued, exactly `total` entries per array downloaded.
+// `binned` (host_stats.inc): entry i of row r is a hit iff score >= binned->threshold[r][binned->bin[i]] - the count and
+// write passes of select_stats.hip in the place of select_hits.hip's; minScore is not read (null).
 static int selectHitRows(Workspace* ws, Search* s, const int32_t* d_score, const int32_t* d_endI, const int32_t* d_endJ,
                          int rows, int64_t n, int64_t start, const int* minScore, const int* skip, int64_t room,
-                         HitRows* out) {
+                         HitRows* out, const BinnedArgs* binned = nullptr) {
     const bool ends = d_endI != nullptr;
     void* p;
     RC_TRY(ws->get(kHitsScratch, hitsScratchBytes(rows, n), &p));
     const HitsScratch sc = hitsScratchLayout(p, rows, n);
-    RC_TRY(ws->stageUpload(sc.minScore, minScore, sizeof(int) * (size_t)rows, ws->stream));
+    if (!binned) RC_TRY(ws->stageUpload(sc.minScore, minScore, sizeof(int) * (size_t)rows, ws->stream));
     if (skip) RC_TRY(ws->stageUpload(sc.skip, skip, sizeof(int) * (size_t)rows, ws->stream));
     else HIP_TRY(hipMemsetAsync(sc.skip, 0, sizeof(int) * (size_t)rows, ws->stream));
     HitsArgs a{};
@@ -82,7 +84,7 @@ static int selectHitRows(Workspace* ws, Search* s, const int32_t* d_score, const
     a.rows = rows;
     a.start = start;
     a.scratch = p;
-    hipError_t e = launchHitsCount(a, ws->stream);
+    hipError_t e = binned ? launchHitsBinnedCount(a, *binned, ws->stream) : launchHitsCount(a, ws->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(MIOPAL_ERR_HIP, "hit selection launch (count): %s", hipGetErrorString(e));
@@ -110,7 +112,7 @@ static int selectHitRows(Workspace* ws, Search* s, const int32_t* d_score, const
     a.outScore = (int32_t*)(base + slot.offScore);
     a.outEndQ = ends ? (int32_t*)(base + slot.offEndQ) : nullptr;
     a.outEndT = ends ? (int32_t*)(base + slot.offEndT) : nullptr;
-    e = launchHitsWrite(a, ws->stream);
+    e = binned ? launchHitsBinnedWrite(a, *binned, ws->stream) : launchHitsWrite(a, ws->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(MIOPAL_ERR_HIP, "hit selection launch (write): %s", hipGetErrorString(e));
@@ -280,23 +282,30 @@ static int searchBatchHitsImpl(MiopalDb* db, const unsigned char* queries, const
 // miopalTestSelectHits (test hook): the three kernels alone, on rows the caller supplies - launchHitsCount and
 // launchHitsWrite as selectHitRows calls them (the same HitsArgs and scratch, one stream, the host between them), with
 // no search and no handle in front of them. Device 0.
+// miopalTestSelectHitsBinned: `binned` - the bins built on the device from length[stride] (length_bins_kernel), the
+// table threshold[rows][kStatBins] in the place of minScore, and select_stats.hip's count and write passes.
 static int testSelectHitsImpl(const int* score, const int* endTarget, const int* endQuery, int rows, int64_t stride,
                               const int* minScore, int64_t start, int64_t* hitOffsets, int64_t** targetIndex,
-                              int** outScore, int** outEndTarget, int** outEndQuery) {
+                              int** outScore, int** outEndTarget, int** outEndQuery, bool binned = false,
+                              const int32_t* length = nullptr, const int32_t* threshold = nullptr) {
     constexpr int64_t kMaxEntries = (int64_t)1 << 27;
     if (rows < 1 || stride < 1) return fail(MIOPAL_ERR_BAD_ARGUMENT, "rows = %d, stride = %lld: both at least 1", rows, (long long)stride);
-    if (!score || !minScore) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null score rows / minScore list");
+    if (!score || (!binned && !minScore)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null score rows / minScore list");
+    if (binned && (!length || !threshold)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null lengths / threshold table");
     if ((endTarget == nullptr) != (endQuery == nullptr)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "one end array without the other");
     const bool ends = endTarget != nullptr;
     if (!hitOffsets || !targetIndex || !outScore) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null hitOffsets / target / score outputs");
     if (ends && (!outEndTarget || !outEndQuery)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null end-location outputs");
     if (stride > kMaxEntries || rows > kMaxEntries / stride)
         return fail(MIOPAL_ERR_BAD_ARGUMENT, "%d rows x %lld entries: more than 2^27", rows, (long long)stride);
+    if (binned)
+        for (int64_t i = 0; i < stride; ++i)
+            if (length[i] < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "negative length at %lld", (long long)i);
     if (physicalDeviceCount() < 1) return fail(OPAL_ERR_NO_SIMD_SUPPORT, "no usable gfx950 device");
     HIP_TRY(hipSetDevice(usableDevices()[0]));
 
     const size_t inBytes = sizeof(int32_t) * (size_t)rows * (size_t)stride;
-    DeviceBytes dScore, dEndI, dEndJ, dScratch, dOut;
+    DeviceBytes dScore, dEndI, dEndJ, dScratch, dOut, dLength, dBin, dTable;
     OwnedStream stream;
     HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
     HIP_TRY(hipMalloc(&dScore.p, inBytes));
@@ -309,8 +318,20 @@ static int testSelectHitsImpl(const int* score, const int* endTarget, const int*
         HIP_TRY(hipMemcpyAsync(dEndJ.p, endTarget, inBytes, hipMemcpyHostToDevice, stream.s));
     }
     const HitsScratch sc = hitsScratchLayout(dScratch.p, rows, stride);
-    HIP_TRY(hipMemcpyAsync(sc.minScore, minScore, sizeof(int) * (size_t)rows, hipMemcpyHostToDevice, stream.s));
+    if (!binned) HIP_TRY(hipMemcpyAsync(sc.minScore, minScore, sizeof(int) * (size_t)rows, hipMemcpyHostToDevice, stream.s));
     HIP_TRY(hipMemsetAsync(sc.skip, 0, sizeof(int) * (size_t)rows, stream.s));
+    BinnedArgs table{};
+    if (binned) {
+        const size_t tableBytes = sizeof(int32_t) * (size_t)rows * kStatBins;
+        HIP_TRY(hipMalloc(&dLength.p, sizeof(int32_t) * (size_t)stride));
+        HIP_TRY(hipMalloc(&dBin.p, (size_t)stride));
+        HIP_TRY(hipMalloc(&dTable.p, tableBytes));
+        HIP_TRY(hipMemcpyAsync(dLength.p, length, sizeof(int32_t) * (size_t)stride, hipMemcpyHostToDevice, stream.s));
+        HIP_TRY(hipMemcpyAsync(dTable.p, threshold, tableBytes, hipMemcpyHostToDevice, stream.s));
+        HIP_TRY(launchLengthBins(nullptr, (const int32_t*)dLength.p, stride, (uint8_t*)dBin.p, stream.s));
+        table.bin = (const uint8_t*)dBin.p;
+        table.threshold = (const int32_t*)dTable.p;
+    }
     HitsArgs a{};
     a.score = (const int32_t*)dScore.p;
     a.endI = (const int32_t*)dEndI.p;
@@ -319,7 +340,7 @@ static int testSelectHitsImpl(const int* score, const int* endTarget, const int*
     a.rows = rows;
     a.start = start;
     a.scratch = dScratch.p;
-    hipError_t e = launchHitsCount(a, stream.s);
+    hipError_t e = binned ? launchHitsBinnedCount(a, table, stream.s) : launchHitsCount(a, stream.s);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(MIOPAL_ERR_HIP, "hit selection launch (count): %s", hipGetErrorString(e));
@@ -340,7 +361,7 @@ static int testSelectHitsImpl(const int* score, const int* endTarget, const int*
         a.outScore = (int32_t*)(base + slot.offScore);
         a.outEndQ = ends ? (int32_t*)(base + slot.offEndQ) : nullptr;
         a.outEndT = ends ? (int32_t*)(base + slot.offEndT) : nullptr;
-        e = launchHitsWrite(a, stream.s);
+        e = binned ? launchHitsBinnedWrite(a, table, stream.s) : launchHitsWrite(a, stream.s);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             return fail(MIOPAL_ERR_HIP, "hit selection launch (write): %s", hipGetErrorString(e));

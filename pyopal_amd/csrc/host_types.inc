@@ -49,6 +49,10 @@ struct MiopalDb {
     uint8_t* d_residues = nullptr;
     int64_t* d_offsets = nullptr;
     size_t residueCap = 0, offsetsCap = 0;   // allocated bytes (a handle may be refilled: opalSearchDatabase)
+    // the length bin of every target (select_stats.h), built at the first significance search (host_stats.inc:
+    // ensureBins) and set, under the mutex, only once the array is complete
+    std::mutex binsMutex;
+    uint8_t* d_bins = nullptr;
     // device blocks of dropped views, kept for the views of the next filling (at most kSpareBlocks)
     std::vector<std::pair<void*, size_t>> spareBlocks;
 
@@ -100,6 +104,7 @@ struct MiopalDb {
         for (auto& b : spareBlocks) (void)hipFree(b.first);
         if (d_residues) (void)hipFree(d_residues);
         if (d_offsets) (void)hipFree(d_offsets);
+        if (d_bins) (void)hipFree(d_bins);
     }
 };
 

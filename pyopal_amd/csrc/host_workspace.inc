@@ -15,6 +15,8 @@ enum Slot {
     // miopalSearchHits and its PSSM and batch forms (host_hits.inc): the compaction's thresholds, counts and offsets
     // (a few bytes per block of 4096 scores), and the written hits, sized to their number
     kHitsScratch, kHitsOut,
+    // miopalSearchSignificant and its forms (host_stats.inc): per row the per-bin sums, the ceilings and the thresholds
+    kStatsScratch,
     // miopalSearchBatchTargetTop (host_columns.inc): the running state and the answer, in the workspace the call holds
     // throughout; a chunk's skip flags, in the workspace that produced the chunk
     kColumnsState, kColumnsOut, kColumnsSkip,

@@ -43,6 +43,9 @@ HitsScratch hitsScratchLayout(void* base, int rows, int64_t stride);
 // count and offsets of every group of kTopRowsPerLaunch rows, enqueued on `stream` (no host synchronisation);
 // afterwards rowOffset is complete
 hipError_t launchHitsCount(const HitsArgs& a, hipStream_t stream);
+// the offsets scan alone, of the group of `rows` rows from r0 whose blockCount is complete (nb: blocksPerRow): for a
+// count pass of another file (select_stats.hip)
+hipError_t launchHitsOffsets(const HitsScratch& sc, int nb, int r0, int rows, hipStream_t stream);
 // the write of every group; never writes at or beyond a.capacity
 hipError_t launchHitsWrite(const HitsArgs& a, hipStream_t stream);
 

@@ -174,6 +174,11 @@ hipError_t launchHitsCount(const HitsArgs& a, hipStream_t stream) {
     return hipSuccess;
 }
 
+hipError_t launchHitsOffsets(const HitsScratch& sc, int nb, int r0, int rows, hipStream_t stream) {
+    hits_offsets_kernel<<<1, kScanThreads, 0, stream>>>(sc, nb, r0, rows);
+    return hipGetLastError();
+}
+
 hipError_t launchHitsWrite(const HitsArgs& a, hipStream_t stream) {
     if (a.rows <= 0 || a.stride <= 0 || a.capacity < 0) return hipErrorInvalidValue;
     const int nb = blocksPerRow(a.stride);

@@ -1239,10 +1239,13 @@ class Aligner:
             raise ValueError(f"min_score must be an integer or hold one per query ({count}), got {len(values)}")
         return np.array([int(v) for v in values] if per_query else [int(min_score)] * count, dtype=np.int32)
 
-    def _hit_arrays(self, queries, pssm, database, min_score, mode, algorithm, start, end, device, max_hits, sort, many):
+    def _hit_arrays(self, queries, pssm, database, min_score, mode, algorithm, start, end, device, max_hits, sort, many,
+                    significant=None):
         """The CSR of `hits`, `hits_many` (queries) and `hits_pssm` (pssm): the checks of `_top` / `top_hits_pssm`, the
         device selection, the host sort, and for "full" the pair list behind them. Returns (arrays, (query lengths,
-        target lengths or None)): what `_hit_objects` needs beside the arrays."""
+        target lengths or None)): what `_hit_objects` needs beside the arrays. ``significant``: (max_evalue,
+        exclude_z) of the `significant_hits` forms in the place of ``min_score`` - the arrays then hold "evalue",
+        "zscore" and "fits" (one `ScoreFit` per query) as well, and ``sort`` orders by E-value, then index."""
         if pssm is not None or queries is None:
             if not isinstance(pssm, Pssm):
                 raise TypeError(f"Argument 'pssm' has incorrect type (expected Pssm, got {type(pssm).__name__})")
@@ -1274,7 +1277,10 @@ class Aligner:
                     raise TypeError("Argument 'query' must not be None")
             encoded = [database.alphabet.encode(q) for q in queries]
             count = len(encoded)
-        thresholds = self._hit_thresholds(min_score, count, many)
+        if significant is None:
+            thresholds = self._hit_thresholds(min_score, count, many)
+        else:
+            cuts, exclude_z = self._evalue_cuts(significant[0], count, many), self._exclude_z(significant[1])
         query_lengths = [len(pssm)] if pssm is not None else [len(e) for e in encoded]
         ends = mode != "score"
         with database.lock.read:
@@ -1292,12 +1298,34 @@ class Aligner:
                 if mode == "full":
                     out.update(start_q=np.zeros(0, dtype=np.int32), start_t=np.zeros(0, dtype=np.int32),
                                aln_flat=np.zeros(0, dtype=np.uint8), aln_off=np.zeros(1, dtype=np.int64))
+                if significant is not None:
+                    out.update(evalue=np.zeros(0, dtype=np.float64), zscore=np.zeros(0, dtype=np.float64),
+                               fits=[ScoreFit() for _ in range(count)])
                 return out, (query_lengths, None)
             if _capi.lib().miopalDeviceCount() < 1:
                 raise RuntimeError("no supported SIMD backend available")
             mirror = database._device_mirror(device)
             search_mode = "score" if mode == "full" else mode
-            if pssm is not None:
+            if significant is not None:
+                arrays, matrix = None, None
+                if pssm is not None:
+                    got = mirror.search_pssm_significant(pssm.scores, self.gap_open, self.gap_extend, search_mode,
+                                                         algorithm, start, end, float(cuts[0]), exclude_z, max_hits)
+                else:
+                    matrix = _int_matrix_array(self._int_matrix)
+                    arrays = [np.frombuffer(e, dtype=np.uint8) for e in encoded]
+                    if many:
+                        got = mirror.search_batch_significant(arrays, matrix, self.gap_open, self.gap_extend, search_mode,
+                                                              algorithm, start, end, cuts, exclude_z, max_hits)
+                        got.pop("_fits_owner", None)
+                    else:
+                        got = mirror.search_significant(arrays[0], matrix, self.gap_open, self.gap_extend, search_mode,
+                                                        algorithm, start, end, float(cuts[0]), exclude_z, max_hits)
+                if "fit" in got:
+                    got["offsets"] = np.array([0, got.pop("count")], dtype=np.int64)
+                    got["fits"] = [got.pop("fit")]
+                got["fits"] = [ScoreFit(f) for f in got["fits"]]
+            elif pssm is not None:
                 got = mirror.search_pssm_hits(pssm.scores, self.gap_open, self.gap_extend, search_mode, algorithm, start,
                                               end, int(thresholds[0]), max_hits)
                 got["offsets"] = np.array([0, got.pop("count")], dtype=np.int64)
@@ -1315,14 +1343,23 @@ class Aligner:
             offsets = got["offsets"]
             owner = np.repeat(np.arange(count, dtype=np.int32), np.diff(offsets))
             if sort and len(owner):
-                # best first inside every query: score descending, then index ascending (`top_hits`' order)
-                order = np.lexsort((got["target"], -got["score"].astype(np.int64), owner))
-                for key in ("target", "score", "end_q", "end_t"):
+                # best first inside every query: score descending, then index ascending (`top_hits`' order); the
+                # significant forms: E-value ascending, then index
+                first = got["evalue"] if significant is not None else -got["score"].astype(np.int64)
+                order = np.lexsort((got["target"], first, owner))
+                for key in ("target", "score", "end_q", "end_t", "evalue"):
                     if key in got:
                         got[key] = got[key][order]
+            if significant is not None:
+                lengths = np.diff(mirror.offsets)[got["target"]]
+                got["zscore"] = np.zeros(len(owner), dtype=np.float64)
+                for i, fit in enumerate(got["fits"]):
+                    span = slice(int(offsets[i]), int(offsets[i + 1]))
+                    got["zscore"][span] = fit.zscore(got["score"][span], lengths[span])
             if mode == "full":
                 # every (query, hit) pair in one pair-list call, in the order chosen above
                 target = got["target"]
+                extra = {key: got[key] for key in ("evalue", "zscore", "fits") if key in got}
                 if pssm is not None:
                     got = mirror.align_pairs_pssm([pssm.scores], [pssm.consensus], owner, target, self.gap_open,
                                                   self.gap_extend, "full", algorithm)
@@ -1330,8 +1367,101 @@ class Aligner:
                     got = mirror.align_pairs(arrays, owner, target, matrix, self.gap_open, self.gap_extend, "full",
                                              algorithm)
                 got.pop("aln", None)
-                got.update(offsets=offsets, target=target)
+                got.update(offsets=offsets, target=target, **extra)
             return got, (query_lengths, np.diff(mirror.offsets) if mode == "full" else None)
+
+    @staticmethod
+    def _evalue_cuts(max_evalue, count, many):
+        """``max_evalue`` as one float64 per query: a finite positive number, or (significant_hits_many) a sequence
+        of ``count`` of them."""
+        per_query = many and not isinstance(max_evalue, (int, float, np.number, str)) and np.ndim(max_evalue) == 1
+        values = list(max_evalue) if per_query else [max_evalue]
+        for v in values:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError(f"max_evalue must be a number, not {type(v).__name__}")
+            if not np.isfinite(v) or not v > 0:
+                raise ValueError("max_evalue must be finite and positive")
+        if per_query and len(values) != count:
+            raise ValueError(f"max_evalue must be a number or hold one per query ({count}), got {len(values)}")
+        return np.array([float(v) for v in values] if per_query else [float(max_evalue)] * count, dtype=np.float64)
+
+    @staticmethod
+    def _exclude_z(exclude_z):
+        if isinstance(exclude_z, bool) or not isinstance(exclude_z, (int, float, np.integer, np.floating)):
+            raise TypeError(f"exclude_z must be a number, not {type(exclude_z).__name__}")
+        if np.isnan(exclude_z):
+            raise ValueError("exclude_z must not be NaN")
+        return float(exclude_z)
+
+    def significant_hits(self, query, database: BaseDatabase, max_evalue: float, *, mode: str = "score",
+                         algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                         exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
+                         sort: bool = False) -> "SignificantHits":
+        """Extension: every target of ``database[start:end]`` with an E-value of at most ``max_evalue`` (include/miopal.h,
+        miopalSearchSignificant) - `hits` with the cut stated the way a search states it, "include below 1e-3". The
+        search is its own calibration sample: the scores are regressed on ln(target length) per quarter-octave length
+        bin, from integer sums gathered on the GPU, standardised, and the z-scores read against the extreme-value
+        distribution; the cut becomes one integer threshold per length bin and the hits are compacted on the GPU.
+        ``exclude_z``: targets more than that many standard deviations above the line are left out of the fit (up to
+        three refits; 0: one pass). Returns a `SignificantHits`: ``.results`` (what `hits` returns, database order),
+        ``.evalues`` / ``.zscores`` (float64) and ``.fit`` (a `ScoreFit`); iterating yields (result, evalue).
+        ``sort=True``: E-value ascending, then index. ``mode="full"`` aligns the hits in one pair-list call. The
+        z-score holds for any algorithm; the E-value is calibrated for local ("sw") scores."""
+        return self._significant_objects(self._hit_arrays([query], None, database, None, mode, algorithm, start, end,
+                                                          device, max_hits, sort, False, (max_evalue, exclude_z)), mode)[0]
+
+    def significant_hits_arrays(self, query, database: BaseDatabase, max_evalue: float, *, mode: str = "score",
+                                algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                                exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
+                                sort: bool = False) -> typing.Dict[str, typing.Any]:
+        """`significant_hits` without result objects: `hits_arrays`' dict plus "evalue", "zscore" and "fit"."""
+        out = self._hit_arrays([query], None, database, None, mode, algorithm, start, end, device, max_hits, sort, False,
+                               (max_evalue, exclude_z))[0]
+        out["fit"] = out.pop("fits")[0]
+        return out
+
+    def significant_hits_many(self, queries, database: BaseDatabase, max_evalue, *, mode: str = "score",
+                              algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                              exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
+                              sort: bool = False) -> typing.List["SignificantHits"]:
+        """Extension: `significant_hits` of every query in one batched search (miopalSearchBatchSignificant); one
+        `SignificantHits` per query. ``max_evalue``: a number, or one per query."""
+        return self._significant_objects(self._hit_arrays(queries, None, database, None, mode, algorithm, start, end,
+                                                          device, max_hits, sort, True, (max_evalue, exclude_z)), mode)
+
+    def significant_hits_many_arrays(self, queries, database: BaseDatabase, max_evalue, *, mode: str = "score",
+                                     algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                                     exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
+                                     sort: bool = False) -> typing.Dict[str, typing.Any]:
+        """`significant_hits_many` as `hits_many_arrays`' CSR plus "evalue", "zscore" and "fits" (one per query)."""
+        return self._hit_arrays(queries, None, database, None, mode, algorithm, start, end, device, max_hits, sort, True,
+                                (max_evalue, exclude_z))[0]
+
+    def significant_hits_pssm(self, pssm: "Pssm", database: BaseDatabase, max_evalue: float, *, mode: str = "score",
+                              algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                              exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
+                              sort: bool = False) -> "SignificantHits":
+        """Extension: `significant_hits` with a `Pssm` in the place of the query and the aligner's matrix
+        (miopalSearchPssmSignificant): the inclusion step of an iterated profile search."""
+        return self._significant_objects(self._hit_arrays(None, pssm, database, None, mode, algorithm, start, end, device,
+                                                          max_hits, sort, False, (max_evalue, exclude_z)), mode)[0]
+
+    def significant_hits_pssm_arrays(self, pssm: "Pssm", database: BaseDatabase, max_evalue: float, *,
+                                     mode: str = "score", algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX,
+                                     device: int = 0, exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
+                                     sort: bool = False) -> typing.Dict[str, typing.Any]:
+        """`significant_hits_pssm` without result objects (`significant_hits_arrays`' dict)."""
+        out = self._hit_arrays(None, pssm, database, None, mode, algorithm, start, end, device, max_hits, sort, False,
+                               (max_evalue, exclude_z))[0]
+        out["fit"] = out.pop("fits")[0]
+        return out
+
+    def _significant_objects(self, arrays_and_lengths, mode):
+        out, lengths = arrays_and_lengths
+        offsets = out["offsets"].tolist()
+        return [SignificantHits(results, out["evalue"][offsets[i]:offsets[i + 1]], out["zscore"][offsets[i]:offsets[i + 1]],
+                                out["fits"][i])
+                for i, results in enumerate(self._hit_objects(out, lengths, mode))]
 
     @staticmethod
     def _hit_objects(out, lengths, mode):
@@ -1354,6 +1484,77 @@ class Aligner:
                                    text[off[p]:off[p + 1]])
                         for p, (q, t) in enumerate(zip(owner, target))]
         return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+
+
+class ScoreFit:
+    """The score statistics behind a `significant_hits` call (include/miopal.h, MiopalScoreFit): per quarter-octave
+    length bin the integer sums gathered on the GPU, the line mean score = ``intercept`` + ``slope`` ln(length) with
+    the spread ``sigma`` fitted to them, and the integer threshold per bin the E-value cut became. ``degenerate``: too
+    few targets (or no spread) for a fit - nothing is a hit, z-scores and E-values are NaN."""
+
+    def __init__(self, raw: typing.Optional[_capi.ScoreFit] = None):
+        bins = _capi.MIOPAL_STAT_BINS
+        if raw is None:
+            raw = _capi.ScoreFit()
+            raw.degenerate = 1
+            for b in range(bins):
+                raw.ceiling[b] = raw.threshold[b] = 2 ** 31 - 1
+        self.targets, self.used, self.passes = int(raw.targets), int(raw.used), int(raw.passes)
+        self.degenerate = bool(raw.degenerate)
+        self.intercept, self.slope, self.sigma, self.z_cut = (float(raw.intercept), float(raw.slope), float(raw.sigma),
+                                                              float(raw.zCut))
+        self.bin_targets = np.array(raw.binTargets, dtype=np.int64)
+        self.bin_length = np.array(raw.binLength, dtype=np.int64)
+        self.all = np.array(raw.all, dtype=np.int64).reshape(bins, 3)
+        self.kept = np.array(raw.kept, dtype=np.int64).reshape(bins, 3)
+        self.ceilings = np.array(raw.ceiling, dtype=np.int32)
+        self.thresholds = np.array(raw.threshold, dtype=np.int32)
+
+    def bin_means(self) -> np.ndarray:
+        """The line's mean score of every bin (NaN for bin 0 and bins that hold no targets)."""
+        mean = np.full(_capi.MIOPAL_STAT_BINS, np.nan)
+        held = self.bin_targets > 0
+        held[0] = False
+        if not self.degenerate:
+            mean[held] = self.intercept + self.slope * np.log(self.bin_length[held] / self.bin_targets[held])
+        return mean
+
+    def zscore(self, score, length) -> np.ndarray:
+        """(score - mean of the length's bin) / sigma, elementwise."""
+        bins = _capi.length_bins(length)
+        if self.degenerate:
+            return np.full(np.broadcast(np.asarray(score), bins).shape, np.nan)
+        return (np.asarray(score, dtype=np.float64) - self.bin_means()[bins]) / self.sigma
+
+    def evalue(self, score, length) -> np.ndarray:
+        """targets x P(z), P the upper tail of a Gumbel variable with mean 0 and variance 1."""
+        z = self.zscore(score, length)
+        return self.targets * -np.expm1(-np.exp(-(np.pi / np.sqrt(6.0)) * z - np.euler_gamma))
+
+    def threshold(self, length) -> np.ndarray:
+        """The smallest score that makes a target of that length a hit (2^31 - 1: never)."""
+        return self.thresholds[_capi.length_bins(length)]
+
+    def __repr__(self):
+        return (f"ScoreFit(targets={self.targets}, used={self.used}, passes={self.passes}, intercept={self.intercept:.4g}, "
+                f"slope={self.slope:.4g}, sigma={self.sigma:.4g}, z_cut={self.z_cut:.4g}, degenerate={self.degenerate})")
+
+
+class SignificantHits:
+    """What `Aligner.significant_hits` returns: ``results`` (the objects `Aligner.hits` returns), ``evalues`` and
+    ``zscores`` (float64, the same order) and ``fit`` (a `ScoreFit`). Iterating yields (result, evalue)."""
+
+    def __init__(self, results, evalues, zscores, fit):
+        self.results, self.evalues, self.zscores, self.fit = results, evalues, zscores, fit
+
+    def __len__(self):
+        return len(self.results)
+
+    def __iter__(self):
+        return iter(zip(self.results, self.evalues.tolist()))
+
+    def __repr__(self):
+        return f"SignificantHits({len(self.results)} hits, {self.fit!r})"
 
 
 class Pssm:
