@@ -142,8 +142,10 @@ int miopalSearchFlat(MiopalDb* db, const unsigned char* query, int queryLength, 
  * the strip at hand in LDS instead of the matrix ("Position-specific scoring matrices").
  * The k best hits and pair lists take a PSSM too: miopalSearchPssmTop and miopalAlignPairsPssm, below.
  * Out of scope: PSSM forms of miopalSearchBatch and miopalSearchBatchTop (their kernels take queries of at
- * most 64 rows, which few PSSMs are), of opalSearchDatabase and of the multi-GPU shard driver; and building
- * a PSSM from an alignment (pseudocounts, background frequencies) - the caller brings the numbers.
+ * most 64 rows, which few PSSMs are), of opalSearchDatabase and of the multi-GPU shard driver. The columns a PSSM
+ * is built from come from miopalProfileColumns, below; the pseudocounts and log-odds on top of them are the
+ * caller's (Pssm.from_columns in the Python layer). Still out of scope there: per-column reduced alignments as
+ * PSI-BLAST weights them, composition-based statistics, insertion-aware profiles.
  */
 int miopalSearchPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
                      int gapOpen, int gapExt, int alphabetLength, int searchType, int mode,
@@ -504,6 +506,42 @@ int miopalAlignPairsPssm(MiopalDb* db, const int* rowScores, const unsigned char
 void miopalLastPairRouting(int64_t counts[4]);
 
 /*
+ * Query-anchored profile columns from hits: the step between two rounds of an iterated profile search. The
+ * alignments of one query - (query, scoreMatrix), or for miopalProfileColumnsPssm the PSSM (rowScores, consensus) of
+ * miopalSearchPssm - with the targets targets[0 .. nTargets) (absolute indices, any order, repeats allowed) are
+ * projected onto the query's rows, counted and weighted on the device; the operations never cross PCIe.
+ * Members: member 0 is the query itself (row: query[i], or consensus[i], 255 = no residue); member 1 + p is target
+ * targets[p], aligned as miopalAlignPairs / miopalAlignPairsPssm align that pair with OPAL_SEARCH_ALIGNMENT.
+ * A member's row[0 .. queryLength): every entry 255 (not covered), then, walking the operations from (startQuery,
+ * startTarget): OPAL_ALIGN_MATCH / MISMATCH at query row i with target residue t: row[i] = t; OPAL_ALIGN_DEL (a query
+ * residue against a gap): row[i] = alphabetLength, the gap letter; OPAL_ALIGN_INS: nothing is recorded. An empty
+ * alignment (an empty target, a Smith-Waterman score of 0) leaves the row all 255.
+ * Outputs (host arrays of the caller), with A = alphabetLength:
+ *   counts[queryLength][A + 1]    members with row[i] == a; index A is the gap letter
+ *   memberWeight[nTargets + 1]    with k_i the letters a < A that occur in column i and term[i][a] =
+ *                                 floor(2^32 / (k_i counts[i][a])) for those letters (64-bit unsigned division): the sum
+ *                                 of term[i][row[i]] over the member's rows with a letter - Henikoff position-based
+ *                                 weights in 32.32 fixed point (MIOPAL_PROFILE_WEIGHT_ONE is 1.0)
+ *   weighted[queryLength][A + 1]  the sum of memberWeight over the members with row[i] == a
+ *   msa[nTargets + 1][queryLength] the rows (NULL: not wanted - the multiple alignment then never leaves the device)
+ * All integer sums, the same in any order; none exceeds queryLength * 2^32.
+ * Checked before any device call, with the existing codes: the checks of miopalAlignPairs / miopalAlignPairsPssm in
+ * that function's order (the messages name "target p"); then NULL counts / weighted / memberWeight; then
+ * (nTargets + 1) * queryLength above 4 GiB (MIOPAL_ERR_BAD_ARGUMENT, the message states the bytes). nTargets = 0: the
+ * profile of the query alone, answered on the host. queryLength = 0: nothing is written. On an error every output is as
+ * it was. miopalLastPairRouting reports the call like a plain pair list. Thread safety as miopalSearch.
+ */
+#define MIOPAL_PROFILE_WEIGHT_ONE (1ll << 32)
+int miopalProfileColumns(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                         const int* scoreMatrix, int alphabetLength, int mode,
+                         const int64_t* targets, int64_t nTargets,
+                         int64_t* counts, int64_t* weighted, int64_t* memberWeight, unsigned char* msa);
+int miopalProfileColumnsPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
+                             int gapOpen, int gapExt, int alphabetLength, int mode,
+                             const int64_t* targets, int64_t nTargets,
+                             int64_t* counts, int64_t* weighted, int64_t* memberWeight, unsigned char* msa);
+
+/*
  * How the calling thread's most recent miopalSearchBatch ran (diagnostics for tests):
  *   counts[0] (query, target) pairs settled by the batch kernels
  *   counts[1] (query, target) pairs run by the wavefront-per-pair kernel
@@ -656,6 +694,17 @@ int miopalTestSelectColumns(const int* score, const int* endTarget, const int* e
                             const int32_t* pieceFirst, const int32_t* pieceCount, int pieces,
                             const unsigned char* skip, int m, int minScore,
                             int* count, int32_t* queryIndex, int* outScore, int* outEndTarget, int* outEndQuery);
+
+/*
+ * Test hook: the count / terms / member weights / weighted kernels of miopalProfileColumns alone, on device 0, on a
+ * host multiple alignment msa[members][queryLength] whose entries are a letter (< alphabetLength), the gap
+ * (== alphabetLength) or 255. counts, weighted ([queryLength][alphabetLength + 1]) and memberWeight ([members]) as
+ * miopalProfileColumns returns them.
+ * MIOPAL_ERR_BAD_ARGUMENT, before any device call: members < 1, queryLength < 1, an alphabet length out of range, a
+ * null pointer, members x queryLength above 2^27, an entry that is neither a letter, the gap nor 255.
+ */
+int miopalTestProfileColumns(const unsigned char* msa, int64_t members, int queryLength, int alphabetLength,
+                             int64_t* counts, int64_t* weighted, int64_t* memberWeight);
 
 #ifdef __cplusplus
 }

@@ -7,12 +7,13 @@ Drop-in for the names of ``pyopal`` (``src/pyopal/__init__.py:4-13``)::
 
 from . import lib
 from ._align import align
-from .lib import (Aligner, Alphabet, BaseDatabase, Database, EndResult, FullResult, Pssm, ScoreFit, ScoreResult,
-                  SignificantHits, __version__)
+from .lib import (Aligner, Alphabet, BaseDatabase, Database, EndResult, FullResult, ProfileColumns, Pssm, ScoreFit,
+                  ScoreResult, SignificantHits, __version__, matrix_lambda)
 from .matrices import ScoringMatrix
 
-# (Pssm, the query type of Aligner.align_pssm, and ScoreFit / SignificantHits of Aligner.significant_hits are
-# extensions: importable, not among the reference's names)
+# (Pssm, the query type of Aligner.align_pssm, ScoreFit / SignificantHits of Aligner.significant_hits, and
+# ProfileColumns / matrix_lambda of Aligner.profile_columns and Pssm.from_columns are extensions: importable, not among
+# the reference's names)
 __all__ = [
     "Alphabet",
     "Aligner",

@@ -22,6 +22,8 @@ MIOPAL_MAX_TOP = 4096   # include/miopal.h: the largest k of miopalSearchTop / m
 MIOPAL_MAX_TARGET_TOP = 8   # include/miopal.h: the largest m of miopalSearchBatchTargetTop
 MIOPAL_STAT_BINS = 128   # include/miopal.h: the length bins of miopalSearchSignificant's statistics
 MIOPAL_FIT_MAX_REFITS = 3
+MIOPAL_PROFILE_WEIGHT_ONE = 1 << 32   # include/miopal.h: 1.0 of miopalProfileColumns' 32.32 fixed-point weights
+PROFILE_UNCOVERED = 255   # an entry of a member's row that its alignment does not cover
 
 SEARCH = {"score": 0, "end": 1, "full": 2}
 MODE = {"nw": 0, "hw": 1, "ov": 2, "sw": 3}
@@ -84,7 +86,9 @@ EXPORTS = [
     "miopalSearchHits", "miopalSearchPssmHits", "miopalSearchBatchHits", "miopalSearchBatchTargetTop",
     "miopalSearchSignificant", "miopalSearchPssmSignificant", "miopalSearchBatchSignificant",
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
+    "miopalProfileColumns", "miopalProfileColumnsPssm",
     # test hooks
+    "miopalTestProfileColumns",
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
     "miopalTestSelectHits", "miopalTestSelectColumns", "miopalTestRowStats", "miopalTestSelectHitsBinned",
 ]
@@ -210,6 +214,14 @@ def lib() -> ctypes.CDLL:
                                            c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp]
         L.miopalLastPairRouting.restype = None
         L.miopalLastPairRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
+        L.miopalProfileColumns.restype = c_int
+        L.miopalProfileColumns.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_i64,
+                                           c_vp, c_vp, c_vp, c_vp]
+        L.miopalProfileColumnsPssm.restype = c_int
+        L.miopalProfileColumnsPssm.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64,
+                                               c_vp, c_vp, c_vp, c_vp]
+        L.miopalTestProfileColumns.restype = c_int
+        L.miopalTestProfileColumns.argtypes = [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]
         L.miopalLastBatchRouting.restype = None
         L.miopalLastBatchRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
         L.miopalSearchFlat.restype = c_int
@@ -541,6 +553,24 @@ def select_columns_rows(score: np.ndarray, m: int, min_score: typing.Optional[in
                                        len(pieces), _ptr(flags), m, -(2 ** 31) if min_score is None else min_score,
                                        _ptr(out["count"]), _ptr(out["query"]), _ptr(out["score"]), _ptr(out.get("end_t")),
                                        _ptr(out.get("end_q")))
+    raise_for(rc)
+    return out
+
+
+def profile_columns_rows(msa: np.ndarray, alphabet_length: int) -> typing.Dict[str, np.ndarray]:
+    """miopalTestProfileColumns (test hook): the count / terms / member weights / weighted kernels of `profile_columns`
+    alone, on a multiple alignment the caller supplies - ``msa``: uint8 of shape (members, Q), entries a letter
+    (< ``alphabet_length``), the gap (== ``alphabet_length``) or 255. Returns "counts" and "weighted" (int64,
+    (Q, alphabet_length + 1)) and "member_weights" (int64, (members,)). The C side checks the arguments."""
+    msa = np.ascontiguousarray(msa, dtype=np.uint8)
+    if msa.ndim != 2:
+        raise ValueError("msa must have shape (members, positions)")
+    members, q = msa.shape
+    width = max(int(alphabet_length), 0) + 1
+    out = {"counts": np.zeros((q, width), dtype=np.int64), "weighted": np.zeros((q, width), dtype=np.int64),
+           "member_weights": np.zeros(members, dtype=np.int64)}
+    rc = lib().miopalTestProfileColumns(_ptr(msa), members, q, alphabet_length, _ptr(out["counts"]), _ptr(out["weighted"]),
+                                        _ptr(out["member_weights"]))
     raise_for(rc)
     return out
 
@@ -1104,6 +1134,55 @@ class DeviceDatabase:
                                               gap_open, gap_extend, self.alphabet_length, st, MODE[algorithm], score,
                                               et, eq, s_t, s_q, ctypes.byref(ops_ptr), aoff)
         return self._pair_list(call, pair_pssm, pair_target, mode)
+
+    def profile_columns(self, query: np.ndarray, matrix: np.ndarray, targets, gap_open: int = 3, gap_extend: int = 1,
+                        algorithm: str = "sw", return_msa: bool = False) -> typing.Dict[str, typing.Any]:
+        """miopalProfileColumns: the alignments of ``query`` (encoded residues) with the targets ``targets`` (absolute
+        indices, any order, repeats allowed) - `align_pairs`' in mode "full" - projected onto the query's rows, counted
+        and weighted on the device. Returns "counts" and "weighted" (int64, (Q, alphabet length + 1), the last column
+        the gap letter), "member_weights" (int64, one per member, the query first; 32.32 fixed point) and "msa" (uint8,
+        (members, Q); None unless ``return_msa``)."""
+        q = np.ascontiguousarray(query, dtype=np.uint8).ravel()
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+
+        def call(pt, n, counts, weighted, weights, msa):
+            return lib().miopalProfileColumns(self._h, _ptr(q) if len(q) else None, len(q), gap_open, gap_extend, _ptr(S),
+                                              self.alphabet_length, MODE[algorithm], pt, n, counts, weighted, weights, msa)
+        return self._profile(call, len(q), targets, return_msa)
+
+    def profile_columns_pssm(self, row_scores: np.ndarray, consensus: np.ndarray, targets, gap_open: int = 3,
+                             gap_extend: int = 1, algorithm: str = "sw",
+                             return_msa: bool = False) -> typing.Dict[str, typing.Any]:
+        """miopalProfileColumnsPssm: `profile_columns` with a position-specific scoring matrix (``row_scores``: integers
+        of shape (Q, alphabet length); ``consensus``: one residue or 255 per row, the query's own row of the multiple
+        alignment) in the place of (query, matrix)."""
+        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
+        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
+            raise ValueError(f"row_scores must have shape (positions, {self.alphabet_length})")
+        cons = np.ascontiguousarray(consensus, dtype=np.uint8).ravel()
+        if len(cons) != len(rows):
+            raise ValueError("consensus must have one entry per row")
+
+        def call(pt, n, counts, weighted, weights, msa):
+            return lib().miopalProfileColumnsPssm(self._h, _ptr(rows) if len(rows) else None,
+                                                  _ptr(cons) if len(rows) else None, len(rows), gap_open, gap_extend,
+                                                  self.alphabet_length, MODE[algorithm], pt, n, counts, weighted, weights,
+                                                  msa)
+        return self._profile(call, len(rows), targets, return_msa)
+
+    def _profile(self, call, q, targets, return_msa) -> typing.Dict[str, typing.Any]:
+        """The outputs of one profile call: ``call(targets, n, counts, weighted, member weights, msa)`` makes the C call
+        with these pointers and returns its code."""
+        pt = np.ascontiguousarray(targets, dtype=np.int64).ravel()
+        n = len(pt)
+        width = self.alphabet_length + 1
+        out = {"counts": np.zeros((q, width), dtype=np.int64), "weighted": np.zeros((q, width), dtype=np.int64),
+               "member_weights": np.zeros(n + 1, dtype=np.int64),
+               "msa": np.full((n + 1, q), PROFILE_UNCOVERED, dtype=np.uint8) if return_msa else None}
+        rc = call(_ptr(pt) if n else None, n, _ptr(out["counts"]), _ptr(out["weighted"]), _ptr(out["member_weights"]),
+                  _ptr(out["msa"]))
+        raise_for(rc)
+        return out
 
     def _pair_list(self, call, pair_query, pair_target, mode) -> typing.Dict[str, typing.Any]:
         """The outputs of one pair-list call (`align_pairs`, `align_pairs_pssm`): ``call(search type, pair queries,

@@ -37,6 +37,7 @@
 #include "common.h"
 #include "full_plan_selftest.h"
 #include "launch_layer_selftest.h"
+#include "profile_columns.h"
 #include "score_ranges_selftest.h"
 #include "select_columns.h"
 #include "select_hits.h"
@@ -684,6 +685,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_stats.inc"
 #include "host_columns.inc"
 #include "host_pairs.inc"
+#include "host_profile.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                  int64_t end, int* score, int* endTarget, int* endQuery, int* startTarget,
@@ -1085,6 +1087,48 @@ int miopalAlignPairsPssm(MiopalDb* db, const int* rowScores, const unsigned char
         }
     }
     return 0;
+    });
+}
+
+// miopalProfileColumns: miopalAlignPairs' checks in its order for the list (query, targets[p]), then the outputs and
+// the size of the multiple alignment, then the pair list with the projection in the place of gather + download and the
+// column kernels (host_profile.inc)
+int miopalProfileColumns(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                         const int* scoreMatrix, int alphabetLength, int mode, const int64_t* targets, int64_t nTargets,
+                         int64_t* counts, int64_t* weighted, int64_t* memberWeight, unsigned char* msa) {
+    return guarded([&]() -> int {
+    return profileColumnsImpl(db, query, queryLength, gapOpen, gapExt, scoreMatrix, alphabetLength, mode, targets, nTargets,
+                              counts, weighted, memberWeight, msa, nullptr);
+    });
+}
+
+// ... with a position-specific scoring matrix: what needs no handle is checked here, in miopalAlignPairsPssm's order
+// (one PSSM of queryLength rows; an alignment search, so the consensus is required), then the same
+int miopalProfileColumnsPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
+                             int gapOpen, int gapExt, int alphabetLength, int mode, const int64_t* targets,
+                             int64_t nTargets, int64_t* counts, int64_t* weighted, int64_t* memberWeight,
+                             unsigned char* msa) {
+    return guarded([&]() -> int {
+    const int Q = queryLength, A = alphabetLength;
+    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
+    if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
+    if (Q > INT32_MAX - 64) return fail(MIOPAL_ERR_BAD_ARGUMENT, "a PSSM holds 2^31 - 65 rows at most");
+    if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
+    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    if (Q > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
+    for (int i = 0; i < Q; ++i)
+        if (consensus[i] >= A && consensus[i] != 255)
+            return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %d", consensus[i], i);
+    static const int kNoRows[1] = {0};
+    return profileColumnsImpl(db, consensus, Q, gapOpen, gapExt, nullptr, A, mode, targets, nTargets, counts, weighted,
+                              memberWeight, msa, Q > 0 ? rowScores : kNoRows);
+    });
+}
+
+int miopalTestProfileColumns(const unsigned char* msa, int64_t members, int queryLength, int alphabetLength,
+                             int64_t* counts, int64_t* weighted, int64_t* memberWeight) {
+    return guarded([&]() -> int {
+    return testProfileColumnsImpl(msa, members, queryLength, alphabetLength, counts, weighted, memberWeight);
     });
 }
 

@@ -22,6 +22,10 @@
 // (pairlist_forward_kernel<., ., true>) as well as the scan and the direction pass of `full` (perpair_kernel<., false,
 // true>) - needs the whole list's table in LDS (perPairPssmBytes of the total rows: 493 rows at 32 letters, 651 at
 // 24); a list with more rows runs one wavefront per pair throughout.
+//
+// A `full` list may be given a consumer (PairChunkConsumer below; miopalProfileColumns, host_profile.inc): per chunk it
+// is handed what the walk left on the device in the place of gather + download, and the operations never reach the
+// host. Without one the function runs the statements it always ran.
 namespace {
 
 constexpr int64_t kPairChunkMax = int64_t(1) << 22;   // pairs per chunk at most (56-byte jobs, twice)
@@ -48,15 +52,39 @@ int64_t pairChunkCapacity(int64_t maxQ, int64_t maxL, bool full) {
     return std::max<int64_t>(cap, 1);
 }
 
+// What the walk of a chunk of a `full` list left on the device, for a consumer that takes the operations where they
+// are (host_profile.inc): the operations of the chunk's pair k end with slot k of `slots` (slotOps bytes each;
+// opsLen[k] of them), start at cell (startQ[k], startT[k]) of the pair, and its target begins at residue tOff[k];
+// pairs[k] is its position in the caller's list. All device pointers but `pairs`; valid until the consumer returns.
+struct PairChunk {
+    Workspace* ws;
+    int count;
+    const int64_t* pairs;
+    const uint8_t* slots;
+    int64_t slotOps;
+    const int32_t *opsLen, *startQ, *startT;
+    const int64_t* tOff;
+};
+// The consumer of alignPairsImpl: with one, a chunk's operations are neither gathered nor downloaded - chunk() enqueues
+// what it does with them on the chunk's stream, behind the walk, and they are final for it when the chunk's small
+// arrays have come down. checks(): the consumer's own argument checks, after the list's and before any device call.
+// noun: what the messages call an entry of the list.
+struct PairChunkConsumer {
+    const char* noun = "pair";
+    std::function<int()> checks;
+    std::function<int(const PairChunk&)> chunk;
+};
+
 }  // namespace
 
 static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
                           const int32_t* pairQuery, const int64_t* pairTarget, int64_t nPairs, int open, int ext,
                           const int* matrix, int A, int searchType, int mode, int* score, int* endTarget,
                           int* endQuery, int* startTarget, int* startQuery, HostBytes* outOps, int64_t* opsOff,
-                          const int* pssmRows = nullptr) {
+                          const int* pssmRows = nullptr, const PairChunkConsumer* consumer = nullptr) {
     for (int k = 0; k < 4; ++k) g_lastPairRouting[k] = 0;
     const bool pssm = pssmRows != nullptr;
+    const char* const noun = consumer ? consumer->noun : "pair";
     // what can be said without the handle first (a caller's mistake is reported whatever the handle's state): the search,
     // the queries and their residues, the pair list's query side, the outputs
     if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
@@ -74,7 +102,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
     if (nPairs < 0 || (nPairs > 0 && (!pairQuery || !pairTarget))) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad pair list");
     for (int64_t p = 0; p < nPairs; ++p)
         if (pairQuery[p] < 0 || pairQuery[p] >= nQueries)
-            return fail(MIOPAL_ERR_BAD_ARGUMENT, "pair %lld: %s index %d outside [0, %d)", (long long)p, pssm ? "PSSM" : "query", pairQuery[p], nQueries);
+            return fail(MIOPAL_ERR_BAD_ARGUMENT, "%s %lld: %s index %d outside [0, %d)", noun, (long long)p, pssm ? "PSSM" : "query", pairQuery[p], nQueries);
     const bool locate = searchType >= OPAL_SEARCH_SCORE_END, full = searchType == OPAL_SEARCH_ALIGNMENT;
     if (full && (!outOps || !opsOff)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null alignment outputs");
     if (nPairs > 0) {
@@ -92,7 +120,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
     int64_t maxQ = 0, maxL = 0;
     for (int64_t p = 0; p < nPairs; ++p) {
         if (pairTarget[p] < 0 || pairTarget[p] >= db->count)
-            return fail(MIOPAL_ERR_BAD_ARGUMENT, "pair %lld: target index %lld outside [0, %lld)", (long long)p,
+            return fail(MIOPAL_ERR_BAD_ARGUMENT, "%s %lld: target index %lld outside [0, %lld)", noun, (long long)p,
                         (long long)pairTarget[p], (long long)db->count);
         maxQ = std::max(maxQ, queryOffsets[pairQuery[p] + 1] - queryOffsets[pairQuery[p]]);
         maxL = std::max<int64_t>(maxL, dbLen(db, pairTarget[p]));
@@ -106,6 +134,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
         const int minScore = nEntries ? *std::min_element(entries, entries + nEntries) : 0;
         if (nPairs > 0) RC_TRY(checkInt32Range({open, ext, maxScore, minScore}, maxQ, maxL));
     }
+    if (consumer) RC_TRY(consumer->checks());
     if (full) opsOff[0] = 0;
     if (nPairs == 0) return 0;
 
@@ -366,9 +395,9 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                 // ---- directions: one lane or one wavefront per pair (full_plan.h; ms; the chunk is one batch) ------
                 const double cells = traceCells(windowStrips, maxWindow);
                 const bool traceLane = lanePossible && (forceLane || traceLaneMs(1, (double)nc, cells) <= traceWaveMs(1, (double)nc, cells));
-                void *pd, *pslots, *pcompact, *pblock, *ptotals;
+                void *pd, *pslots, *pcompact = nullptr, *pblock, *ptotals;
                 RC_TRY(ws->get(kOps, (size_t)(nc * slotOps), &pslots));
-                RC_TRY(ws->get(kCompactOps, (size_t)(nc * slotOps), &pcompact));
+                if (!consumer) RC_TRY(ws->get(kCompactOps, (size_t)(nc * slotOps), &pcompact));
                 RC_TRY(ws->get(kOpsOff, (size_t)((nc + 255) / 256) * sizeof(int64_t), &pblock));
                 RC_TRY(ws->get(kOpsTotals, 2 * sizeof(int64_t), &ptotals));
                 HIP_TRY(hipMemsetAsync(ptotals, 0, 2 * sizeof(int64_t), stream));
@@ -420,12 +449,19 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                 }
                 fillWalk(&wa, (const PairJob*)(traceLane ? psorted : pjobs), nc, db, s, totalQuery, pd, pslots, slotOps, plen);
                 HIP_TRY(launchWalk(wa, stream));
-                HIP_TRY(launchGatherOps(nc, (const uint8_t*)pslots, slotOps, (const int32_t*)plen, (int64_t*)pblock,
-                                        (const int64_t*)ptotals, (int64_t*)ptotals + 1, (uint8_t*)pcompact, stream));
+                if (consumer) {
+                    // (the operations stay where the walk left them: the consumer's kernels read the slots)
+                    RC_TRY(consumer->chunk(PairChunk{ws, nc, order.data() + ch.first, (const uint8_t*)pslots, slotOps,
+                                                     (const int32_t*)plen, (const int32_t*)psq, (const int32_t*)pst,
+                                                     (const int64_t*)ptoff}));
+                } else {
+                    HIP_TRY(launchGatherOps(nc, (const uint8_t*)pslots, slotOps, (const int32_t*)plen, (int64_t*)pblock,
+                                            (const int64_t*)ptotals, (int64_t*)ptotals + 1, (uint8_t*)pcompact, stream));
+                }
                 // ---- one download: the small arrays (they carry the total), then the operations ---------------------
                 hsq.resize((size_t)nc); hst.resize((size_t)nc); hlen.resize((size_t)nc); hts.resize((size_t)nc);
                 int64_t total = 0;
-                RC_TRY(ws->stageDownload(&total, (const int64_t*)ptotals + 1, sizeof(int64_t)));
+                if (!consumer) RC_TRY(ws->stageDownload(&total, (const int64_t*)ptotals + 1, sizeof(int64_t)));
                 RC_TRY(ws->stageDownload(hs.data(), ps, (size_t)nc * sizeof(int32_t)));
                 RC_TRY(ws->stageDownload(hi.data(), pi, (size_t)nc * sizeof(int32_t)));
                 RC_TRY(ws->stageDownload(hj.data(), pj, (size_t)nc * sizeof(int32_t)));
@@ -434,11 +470,13 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                 RC_TRY(ws->stageDownload(hlen.data(), plen, (size_t)nc * sizeof(int32_t)));
                 RC_TRY(ws->stageDownload(hts.data(), pts, (size_t)nc * sizeof(int32_t)));
                 RC_TRY(ws->finishDownloads());
-                if (total < 0 || total > nc * slotOps) return fail(MIOPAL_ERR_INTERNAL, "bad operation count");
-                const size_t at = outOps->size;
-                if (!outOps->resize(at + (size_t)total)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
-                RC_TRY(ws->stageDownload(outOps->data + at, pcompact, (size_t)total));
-                RC_TRY(ws->finishDownloads());
+                if (!consumer) {
+                    if (total < 0 || total > nc * slotOps) return fail(MIOPAL_ERR_INTERNAL, "bad operation count");
+                    const size_t at = outOps->size;
+                    if (!outOps->resize(at + (size_t)total)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+                    RC_TRY(ws->stageDownload(outOps->data + at, pcompact, (size_t)total));
+                    RC_TRY(ws->finishDownloads());
+                }
                 int64_t sum = 0;
                 for (int k = 0; k < nc; ++k) {
                     const int64_t p = order[(size_t)(ch.first + k)];
@@ -450,7 +488,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                     lensByPair[(size_t)p] = hlen[(size_t)k];
                     sum += hlen[(size_t)k];
                 }
-                if (sum != total) return fail(MIOPAL_ERR_INTERNAL, "operation offsets disagree with the device");
+                if (!consumer && sum != total) return fail(MIOPAL_ERR_INTERNAL, "operation offsets disagree with the device");
             }
             for (int k = 0; k < nc; ++k) {
                 const int64_t p = order[(size_t)(ch.first + k)];
@@ -466,7 +504,7 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
             g_lastPairRouting[3] += 1;
         }
     }
-    if (full) {
+    if (full && !consumer) {
         for (int64_t p = 0; p < nPairs; ++p) opsOff[p + 1] = opsOff[p] + lensByPair[(size_t)p];
         if ((size_t)opsOff[nPairs] != outOps->size) return fail(MIOPAL_ERR_INTERNAL, "operation offsets disagree with the device");
         if (!inPairOrder && outOps->size > 0) {

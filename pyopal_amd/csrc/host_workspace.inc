@@ -22,6 +22,9 @@ enum Slot {
     kColumnsState, kColumnsOut, kColumnsSkip,
     kPssmRows,     // miopalSearchPssm: the rows, [Q][A] ints
     kSplitState,   // column split of the one-strip Smith-Waterman kernel: a wavefront's DP state at the cut that starts its interval
+    // miopalProfileColumns (host_profile.inc): the multiple alignment and the tables, in the workspace the call holds
+    // throughout; a chunk's member indices, in the workspace that produced the chunk
+    kProfileMsa, kProfileTables, kProfileMember,
     kSlots
 };
 

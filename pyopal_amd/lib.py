@@ -925,6 +925,87 @@ class Aligner:
                                       self.gap_open, self.gap_extend, mode, algorithm)
         return self._pair_objects(out, mirror, [len(p) for p in pssms], pair_pssm, pair_target, mode)
 
+    def profile_columns(self, query, database: BaseDatabase, targets, *, algorithm: str = "sw", return_msa: bool = False,
+                        device: int = 0) -> "ProfileColumns":
+        """Extension: the query-anchored profile columns of ``query`` and the targets ``targets`` (include/miopal.h,
+        miopalProfileColumns) - the step between two rounds of an iterated profile search. ``query``: a sequence, or a
+        `Pssm` (the aligner's matrix is then not used); ``targets``: a sequence or array of integer target indices, any
+        order, repeats allowed - ``[h.target_index for h in hits]``. Every target is aligned as
+        ``align_pairs(..., mode="full")`` aligns it, the alignments are projected onto the query's positions, and the
+        letters per position are counted and weighted (Henikoff position-based weights) on the GPU in integers: only
+        the columns and one weight per member come back. Returns a `ProfileColumns`; ``return_msa=True`` also brings
+        the multiple alignment. An empty ``targets`` is the profile of the query alone and needs no device."""
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        if query is None:
+            raise TypeError("Argument 'query' must not be None")
+        if isinstance(query, Pssm):
+            if query.alphabet != database.alphabet:
+                raise ValueError("database and PSSM have different alphabets")
+            codes = query.consensus
+        else:
+            if database.alphabet != self.alphabet:
+                raise ValueError("database and score matrix have different alphabets")
+            codes = np.frombuffer(database.alphabet.encode(query), dtype=np.uint8)
+        targets = np.asarray(targets if len(targets) else np.zeros(0, dtype=np.int64))
+        if targets.ndim != 1 or not np.issubdtype(targets.dtype, np.integer):
+            raise ValueError("targets must be a sequence of integer target indices")
+        targets = targets.astype(np.int64, copy=False)
+        alphabet = database.alphabet
+        with database.lock.read:
+            if len(targets) and (targets.min() < 0 or targets.max() >= database._get_size()):
+                raise IndexError("target index outside the database")
+            if len(targets) == 0:
+                return ProfileColumns.of_query(codes, alphabet, return_msa)
+            if _capi.lib().miopalDeviceCount() < 1:
+                raise RuntimeError("no supported SIMD backend available")
+            mirror = database._device_mirror(device)
+            if isinstance(query, Pssm):
+                out = mirror.profile_columns_pssm(query.scores, codes, targets, self.gap_open, self.gap_extend, algorithm,
+                                                  return_msa)
+            else:
+                out = mirror.profile_columns(codes, _int_matrix_array(self._int_matrix), targets, self.gap_open,
+                                             self.gap_extend, algorithm, return_msa)
+        return ProfileColumns(out["counts"], out["weighted"], out["member_weights"], alphabet, codes, out["msa"])
+
+    def iterated_search(self, query, database: BaseDatabase, max_evalue: float, *, rounds: int = 3, algorithm: str = "sw",
+                        background=None, pseudocount: float = 10.0, exclude_z: float = 5.0, device: int = 0):
+        """Extension: an iterated profile search composed of the public steps. Round 1 is ``significant_hits(query)``;
+        every further round builds the next `Pssm` from the hits of the one before - `profile_columns` with the round's
+        query and its hit indices, then `Pssm.from_columns` with `matrix_lambda` of the aligner's matrix - and searches
+        with `significant_hits_pssm`. It stops when the set of hit indices repeats or after ``rounds`` searches.
+        ``background``: one frequency per letter; None: the residue composition of the database's sequences. Returns
+        ``(the SignificantHits of the last search, the last Pssm or None, the hit-index arrays of every round)``."""
+        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)):
+            raise TypeError(f"rounds must be an integer, not {type(rounds).__name__}")
+        if rounds < 1:
+            raise ValueError(f"rounds must be at least 1, got {rounds}")
+        kw = dict(algorithm=algorithm, exclude_z=exclude_z, device=device)
+        hits = self.significant_hits(query, database, max_evalue, **kw)
+        found = [np.array(sorted(h.target_index for h in hits.results), dtype=np.int64)]
+        if rounds == 1:
+            return hits, None, found
+        if background is None:
+            with database.lock.read:
+                residues = np.frombuffer(b"".join(database._get_encoded()), dtype=np.uint8)
+            background = np.bincount(residues, minlength=len(self.alphabet))[:len(self.alphabet)].astype(np.float64)
+        background = np.asarray(background, dtype=np.float64) / np.sum(background)
+        lam = matrix_lambda(self.scoring_matrix, background)
+        current, pssm = query, None
+        prior = Pssm.from_sequence(query, self.scoring_matrix)
+        while len(found) < rounds:
+            columns = self.profile_columns(current, database, found[-1], algorithm=algorithm, device=device)
+            pssm = Pssm.from_columns(columns, prior, background, lam, pseudocount=pseudocount)
+            hits = self.significant_hits_pssm(pssm, database, max_evalue, **kw)
+            found.append(np.array(sorted(h.target_index for h in hits.results), dtype=np.int64))
+            if any(np.array_equal(found[-1], earlier) for earlier in found[:-1]):
+                break
+            current = prior = pssm
+        return hits, pssm, found
+
     def top_hits_pssm(self, pssm: "Pssm", database: BaseDatabase, k: int = 10, *, mode: str = "score",
                       algorithm: str = "sw", min_score: typing.Optional[int] = None, start: int = 0,
                       end: int = UINT32_MAX, device: int = 0) -> typing.List[ScoreResult]:
@@ -1565,8 +1646,10 @@ class Pssm:
     letters (default: the protein alphabet). ``consensus``: the residue a position counts as when an alignment tells
     matches from mismatches - a string over the alphabet or ``Q`` residue codes (255: no residue, never a match);
     default: each row's best-scoring letter, the lowest index on ties. Kept as a read-only ``uint8`` array of
-    codes; `consensus_sequence` is its text. The numbers are the caller's: nothing here builds a PSSM from an
-    alignment (pseudocounts, background frequencies)."""
+    codes; `consensus_sequence` is its text. `from_columns` builds the next round's PSSM from the `ProfileColumns`
+    of a search's hits (position-based sequence weights, pseudocounts from the prior round, log-odds against a
+    background). Still out of scope: per-column reduced alignments as PSI-BLAST weights them, composition-based
+    statistics, insertion-aware profiles."""
 
     NO_RESIDUE = 255
     __slots__ = ("scores", "alphabet", "consensus")
@@ -1618,6 +1701,46 @@ class Pssm:
         table = _int_matrix_array(matrix.int_array()).reshape(len(alphabet), len(alphabet))
         return cls(table[codes], alphabet, codes)
 
+    @classmethod
+    def from_columns(cls, columns: "ProfileColumns", prior: "Pssm", background, lam: float, *,
+                     pseudocount: float = 10.0) -> "Pssm":
+        """The PSSM of the next round from the columns of this round's hits. ``prior``: a `Pssm` of the same length and
+        alphabet - the round's query, ``Pssm.from_sequence(...)`` in round 1; ``background``: one frequency ``p_a`` per
+        letter; ``lam``: the scale of the scores (`matrix_lambda`). In float64, with ``f = columns.frequencies()``,
+        ``alpha_i = max(k_i - 1, 0)`` (``k_i = columns.distinct``), ``beta = pseudocount``, ``g_ia = p_a exp(lam
+        prior[i][a])`` normalised over the letters with ``p_a > 0`` and ``q_ia = (alpha_i f_ia + beta g_ia) / (alpha_i +
+        beta)``: the new score is ``rint(ln(q_ia / p_a) / lam)``, clipped to int16. A letter with ``p_a == 0`` keeps the
+        prior's score, a position whose weighted row is empty the prior's row; the consensus is the prior's. A position
+        only the query covers has ``alpha = 0``: it keeps its prior row up to the normalisation."""
+        if not isinstance(columns, ProfileColumns):
+            raise TypeError(f"Argument 'columns' has incorrect type (expected ProfileColumns, got {type(columns).__name__})")
+        if not isinstance(prior, Pssm):
+            raise TypeError(f"Argument 'prior' has incorrect type (expected Pssm, got {type(prior).__name__})")
+        if prior.alphabet != columns.alphabet or len(prior) != len(columns):
+            raise ValueError("columns and prior differ in length or alphabet")
+        A = len(prior.alphabet)
+        p = np.asarray(background, dtype=np.float64)
+        if p.shape != (A,) or not np.all(np.isfinite(p)) or np.any(p < 0) or not np.any(p > 0):
+            raise ValueError(f"background must hold {A} frequencies, none negative, one positive at least")
+        lam, beta = float(lam), float(pseudocount)
+        if not (np.isfinite(lam) and lam > 0):
+            raise ValueError("lam must be finite and positive")
+        if not (np.isfinite(beta) and beta > 0):
+            raise ValueError("pseudocount must be finite and positive")
+        letters = p > 0
+        f = columns.frequencies()
+        alpha = np.maximum(columns.distinct.astype(np.float64) - 1.0, 0.0)[:, None]
+        g = np.zeros((len(prior), A), dtype=np.float64)
+        g[:, letters] = p[letters] * np.exp(lam * prior.scores[:, letters].astype(np.float64))
+        g /= g.sum(axis=1, keepdims=True) if len(prior) else 1.0
+        q = (alpha * f + beta * g) / (alpha + beta)
+        scores = np.array(prior.scores, dtype=np.int64)
+        fresh = np.rint(np.log(q[:, letters] / p[letters]) / lam)
+        scores[:, letters] = np.clip(fresh, -(2 ** 15), 2 ** 15 - 1).astype(np.int64)
+        empty = columns.weighted[:, :A].sum(axis=1) == 0
+        scores[empty] = prior.scores[empty]
+        return cls(scores, prior.alphabet, prior.consensus)
+
     @property
     def consensus_sequence(self) -> str:
         """The consensus as text; ``-`` where a position has no residue."""
@@ -1640,6 +1763,104 @@ class Pssm:
 
     def __repr__(self):
         return f"{type(self).__name__}(<{len(self)} x {len(self.alphabet)}>, consensus={self.consensus_sequence!r})"
+
+
+class ProfileColumns:
+    """What `Aligner.profile_columns` returns: the query-anchored columns of a query and its aligned targets
+    (include/miopal.h, miopalProfileColumns). With ``Q`` positions, ``A`` letters and ``n`` targets: ``counts`` and
+    ``weighted`` are int64 of shape ``(Q, A + 1)`` - per position the members that show letter ``a`` there, and the
+    sum of their weights; column ``A`` is the gap letter (a query position against a gap). ``member_weights``: int64,
+    ``n + 1`` Henikoff position-based weights in 32.32 fixed point (``WEIGHT_ONE`` is 1.0), the query first. ``msa``:
+    uint8 ``(n + 1, Q)`` - a letter, ``A`` for the gap, 255 where the member's alignment does not cover the position -
+    or None when it was not asked for. ``alphabet``; ``consensus``: the query's codes (255: no residue)."""
+
+    WEIGHT_ONE = _capi.MIOPAL_PROFILE_WEIGHT_ONE
+    UNCOVERED = _capi.PROFILE_UNCOVERED
+    __slots__ = ("counts", "weighted", "member_weights", "alphabet", "consensus", "msa")
+
+    def __init__(self, counts, weighted, member_weights, alphabet, consensus, msa=None):
+        if isinstance(alphabet, str):
+            alphabet = Alphabet(alphabet)
+        elif not isinstance(alphabet, Alphabet):
+            raise TypeError(f"expected str or Alphabet, found {type(alphabet).__name__}")
+        self.alphabet = alphabet
+        self.consensus = np.array(consensus, dtype=np.uint8).ravel()
+        shape = (len(self.consensus), len(alphabet) + 1)
+        self.counts = np.ascontiguousarray(counts, dtype=np.int64)
+        self.weighted = np.ascontiguousarray(weighted, dtype=np.int64)
+        if self.counts.shape != shape or self.weighted.shape != shape:
+            raise ValueError(f"counts and weighted must have shape {shape}")
+        self.member_weights = np.ascontiguousarray(member_weights, dtype=np.int64).ravel()
+        self.msa = None if msa is None else np.ascontiguousarray(msa, dtype=np.uint8)
+        if self.msa is not None and self.msa.shape != (len(self.member_weights), shape[0]):
+            raise ValueError("msa must hold one row per member and one entry per position")
+
+    @classmethod
+    def of_query(cls, codes, alphabet, return_msa: bool = False) -> "ProfileColumns":
+        """The profile of the query alone (no targets), in integers on the host: every position with a residue shows
+        one letter once, and the query's weight is one per such position."""
+        codes = np.array(codes, dtype=np.uint8).ravel()
+        A = len(alphabet)
+        at = np.flatnonzero(codes < A)
+        weight = len(at) * cls.WEIGHT_ONE
+        counts = np.zeros((len(codes), A + 1), dtype=np.int64)
+        weighted = np.zeros((len(codes), A + 1), dtype=np.int64)
+        counts[at, codes[at]] = 1
+        weighted[at, codes[at]] = weight
+        msa = np.where(codes < A, codes, cls.UNCOVERED).astype(np.uint8)[None, :] if return_msa else None
+        return cls(counts, weighted, [weight], alphabet, codes, msa)
+
+    @property
+    def distinct(self) -> np.ndarray:
+        """``k_i``: the letters (the gap is none) that occur at position ``i``."""
+        return np.count_nonzero(self.counts[:, :len(self.alphabet)], axis=1).astype(np.int64)
+
+    def frequencies(self) -> np.ndarray:
+        """``weighted[:, :A]`` normalised per position, float64; a position with nothing in it gives zeros."""
+        w = self.weighted[:, :len(self.alphabet)].astype(np.float64)
+        total = w.sum(axis=1, keepdims=True)
+        return np.divide(w, total, out=np.zeros_like(w), where=total > 0)
+
+    def __len__(self) -> int:
+        return len(self.consensus)
+
+    def __repr__(self):
+        return f"{type(self).__name__}(<{len(self)} x {len(self.alphabet) + 1}>, members={len(self.member_weights)})"
+
+
+def matrix_lambda(scoring_matrix, background) -> float:
+    """The scale of a scoring matrix under a background: the positive root ``lam`` of ``sum_ab p_a p_b exp(lam S_ab) =
+    1``, by bisection. ``scoring_matrix``: a `ScoringMatrix` or a name; ``background``: one frequency per letter
+    (normalised here). ValueError when the expected score is not negative or no entry between letters of positive
+    frequency is positive - there is no such root then."""
+    matrix = resolve_scoring_matrix(scoring_matrix, "found")
+    n = len(matrix.alphabet)
+    S = np.asarray(matrix.matrix, dtype=np.float64).reshape(n, n)
+    p = np.asarray(background, dtype=np.float64)
+    if p.shape != (n,) or not np.all(np.isfinite(p)) or np.any(p < 0) or not np.any(p > 0):
+        raise ValueError(f"background must hold {n} frequencies, none negative, one positive at least")
+    p = p / p.sum()
+    pp = np.outer(p, p)
+    held = pp > 0
+    if not np.sum(pp[held] * S[held]) < 0:
+        raise ValueError("the expected score under the background is not negative")
+    if not np.any(S[held] > 0):
+        raise ValueError("no positive score between letters of the background")
+
+    def excess(lam):
+        return float(np.sum(pp[held] * np.exp(lam * S[held]))) - 1.0
+    lo, hi = 0.0, 1.0
+    while excess(hi) <= 0:   # (convex, 0 at 0 with a negative slope, unbounded: positive from the root on)
+        lo, hi = hi, 2.0 * hi
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid == lo or mid == hi:
+            break
+        if excess(mid) <= 0:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
 
 
 class BatchResultArrays:
