@@ -165,6 +165,27 @@ struct EventPair {
     }
 };
 
+// Device memory and a stream of a call that runs without a handle (the test hooks of the selection kernels, the
+// handle's length bins while they are built): released on every way out
+struct DeviceBytes {
+    void* p = nullptr;
+    DeviceBytes() = default;
+    DeviceBytes(const DeviceBytes&) = delete;
+    DeviceBytes& operator=(const DeviceBytes&) = delete;
+    ~DeviceBytes() {
+        if (p) (void)hipFree(p);
+    }
+};
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream&) = delete;
+    OwnedStream& operator=(const OwnedStream&) = delete;
+    ~OwnedStream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
 struct PhaseTimer {
     bool on;
     double t0;
@@ -781,56 +802,67 @@ int miopalSearchFlat(MiopalDb* db, const unsigned char* query, int queryLength, 
     });
 }
 
-// miopalSearchFlat with a position-specific scoring matrix as the score source (include/miopal.h). The order of the
-// checks is deliberate and part of the header's contract: what needs no handle first, then the null handle, then what
-// depends on the handle (miopalAlignPairs' order; miopalSearch looks at the handle first). The codes are
-// miopalSearch's; only which error is reported when several arguments are bad differs. A caller without a device -
-// it cannot hold a handle - is still told what is wrong with its PSSM. None of the checks touches a device.
+// What the entry points that take a position-specific scoring matrix share (include/miopal.h). The order of their
+// checks is deliberate and part of the header's contract: what needs no handle first (checkBeforeHandle, then the entry
+// point's own refusals that need none: the consensus, alignments, k, the outputs, the fit, the cut), then the null
+// handle and what depends on the handle (checkHandle) - miopalAlignPairs' order; miopalSearch looks at the handle
+// first. The codes are miopalSearch's; only which error is reported when several arguments are bad differs. A caller
+// without a device - it cannot hold a handle - is still told what is wrong with its PSSM. None of the checks touches
+// a device. (Not validate()'s checks under another name: its messages differ.)
+// (no rows: an empty query has no scores; the score source still says "position-specific")
+static const int kNoRows[1] = {0};
+struct PssmQuery {
+    static int checkBeforeHandle(int mode, int searchType, int Q, const int* rowScores, int A) {
+        if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
+        if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
+            return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
+        if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
+        if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
+        if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+        return 0;
+    }
+    static int checkHandle(const MiopalDb* db, int A, int64_t start, int64_t end) {
+        if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
+        if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
+        if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
+        return 0;
+    }
+    // what the implementations get where a plain search has its matrix and its query. Without a consensus - score and
+    // end searches, every selection - each position is "no residue": the int32 kernels upload it with the rows and
+    // never read it.
+    PssmQuery(const int* rowScores, const unsigned char* consensus, int Q)
+        : rows_(Q > 0 ? rowScores : kNoRows), given(consensus), none(given ? 0 : (size_t)std::max(Q, 1), 255) {}
+    const int* rows() const { return rows_; }
+    const unsigned char* consensus() const { return given ? given : none.data(); }
+    const int* const rows_;
+    const unsigned char* const given;
+    const std::vector<unsigned char> none;
+};
+
+// miopalSearchFlat with a position-specific scoring matrix as the score source
 int miopalSearchPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
                      int gapOpen, int gapExt, int alphabetLength, int searchType, int mode,
                      int64_t start, int64_t end, int* score, int* endTarget, int* endQuery,
                      int* startTarget, int* startQuery, unsigned char** operations, int64_t* operationOffsets) {
     return guarded([&]() -> int {
     const int Q = queryLength, A = alphabetLength;
-    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
-    if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
-        return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
-    if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
-    if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
-    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    RC_TRY(PssmQuery::checkBeforeHandle(mode, searchType, Q, rowScores, A));
     const bool full = searchType == OPAL_SEARCH_ALIGNMENT;
     if (full && Q > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
     if (consensus)
         for (int i = 0; i < Q; ++i)
             if (consensus[i] >= A && consensus[i] != 255)
                 return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %d", consensus[i], i);
-    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
-    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
-    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
+    RC_TRY(PssmQuery::checkHandle(db, A, start, end));
     if (full && !operations) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null alignment outputs");
     if (operations) *operations = nullptr;
     if (end == start) return 0;
-    {
-        // miopalSearch's range check for its 32-bit kernels, with the extreme entries of the rows
-        ScoreModel m{gapOpen, gapExt, 0, 0};
-        if (Q > 0) {
-            m.maxScore = *std::max_element(rowScores, rowScores + (size_t)Q * A);
-            m.minScore = *std::min_element(rowScores, rowScores + (size_t)Q * A);
-        }
-        RC_TRY(checkInt32Range(m, Q, db->maxLen));
-    }
-    // (without a consensus - score and end searches - every position is "no residue": the kernels never read it)
-    std::vector<unsigned char> none;
-    if (!consensus) {
-        none.assign((size_t)std::max(Q, 1), 255);
-        consensus = none.data();
-    }
-    // (no rows: an empty query has no scores; the score source still says "position-specific")
-    static const int kNoRows[1] = {0};
+    RC_TRY(checkPssmRange(db, rowScores, Q, A, gapOpen, gapExt));
+    const PssmQuery pssm(rowScores, consensus, Q);
     HostBytes ops;
-    RC_TRY(searchImpl(db, consensus, Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, score, endTarget,
+    RC_TRY(searchImpl(db, pssm.consensus(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, score, endTarget,
                       endQuery, startTarget, startQuery, nullptr, nullptr, full ? &ops : nullptr,
-                      full ? operationOffsets : nullptr, Q > 0 ? rowScores : kNoRows));
+                      full ? operationOffsets : nullptr, pssm.rows()));
     if (full) {
         if (!ops.data && !ops.resize(0)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
         *operations = ops.release();
@@ -839,32 +871,21 @@ int miopalSearchPssm(MiopalDb* db, const int* rowScores, const unsigned char* co
     });
 }
 
-// miopalSearchTop with a position-specific scoring matrix as the score source: miopalSearchPssm's checks in its
-// order (no consensus: nothing is aligned), with the two refusals of the selection that need no handle - alignments,
-// k - among the first; then searchTopImpl with the rows where the matrix stands.
+// miopalSearchTop with a position-specific scoring matrix as the score source: the two refusals of the selection that
+// need no handle - alignments, k - before the handle; then searchTopImpl with the rows where the matrix stands.
 int miopalSearchPssmTop(MiopalDb* db, const int* rowScores, int queryLength, int gapOpen, int gapExt,
                         int alphabetLength, int searchType, int mode, int64_t start, int64_t end, int k, int minScore,
                         int* count, int64_t* targetIndex, int* score, int* endTarget, int* endQuery) {
     return guarded([&]() -> int {
     const int Q = queryLength, A = alphabetLength;
-    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
-    if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
-        return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
-    if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
-    if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
-    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    RC_TRY(PssmQuery::checkBeforeHandle(mode, searchType, Q, rowScores, A));
     if (searchType == OPAL_SEARCH_ALIGNMENT)
         return fail(OPAL_ERR_INVALID_MODE, "miopalSearchPssmTop: alignments are not selected on the device");
     if (k < 0 || k > MIOPAL_MAX_TOP) return fail(MIOPAL_ERR_BAD_ARGUMENT, "k = %d outside [0, %d]", k, MIOPAL_MAX_TOP);
-    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
-    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
-    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
-    // (no rows: an empty query has no scores; the score source still says "position-specific")
-    static const int kNoRows[1] = {0};
-    // (no consensus: every position is "no residue" - the int32 kernels upload it with the rows and never read it)
-    const std::vector<unsigned char> none((size_t)std::max(Q, 1), 255);
-    return searchTopImpl(db, none.data(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, k, minScore, 0, count,
-                         targetIndex, score, endTarget, endQuery, Q > 0 ? rowScores : kNoRows);
+    RC_TRY(PssmQuery::checkHandle(db, A, start, end));
+    const PssmQuery pssm(rowScores, nullptr, Q);
+    return searchTopImpl(db, pssm.consensus(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, k, minScore, 0,
+                         count, targetIndex, score, endTarget, endQuery, pssm.rows());
     });
 }
 
@@ -894,25 +915,15 @@ int miopalSearchPssmHits(MiopalDb* db, const int* rowScores, int queryLength, in
                          int64_t* count, int64_t** targetIndex, int** score, int** endTarget, int** endQuery) {
     return guarded([&]() -> int {
     const int Q = queryLength, A = alphabetLength;
-    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
-    if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
-        return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
-    if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
-    if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
-    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    RC_TRY(PssmQuery::checkBeforeHandle(mode, searchType, Q, rowScores, A));
     if (searchType == OPAL_SEARCH_ALIGNMENT)
         return fail(OPAL_ERR_INVALID_MODE, "miopalSearchPssmHits: alignments are not selected on the device");
     RC_TRY(checkHitsOutputs(searchType, count, targetIndex, score, endTarget, endQuery));
-    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
-    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
-    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
-    // (no rows: an empty query has no scores; the score source still says "position-specific")
-    static const int kNoRows[1] = {0};
-    // (no consensus: every position is "no residue" - the int32 kernels upload it with the rows and never read it)
-    const std::vector<unsigned char> none((size_t)std::max(Q, 1), 255);
+    RC_TRY(PssmQuery::checkHandle(db, A, start, end));
+    const PssmQuery pssm(rowScores, nullptr, Q);
     HitRows rows;
-    RC_TRY(searchHitsImpl(db, none.data(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, minScore, maxHits,
-                          &rows, Q > 0 ? rowScores : kNoRows));
+    RC_TRY(searchHitsImpl(db, pssm.consensus(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, minScore,
+                          maxHits, &rows, pssm.rows()));
     return finishHits(rows, searchType, maxHits, count, targetIndex, score, endTarget, endQuery);
     });
 }
@@ -967,29 +978,19 @@ int miopalSearchPssmSignificant(MiopalDb* db, const int* rowScores, int queryLen
                                 int64_t** targetIndex, int** score, int** endTarget, int** endQuery, double** evalue) {
     return guarded([&]() -> int {
     const int Q = queryLength, A = alphabetLength;
-    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
-    if (searchType < OPAL_SEARCH_SCORE || searchType > OPAL_SEARCH_ALIGNMENT)
-        return fail(OPAL_ERR_INVALID_MODE, "invalid search type %d", searchType);
-    if (Q < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad query length %d", Q);
-    if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
-    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    RC_TRY(PssmQuery::checkBeforeHandle(mode, searchType, Q, rowScores, A));
     if (searchType == OPAL_SEARCH_ALIGNMENT)
         return fail(OPAL_ERR_INVALID_MODE, "miopalSearchPssmSignificant: alignments are not selected on the device");
     RC_TRY(checkHitsOutputs(searchType, count, targetIndex, score, endTarget, endQuery));
     RC_TRY(checkSignificantArgs(fit, evalue));
     RC_TRY(checkEvalueCut(maxEvalue, excludeZ));
-    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
-    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
-    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
-    // (no rows: an empty query has no scores; the score source still says "position-specific")
-    static const int kNoRows[1] = {0};
-    // (no consensus: every position is "no residue" - the int32 kernels upload it with the rows and never read it)
-    const std::vector<unsigned char> none((size_t)std::max(Q, 1), 255);
+    RC_TRY(PssmQuery::checkHandle(db, A, start, end));
+    const PssmQuery pssm(rowScores, nullptr, Q);
     HitRows rows;
     std::vector<double> ev;
     SliceLengths lengths;
-    RC_TRY(searchSignificantImpl(db, none.data(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, maxEvalue,
-                                 excludeZ, maxHits, &lengths, fit, &rows, &ev, Q > 0 ? rowScores : kNoRows));
+    RC_TRY(searchSignificantImpl(db, pssm.consensus(), Q, gapOpen, gapExt, nullptr, A, searchType, mode, start, end, maxEvalue,
+                                 excludeZ, maxHits, &lengths, fit, &rows, &ev, pssm.rows()));
     return finishSignificant(rows, ev, searchType, maxHits, count, targetIndex, score, endTarget, endQuery, evalue);
     });
 }
@@ -1043,6 +1044,9 @@ int miopalTestSelectColumns(const int* score, const int* endTarget, const int* e
 // miopalAlignPairs with a list of position-specific scoring matrices as the score source: what needs no handle is
 // checked here, in miopalSearchPssm's order, then alignPairsImpl with the rows where the matrix stands, the
 // consensus where the queries stand and the row offsets where the query offsets stand.
+// (Its own checks, not PssmQuery's: the list's checks sit between the search type and the rows, the rows are counted
+// over the whole list, the filler consensus is indexed in the offsets' coordinates, and alignPairsImpl makes the
+// handle's checks with the pair list's. Only kNoRows is shared.)
 int miopalAlignPairsPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, const int64_t* rowOffsets,
                          int nPssms, const int32_t* pairPssm, const int64_t* pairTarget, int64_t nPairs, int gapOpen,
                          int gapExt, int alphabetLength, int searchType, int mode, int* score, int* endTarget,
@@ -1073,7 +1077,6 @@ int miopalAlignPairsPssm(MiopalDb* db, const int* rowScores, const unsigned char
         none.assign((size_t)(first + std::max<int64_t>(totalRows, 1)), 255);   // (indexed in the offsets' coordinates)
         consensus = none.data();
     }
-    static const int kNoRows[1] = {0};
     HostBytes ops;
     RC_TRY(alignPairsImpl(db, consensus, rowOffsets, nPssms, pairPssm, pairTarget, nPairs, gapOpen, gapExt, nullptr, A,
                           searchType, mode, score, endTarget, endQuery, startTarget, startQuery,
@@ -1103,7 +1106,9 @@ int miopalProfileColumns(MiopalDb* db, const unsigned char* query, int queryLeng
 }
 
 // ... with a position-specific scoring matrix: what needs no handle is checked here, in miopalAlignPairsPssm's order
-// (one PSSM of queryLength rows; an alignment search, so the consensus is required), then the same
+// (one PSSM of queryLength rows; an alignment search, so the consensus is required), then the same.
+// (Its own checks, not PssmQuery's: no search type, and the cap on the rows sits between the length and the rows;
+// profileColumnsImpl's pair list makes the handle's checks. Only kNoRows is shared.)
 int miopalProfileColumnsPssm(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
                              int gapOpen, int gapExt, int alphabetLength, int mode, const int64_t* targets,
                              int64_t nTargets, int64_t* counts, int64_t* weighted, int64_t* memberWeight,
@@ -1119,7 +1124,6 @@ int miopalProfileColumnsPssm(MiopalDb* db, const int* rowScores, const unsigned 
     for (int i = 0; i < Q; ++i)
         if (consensus[i] >= A && consensus[i] != 255)
             return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %d", consensus[i], i);
-    static const int kNoRows[1] = {0};
     return profileColumnsImpl(db, consensus, Q, gapOpen, gapExt, nullptr, A, mode, targets, nTargets, counts, weighted,
                               memberWeight, msa, Q > 0 ? rowScores : kNoRows);
     });

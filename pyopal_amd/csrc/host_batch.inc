@@ -51,6 +51,24 @@ void planBatchQuery(const unsigned char* query, int Q, int open, int ext, const 
     p.rows = R;
 }
 
+// Which rows of a chunk hold nothing: batchImpl's plan once more, for the sinks that select on a chunk's device rows
+// (a query that is no member of its chunk takes the single-query path; its row is never read). skip[r] is set for
+// the queries i0 + r, r < rows, that do; true if any is. `model`: the gaps and the matrix's extremes, found once per call.
+bool skippedRows(const unsigned char* queries, const int64_t* queryOffsets, int64_t i0, int rows, const ScoreModel& model,
+                 const int* matrix, int A, int searchType, int mode, int64_t maxLen, std::vector<int>* skip) {
+    skip->assign((size_t)rows, 0);
+    bool any = false;
+    for (int r = 0; r < rows; ++r) {
+        const int64_t i = i0 + r;
+        BatchPlan plan;
+        planBatchQuery(queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), model.open, model.ext, matrix,
+                       A, model.maxScore, model.minScore, searchType, mode, maxLen, &plan);
+        (*skip)[(size_t)r] = plan.rows == 0;
+        any = any || plan.rows == 0;
+    }
+    return any;
+}
+
 }  // namespace
 
 // the checks of miopalSearch, query by query (and the model and slice once when the list is empty)

@@ -119,41 +119,22 @@ static int searchBatchTargetTopImpl(MiopalDb* db, const unsigned char* queries, 
     RC_TRY(mine.acquireInternal());
     ColumnsFold fold{mine.ws, n, m, minScore, locate};
     RC_TRY(fold.begin());
-    // (the plan of batchImpl: a query that is no member of its chunk takes the single-query path)
-    const int maxScore = *std::max_element(matrix, matrix + A * A);
-    const int lowScore = *std::min_element(matrix, matrix + A * A);
+    ScoreModel model{open, ext, 0, 0};
+    scoreExtremes(matrix, (size_t)A * A, &model.maxScore, &model.minScore);
     BatchSink sink;
     sink.checkOutputs = [](bool) { return 0; };
     sink.chunk = [&](Workspace* ws, int64_t i0, int rows, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ) -> int {
         // rows of queries on the single-query path hold nothing: never read
-        std::vector<int32_t> skip((size_t)rows, 0);
-        bool any = false;
-        for (int r = 0; r < rows; ++r) {
-            const int64_t i = i0 + r;
-            BatchPlan plan;
-            planBatchQuery(queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext, matrix, A,
-                           maxScore, lowScore, searchType, mode, db->maxLen, &plan);
-            skip[(size_t)r] = plan.rows == 0;
-            any = any || plan.rows == 0;
-        }
+        std::vector<int> skip;
+        const bool any = skippedRows(queries, queryOffsets, i0, rows, model, matrix, A, searchType, mode, db->maxLen, &skip);
         return fold.fold(ws, nullptr, d_score, d_endI, d_endJ, i0, rows, any ? skip.data() : nullptr);
     };
     sink.single = [&](int i) -> int {
-        // searchTopImpl's score / end pass, the results left in the device slots of a workspace of its own
-        WorkspaceLease lease(db);
-        RC_TRY(lease.acquireInternal());
-        Workspace* ws = lease.ws;
-        Search s{db, ws, ws->stream, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext, A,
-                 searchType, mode, matrix, start, end, n};
-        RC_TRY(s.prepare());
-        void *ps, *pi = nullptr, *pj = nullptr;
-        RC_TRY(ws->get(kScore, (size_t)n * sizeof(int32_t), &ps));
-        if (locate) {
-            RC_TRY(ws->get(kEndI, (size_t)n * sizeof(int32_t), &pi));
-            RC_TRY(ws->get(kEndJ, (size_t)n * sizeof(int32_t), &pj));
-        }
-        RC_TRY(s.scorePass((int32_t*)ps, (int32_t*)pi, (int32_t*)pj));
-        return fold.fold(ws, &s, (int32_t*)ps, (int32_t*)pi, (int32_t*)pj, i, 1, nullptr);
+        // the score-row pass in a workspace of its own (ScoreRows sets the call's device once more: harmless)
+        ScoreRows rows(db, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext, matrix, nullptr,
+                       A, searchType, mode, start, end);
+        RC_TRY(rows.run());
+        return fold.fold(rows.ws, &rows.s, rows.d_score, rows.d_endI, rows.d_endJ, i, 1, nullptr);
     };
     RC_TRY(batchImpl(db, queries, queryOffsets, nQueries, open, ext, matrix, A, searchType, mode, start, end, sink));
     // nothing failed: the outputs are written from here on

@@ -47,6 +47,80 @@ struct HitRows {
     int64_t total() const { return rowOffset.back(); }
 };
 
+// The answer of a batch, collected piece by piece and put together as a CSR at the end (miopalSearchBatchHits,
+// miopalSearchBatchSignificant). Chunks and single-path queries arrive out of query order: one piece per chunk (queries
+// [first, first + rows)) or per single-path query (rows = 1), with one E-value per hit beside it in the significant form.
+struct HitPieces {
+    struct Piece {
+        int64_t first;
+        std::unique_ptr<HitRows> rows;
+        std::vector<double> ev;
+    };
+    std::vector<Piece> pieces;
+    std::vector<int64_t> counts;   // hits per query
+    int64_t maxHits, running = 0;
+    bool over = false;
+    HitArrays all;
+    double* allEv = nullptr;
+    HitPieces(int nQueries, int64_t maxHits_) : counts((size_t)nQueries, 0), maxHits(maxHits_) {}
+    HitPieces(const HitPieces&) = delete;
+    HitPieces& operator=(const HitPieces&) = delete;
+    ~HitPieces() { free(allEv); }
+    // the room left for a piece; once the bound is passed the later pieces are only counted
+    int64_t room() const { return over ? 0 : maxHits < 0 ? -1 : maxHits - running; }
+    void take(int64_t first, std::unique_ptr<HitRows> got, std::vector<double> ev = {}) {
+        const int nr = (int)got->rowOffset.size() - 1;
+        for (int r = 0; r < nr; ++r) counts[(size_t)(first + r)] += got->rowOffset[(size_t)r + 1] - got->rowOffset[(size_t)r];
+        running += got->total();
+        if (!got->written) over = true;
+        pieces.push_back(Piece{first, std::move(got), std::move(ev)});
+    }
+    // the arrays of the whole answer (none once the bound is passed): the one step of the end that can fail, made
+    // before any output is touched
+    int reserve(bool locate, bool withEvalues) {
+        if (over) return 0;
+        RC_TRY(all.alloc(running, locate));
+        if (withEvalues && running > 0) {
+            allEv = (double*)malloc(sizeof(double) * (size_t)running);
+            if (!allEv) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+        }
+        return 0;
+    }
+    // hitOffsets - also when there are too many hits - then the arrays, which change hands (evalue: null in the hits form)
+    int assemble(int nQueries, bool locate, int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget,
+                 int** endQuery, double** evalue) {
+        hitOffsets[0] = 0;
+        for (int i = 0; i < nQueries; ++i) hitOffsets[i + 1] = hitOffsets[i] + counts[(size_t)i];
+        if (over) return fail(MIOPAL_ERR_TOO_MANY_HITS, "%lld hits, maxHits = %lld", (long long)running, (long long)maxHits);
+        for (const Piece& piece : pieces) {
+            const HitRows& h = *piece.rows;
+            if (h.total() == 0) continue;
+            // (row by row: the hits of a single-path query lie between those of its neighbours in the chunk)
+            for (size_t r = 0; r + 1 < h.rowOffset.size(); ++r) {
+                const size_t from = (size_t)h.rowOffset[r], len = (size_t)(h.rowOffset[r + 1] - h.rowOffset[r]);
+                if (len == 0) continue;
+                const size_t at = (size_t)hitOffsets[piece.first + (int64_t)r];
+                memcpy(all.target + at, h.hits.target + from, sizeof(int64_t) * len);
+                memcpy(all.score + at, h.hits.score + from, sizeof(int) * len);
+                if (evalue) memcpy(allEv + at, piece.ev.data() + from, sizeof(double) * len);
+                if (locate) {
+                    memcpy(all.endT + at, h.hits.endT + from, sizeof(int) * len);
+                    memcpy(all.endQ + at, h.hits.endQ + from, sizeof(int) * len);
+                }
+            }
+        }
+        // (arrays the search type does not produce: NULL where the caller gave a place for them)
+        if (!locate && endTarget) *endTarget = nullptr;
+        if (!locate && endQuery) *endQuery = nullptr;
+        all.release(targetIndex, score, locate ? endTarget : nullptr, locate ? endQuery : nullptr);
+        if (evalue) {
+            *evalue = allEv;
+            allEv = nullptr;
+        }
+        return 0;
+    }
+};
+
 // the device slot of the written hits: [target] [score] ([endQuery] [endTarget])
 struct HitsOutSlot {
     size_t offScore, offEndQ, offEndT, bytes;
@@ -135,42 +209,21 @@ static int checkHitsOutputs(int searchType, const void* counts, int64_t** target
     return 0;
 }
 
-// One query: searchTopImpl's score / end pass - the results left in the workspace's device slots - then the selection
-// on the same stream. The caller has refused alignments and checked its outputs (after validate() for the plain
-// form, before the handle for the PSSM form: searchTopImpl's and miopalSearchPssmTop's orders).
+// One query: the score-row pass (ScoreRows, host_search.inc), then the selection on the same stream. The caller has
+// refused alignments and checked its outputs (after validate() for the plain form, before the handle for the PSSM
+// form: searchTopImpl's and miopalSearchPssmTop's orders). pssmRows: the range check of the rows (validate()'s place;
+// an empty slice has none) comes before `out` is touched.
 static int searchHitsImpl(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                           const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                           int64_t end, int minScore, int64_t room, HitRows* out, const int* pssmRows = nullptr) {
-    const bool locate = searchType == OPAL_SEARCH_SCORE_END;
     const int64_t n = end - start;
-    if (pssmRows && n > 0) {
-        // miopalSearch's range check for its 32-bit kernels, with the extreme entries of the rows (validate()'s place)
-        ScoreModel m{gapOpen, gapExt, 0, 0};
-        if (queryLength > 0) {
-            m.maxScore = *std::max_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
-            m.minScore = *std::min_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
-        }
-        RC_TRY(checkInt32Range(m, queryLength, db->maxLen));
-    }
+    if (pssmRows && n > 0) RC_TRY(checkPssmRange(db, pssmRows, queryLength, alphabetLength, gapOpen, gapExt));
     out->rowOffset.assign(2, 0);
     out->written = true;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(db->device));
-    WorkspaceLease lease(db);
-    RC_TRY(lease.acquireInternal());
-    Workspace* ws = lease.ws;
-    Search s{db, ws, ws->stream, query, queryLength, gapOpen, gapExt, alphabetLength, searchType, mode,
-             scoreMatrix, start, end, n};
-    s.pssmRows = pssmRows;
-    RC_TRY(s.prepare());
-    void *ps, *pi = nullptr, *pj = nullptr;
-    RC_TRY(ws->get(kScore, (size_t)n * sizeof(int32_t), &ps));
-    if (locate) {
-        RC_TRY(ws->get(kEndI, (size_t)n * sizeof(int32_t), &pi));
-        RC_TRY(ws->get(kEndJ, (size_t)n * sizeof(int32_t), &pj));
-    }
-    RC_TRY(s.scorePass((int32_t*)ps, (int32_t*)pi, (int32_t*)pj));
-    return selectHitRows(ws, &s, (int32_t*)ps, (int32_t*)pi, (int32_t*)pj, 1, n, start, &minScore, nullptr, room, out);
+    ScoreRows rows(db, query, queryLength, gapOpen, gapExt, scoreMatrix, pssmRows, alphabetLength, searchType, mode, start, end);
+    RC_TRY(rows.run());
+    return selectHitRows(rows.ws, &rows.s, rows.d_score, rows.d_endI, rows.d_endJ, 1, n, start, &minScore, nullptr, room, out);
 }
 
 // the end of miopalSearchHits / miopalSearchPssmHits: the count, and the arrays unless there are too many
@@ -202,81 +255,34 @@ static int searchBatchHitsImpl(MiopalDb* db, const unsigned char* queries, const
     if (nQueries > 0 && !minScore) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null minScore list");
     const bool locate = searchType == OPAL_SEARCH_SCORE_END;
     const int64_t n = end - start;
-    // one piece per chunk (queries [first, first + rows)) or per single-path query (rows = 1)
-    struct Piece {
-        int64_t first;
-        std::unique_ptr<HitRows> rows;
-    };
-    std::vector<Piece> pieces;
-    std::vector<int64_t> counts((size_t)nQueries, 0);
-    int64_t running = 0;
-    bool over = false;
-    // the room left for a piece; once the bound is passed the later pieces are only counted
-    auto room = [&]() -> int64_t { return over ? 0 : maxHits < 0 ? -1 : maxHits - running; };
-    auto taken = [&](int64_t first, std::unique_ptr<HitRows> got) {
-        const int nr = (int)got->rowOffset.size() - 1;
-        for (int r = 0; r < nr; ++r) counts[(size_t)(first + r)] += got->rowOffset[(size_t)r + 1] - got->rowOffset[(size_t)r];
-        running += got->total();
-        if (!got->written) over = true;
-        pieces.push_back(Piece{first, std::move(got)});
-    };
+    HitPieces pieces(nQueries, maxHits);
     if (n > 0 && nQueries > 0) {
-        // (the plan of batchImpl: a query that is no member of its chunk takes the single-query path)
-        const int maxScore = *std::max_element(matrix, matrix + A * A);
-        const int lowScore = *std::min_element(matrix, matrix + A * A);
+        ScoreModel model{open, ext, 0, 0};
+        scoreExtremes(matrix, (size_t)A * A, &model.maxScore, &model.minScore);
         BatchSink sink;
         sink.checkOutputs = [](bool) { return 0; };
         sink.chunk = [&](Workspace* ws, int64_t i0, int rows, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ) -> int {
             // rows of queries on the single-query path hold nothing: neither counted nor downloaded
-            std::vector<int> skip((size_t)rows, 0);
-            for (int r = 0; r < rows; ++r) {
-                const int64_t i = i0 + r;
-                BatchPlan plan;
-                planBatchQuery(queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext, matrix, A,
-                               maxScore, lowScore, searchType, mode, db->maxLen, &plan);
-                skip[(size_t)r] = plan.rows == 0;
-            }
+            std::vector<int> skip;
+            skippedRows(queries, queryOffsets, i0, rows, model, matrix, A, searchType, mode, db->maxLen, &skip);
             std::unique_ptr<HitRows> got(new HitRows());
-            RC_TRY(selectHitRows(ws, nullptr, d_score, d_endI, d_endJ, rows, n, start, minScore + i0, skip.data(), room(),
-                                 got.get()));
-            taken(i0, std::move(got));
+            RC_TRY(selectHitRows(ws, nullptr, d_score, d_endI, d_endJ, rows, n, start, minScore + i0, skip.data(),
+                                 pieces.room(), got.get()));
+            pieces.take(i0, std::move(got));
             return 0;
         };
         sink.single = [&](int i) -> int {
             std::unique_ptr<HitRows> got(new HitRows());
             RC_TRY(searchHitsImpl(db, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext,
-                                  matrix, A, searchType, mode, start, end, minScore[i], room(), got.get()));
-            taken(i, std::move(got));
+                                  matrix, A, searchType, mode, start, end, minScore[i], pieces.room(), got.get()));
+            pieces.take(i, std::move(got));
             return 0;
         };
         RC_TRY(batchImpl(db, queries, queryOffsets, nQueries, open, ext, matrix, A, searchType, mode, start, end, sink));
     }
     // nothing failed: the outputs are written from here on
-    HitArrays all;
-    if (!over) RC_TRY(all.alloc(running, locate));
-    hitOffsets[0] = 0;
-    for (int i = 0; i < nQueries; ++i) hitOffsets[i + 1] = hitOffsets[i] + counts[(size_t)i];
-    if (over) return fail(MIOPAL_ERR_TOO_MANY_HITS, "%lld hits, maxHits = %lld", (long long)running, (long long)maxHits);
-    for (const Piece& piece : pieces) {
-        const HitRows& h = *piece.rows;
-        if (h.total() == 0) continue;
-        // (row by row: the hits of a single-path query lie between those of its neighbours in the chunk)
-        for (size_t r = 0; r + 1 < h.rowOffset.size(); ++r) {
-            const size_t from = (size_t)h.rowOffset[r], len = (size_t)(h.rowOffset[r + 1] - h.rowOffset[r]);
-            if (len == 0) continue;
-            const size_t at = (size_t)hitOffsets[piece.first + (int64_t)r];
-            memcpy(all.target + at, h.hits.target + from, sizeof(int64_t) * len);
-            memcpy(all.score + at, h.hits.score + from, sizeof(int) * len);
-            if (locate) {
-                memcpy(all.endT + at, h.hits.endT + from, sizeof(int) * len);
-                memcpy(all.endQ + at, h.hits.endQ + from, sizeof(int) * len);
-            }
-        }
-    }
-    if (!locate && endTarget) *endTarget = nullptr;
-    if (!locate && endQuery) *endQuery = nullptr;
-    all.release(targetIndex, score, locate ? endTarget : nullptr, locate ? endQuery : nullptr);
-    return 0;
+    RC_TRY(pieces.reserve(locate, false));
+    return pieces.assemble(nQueries, locate, hitOffsets, targetIndex, score, endTarget, endQuery, nullptr);
 }
 
 // miopalTestSelectHits (test hook): the three kernels alone, on rows the caller supplies - launchHitsCount and

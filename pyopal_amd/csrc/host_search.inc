@@ -12,6 +12,12 @@ static inline bool smallSearchAllowed(const MiopalDb* db) {
     return !tuned(Tune::NO_SMALL_SEARCH);
 }
 
+// the extreme entries of a score source (a matrix, the rows of a PSSM); no entries: no scores, 0 and 0
+static inline void scoreExtremes(const int* entries, size_t count, int* maxScore, int* minScore) {
+    *maxScore = count ? *std::max_element(entries, entries + count) : 0;
+    *minScore = count ? *std::min_element(entries, entries + count) : 0;
+}
+
 // ---- one search ----------------------------------------------------------------
 struct Search {
     MiopalDb* db;
@@ -80,14 +86,9 @@ struct Search {
             faultSpinCap = g_fault[2];
             g_fault[0] = 0;
         }
-        if (pssmRows) {
-            // (the extreme entries of the rows where the matrix's stand; no rows: no scores, as for an empty query)
-            maxScore = Q > 0 ? *std::max_element(pssmRows, pssmRows + (size_t)Q * A) : 0;
-            minScore = Q > 0 ? *std::min_element(pssmRows, pssmRows + (size_t)Q * A) : 0;
-            return 0;
-        }
-        maxScore = *std::max_element(matrix, matrix + A * A);
-        minScore = *std::min_element(matrix, matrix + A * A);
+        // (the extreme entries of the rows where the matrix's stand; no rows: no scores, as for an empty query)
+        if (pssmRows) scoreExtremes(pssmRows, (size_t)std::max(Q, 0) * A, &maxScore, &minScore);
+        else scoreExtremes(matrix, (size_t)A * A, &maxScore, &minScore);
         return 0;
     }
 
@@ -1380,5 +1381,48 @@ struct Search {
         }
         jobs.insert(jobs.end(), sideJobs.begin(), sideJobs.end());
         return runPairs(jobs, false, d_score, d_endI, d_endJ, nullptr);
+    }
+};
+
+// miopalSearch's range check for its 32-bit kernels with the extreme entries of a PSSM's rows ([Q][A]) where the
+// matrix's stand: made by the PSSM entry points themselves, in validate()'s place and before any device call. The
+// plain forms have no such check in front of their score pass.
+static int checkPssmRange(const MiopalDb* db, const int* rows, int Q, int A, int open, int ext) {
+    ScoreModel m{open, ext, 0, 0};
+    scoreExtremes(rows, (size_t)std::max(Q, 0) * A, &m.maxScore, &m.minScore);
+    return checkInt32Range(m, Q, db->maxLen);
+}
+
+// The score-row pass of one query, for the entry points that select on the device: a workspace leased for the call,
+// the search, and searchImpl's score / end pass with the results left in the workspace's device slots (d_endI and
+// d_endJ: null without end locations). The selection is enqueued on ws->stream behind it - the score pass has joined
+// its side-stream jobs and flagged lanes into that stream - downloads on `ws` and checks s.d_stripError, so this
+// object outlives it. `matrix` or `pssmRows` is the score source (the other null; with rows, `query` is the consensus).
+struct ScoreRows {
+    WorkspaceLease lease;
+    Workspace* ws = nullptr;
+    Search s;
+    int32_t *d_score = nullptr, *d_endI = nullptr, *d_endJ = nullptr;
+    ScoreRows(MiopalDb* db, const unsigned char* query, int Q, int open, int ext, const int* matrix, const int* pssmRows,
+              int A, int searchType, int mode, int64_t start, int64_t end)
+        : lease(db), s{db, nullptr, nullptr, query, Q, open, ext, A, searchType, mode, matrix, start, end, end - start} {
+        s.pssmRows = pssmRows;
+    }
+    int run() {
+        HIP_TRY(hipSetDevice(s.db->device));
+        RC_TRY(lease.acquireInternal());
+        s.ws = ws = lease.ws;
+        s.stream = ws->stream;
+        RC_TRY(s.prepare());
+        void *ps, *pi = nullptr, *pj = nullptr;
+        RC_TRY(ws->get(kScore, (size_t)s.n * sizeof(int32_t), &ps));
+        if (s.searchType == OPAL_SEARCH_SCORE_END) {
+            RC_TRY(ws->get(kEndI, (size_t)s.n * sizeof(int32_t), &pi));
+            RC_TRY(ws->get(kEndJ, (size_t)s.n * sizeof(int32_t), &pj));
+        }
+        d_score = (int32_t*)ps;
+        d_endI = (int32_t*)pi;
+        d_endJ = (int32_t*)pj;
+        return s.scorePass(d_score, d_endI, d_endJ);
     }
 };

@@ -286,16 +286,8 @@ static int searchSignificantImpl(MiopalDb* db, const unsigned char* query, int q
                                  int64_t end, double maxEvalue, double excludeZ, int64_t room, SliceLengths* lengths,
                                  MiopalScoreFit* fit, HitRows* out, std::vector<double>* evalue,
                                  const int* pssmRows = nullptr) {
-    const bool locate = searchType == OPAL_SEARCH_SCORE_END;
     const int64_t n = end - start;
-    if (pssmRows && n > 0) {
-        ScoreModel m{gapOpen, gapExt, 0, 0};
-        if (queryLength > 0) {
-            m.maxScore = *std::max_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
-            m.minScore = *std::min_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
-        }
-        RC_TRY(checkInt32Range(m, queryLength, db->maxLen));
-    }
+    if (pssmRows && n > 0) RC_TRY(checkPssmRange(db, pssmRows, queryLength, alphabetLength, gapOpen, gapExt));
     out->rowOffset.assign(2, 0);
     out->written = true;
     evalue->clear();
@@ -303,24 +295,11 @@ static int searchSignificantImpl(MiopalDb* db, const unsigned char* query, int q
         emptyFit(fit);
         return 0;
     }
-    HIP_TRY(hipSetDevice(db->device));
-    WorkspaceLease lease(db);
-    RC_TRY(lease.acquireInternal());
-    Workspace* ws = lease.ws;
-    Search s{db, ws, ws->stream, query, queryLength, gapOpen, gapExt, alphabetLength, searchType, mode,
-             scoreMatrix, start, end, n};
-    s.pssmRows = pssmRows;
-    RC_TRY(s.prepare());
-    void *ps, *pi = nullptr, *pj = nullptr;
-    RC_TRY(ws->get(kScore, (size_t)n * sizeof(int32_t), &ps));
-    if (locate) {
-        RC_TRY(ws->get(kEndI, (size_t)n * sizeof(int32_t), &pi));
-        RC_TRY(ws->get(kEndJ, (size_t)n * sizeof(int32_t), &pj));
-    }
-    RC_TRY(s.scorePass((int32_t*)ps, (int32_t*)pi, (int32_t*)pj));
+    ScoreRows rows(db, query, queryLength, gapOpen, gapExt, scoreMatrix, pssmRows, alphabetLength, searchType, mode, start, end);
+    RC_TRY(rows.run());
     MiopalScoreFit got;
-    RC_TRY(significantRows(db, ws, &s, (int32_t*)ps, (int32_t*)pi, (int32_t*)pj, 1, n, start, lengths, &maxEvalue, excludeZ,
-                           nullptr, room, &got, out, evalue));
+    RC_TRY(significantRows(db, rows.ws, &rows.s, rows.d_score, rows.d_endI, rows.d_endJ, 1, n, start, lengths, &maxEvalue,
+                           excludeZ, nullptr, room, &got, out, evalue));
     *fit = got;
     return 0;
 }
@@ -364,93 +343,40 @@ static int searchBatchSignificantImpl(MiopalDb* db, const unsigned char* queries
     if (std::isnan(excludeZ)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "excludeZ is not a number");
     const bool locate = searchType == OPAL_SEARCH_SCORE_END;
     const int64_t n = end - start;
-    struct Piece {
-        int64_t first;
-        std::unique_ptr<HitRows> rows;
-        std::vector<double> ev;
-    };
-    std::vector<Piece> pieces;
-    std::vector<int64_t> counts((size_t)nQueries, 0);
+    HitPieces pieces(nQueries, maxHits);
     std::vector<MiopalScoreFit> got((size_t)nQueries);
     for (auto& f : got) emptyFit(&f);
     SliceLengths lengths;
-    int64_t running = 0;
-    bool over = false;
-    auto room = [&]() -> int64_t { return over ? 0 : maxHits < 0 ? -1 : maxHits - running; };
-    auto taken = [&](int64_t first, std::unique_ptr<HitRows> rows, std::vector<double>&& ev) {
-        const int nr = (int)rows->rowOffset.size() - 1;
-        for (int r = 0; r < nr; ++r) counts[(size_t)(first + r)] += rows->rowOffset[(size_t)r + 1] - rows->rowOffset[(size_t)r];
-        running += rows->total();
-        if (!rows->written) over = true;
-        pieces.push_back(Piece{first, std::move(rows), std::move(ev)});
-    };
     if (n > 0 && nQueries > 0) {
-        const int maxScore = *std::max_element(matrix, matrix + A * A);
-        const int lowScore = *std::min_element(matrix, matrix + A * A);
+        ScoreModel model{open, ext, 0, 0};
+        scoreExtremes(matrix, (size_t)A * A, &model.maxScore, &model.minScore);
         BatchSink sink;
         sink.checkOutputs = [](bool) { return 0; };
         sink.chunk = [&](Workspace* ws, int64_t i0, int rows, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ) -> int {
-            std::vector<int> skip((size_t)rows, 0);
-            for (int r = 0; r < rows; ++r) {
-                const int64_t i = i0 + r;
-                BatchPlan plan;
-                planBatchQuery(queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext, matrix, A,
-                               maxScore, lowScore, searchType, mode, db->maxLen, &plan);
-                skip[(size_t)r] = plan.rows == 0;
-            }
+            std::vector<int> skip;
+            skippedRows(queries, queryOffsets, i0, rows, model, matrix, A, searchType, mode, db->maxLen, &skip);
             std::unique_ptr<HitRows> rowsGot(new HitRows());
             std::vector<double> ev;
             RC_TRY(significantRows(db, ws, nullptr, d_score, d_endI, d_endJ, rows, n, start, &lengths, maxEvalue + i0, excludeZ,
-                                   skip.data(), room(), got.data() + i0, rowsGot.get(), &ev));
-            taken(i0, std::move(rowsGot), std::move(ev));
+                                   skip.data(), pieces.room(), got.data() + i0, rowsGot.get(), &ev));
+            pieces.take(i0, std::move(rowsGot), std::move(ev));
             return 0;
         };
         sink.single = [&](int i) -> int {
             std::unique_ptr<HitRows> rowsGot(new HitRows());
             std::vector<double> ev;
             RC_TRY(searchSignificantImpl(db, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open, ext,
-                                         matrix, A, searchType, mode, start, end, maxEvalue[i], excludeZ, room(), &lengths,
-                                         &got[(size_t)i], rowsGot.get(), &ev));
-            taken(i, std::move(rowsGot), std::move(ev));
+                                         matrix, A, searchType, mode, start, end, maxEvalue[i], excludeZ, pieces.room(),
+                                         &lengths, &got[(size_t)i], rowsGot.get(), &ev));
+            pieces.take(i, std::move(rowsGot), std::move(ev));
             return 0;
         };
         RC_TRY(batchImpl(db, queries, queryOffsets, nQueries, open, ext, matrix, A, searchType, mode, start, end, sink));
     }
-    // nothing failed: the outputs are written from here on
-    HitArrays all;
-    double* allEv = nullptr;
-    if (!over) {
-        RC_TRY(all.alloc(running, locate));
-        if (running > 0) {
-            allEv = (double*)malloc(sizeof(double) * (size_t)running);
-            if (!allEv) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
-        }
-    }
+    // nothing failed: the outputs are written from here on (the fits also when there are too many hits)
+    RC_TRY(pieces.reserve(locate, true));
     for (int i = 0; i < nQueries; ++i) fits[i] = got[(size_t)i];
-    hitOffsets[0] = 0;
-    for (int i = 0; i < nQueries; ++i) hitOffsets[i + 1] = hitOffsets[i] + counts[(size_t)i];
-    if (over) return fail(MIOPAL_ERR_TOO_MANY_HITS, "%lld hits, maxHits = %lld", (long long)running, (long long)maxHits);
-    for (const Piece& piece : pieces) {
-        const HitRows& h = *piece.rows;
-        if (h.total() == 0) continue;
-        for (size_t r = 0; r + 1 < h.rowOffset.size(); ++r) {
-            const size_t from = (size_t)h.rowOffset[r], len = (size_t)(h.rowOffset[r + 1] - h.rowOffset[r]);
-            if (len == 0) continue;
-            const size_t at = (size_t)hitOffsets[piece.first + (int64_t)r];
-            memcpy(all.target + at, h.hits.target + from, sizeof(int64_t) * len);
-            memcpy(all.score + at, h.hits.score + from, sizeof(int) * len);
-            memcpy(allEv + at, piece.ev.data() + from, sizeof(double) * len);
-            if (locate) {
-                memcpy(all.endT + at, h.hits.endT + from, sizeof(int) * len);
-                memcpy(all.endQ + at, h.hits.endQ + from, sizeof(int) * len);
-            }
-        }
-    }
-    if (!locate && endTarget) *endTarget = nullptr;
-    if (!locate && endQuery) *endQuery = nullptr;
-    all.release(targetIndex, score, locate ? endTarget : nullptr, locate ? endQuery : nullptr);
-    *evalue = allEv;
-    return 0;
+    return pieces.assemble(nQueries, locate, hitOffsets, targetIndex, score, endTarget, endQuery, evalue);
 }
 
 // miopalTestRowStats (test hook): length_bins_kernel and rows_stats_kernel alone, on rows the caller supplies -

@@ -111,11 +111,11 @@ static int selectTopRows(Workspace* ws, Search* s, const int32_t* d_score, const
     return 0;
 }
 
-// miopalSearchTop: searchImpl's score / end pass with the results left in the workspace's device slots, then the
-// selection on the same stream (the score pass has joined its side-stream jobs and flagged lanes into it).
-// Writes row `outRow` of the outputs.
+// miopalSearchTop: the score-row pass (ScoreRows, host_search.inc), then the selection on the same stream. Writes row
+// `outRow` of the outputs.
 // (pssmRows, miopalSearchPssmTop: the score source is [queryLength][alphabetLength] rows, as in searchImpl; scoreMatrix
-// is null, `query` a consensus of 255s - no alignment reads it - and the caller has made miopalSearchPssm's checks)
+// is null, `query` a consensus of 255s - no alignment reads it - and the caller has made miopalSearchPssm's checks;
+// the range check of the rows comes before "nothing to select", as validate() does for the plain form's arguments)
 static int searchTopImpl(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                          const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                          int64_t end, int k, int minScore, int64_t outRow, int* count, int64_t* targetIndex, int* score,
@@ -124,36 +124,15 @@ static int searchTopImpl(MiopalDb* db, const unsigned char* query, int queryLeng
     RC_TRY(checkTopArgs(searchType, k, count, targetIndex, score, endTarget, endQuery));
     const bool locate = searchType == OPAL_SEARCH_SCORE_END;
     const int64_t n = end - start;
-    if (pssmRows && n > 0) {
-        // miopalSearch's range check for its 32-bit kernels, with the extreme entries of the rows (validate()'s place)
-        ScoreModel m{gapOpen, gapExt, 0, 0};
-        if (queryLength > 0) {
-            m.maxScore = *std::max_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
-            m.minScore = *std::min_element(pssmRows, pssmRows + (size_t)queryLength * alphabetLength);
-        }
-        RC_TRY(checkInt32Range(m, queryLength, db->maxLen));
-    }
+    if (pssmRows && n > 0) RC_TRY(checkPssmRange(db, pssmRows, queryLength, alphabetLength, gapOpen, gapExt));
     if (k == 0 || n == 0) {
         emptyTopRows((int)outRow, (int)outRow + 1, k, count, targetIndex, score, locate ? endTarget : nullptr,
                      locate ? endQuery : nullptr);
         return 0;
     }
-    HIP_TRY(hipSetDevice(db->device));
-    WorkspaceLease lease(db);
-    RC_TRY(lease.acquireInternal());
-    Workspace* ws = lease.ws;
-    Search s{db, ws, ws->stream, query, queryLength, gapOpen, gapExt, alphabetLength, searchType, mode,
-             scoreMatrix, start, end, n};
-    s.pssmRows = pssmRows;
-    RC_TRY(s.prepare());
-    void *ps, *pi = nullptr, *pj = nullptr;
-    RC_TRY(ws->get(kScore, (size_t)n * sizeof(int32_t), &ps));
-    if (locate) {
-        RC_TRY(ws->get(kEndI, (size_t)n * sizeof(int32_t), &pi));
-        RC_TRY(ws->get(kEndJ, (size_t)n * sizeof(int32_t), &pj));
-    }
-    RC_TRY(s.scorePass((int32_t*)ps, (int32_t*)pi, (int32_t*)pj));
-    return selectTopRows(ws, &s, (int32_t*)ps, (int32_t*)pi, (int32_t*)pj, 1, n, start, k, minScore, outRow, count,
+    ScoreRows rows(db, query, queryLength, gapOpen, gapExt, scoreMatrix, pssmRows, alphabetLength, searchType, mode, start, end);
+    RC_TRY(rows.run());
+    return selectTopRows(rows.ws, &rows.s, rows.d_score, rows.d_endI, rows.d_endJ, 1, n, start, k, minScore, outRow, count,
                          targetIndex, score, endTarget, endQuery);
 }
 
@@ -191,27 +170,6 @@ static int searchBatchTopImpl(MiopalDb* db, const unsigned char* queries, const 
 // miopalTestSelectTop (test hook): the selection alone, on rows the caller supplies - launchSelectTop as selectTopRows
 // calls it (the same TopArgs, scratch from topScratchBytes, one stream), with no search and no handle in front of
 // it, so that a test can build a row for every arm of the five kernels. Device 0.
-namespace {
-struct DeviceBytes {
-    void* p = nullptr;
-    DeviceBytes() = default;
-    DeviceBytes(const DeviceBytes&) = delete;
-    DeviceBytes& operator=(const DeviceBytes&) = delete;
-    ~DeviceBytes() {
-        if (p) (void)hipFree(p);
-    }
-};
-struct OwnedStream {
-    hipStream_t s = nullptr;
-    OwnedStream() = default;
-    OwnedStream(const OwnedStream&) = delete;
-    OwnedStream& operator=(const OwnedStream&) = delete;
-    ~OwnedStream() {
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
-}  // namespace
-
 static int testSelectTopImpl(const int* score, const int* endTarget, const int* endQuery, int rows, int64_t stride, int k,
                              int minScore, int64_t start, int* count, int64_t* targetIndex, int* outScore,
                              int* outEndTarget, int* outEndQuery, int* gaveUp) {
