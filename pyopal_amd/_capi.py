@@ -130,131 +130,73 @@ def lib() -> ctypes.CDLL:
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         _share_hip_runtime()
         L = ctypes.CDLL(LIB_PATH)
-        c_int, c_i64, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+        c_int, c_i64, c_vp, c_dbl = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double
+        pp, p_i64 = ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)
         L.miopalDeviceCount.restype = c_int
         L.miopalLastError.restype = ctypes.c_char_p
-        L.miopalDbCreate.restype = c_int
-        L.miopalDbCreate.argtypes = [ctypes.POINTER(c_vp), c_vp, c_vp, c_i64, c_int, c_int]
-        L.miopalDbCreateFlat.restype = c_int
-        L.miopalDbCreateFlat.argtypes = [ctypes.POINTER(c_vp), c_vp, c_vp, c_i64, c_int, c_int]
-        L.miopalDbCreateSubset.restype = c_int
-        L.miopalDbCreateSubset.argtypes = [ctypes.POINTER(c_vp), c_vp, c_vp, c_i64]
-        L.miopalSelfTest.restype = c_int
-        L.miopalSelfTest.argtypes = [c_int]
-        L.miopalTestInjectFault.restype = None
-        L.miopalTestInjectFault.argtypes = [c_int, c_int, c_int]
-        L.miopalSetTuning.restype = c_int
-        L.miopalSetTuning.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-        L.miopalGetTuning.restype = ctypes.c_char_p
-        L.miopalGetTuning.argtypes = [ctypes.c_char_p]
-        L.miopalDbSetOption.restype = c_int
-        L.miopalDbSetOption.argtypes = [c_vp, ctypes.c_char_p, c_i64]
-        L.miopalTestSetLogicalDevices.restype = c_int
-        L.miopalTestSetLogicalDevices.argtypes = [c_int]
-        L.miopalDbDestroy.restype = None
-        L.miopalDbDestroy.argtypes = [c_vp]
-        for name in ("miopalDbCount", "miopalDbTotalLength", "miopalDbDeviceBytes", "miopalDbReleaseWorkspaces"):
-            getattr(L, name).restype = c_i64
-            getattr(L, name).argtypes = [c_vp]
-        L.miopalSearch.restype = c_int
-        L.miopalSearch.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                   c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.miopalSearchBatch.restype = c_int
-        L.miopalSearchBatch.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                        c_i64, c_i64, c_vp, c_vp, c_vp]
-        L.miopalSearchTop.restype = c_int
-        L.miopalSearchTop.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                      c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.miopalSearchBatchTop.restype = c_int
-        L.miopalSearchBatchTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                           c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.miopalTestSelectTop.restype = c_int
-        L.miopalTestSelectTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_i64,
-                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
-        pp = ctypes.POINTER(c_vp)
-        L.miopalSearchHits.restype = c_int
-        L.miopalSearchHits.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                       c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_i64), pp, pp, pp, pp]
-        L.miopalSearchPssmHits.restype = c_int
-        L.miopalSearchPssmHits.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                           c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_i64), pp, pp, pp, pp]
-        L.miopalSearchBatchHits.restype = c_int
-        L.miopalSearchBatchHits.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                            c_i64, c_i64, c_vp, c_i64, c_vp, pp, pp, pp, pp]
-        L.miopalTestSelectHits.restype = c_int
-        L.miopalTestSelectHits.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp, pp, pp, pp, pp]
-        c_dbl = ctypes.c_double
-        L.miopalSearchSignificant.restype = c_int
-        L.miopalSearchSignificant.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_i64, c_i64,
-                                              c_dbl, c_dbl, c_i64, c_vp, ctypes.POINTER(c_i64), pp, pp, pp, pp, pp]
-        L.miopalSearchPssmSignificant.restype = c_int
-        L.miopalSearchPssmSignificant.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64,
-                                                  c_dbl, c_dbl, c_i64, c_vp, ctypes.POINTER(c_i64), pp, pp, pp, pp, pp]
-        L.miopalSearchBatchSignificant.restype = c_int
-        L.miopalSearchBatchSignificant.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                                   c_i64, c_i64, c_vp, c_dbl, c_i64, c_vp, c_vp, pp, pp, pp, pp, pp]
-        L.miopalTestRowStats.restype = c_int
-        L.miopalTestRowStats.argtypes = [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.miopalTestSelectHitsBinned.restype = c_int
-        L.miopalTestSelectHitsBinned.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_i64, c_vp, pp, pp, pp, pp]
-        L.miopalSearchBatchTargetTop.restype = c_int
-        L.miopalSearchBatchTargetTop.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                                 c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.miopalTestSelectColumns.restype = c_int
-        L.miopalTestSelectColumns.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_vp, c_int, c_int,
-                                              c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.miopalAlignPairs.restype = c_int
-        L.miopalAlignPairs.argtypes = [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_int,
-                                       c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp]
-        L.miopalSearchPssmTop.restype = c_int
-        L.miopalSearchPssmTop.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                          c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.miopalAlignPairsPssm.restype = c_int
-        L.miopalAlignPairsPssm.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_int,
-                                           c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp]
-        L.miopalLastPairRouting.restype = None
-        L.miopalLastPairRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
-        L.miopalProfileColumns.restype = c_int
-        L.miopalProfileColumns.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_i64,
-                                           c_vp, c_vp, c_vp, c_vp]
-        L.miopalProfileColumnsPssm.restype = c_int
-        L.miopalProfileColumnsPssm.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64,
-                                               c_vp, c_vp, c_vp, c_vp]
-        L.miopalTestProfileColumns.restype = c_int
-        L.miopalTestProfileColumns.argtypes = [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]
-        L.miopalLastBatchRouting.restype = None
-        L.miopalLastBatchRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
-        L.miopalSearchFlat.restype = c_int
-        L.miopalSearchFlat.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                       c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                       ctypes.POINTER(c_vp), c_vp]
-        L.miopalSearchPssm.restype = c_int
-        L.miopalSearchPssm.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                       c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                       ctypes.POINTER(c_vp), c_vp]
-        L.miopalSearchFlatInto.restype = c_int
-        L.miopalSearchFlatInto.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int,
-                                           c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                           ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_vp]
-        L.miopalSearchDeviceScores.restype = c_int
-        L.miopalSearchDeviceScores.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int,
-                                               c_i64, c_i64, c_vp, c_vp]
-        L.miopalSetProfiling.restype = None
-        L.miopalSetProfiling.argtypes = [c_vp, c_int]
-        L.miopalReleaseCaches.restype = None
-        L.miopalReleaseCaches.argtypes = []
-        L.miopalLastFullRouting.restype = c_int
-        L.miopalLastFullRouting.argtypes = []
-        L.miopalLastRouting.restype = None
-        L.miopalLastRouting.argtypes = [ctypes.POINTER(ctypes.c_int64)]
-        L.miopalLastKernelTime.restype = c_int
-        L.miopalLastKernelTime.argtypes = [c_vp, ctypes.POINTER(ctypes.c_float)]
-        L.miopalSearchResults.restype = c_int
-        L.miopalSearchResults.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int,
-                                          c_int, c_int, c_i64, c_i64]
-        L.opalSearchDatabase.restype = c_int
-        L.opalSearchDatabase.argtypes = [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_int,
-                                         c_vp, c_int, c_int, c_int]
+        # (restype, argtypes) of everything else. The search entry points are made of a few pieces (include/miopal.h):
+        # the handle with one of three query sides, the slice, and what the family adds behind it.
+        one = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int]           # db, query, length, gapOpen, gapExt, matrix, A
+        pssm = [c_vp, c_vp, c_int, c_int, c_int, c_int]                # db, rows, length, gapOpen, gapExt, A
+        pssm_full = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int]     # db, rows, consensus, length, gapOpen, gapExt, A
+        batch = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int]   # db, queries, offsets, n, gapOpen, gapExt, matrix, A
+        middle = [c_int, c_int, c_i64, c_i64]                          # searchType, mode, start, end
+        pair_list = [c_vp, c_vp, c_i64]                                # pair queries, pair targets, pairs
+        flat = [c_vp] * 5 + [pp]                                       # score, endT, endQ, startT, startQ, operations
+        top = [c_int, c_int] + [c_vp] * 5                              # k, minScore, count, index, score, endT, endQ
+        found = [pp] * 4                                               # target, score, endT, endQ
+        columns = [c_int, c_vp, c_i64] + [c_vp] * 4                    # mode, targets, n, counts, weighted, weights, msa
+        rows = [c_vp, c_vp, c_vp, c_int, c_i64]                        # (test hooks) score, endT, endQ, rows, stride
+        table = {
+            "miopalDbCreate": (c_int, [pp, c_vp, c_vp, c_i64, c_int, c_int]),
+            "miopalDbCreateFlat": (c_int, [pp, c_vp, c_vp, c_i64, c_int, c_int]),
+            "miopalDbCreateSubset": (c_int, [pp, c_vp, c_vp, c_i64]),
+            "miopalDbDestroy": (None, [c_vp]),
+            "miopalDbCount": (c_i64, [c_vp]), "miopalDbTotalLength": (c_i64, [c_vp]),
+            "miopalDbDeviceBytes": (c_i64, [c_vp]), "miopalDbReleaseWorkspaces": (c_i64, [c_vp]),
+            "miopalDbSetOption": (c_int, [c_vp, ctypes.c_char_p, c_i64]),
+            "miopalSetTuning": (c_int, [ctypes.c_char_p, ctypes.c_char_p]),
+            "miopalGetTuning": (ctypes.c_char_p, [ctypes.c_char_p]),
+            "miopalSetProfiling": (None, [c_vp, c_int]),
+            "miopalReleaseCaches": (None, []),
+            "miopalLastFullRouting": (c_int, []),
+            "miopalLastRouting": (None, [p_i64]), "miopalLastPairRouting": (None, [p_i64]),
+            "miopalLastBatchRouting": (None, [p_i64]),
+            "miopalLastKernelTime": (c_int, [c_vp, ctypes.POINTER(ctypes.c_float)]),
+            "miopalSearch": (c_int, one + middle + [c_vp] * 7),
+            "miopalSearchFlat": (c_int, one + middle + flat + [c_vp]),
+            "miopalSearchFlatInto": (c_int, one + middle + flat + [p_i64, c_vp]),
+            "miopalSearchPssm": (c_int, pssm_full + middle + flat + [c_vp]),
+            "miopalSearchDeviceScores": (c_int, one + middle[1:] + [c_vp, c_vp]),
+            "miopalSearchBatch": (c_int, batch + middle + [c_vp] * 3),
+            "miopalSearchBatchTargetTop": (c_int, batch + middle + top),
+            "miopalAlignPairs": (c_int, batch[:4] + pair_list + batch[4:] + middle[:2] + flat + [c_vp]),
+            "miopalAlignPairsPssm": (c_int, [c_vp] * 4 + [c_int] + pair_list + pssm[3:] + middle[:2] + flat + [c_vp]),
+            "miopalProfileColumns": (c_int, one + columns),
+            "miopalProfileColumnsPssm": (c_int, pssm_full + columns),
+            "miopalSearchResults": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_i64, c_i64]),
+            "opalSearchDatabase": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int]),
+            # test hooks
+            "miopalSelfTest": (c_int, [c_int]),
+            "miopalTestInjectFault": (None, [c_int, c_int, c_int]),
+            "miopalTestSetLogicalDevices": (c_int, [c_int]),
+            "miopalTestSelectTop": (c_int, rows + [c_int, c_int, c_i64] + [c_vp] * 6),
+            "miopalTestSelectHits": (c_int, rows + [c_vp, c_i64, c_vp] + found),
+            "miopalTestSelectHitsBinned": (c_int, rows + [c_vp, c_vp, c_i64, c_vp] + found),
+            "miopalTestSelectColumns": (c_int, rows + [c_vp, c_vp, c_int, c_vp, c_int, c_int] + [c_vp] * 5),
+            "miopalTestRowStats": (c_int, [c_vp, c_int, c_i64] + [c_vp] * 5),
+            "miopalTestProfileColumns": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
+        }
+        # top / hits / significant of every query side: one row of outputs, or (Batch) a count per query and a CSR
+        for side, head in (("", one), ("Pssm", pssm), ("Batch", batch)):
+            table[f"miopalSearch{side}Top"] = (c_int, head + middle + top)
+            cut, counts = ([c_vp], [c_vp]) if side == "Batch" else ([c_int], [p_i64])
+            table[f"miopalSearch{side}Hits"] = (c_int, head + middle + cut + [c_i64] + counts + found)
+            cut = [c_vp, c_dbl] if side == "Batch" else [c_dbl, c_dbl]   # max E-value(s), exclude_z
+            table[f"miopalSearch{side}Significant"] = (c_int, head + middle + cut + [c_i64, c_vp] + counts + found + [pp])
+        for name, (restype, argtypes) in table.items():
+            getattr(L, name).restype = restype
+            getattr(L, name).argtypes = argtypes
         _lib = L
         _libc = ctypes.CDLL(None)
         _libc.free.argtypes = [c_vp]
@@ -356,7 +298,7 @@ def select_top_rows(score: np.ndarray, k: int, min_score: typing.Optional[int] =
         out.update(end_t=np.empty(shape, dtype=np.int32), end_q=np.empty(shape, dtype=np.int32))
     gave_up = ctypes.c_int(-1)
     rc = lib().miopalTestSelectTop(_ptr(score), _ptr(ends[1]), _ptr(ends[0]), rows, stride, k,
-                                   -(2 ** 31) if min_score is None else min_score, start, _ptr(out["count"]),
+                                   _floor(min_score), start, _ptr(out["count"]),
                                    _ptr(out["target"]), _ptr(out["score"]), _ptr(out.get("end_t")),
                                    _ptr(out.get("end_q")), ctypes.byref(gave_up))
     raise_for(rc)
@@ -550,7 +492,7 @@ def select_columns_rows(score: np.ndarray, m: int, min_score: typing.Optional[in
     if ends[0] is not None or ends[1] is not None:
         out.update(end_t=np.empty(shape, dtype=np.int32), end_q=np.empty(shape, dtype=np.int32))
     rc = lib().miopalTestSelectColumns(_ptr(score), _ptr(ends[1]), _ptr(ends[0]), rows, stride, _ptr(first), _ptr(counts),
-                                       len(pieces), _ptr(flags), m, -(2 ** 31) if min_score is None else min_score,
+                                       len(pieces), _ptr(flags), m, _floor(min_score),
                                        _ptr(out["count"]), _ptr(out["query"]), _ptr(out["score"]), _ptr(out.get("end_t")),
                                        _ptr(out.get("end_q")))
     raise_for(rc)
@@ -595,6 +537,45 @@ class _LazyAlignments:
     def __iter__(self):
         for k in range(len(self)):
             yield self[k]
+
+
+def _floor(min_score):
+    """``min_score`` as the C ABI takes it: INT_MIN stands for no bound"""
+    return -(2 ** 31) if min_score is None else min_score
+
+
+def _bound(max_hits):
+    """``max_hits`` as the C ABI takes it: -1 stands for no bound"""
+    return -1 if max_hits is None else max_hits
+
+
+def _packed(items, nothing):
+    """A list of arrays laid end to end along their first axis -> (flat, offsets); ``nothing``: what stands for
+    ``flat`` when there is not one entry in it."""
+    offsets = np.zeros(len(items) + 1, dtype=np.int64)
+    if items:
+        np.cumsum([len(q) for q in items], out=offsets[1:])
+    return (np.concatenate(items) if offsets[-1] else nothing), offsets
+
+
+def _pssm_rows(row_scores, alphabet_length, shape):
+    """the rows of a PSSM as the C ABI takes them; ``shape``: how the refusal of any other shape begins"""
+    rows = np.ascontiguousarray(row_scores, dtype=np.int32)
+    if rows.ndim != 2 or rows.shape[1] != alphabet_length:
+        raise ValueError(f"{shape}, {alphabet_length})")
+    return rows
+
+
+class _QuerySide(typing.NamedTuple):
+    """What a call searches with, as the C ABI takes it: a query with a matrix, a PSSM, or a list of queries with a
+    matrix (`DeviceDatabase._query_side`, `_pssm_side`, `_batch_side`)."""
+    name: str                       # "", "Pssm", "Batch": the C functions that take it are miopalSearch<name>...
+    queries: tuple                  # their arguments after the handle: (query, length) / (rows, [consensus,] length) /
+                                    # (queries, offsets, n) ...
+    scoring: tuple                  # ... and (gapOpen, gapExt, [matrix,] alphabet length)
+    rows: typing.Optional[int]      # None: one query, one row of outputs; else the queries: a row each, or a CSR
+    length: typing.Optional[int]    # of the one query
+    keep: tuple                     # the arrays the pointers point into
 
 
 class DeviceDatabase:
@@ -656,6 +637,38 @@ class DeviceDatabase:
         """Per-handle option (include/miopal.h, miopalDbSetOption): "reserve_cus", "small_search"."""
         raise_for(lib().miopalDbSetOption(self._h, name.encode(), int(value)))
 
+    def _clamp(self, end: typing.Optional[int]) -> int:
+        """the end of a slice: None is the end of the database, nothing reaches past it"""
+        return self.count if end is None else min(end, self.count)
+
+    # -- the query side of a call ---------------------------------------------------------------------------------
+    def _query_side(self, query, matrix, gap_open, gap_extend, null_when_empty=False) -> _QuerySide:
+        q = np.ascontiguousarray(query, dtype=np.uint8).ravel()
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        return _QuerySide("", (None if null_when_empty and not len(q) else _ptr(q), len(q)),
+                          (gap_open, gap_extend, _ptr(S), self.alphabet_length), None, len(q), (q, S))
+
+    def _pssm_side(self, row_scores, consensus, gap_open, gap_extend, with_consensus=False,
+                   shape="row_scores must have shape (query length",
+                   per_row="consensus must have one entry per row of row_scores") -> _QuerySide:
+        """``with_consensus``: the C function takes a consensus behind the rows (None: a null pointer)"""
+        rows = _pssm_rows(row_scores, self.alphabet_length, shape)
+        cons = None
+        if consensus is not None:
+            cons = np.ascontiguousarray(consensus, dtype=np.uint8).ravel()
+            if len(cons) != len(rows):
+                raise ValueError(per_row)
+        pointers = (_ptr(rows), _ptr(cons)) if len(rows) else (None, None)
+        return _QuerySide("Pssm", pointers[:2 if with_consensus else 1] + (len(rows),),
+                          (gap_open, gap_extend, self.alphabet_length), None, len(rows), (rows, cons))
+
+    def _batch_side(self, queries, matrix, gap_open, gap_extend) -> _QuerySide:
+        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
+        flat, offsets = _packed(qs, np.zeros(1, dtype=np.uint8))   # (a valid pointer for queries of length 0)
+        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        return _QuerySide("Batch", (_ptr(flat), _ptr(offsets), len(qs)),
+                          (gap_open, gap_extend, _ptr(S), self.alphabet_length), len(qs), None, (flat, offsets, S))
+
     def search(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
                mode: str = "score", algorithm: str = "sw", start: int = 0,
                end: typing.Optional[int] = None,
@@ -671,7 +684,7 @@ class DeviceDatabase:
         the earlier result goes: 1.3 ms of a 11.5-ms `full` search for the arrays, 17 of 113 ms for the
         operations of a 300-residue query). An operations buffer that is too small stays with the earlier
         result, untouched."""
-        end = self.count if end is None else min(end, self.count)
+        end = self._clamp(end)
         q = np.ascontiguousarray(query, dtype=np.uint8)
         S = np.ascontiguousarray(matrix, dtype=np.int32)
 
@@ -746,24 +759,14 @@ class DeviceDatabase:
         ``row_scores``: integers of shape (query length, alphabet length), entry [i, t] the score of query position
         i against target residue t. ``consensus``: one residue per position (or 255, "never a match"); only mode
         "full" reads it, to tell matches from mismatches, and requires it. Returns `search`'s dict."""
-        end = self.count if end is None else min(end, self.count)
-        n = max(end - start, 0)
-        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
-        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
-            raise ValueError(f"row_scores must have shape (query length, {self.alphabet_length})")
-        cons = None
-        if consensus is not None:
-            cons = np.ascontiguousarray(consensus, dtype=np.uint8).ravel()
-            if len(cons) != len(rows):
-                raise ValueError("consensus must have one entry per row of row_scores")
+        end = self._clamp(end)
+        side = self._pssm_side(row_scores, consensus, gap_open, gap_extend, with_consensus=True)
 
         def call(st, score, et, eq, s_t, s_q, ops_ptr, ops_cap, aoff):
             # (no lending form of this entry point: nothing is reused, the operations come in a buffer of their own)
-            return lib().miopalSearchPssm(self._h, _ptr(rows) if len(rows) else None,
-                                          _ptr(cons) if cons is not None and len(cons) else None, len(rows), gap_open,
-                                          gap_extend, self.alphabet_length, st, MODE[algorithm], start, end,
+            return lib().miopalSearchPssm(self._h, *side.queries, *side.scoring, st, MODE[algorithm], start, end,
                                           score, et, eq, s_t, s_q, ctypes.byref(ops_ptr), aoff)
-        return self._flat_search(call, mode, n)
+        return self._flat_search(call, mode, max(end - start, 0))
 
     def search_batch(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
                      gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
@@ -771,36 +774,89 @@ class DeviceDatabase:
         """miopalSearchBatch: every query (encoded residues) against the slice [start, end). Returns 2-D int32
         arrays of shape (len(queries), end - start): "score", and for mode "end" also "end_t" / "end_q"; row i
         equals search(queries[i], ...). Mode "full" is refused (OPAL_ERR_INVALID_MODE)."""
-        end = self.count if end is None else min(end, self.count)
-        n = max(end - start, 0)
-        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
-        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
-        if qs:
-            np.cumsum([len(q) for q in qs], out=offsets[1:])
-        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
-        if flat.size == 0:
-            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
-        st = SEARCH[mode]
-        out = {"score": np.empty((len(qs), n), dtype=np.int32)}
-        et = eq = None
-        if st >= 1:
-            et = np.empty((len(qs), n), dtype=np.int32)
-            eq = np.empty((len(qs), n), dtype=np.int32)
-        rc = lib().miopalSearchBatch(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
-                                     self.alphabet_length, st, MODE[algorithm], start, end, _ptr(out["score"]),
-                                     _ptr(et), _ptr(eq))
+        end = self._clamp(end)
+        side = self._batch_side(queries, matrix, gap_open, gap_extend)
+        shape = (side.rows, max(end - start, 0))
+        out = {"score": np.empty(shape, dtype=np.int32)}
+        if SEARCH[mode] >= 1:
+            out.update(end_t=np.empty(shape, dtype=np.int32), end_q=np.empty(shape, dtype=np.int32))
+        rc = lib().miopalSearchBatch(self._h, *side.queries, *side.scoring, SEARCH[mode], MODE[algorithm], start, end,
+                                     _ptr(out["score"]), _ptr(out.get("end_t")), _ptr(out.get("end_q")))
         raise_for(rc)
-        if st >= 1:
-            out.update(end_t=et, end_q=eq)
         return out
 
-    def _top_outputs(self, rows, k, mode):
-        shape = (k,) if rows is None else (rows, k)
-        out = {"count": np.zeros(1 if rows is None else rows, dtype=np.int32),
+    # -- top / hits / significant: one body per family, the query side an argument --------------------------------
+    def _search_top(self, side: _QuerySide, mode, algorithm, start, end, k, min_score) -> typing.Dict[str, typing.Any]:
+        shape = (k,) if side.rows is None else (side.rows, k)
+        out = {"count": np.zeros(1 if side.rows is None else side.rows, dtype=np.int32),
                "target": np.empty(shape, dtype=np.int64), "score": np.empty(shape, dtype=np.int32)}
         if mode == "end":
             out.update(end_t=np.empty(shape, dtype=np.int32), end_q=np.empty(shape, dtype=np.int32))
+        rc = getattr(lib(), f"miopalSearch{side.name}Top")(
+            self._h, *side.queries, *side.scoring, SEARCH[mode], MODE[algorithm], start, self._clamp(end), k,
+            _floor(min_score), _ptr(out["count"]), _ptr(out["target"]), _ptr(out["score"]), _ptr(out.get("end_t")),
+            _ptr(out.get("end_q")))
+        raise_for(rc)
+        if side.rows is None:
+            out["count"] = int(out["count"][0])
+        return out
+
+    def _search_hits(self, side: _QuerySide, mode, algorithm, start, end, min_score, max_hits):
+        single = side.rows is None
+        if single:
+            cut = _floor(min_score)
+        else:
+            thresholds = np.ascontiguousarray(np.broadcast_to(np.asarray(_floor(min_score), dtype=np.int32), (side.rows,)))
+            cut = _ptr(thresholds) if side.rows else None
+        counts = ctypes.c_int64(-1) if single else np.zeros(side.rows + 1, dtype=np.int64)
+        ptrs = _HitPointers()
+        rc = getattr(lib(), f"miopalSearch{side.name}Hits")(
+            self._h, *side.queries, *side.scoring, SEARCH[mode], MODE[algorithm], start, self._clamp(end), cut,
+            _bound(max_hits), ctypes.byref(counts) if single else _ptr(counts), *ptrs.refs())
+        return self._found(rc, counts, ptrs, mode)
+
+    def _search_significant(self, side: _QuerySide, mode, algorithm, start, end, max_evalue, exclude_z, max_hits):
+        # what the C side refuses, refused before it is reached: a cut that is not finite and positive, a NaN
+        cuts = np.atleast_1d(np.asarray(max_evalue, dtype=np.float64))
+        if not np.all(np.isfinite(cuts)) or not np.all(cuts > 0):
+            raise ValueError("max_evalue must be finite and positive")
+        if np.isnan(float(exclude_z)):
+            raise ValueError("exclude_z must not be NaN")
+        single = side.rows is None
+        if single:
+            cut = float(max_evalue)
+        else:
+            cuts = np.ascontiguousarray(np.broadcast_to(cuts, (side.rows,)))
+            cut = _ptr(cuts) if side.rows else None
+        fits = (ScoreFit * max(side.rows or 1, 1))()
+        fit = {"fit": fits[0]} if single else {"fits": [fits[i] for i in range(side.rows)]}
+        counts = ctypes.c_int64(-1) if single else np.zeros(side.rows + 1, dtype=np.int64)
+        ptrs, ev = _HitPointers(), ctypes.c_void_p()
+        rc = getattr(lib(), f"miopalSearch{side.name}Significant")(
+            self._h, *side.queries, *side.scoring, SEARCH[mode], MODE[algorithm], start, self._clamp(end), cut,
+            float(exclude_z), _bound(max_hits), ctypes.addressof(fits), ctypes.byref(counts) if single else _ptr(counts),
+            *ptrs.refs(), ctypes.byref(ev))
+        out = self._found(rc, counts, ptrs, mode, fit)
+        out["evalue"] = _take_malloced(ev, len(out["target"]), np.float64)
+        out.update(fit)
+        if not single:
+            out["_fits_owner"] = fits
+        return out
+
+    @staticmethod
+    def _found(rc, counts, ptrs, mode, fit=None) -> typing.Dict[str, typing.Any]:
+        """What a hit search found. One query (``counts`` a c_int64): "count" and the arrays; a list (``counts`` the
+        offsets): the CSR with "offsets". TooManyHits carries the count or the offsets as ``counts``, and the fit(s) of
+        a significance search as ``fit`` / ``fits``."""
+        single = isinstance(counts, ctypes.c_int64)
+        found = int(counts.value) if single else counts
+        if rc == MIOPAL_ERR_TOO_MANY_HITS:
+            err = TooManyHits(f"more hits than max_hits (code={rc}): {last_error()}", found)
+            vars(err).update(fit or {})
+            raise err
+        raise_for(rc)
+        out = {"count": found} if single else {"offsets": found}
+        out.update(ptrs.arrays(found if single else int(found[-1]), mode == "end"))
         return out
 
     def search_top(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
@@ -810,18 +866,7 @@ class DeviceDatabase:
         "target" (int64, absolute indices), "score" and for mode "end" "end_t" / "end_q", arrays of shape (k,):
         best first (score descending, index ascending), -1 past the count. ``min_score``: only targets scoring at
         least that many count (None: no bound). Mode "full" is refused (OPAL_ERR_INVALID_MODE)."""
-        end = self.count if end is None else min(end, self.count)
-        q = np.ascontiguousarray(query, dtype=np.uint8)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
-        out = self._top_outputs(None, k, mode)
-        rc = lib().miopalSearchTop(self._h, _ptr(q), len(q), gap_open, gap_extend, _ptr(S), self.alphabet_length,
-                                   SEARCH[mode], MODE[algorithm], start, end, k,
-                                   -(2 ** 31) if min_score is None else min_score, _ptr(out["count"]),
-                                   _ptr(out["target"]), _ptr(out["score"]), _ptr(out.get("end_t")),
-                                   _ptr(out.get("end_q")))
-        raise_for(rc)
-        out["count"] = int(out["count"][0])
-        return out
+        return self._search_top(self._query_side(query, matrix, gap_open, gap_extend), mode, algorithm, start, end, k, min_score)
 
     def search_pssm_top(self, row_scores: np.ndarray, gap_open: int = 3, gap_extend: int = 1, mode: str = "score",
                         algorithm: str = "sw", start: int = 0, end: typing.Optional[int] = None, k: int = 10,
@@ -829,19 +874,7 @@ class DeviceDatabase:
         """miopalSearchPssmTop: `search_top` with a position-specific scoring matrix (``row_scores`` as in
         `search_pssm`) in the place of (query, matrix). Returns `search_top`'s dict; entry i equals what
         `search_pssm` gives for ``target[i]``."""
-        end = self.count if end is None else min(end, self.count)
-        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
-        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
-            raise ValueError(f"row_scores must have shape (query length, {self.alphabet_length})")
-        out = self._top_outputs(None, k, mode)
-        rc = lib().miopalSearchPssmTop(self._h, _ptr(rows) if len(rows) else None, len(rows), gap_open, gap_extend,
-                                       self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end, k,
-                                       -(2 ** 31) if min_score is None else min_score, _ptr(out["count"]),
-                                       _ptr(out["target"]), _ptr(out["score"]), _ptr(out.get("end_t")),
-                                       _ptr(out.get("end_q")))
-        raise_for(rc)
-        out["count"] = int(out["count"][0])
-        return out
+        return self._search_top(self._pssm_side(row_scores, None, gap_open, gap_extend), mode, algorithm, start, end, k, min_score)
 
     def search_batch_top(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
                          gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
@@ -849,23 +882,7 @@ class DeviceDatabase:
                          min_score: typing.Optional[int] = None) -> typing.Dict[str, np.ndarray]:
         """miopalSearchBatchTop: search_top of every query in one batched call. "count" has one entry per query;
         the other arrays have shape (len(queries), k); row i equals search_top(queries[i], ...)."""
-        end = self.count if end is None else min(end, self.count)
-        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
-        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
-        if qs:
-            np.cumsum([len(q) for q in qs], out=offsets[1:])
-        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
-        if flat.size == 0:
-            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
-        out = self._top_outputs(len(qs), k, mode)
-        rc = lib().miopalSearchBatchTop(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
-                                        self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end, k,
-                                        -(2 ** 31) if min_score is None else min_score, _ptr(out["count"]),
-                                        _ptr(out["target"]), _ptr(out["score"]), _ptr(out.get("end_t")),
-                                        _ptr(out.get("end_q")))
-        raise_for(rc)
-        return out
+        return self._search_top(self._batch_side(queries, matrix, gap_open, gap_extend), mode, algorithm, start, end, k, min_score)
 
     def search_hits(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
                     mode: str = "score", algorithm: str = "sw", start: int = 0, end: typing.Optional[int] = None,
@@ -876,25 +893,7 @@ class DeviceDatabase:
         "end" "end_t" / "end_q", arrays of count entries that own the buffers the library allocated. With more than
         ``max_hits`` hits (None: no bound): TooManyHits, its ``counts`` the number of hits. Mode "full" is refused
         (OPAL_ERR_INVALID_MODE)."""
-        end = self.count if end is None else min(end, self.count)
-        q = np.ascontiguousarray(query, dtype=np.uint8)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
-        count = ctypes.c_int64(-1)
-        ptrs = _HitPointers()
-        rc = lib().miopalSearchHits(self._h, _ptr(q), len(q), gap_open, gap_extend, _ptr(S), self.alphabet_length,
-                                    SEARCH[mode], MODE[algorithm], start, end,
-                                    -(2 ** 31) if min_score is None else min_score, -1 if max_hits is None else max_hits,
-                                    ctypes.byref(count), *ptrs.refs())
-        return self._hits_result(rc, int(count.value), ptrs, mode)
-
-    @staticmethod
-    def _hits_result(rc, count, ptrs, mode):
-        if rc == MIOPAL_ERR_TOO_MANY_HITS:
-            raise TooManyHits(f"more hits than max_hits (code={rc}): {last_error()}", count)
-        raise_for(rc)
-        out = {"count": count}
-        out.update(ptrs.arrays(count, mode == "end"))
-        return out
+        return self._search_hits(self._query_side(query, matrix, gap_open, gap_extend), mode, algorithm, start, end, min_score, max_hits)
 
     def search_pssm_hits(self, row_scores: np.ndarray, gap_open: int = 3, gap_extend: int = 1, mode: str = "score",
                          algorithm: str = "sw", start: int = 0, end: typing.Optional[int] = None,
@@ -903,17 +902,7 @@ class DeviceDatabase:
         """miopalSearchPssmHits: `search_hits` with a position-specific scoring matrix (``row_scores`` as in
         `search_pssm`) in the place of (query, matrix). Returns `search_hits`' dict; hit i equals what `search_pssm`
         gives for ``target[i]``."""
-        end = self.count if end is None else min(end, self.count)
-        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
-        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
-            raise ValueError(f"row_scores must have shape (query length, {self.alphabet_length})")
-        count = ctypes.c_int64(-1)
-        ptrs = _HitPointers()
-        rc = lib().miopalSearchPssmHits(self._h, _ptr(rows) if len(rows) else None, len(rows), gap_open, gap_extend,
-                                        self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end,
-                                        -(2 ** 31) if min_score is None else min_score,
-                                        -1 if max_hits is None else max_hits, ctypes.byref(count), *ptrs.refs())
-        return self._hits_result(rc, int(count.value), ptrs, mode)
+        return self._search_hits(self._pssm_side(row_scores, None, gap_open, gap_extend), mode, algorithm, start, end, min_score, max_hits)
 
     def search_batch_hits(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
                           gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
@@ -923,40 +912,9 @@ class DeviceDatabase:
         query, or None. Returns a CSR: "offsets" (len(queries) + 1,) and "target", "score" (and "end_t" / "end_q") of
         offsets[-1] entries; entries offsets[i]:offsets[i + 1] equal search_hits(queries[i], ...). ``max_hits`` bounds
         the total; TooManyHits carries the offsets in ``counts``."""
-        end = self.count if end is None else min(end, self.count)
-        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
-        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
-        if qs:
-            np.cumsum([len(q) for q in qs], out=offsets[1:])
-        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
-        if flat.size == 0:
-            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
-        thresholds = np.ascontiguousarray(np.broadcast_to(
-            np.asarray(-(2 ** 31) if min_score is None else min_score, dtype=np.int32), (len(qs),)))
-        hit_offsets = np.zeros(len(qs) + 1, dtype=np.int64)
-        ptrs = _HitPointers()
-        rc = lib().miopalSearchBatchHits(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
-                                         self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end,
-                                         _ptr(thresholds) if len(qs) else None, -1 if max_hits is None else max_hits,
-                                         _ptr(hit_offsets), *ptrs.refs())
-        if rc == MIOPAL_ERR_TOO_MANY_HITS:
-            raise TooManyHits(f"more hits than max_hits (code={rc}): {last_error()}", hit_offsets)
-        raise_for(rc)
-        out = {"offsets": hit_offsets}
-        out.update(ptrs.arrays(int(hit_offsets[-1]), mode == "end"))
-        return out
+        return self._search_hits(self._batch_side(queries, matrix, gap_open, gap_extend), mode, algorithm, start, end, min_score, max_hits)
 
     select_hits_rows = staticmethod(select_hits_rows)
-
-    @staticmethod
-    def _check_evalue_cut(max_evalue, exclude_z):
-        """what the C side refuses, refused before it is reached: a cut that is not finite and positive, a NaN"""
-        cuts = np.atleast_1d(np.asarray(max_evalue, dtype=np.float64))
-        if not np.all(np.isfinite(cuts)) or not np.all(cuts > 0):
-            raise ValueError("max_evalue must be finite and positive")
-        if np.isnan(float(exclude_z)):
-            raise ValueError("exclude_z must not be NaN")
 
     def search_significant(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
                            mode: str = "score", algorithm: str = "sw", start: int = 0,
@@ -965,27 +923,8 @@ class DeviceDatabase:
         """miopalSearchSignificant: every target of the slice with an E-value of at most ``max_evalue``, the
         statistics gathered on the device from the search's own scores. Returns `search_hits`' dict plus "evalue"
         (float64, one per hit) and "fit" (a `ScoreFit` structure). TooManyHits carries the fit as ``fit``."""
-        self._check_evalue_cut(max_evalue, exclude_z)
-        end = self.count if end is None else min(end, self.count)
-        q = np.ascontiguousarray(query, dtype=np.uint8)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
-        count = ctypes.c_int64(-1)
-        ptrs, fit, ev = _HitPointers(), ScoreFit(), ctypes.c_void_p()
-        rc = lib().miopalSearchSignificant(self._h, _ptr(q), len(q), gap_open, gap_extend, _ptr(S), self.alphabet_length,
-                                           SEARCH[mode], MODE[algorithm], start, end, float(max_evalue), float(exclude_z),
-                                           -1 if max_hits is None else max_hits, ctypes.addressof(fit),
-                                           ctypes.byref(count), *ptrs.refs(), ctypes.byref(ev))
-        return self._significant_result(rc, int(count.value), ptrs, ev, fit, mode)
-
-    def _significant_result(self, rc, count, ptrs, ev, fit, mode):
-        try:
-            out = self._hits_result(rc, count, ptrs, mode)
-        except TooManyHits as err:
-            err.fit = fit
-            raise
-        out["evalue"] = _take_malloced(ev, count, np.float64)
-        out["fit"] = fit
-        return out
+        return self._search_significant(self._query_side(query, matrix, gap_open, gap_extend), mode, algorithm, start, end, max_evalue, exclude_z,
+                                        max_hits)
 
     def search_pssm_significant(self, row_scores: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
                                 mode: str = "score", algorithm: str = "sw", start: int = 0,
@@ -993,18 +932,8 @@ class DeviceDatabase:
                                 max_hits: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
         """miopalSearchPssmSignificant: `search_significant` with a position-specific scoring matrix (``row_scores``
         as in `search_pssm`) in the place of (query, matrix)."""
-        self._check_evalue_cut(max_evalue, exclude_z)
-        end = self.count if end is None else min(end, self.count)
-        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
-        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
-            raise ValueError(f"row_scores must have shape (query length, {self.alphabet_length})")
-        count = ctypes.c_int64(-1)
-        ptrs, fit, ev = _HitPointers(), ScoreFit(), ctypes.c_void_p()
-        rc = lib().miopalSearchPssmSignificant(self._h, _ptr(rows) if len(rows) else None, len(rows), gap_open, gap_extend,
-                                               self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end,
-                                               float(max_evalue), float(exclude_z), -1 if max_hits is None else max_hits,
-                                               ctypes.addressof(fit), ctypes.byref(count), *ptrs.refs(), ctypes.byref(ev))
-        return self._significant_result(rc, int(count.value), ptrs, ev, fit, mode)
+        return self._search_significant(self._pssm_side(row_scores, None, gap_open, gap_extend), mode, algorithm, start, end, max_evalue, exclude_z,
+                                        max_hits)
 
     def search_batch_significant(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
                                  gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
@@ -1013,37 +942,8 @@ class DeviceDatabase:
         """miopalSearchBatchSignificant: search_significant of every query in one batched call. ``max_evalue``: a
         number or one per query. Returns `search_batch_hits`' CSR plus "evalue" and "fits" (a list of `ScoreFit`
         structures, one per query). TooManyHits carries the offsets in ``counts`` and the fits in ``fits``."""
-        self._check_evalue_cut(max_evalue, exclude_z)
-        end = self.count if end is None else min(end, self.count)
-        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
-        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
-        if qs:
-            np.cumsum([len(q) for q in qs], out=offsets[1:])
-        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
-        if flat.size == 0:
-            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
-        cuts = np.ascontiguousarray(np.broadcast_to(np.asarray(max_evalue, dtype=np.float64), (len(qs),)))
-        fits = (ScoreFit * max(len(qs), 1))()
-        hit_offsets = np.zeros(len(qs) + 1, dtype=np.int64)
-        ptrs, ev = _HitPointers(), ctypes.c_void_p()
-        rc = lib().miopalSearchBatchSignificant(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
-                                                self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end,
-                                                _ptr(cuts) if len(qs) else None, float(exclude_z),
-                                                -1 if max_hits is None else max_hits, ctypes.addressof(fits),
-                                                _ptr(hit_offsets), *ptrs.refs(), ctypes.byref(ev))
-        fit_list = [fits[i] for i in range(len(qs))]
-        if rc == MIOPAL_ERR_TOO_MANY_HITS:
-            err = TooManyHits(f"more hits than max_hits (code={rc}): {last_error()}", hit_offsets)
-            err.fits = fit_list
-            raise err
-        raise_for(rc)
-        out = {"offsets": hit_offsets}
-        out.update(ptrs.arrays(int(hit_offsets[-1]), mode == "end"))
-        out["evalue"] = _take_malloced(ev, int(hit_offsets[-1]), np.float64)
-        out["fits"] = fit_list
-        out["_fits_owner"] = fits
-        return out
+        return self._search_significant(self._batch_side(queries, matrix, gap_open, gap_extend), mode, algorithm, start, end, max_evalue, exclude_z,
+                                        max_hits)
 
     row_stats_rows = staticmethod(row_stats_rows)
     select_hits_binned_rows = staticmethod(select_hits_binned_rows)
@@ -1057,26 +957,17 @@ class DeviceDatabase:
         "end_q", arrays of shape (end - start, m): best first (score descending, query index ascending), -1 past the
         count. ``min_score``: only queries scoring at least that many count (None: no bound). Row t equals the
         reduction of column t of `search_batch`. Mode "full" is refused (OPAL_ERR_INVALID_MODE)."""
-        end = self.count if end is None else min(end, self.count)
+        end = self._clamp(end)
+        side = self._batch_side(queries, matrix, gap_open, gap_extend)
         n = max(end - start, 0)
-        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
-        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
-        if qs:
-            np.cumsum([len(q) for q in qs], out=offsets[1:])
-        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
-        if flat.size == 0:
-            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
         shape = (n, max(m, 0))
         out = {"count": np.zeros(n, dtype=np.int32), "query": np.empty(shape, dtype=np.int32),
                "score": np.empty(shape, dtype=np.int32)}
         if mode == "end":
             out.update(end_t=np.empty(shape, dtype=np.int32), end_q=np.empty(shape, dtype=np.int32))
-        rc = lib().miopalSearchBatchTargetTop(self._h, _ptr(flat), _ptr(offsets), len(qs), gap_open, gap_extend, _ptr(S),
-                                              self.alphabet_length, SEARCH[mode], MODE[algorithm], start, end, m,
-                                              -(2 ** 31) if min_score is None else min_score, _ptr(out["count"]),
-                                              _ptr(out["query"]), _ptr(out["score"]), _ptr(out.get("end_t")),
-                                              _ptr(out.get("end_q")))
+        rc = lib().miopalSearchBatchTargetTop(self._h, *side.queries, *side.scoring, SEARCH[mode], MODE[algorithm], start,
+                                              end, m, _floor(min_score), _ptr(out["count"]), _ptr(out["query"]),
+                                              _ptr(out["score"]), _ptr(out.get("end_t")), _ptr(out.get("end_q")))
         raise_for(rc)
         return out
 
@@ -1089,19 +980,11 @@ class DeviceDatabase:
         ``pair_target[p]`` (absolute index), in one call. Returns `search`'s keys with one entry per pair, in pair
         order: "score", for "end" and "full" also "end_t" / "end_q", for "full" also "start_t" / "start_q",
         "aln_flat", "aln_off" and "aln"; entry p equals ``search(queries[i], ..., start=j, end=j + 1)``."""
-        qs = [np.ascontiguousarray(q, dtype=np.uint8).ravel() for q in queries]
-        offsets = np.zeros(len(qs) + 1, dtype=np.int64)
-        if qs:
-            np.cumsum([len(q) for q in qs], out=offsets[1:])
-        flat = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
-        if flat.size == 0:
-            flat = np.zeros(1, dtype=np.uint8)   # (a valid pointer for queries of length 0)
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
+        side = self._batch_side(queries, matrix, gap_open, gap_extend)
 
         def call(st, pq, pt, n, score, et, eq, s_t, s_q, ops_ptr, aoff):
-            return lib().miopalAlignPairs(self._h, _ptr(flat), _ptr(offsets), len(qs), pq, pt, n, gap_open, gap_extend,
-                                          _ptr(S), self.alphabet_length, st, MODE[algorithm], score, et, eq, s_t, s_q,
-                                          ctypes.byref(ops_ptr), aoff)
+            return lib().miopalAlignPairs(self._h, *side.queries, pq, pt, n, *side.scoring, st, MODE[algorithm], score, et,
+                                          eq, s_t, s_q, ctypes.byref(ops_ptr), aoff)
         return self._pair_list(call, pair_query, pair_target, mode)
 
     def align_pairs_pssm(self, pssm_rows: typing.Sequence[np.ndarray],
@@ -1113,21 +996,14 @@ class DeviceDatabase:
         one residue (or 255) per row of PSSM m - required for mode "full", may be None otherwise. Pair p aligns PSSM
         ``pair_pssm[p]`` with target ``pair_target[p]``; returns `align_pairs`' dict, entry p equal to
         ``search_pssm(pssm_rows[i], consensus[i], ..., start=j, end=j + 1)``."""
-        rows = [np.ascontiguousarray(r, dtype=np.int32) for r in pssm_rows]
-        for r in rows:
-            if r.ndim != 2 or r.shape[1] != self.alphabet_length:
-                raise ValueError(f"every PSSM must have shape (rows, {self.alphabet_length})")
-        offsets = np.zeros(len(rows) + 1, dtype=np.int64)
-        if rows:
-            np.cumsum([len(r) for r in rows], out=offsets[1:])
-        total = int(offsets[-1])
-        flat = np.concatenate(rows) if total else None
+        rows = [_pssm_rows(r, self.alphabet_length, "every PSSM must have shape (rows") for r in pssm_rows]
+        flat, offsets = _packed(rows, None)
         cons = None
         if consensus is not None:
             cs = [np.ascontiguousarray(c, dtype=np.uint8).ravel() for c in consensus]
             if [len(c) for c in cs] != [len(r) for r in rows]:
                 raise ValueError("consensus must have one entry per row of every PSSM")
-            cons = np.concatenate(cs) if total else None
+            cons = np.concatenate(cs) if offsets[-1] else None
 
         def call(st, pq, pt, n, score, et, eq, s_t, s_q, ops_ptr, aoff):
             return lib().miopalAlignPairsPssm(self._h, _ptr(flat), _ptr(cons), _ptr(offsets), len(rows), pq, pt, n,
@@ -1142,13 +1018,8 @@ class DeviceDatabase:
         and weighted on the device. Returns "counts" and "weighted" (int64, (Q, alphabet length + 1), the last column
         the gap letter), "member_weights" (int64, one per member, the query first; 32.32 fixed point) and "msa" (uint8,
         (members, Q); None unless ``return_msa``)."""
-        q = np.ascontiguousarray(query, dtype=np.uint8).ravel()
-        S = np.ascontiguousarray(matrix, dtype=np.int32)
-
-        def call(pt, n, counts, weighted, weights, msa):
-            return lib().miopalProfileColumns(self._h, _ptr(q) if len(q) else None, len(q), gap_open, gap_extend, _ptr(S),
-                                              self.alphabet_length, MODE[algorithm], pt, n, counts, weighted, weights, msa)
-        return self._profile(call, len(q), targets, return_msa)
+        return self._profile(self._query_side(query, matrix, gap_open, gap_extend, null_when_empty=True), algorithm, targets,
+                             return_msa)
 
     def profile_columns_pssm(self, row_scores: np.ndarray, consensus: np.ndarray, targets, gap_open: int = 3,
                              gap_extend: int = 1, algorithm: str = "sw",
@@ -1156,31 +1027,21 @@ class DeviceDatabase:
         """miopalProfileColumnsPssm: `profile_columns` with a position-specific scoring matrix (``row_scores``: integers
         of shape (Q, alphabet length); ``consensus``: one residue or 255 per row, the query's own row of the multiple
         alignment) in the place of (query, matrix)."""
-        rows = np.ascontiguousarray(row_scores, dtype=np.int32)
-        if rows.ndim != 2 or rows.shape[1] != self.alphabet_length:
-            raise ValueError(f"row_scores must have shape (positions, {self.alphabet_length})")
-        cons = np.ascontiguousarray(consensus, dtype=np.uint8).ravel()
-        if len(cons) != len(rows):
-            raise ValueError("consensus must have one entry per row")
+        side = self._pssm_side(row_scores, consensus, gap_open, gap_extend, with_consensus=True,
+                               shape="row_scores must have shape (positions", per_row="consensus must have one entry per row")
+        return self._profile(side, algorithm, targets, return_msa)
 
-        def call(pt, n, counts, weighted, weights, msa):
-            return lib().miopalProfileColumnsPssm(self._h, _ptr(rows) if len(rows) else None,
-                                                  _ptr(cons) if len(rows) else None, len(rows), gap_open, gap_extend,
-                                                  self.alphabet_length, MODE[algorithm], pt, n, counts, weighted, weights,
-                                                  msa)
-        return self._profile(call, len(rows), targets, return_msa)
-
-    def _profile(self, call, q, targets, return_msa) -> typing.Dict[str, typing.Any]:
-        """The outputs of one profile call: ``call(targets, n, counts, weighted, member weights, msa)`` makes the C call
-        with these pointers and returns its code."""
+    def _profile(self, side: _QuerySide, algorithm, targets, return_msa) -> typing.Dict[str, typing.Any]:
+        """One profile call (miopalProfileColumns, miopalProfileColumnsPssm) and its outputs."""
         pt = np.ascontiguousarray(targets, dtype=np.int64).ravel()
-        n = len(pt)
+        n, q = len(pt), side.length
         width = self.alphabet_length + 1
         out = {"counts": np.zeros((q, width), dtype=np.int64), "weighted": np.zeros((q, width), dtype=np.int64),
                "member_weights": np.zeros(n + 1, dtype=np.int64),
                "msa": np.full((n + 1, q), PROFILE_UNCOVERED, dtype=np.uint8) if return_msa else None}
-        rc = call(_ptr(pt) if n else None, n, _ptr(out["counts"]), _ptr(out["weighted"]), _ptr(out["member_weights"]),
-                  _ptr(out["msa"]))
+        rc = getattr(lib(), f"miopalProfileColumns{side.name}")(
+            self._h, *side.queries, *side.scoring, MODE[algorithm], _ptr(pt) if n else None, n, _ptr(out["counts"]),
+            _ptr(out["weighted"]), _ptr(out["member_weights"]), _ptr(out["msa"]))
         raise_for(rc)
         return out
 
@@ -1238,7 +1099,7 @@ class DeviceDatabase:
                              stream: int = 0, gap_open: int = 3, gap_extend: int = 1,
                              algorithm: str = "sw", start: int = 0,
                              end: typing.Optional[int] = None) -> None:
-        end = self.count if end is None else min(end, self.count)
+        end = self._clamp(end)
         q = np.ascontiguousarray(query, dtype=np.uint8)
         S = np.ascontiguousarray(matrix, dtype=np.int32)
         rc = lib().miopalSearchDeviceScores(self._h, _ptr(q), len(q), gap_open, gap_extend, _ptr(S),

@@ -521,6 +521,267 @@ except ImportError as err:  # pragma: no cover
 _RESULT_TYPES = {"score": ScoreResult, "end": EndResult, "full": FullResult}
 
 
+def _empty_arrays(mode: str, shape=(0,), fill: int = 0) -> typing.Dict[str, np.ndarray]:
+    """The arrays of a search that had nothing to do, with the keys and dtypes the device calls give them: "score",
+    for "end" and "full" also "end_q" / "end_t", for "full" (no entries then) also "start_q" / "start_t" and no
+    operations behind one offset."""
+    out = {"score": np.full(shape, fill, dtype=np.int32)}
+    if mode != "score":
+        out.update(end_q=np.full(shape, fill, dtype=np.int32), end_t=np.full(shape, fill, dtype=np.int32))
+    if mode == "full":
+        out.update(start_q=np.zeros(0, dtype=np.int32), start_t=np.zeros(0, dtype=np.int32),
+                   aln_flat=np.zeros(0, dtype=np.uint8), aln_off=np.zeros(1, dtype=np.int64))
+    return out
+
+
+def _result_objects(mode: str, target, query, query_lengths, target_lengths, out) -> typing.List[ScoreResult]:
+    """Arrays as result objects, one per entry: ``target`` the target index of every entry, ``query`` the index of its
+    query in ``query_lengths``, ``target_lengths`` one per target of the database (``query`` and the lengths are only
+    read for "full"), ``out`` the arrays of a device call with one entry each."""
+    score = out["score"].tolist()
+    target = np.asarray(target).tolist()
+    if mode == "score":
+        return [ScoreResult(t, s) for t, s in zip(target, score)]
+    end_q, end_t = out["end_q"].tolist(), out["end_t"].tolist()
+    if mode == "end":
+        return [EndResult(t, s, qe, te) for t, s, qe, te in zip(target, score, end_q, end_t)]
+    start_q, start_t = out["start_q"].tolist(), out["start_t"].tolist()
+    off = out["aln_off"].tolist()
+    text = out["aln_flat"].tobytes().translate(_OPS_TO_TEXT).decode("ascii")
+    return [FullResult(t, score[p], end_q[p], end_t[p], start_q[p], start_t[p], query_lengths[q], int(target_lengths[t]),
+                       text[off[p]:off[p + 1]])
+            for p, (q, t) in enumerate(zip(np.asarray(query).tolist(), target))]
+
+
+def _target_lengths(mirror, mode: str):
+    """what `_result_objects` reads of the targets: for "full" their lengths, otherwise nothing"""
+    return np.diff(mirror.offsets) if mode == "full" and mirror is not None else None
+
+
+def _cut(flat: list, counts: typing.List[int]) -> typing.List[list]:
+    """``flat`` cut into one list per entry of ``counts``"""
+    out, lo = [], 0
+    for c in counts:
+        out.append(flat[lo:lo + c])
+        lo += c
+    return out
+
+
+def _count_argument(name: str, value, low: int, high: int, limit: str) -> int:
+    """``k`` of the top hits, ``m`` of the best queries"""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer, not {type(value).__name__}")
+    if value < low or value > high:
+        raise ValueError(f"{name} must be between {low} and {high} ({limit}), got {int(value)}")
+    return int(value)
+
+
+def _max_hits_argument(max_hits) -> typing.Optional[int]:
+    if max_hits is None:
+        return None
+    if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
+        raise TypeError(f"max_hits must be an integer or None, not {type(max_hits).__name__}")
+    if max_hits < 0:
+        raise ValueError("max_hits must not be negative")
+    return int(max_hits)
+
+
+# --- The query side and the preamble of Aligner's extension entry points ----------------
+
+class _QuerySide:
+    """What an extension entry point of `Aligner` searches with: one sequence or a list of them with the aligner's
+    matrix (`_Sequences`), one `Pssm` or a list of them (`_Profiles`). It makes the checks that depend on which it is,
+    and the device calls: ``on(mirror)`` is its counterpart in `_capi`, which the selections take; their answers
+    come back in one shape, a row or a CSR segment per query, whether the queries are one or many."""
+
+    __slots__ = ("aligner", "given", "many", "lengths")
+
+    def __init__(self, aligner: "Aligner", given, many: bool):
+        self.aligner, self.given, self.many = aligner, given, many
+        self.lengths = None     # one per query, once `check` has run
+
+    def per_query(self, values: np.ndarray):
+        """one value per query (thresholds, E-value cuts) as the device call takes it: the array, or the one number"""
+        return values if self.many else values[0].item()
+
+    def top(self, mirror, mode, algorithm, start, end, k, min_score):
+        """(the count of every query, {"target", "score", "end_t" / "end_q": tables of shape (queries, k)})"""
+        out = mirror._search_top(self.on(mirror), mode, algorithm, start, end, k, min_score)
+        counts = out.pop("count")
+        if self.many:
+            return counts.tolist(), out
+        return [counts], {key: table[None, :] for key, table in out.items()}
+
+    def hits(self, mirror, mode, algorithm, start, end, thresholds, max_hits) -> typing.Dict[str, typing.Any]:
+        """the CSR of `DeviceDatabase.search_batch_hits`"""
+        return self._csr(mirror._search_hits(self.on(mirror), mode, algorithm, start, end, self.per_query(thresholds),
+                                             max_hits))
+
+    def significant(self, mirror, mode, algorithm, start, end, cuts, exclude_z, max_hits) -> typing.Dict[str, typing.Any]:
+        """the CSR of `DeviceDatabase.search_batch_significant`, "fits" a list of `ScoreFit`"""
+        out = self._csr(mirror._search_significant(self.on(mirror), mode, algorithm, start, end, self.per_query(cuts),
+                                                   exclude_z, max_hits))
+        out.pop("_fits_owner", None)
+        out["fits"] = [ScoreFit(f) for f in out["fits"]]
+        return out
+
+    def _csr(self, out):
+        if not self.many:
+            out["offsets"] = np.array([0, out.pop("count")], dtype=np.int64)
+            if "fit" in out:
+                out["fits"] = [out.pop("fit")]
+        return out
+
+
+class _Sequences(_QuerySide):
+    __slots__ = ("arrays",)
+    pair_index, pair_outside = "query_index", "query index of a pair outside the queries"
+
+    def check_type(self) -> None:
+        pass
+
+    def check(self, database: "BaseDatabase") -> None:
+        if database.alphabet != self.aligner.alphabet:
+            raise ValueError("database and score matrix have different alphabets")
+        queries = list(self.given) if self.many else [self.given]
+        for q in queries:
+            if q is None:
+                raise TypeError("Argument 'query' must not be None")
+        self.arrays = [np.frombuffer(database.alphabet.encode(q), dtype=np.uint8) for q in queries]
+        self.lengths = [len(a) for a in self.arrays]
+
+    @property
+    def codes(self) -> np.ndarray:
+        return self.arrays[0]
+
+    def on(self, mirror):
+        a = self.aligner
+        if self.many:
+            return mirror._batch_side(self.arrays, a._matrix, a.gap_open, a.gap_extend)
+        return mirror._query_side(self.arrays[0], a._matrix, a.gap_open, a.gap_extend)
+
+    def search(self, mirror, mode, algorithm, start, end):
+        a = self.aligner
+        if self.many:
+            return mirror.search_batch(self.arrays, a._matrix, a.gap_open, a.gap_extend, mode, algorithm, start, end)
+        return mirror.search(self.arrays[0], a._matrix, a.gap_open, a.gap_extend, mode, algorithm, start, end)
+
+    def align_pairs(self, mirror, pair_query, pair_target, mode, algorithm):
+        a = self.aligner
+        return mirror.align_pairs(self.arrays, pair_query, pair_target, a._matrix, a.gap_open, a.gap_extend, mode, algorithm)
+
+    def profile_columns(self, mirror, targets, algorithm, return_msa):
+        a = self.aligner
+        return mirror.profile_columns(self.arrays[0], a._matrix, targets, a.gap_open, a.gap_extend, algorithm, return_msa)
+
+
+class _Profiles(_QuerySide):
+    __slots__ = ("pssms",)
+    pair_index, pair_outside = "pssm_index", "PSSM index of a pair outside the PSSMs"
+
+    def check_type(self) -> None:
+        if self.many:
+            self.pssms = list(self.given)
+            for pssm in self.pssms:
+                if not isinstance(pssm, Pssm):
+                    raise TypeError("Argument 'pssms' has an item of incorrect type (expected Pssm, got "
+                                    f"{type(pssm).__name__})")
+        else:
+            if not isinstance(self.given, Pssm):
+                raise TypeError(f"Argument 'pssm' has incorrect type (expected Pssm, got {type(self.given).__name__})")
+            self.pssms = [self.given]
+
+    def check(self, database: "BaseDatabase") -> None:
+        for pssm in self.pssms:
+            if pssm.alphabet != database.alphabet:
+                raise ValueError("database and PSSM have different alphabets")
+        self.lengths = [len(pssm) for pssm in self.pssms]
+
+    @property
+    def codes(self) -> np.ndarray:
+        return self.pssms[0].consensus
+
+    def on(self, mirror):
+        return mirror._pssm_side(self.pssms[0].scores, None, self.aligner.gap_open, self.aligner.gap_extend)
+
+    def search(self, mirror, mode, algorithm, start, end):
+        pssm = self.pssms[0]
+        return mirror.search_pssm(pssm.scores, pssm.consensus, self.aligner.gap_open, self.aligner.gap_extend, mode,
+                                  algorithm, start, end)
+
+    def align_pairs(self, mirror, pair_pssm, pair_target, mode, algorithm):
+        return mirror.align_pairs_pssm([p.scores for p in self.pssms], [p.consensus for p in self.pssms], pair_pssm,
+                                       pair_target, self.aligner.gap_open, self.aligner.gap_extend, mode, algorithm)
+
+    def profile_columns(self, mirror, targets, algorithm, return_msa):
+        pssm = self.pssms[0]
+        return mirror.profile_columns_pssm(pssm.scores, pssm.consensus, targets, self.aligner.gap_open,
+                                           self.aligner.gap_extend, algorithm, return_msa)
+
+
+class _Request:
+    """The preamble of every extension entry point of `Aligner` (`align` keeps the reference's own, check for check).
+    Its checks, in this order:
+
+    1. the type of a `Pssm` argument;
+    2. ``mode`` (None: the method has none), then ``algorithm``;
+    3. the method's own count argument (``k``, ``m``, ``max_hits``): ``check()``, whose answer is kept as ``checked``;
+    4. a negative ``start`` or ``end``;
+    5. the type of the database;
+    6. its alphabet against the matrix's or the PSSM's;
+    7. no query is None; the queries are encoded;
+    8. what the method has per query or per entry (thresholds, E-value cuts, pairs, targets): by the method, before
+       it enters the request;
+    9. entering the request takes the database's read lock and checks the slice: an end below the start, the clamp
+       to the size, a start past the end.
+
+    Inside the ``with`` block ``start`` and ``end`` are the clamped slice, ``size`` the database's, and ``mirror()`` the
+    device mirror - asked for only when there is something to compute, so that an empty request needs no device."""
+
+    __slots__ = ("database", "start", "end", "size", "device", "checked", "_mirror")
+
+    def __init__(self, side: _QuerySide, database: "BaseDatabase", mode: typing.Optional[str], algorithm: str,
+                 start: int = 0, end: int = UINT32_MAX, device: int = 0, check: typing.Optional[typing.Callable] = None):
+        side.check_type()
+        if mode is not None and mode not in _OPAL_SEARCH_MODES:
+            raise ValueError(f"invalid search mode: {mode!r}")
+        if algorithm not in _OPAL_ALGORITHMS:
+            raise ValueError(f"invalid algorithm: {algorithm!r}")
+        self.checked = None if check is None else check()
+        if start < 0 or end < 0:
+            raise OverflowError("can't convert negative value to uint32_t")
+        if not isinstance(database, BaseDatabase):
+            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
+                            f"got {type(database).__name__})")
+        side.check(database)
+        self.database, self.start, self.end, self.device = database, start, end, device
+        self._mirror = None
+
+    def __enter__(self) -> "_Request":
+        self.database.lock.read.__enter__()
+        try:
+            self.size = self.database._get_size()
+            if self.end < self.start:
+                raise IndexError("database slice end is lower than start")
+            self.end = min(self.end, self.size)
+            if self.start > self.size:
+                raise IndexError("database slice start is past the end of the database")
+        except BaseException:
+            self.database.lock.read.__exit__(None, None, None)
+            raise
+        return self
+
+    def __exit__(self, exc_type, exc_value, traceback):
+        self.database.lock.read.__exit__(exc_type, exc_value, traceback)
+
+    def mirror(self) -> _capi.DeviceDatabase:
+        if self._mirror is None:
+            if _capi.lib().miopalDeviceCount() < 1:
+                raise RuntimeError("no supported SIMD backend available")
+            self._mirror = self.database._device_mirror(self.device)
+        return self._mirror
+
+
 # --- Aligner ------------------------------------------------------------------------
 
 def resolve_scoring_matrix(spec, verb: str = "found") -> ScoringMatrix:
@@ -563,6 +824,7 @@ class Aligner:
         if not self.scoring_matrix.is_integer():
             raise ValueError("Integer scoring matrix is expected")
         self._int_matrix = self.scoring_matrix.int_array()
+        self._matrix = _int_matrix_array(self._int_matrix)   # (as the device calls of the extensions take it)
 
     def __repr__(self):
         args = []
@@ -659,37 +921,17 @@ class Aligner:
         per target of ``database[start:end]``, without a Python object per target. The
         returned `ResultArrays` builds the reference's result objects on demand
         (``arrays[k]``, iteration), so ``list(arrays) == aligner.align(...)``."""
-        if mode not in _OPAL_SEARCH_MODES:
-            raise ValueError(f"invalid search mode: {mode!r}")
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if start < 0 or end < 0:
-            raise OverflowError("can't convert negative value to uint32_t")
-        if database.alphabet != self.alphabet:
-            raise ValueError("database and score matrix have different alphabets")
-        encoded = database.alphabet.encode(query)
-        with database.lock.read:
-            size = database._get_size()
-            if end < start:
-                raise IndexError("database slice end is lower than start")
-            end = min(end, size)
-            if start > size:
-                raise IndexError("database slice start is past the end of the database")
-            if end == start:
-                out = {"score": np.zeros(0, dtype=np.int32)}
-                if mode != "score":
-                    out.update(end_q=np.zeros(0, dtype=np.int32), end_t=np.zeros(0, dtype=np.int32))
-                if mode == "full":
-                    out.update(start_q=np.zeros(0, dtype=np.int32), start_t=np.zeros(0, dtype=np.int32),
-                               aln_flat=np.zeros(0, dtype=np.uint8), aln_off=np.zeros(1, dtype=np.int64))
-                return ResultArrays(mode, start, len(encoded), [], out)
-            if _capi.lib().miopalDeviceCount() < 1:
-                raise RuntimeError("no supported SIMD backend available")
-            mirror = database._device_mirror(device)
-            out = mirror.search(np.frombuffer(encoded, dtype=np.uint8), _int_matrix_array(self._int_matrix),
-                                self.gap_open, self.gap_extend, mode, algorithm, start, end)
-            lengths = np.diff(mirror.offsets[start:end + 1]) if mode == "full" else None
-            return ResultArrays(mode, start, len(encoded), lengths, out)
+        return self._search_arrays(_Sequences(self, query, False), database, mode, algorithm, start, end, device)
+
+    def _search_arrays(self, side: _QuerySide, database, mode, algorithm, start, end, device) -> "ResultArrays":
+        """`align_arrays` / `align_pssm_arrays`: one search of the slice with one query or PSSM"""
+        with _Request(side, database, mode, algorithm, start, end, device) as request:
+            if request.end == request.start:
+                return ResultArrays(mode, start, side.lengths[0], [], _empty_arrays(mode))
+            mirror = request.mirror()
+            out = side.search(mirror, mode, algorithm, start, request.end)
+            lengths = np.diff(mirror.offsets[start:request.end + 1]) if mode == "full" else None
+            return ResultArrays(mode, start, side.lengths[0], lengths, out)
 
     def align_pssm(self, pssm: "Pssm", database: BaseDatabase, *, mode: str = "score", algorithm: str = "sw",
                    start: int = 0, end: int = UINT32_MAX, device: int = 0) -> typing.List[ScoreResult]:
@@ -717,41 +959,7 @@ class Aligner:
     def align_pssm_arrays(self, pssm: "Pssm", database: BaseDatabase, *, mode: str = "score", algorithm: str = "sw",
                           start: int = 0, end: int = UINT32_MAX, device: int = 0) -> "ResultArrays":
         """`align_pssm` with the results as arrays (`ResultArrays`, as `align_arrays` returns them)."""
-        if not isinstance(pssm, Pssm):
-            raise TypeError(f"Argument 'pssm' has incorrect type (expected Pssm, got {type(pssm).__name__})")
-        if not isinstance(database, BaseDatabase):
-            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
-                            f"got {type(database).__name__})")
-        if mode not in _OPAL_SEARCH_MODES:
-            raise ValueError(f"invalid search mode: {mode!r}")
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if start < 0 or end < 0:
-            raise OverflowError("can't convert negative value to uint32_t")
-        if pssm.alphabet != database.alphabet:
-            raise ValueError("database and PSSM have different alphabets")
-        with database.lock.read:
-            size = database._get_size()
-            if end < start:
-                raise IndexError("database slice end is lower than start")
-            end = min(end, size)
-            if start > size:
-                raise IndexError("database slice start is past the end of the database")
-            if end == start:
-                out = {"score": np.zeros(0, dtype=np.int32)}
-                if mode != "score":
-                    out.update(end_q=np.zeros(0, dtype=np.int32), end_t=np.zeros(0, dtype=np.int32))
-                if mode == "full":
-                    out.update(start_q=np.zeros(0, dtype=np.int32), start_t=np.zeros(0, dtype=np.int32),
-                               aln_flat=np.zeros(0, dtype=np.uint8), aln_off=np.zeros(1, dtype=np.int64))
-                return ResultArrays(mode, start, len(pssm), [], out)
-            if _capi.lib().miopalDeviceCount() < 1:
-                raise RuntimeError("no supported SIMD backend available")
-            mirror = database._device_mirror(device)
-            out = mirror.search_pssm(pssm.scores, pssm.consensus, self.gap_open, self.gap_extend, mode, algorithm,
-                                     start, end)
-            lengths = np.diff(mirror.offsets[start:end + 1]) if mode == "full" else None
-            return ResultArrays(mode, start, len(pssm), lengths, out)
+        return self._search_arrays(_Profiles(self, pssm, False), database, mode, algorithm, start, end, device)
 
     def align_many(self, queries, database: BaseDatabase, *, mode: str = "score", algorithm: str = "sw",
                    start: int = 0, end: int = UINT32_MAX, device: int = 0) -> typing.List[typing.List[ScoreResult]]:
@@ -775,45 +983,16 @@ class Aligner:
         whose ``score`` (and for ``mode="end"`` ``query_end`` / ``target_end``) are ``int32`` arrays of shape
         ``(len(queries), n)``; ``arrays[i]`` is the `ResultArrays` of query ``i``, equal to
         ``align_arrays(queries[i], ...)``. Modes ``score`` and ``end``."""
-        if mode not in _OPAL_SEARCH_MODES:
-            raise ValueError(f"invalid search mode: {mode!r}")
         if mode == "full":
             raise ValueError("align_many_arrays computes scores and end locations only (mode 'score' or 'end')")
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if start < 0 or end < 0:
-            raise OverflowError("can't convert negative value to uint32_t")
-        if not isinstance(database, BaseDatabase):
-            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
-                            f"got {type(database).__name__})")
-        if database.alphabet != self.alphabet:
-            raise ValueError("database and score matrix have different alphabets")
-        queries = list(queries)
-        for q in queries:
-            if q is None:
-                raise TypeError("Argument 'query' must not be None")
-        encoded = [database.alphabet.encode(q) for q in queries]
-        with database.lock.read:
-            size = database._get_size()
-            if end < start:
-                raise IndexError("database slice end is lower than start")
-            end = min(end, size)
-            if start > size:
-                raise IndexError("database slice start is past the end of the database")
-            n = end - start
-            if n == 0 or not encoded:
-                out = {"score": np.zeros((len(encoded), n), dtype=np.int32)}
-                if mode == "end":
-                    out.update(end_q=np.zeros((len(encoded), n), dtype=np.int32),
-                               end_t=np.zeros((len(encoded), n), dtype=np.int32))
-                return BatchResultArrays(mode, start, [len(e) for e in encoded], out)
-            if _capi.lib().miopalDeviceCount() < 1:
-                raise RuntimeError("no supported SIMD backend available")
-            mirror = database._device_mirror(device)
-            out = mirror.search_batch([np.frombuffer(e, dtype=np.uint8) for e in encoded],
-                                      _int_matrix_array(self._int_matrix), self.gap_open, self.gap_extend, mode,
-                                      algorithm, start, end)
-            return BatchResultArrays(mode, start, [len(e) for e in encoded], out)
+        side = _Sequences(self, queries, True)
+        with _Request(side, database, mode, algorithm, start, end, device) as request:
+            n = request.end - start
+            if n == 0 or not side.lengths:
+                out = _empty_arrays(mode, (len(side.lengths), n))
+            else:
+                out = side.search(request.mirror(), mode, algorithm, start, request.end)
+            return BatchResultArrays(mode, start, side.lengths, out)
 
     def align_pairs(self, queries, database: BaseDatabase, pairs, *, mode: str = "score", algorithm: str = "sw",
                     device: int = 0) -> typing.List[ScoreResult]:
@@ -824,62 +1003,37 @@ class Aligner:
         `FullResult` per pair, in pair order, each equal to
         ``self.align(queries[i], database, mode=mode, algorithm=algorithm, start=j, end=j + 1)[0]``: the hits of
         `top_hits_many`, the survivors of a prefilter, the candidate pairs of a clustering step."""
-        if mode not in _OPAL_SEARCH_MODES:
-            raise ValueError(f"invalid search mode: {mode!r}")
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if not isinstance(database, BaseDatabase):
-            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
-                            f"got {type(database).__name__})")
-        if database.alphabet != self.alphabet:
-            raise ValueError("database and score matrix have different alphabets")
-        queries = list(queries)
-        for q in queries:
-            if q is None:
-                raise TypeError("Argument 'query' must not be None")
-        encoded = [database.alphabet.encode(q) for q in queries]
+        return self._pair_list(_Sequences(self, queries, True), database, pairs, mode, algorithm, device)
+
+    def _pair_list(self, side: _QuerySide, database, pairs, mode, algorithm, device) -> typing.List[ScoreResult]:
+        """`align_pairs` / `align_pairs_pssm`: one pair-list call, its arrays as result objects in pair order"""
+        request = _Request(side, database, mode, algorithm, device=device)
         pairs = np.asarray(pairs if len(pairs) else np.zeros((0, 2), dtype=np.int64))
         if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
-            raise ValueError("pairs must be a sequence of (query_index, target_index) integers")
+            raise ValueError(f"pairs must be a sequence of ({side.pair_index}, target_index) integers")
         pairs = pairs.astype(np.int64, copy=False)
-        with database.lock.read:
-            size = database._get_size()
-            if len(pairs):
-                if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= len(queries):
-                    raise IndexError("query index of a pair outside the queries")
-                if pairs[:, 1].min() < 0 or pairs[:, 1].max() >= size:
-                    raise IndexError("target index of a pair outside the database")
+        with request:
             if len(pairs) == 0:
                 return []
-            if _capi.lib().miopalDeviceCount() < 1:
-                raise RuntimeError("no supported SIMD backend available")
-            mirror = database._device_mirror(device)
-            return self._pair_results([np.frombuffer(e, dtype=np.uint8) for e in encoded], mirror,
-                                      _int_matrix_array(self._int_matrix), pairs[:, 0], pairs[:, 1], mode, algorithm)
+            if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= len(side.lengths):
+                raise IndexError(side.pair_outside)
+            if pairs[:, 1].min() < 0 or pairs[:, 1].max() >= request.size:
+                raise IndexError("target index of a pair outside the database")
+            mirror = request.mirror()
+            out = side.align_pairs(mirror, pairs[:, 0], pairs[:, 1], mode, algorithm)
+            return _result_objects(mode, pairs[:, 1], pairs[:, 0], side.lengths, _target_lengths(mirror, mode), out)
 
-    def _pair_results(self, arrays, mirror, matrix, pair_query, pair_target, mode, algorithm):
-        """One `align_pairs` call on the mirror; its arrays as result objects, in pair order."""
-        out = mirror.align_pairs(arrays, pair_query, pair_target, matrix, self.gap_open, self.gap_extend, mode,
-                                 algorithm)
-        return self._pair_objects(out, mirror, [len(a) for a in arrays], pair_query, pair_target, mode)
-
-    @staticmethod
-    def _pair_objects(out, mirror, query_lengths, pair_query, pair_target, mode):
-        """The arrays of a pair-list call (`align_pairs`, `align_pairs_pssm`) as result objects, in pair order."""
-        score = out["score"].tolist()
-        target = np.asarray(pair_target).tolist()
-        if mode == "score":
-            return [ScoreResult(t, s) for t, s in zip(target, score)]
-        end_q, end_t = out["end_q"].tolist(), out["end_t"].tolist()
-        if mode == "end":
-            return [EndResult(t, s, qe, te) for t, s, qe, te in zip(target, score, end_q, end_t)]
-        start_q, start_t = out["start_q"].tolist(), out["start_t"].tolist()
-        off = out["aln_off"].tolist()
-        text = out["aln_flat"].tobytes().translate(_OPS_TO_TEXT).decode("ascii")
-        lengths = np.diff(mirror.offsets)
-        return [FullResult(t, score[p], end_q[p], end_t[p], start_q[p], start_t[p], query_lengths[q], int(lengths[t]),
-                           text[off[p]:off[p + 1]])
-                for p, (q, t) in enumerate(zip(np.asarray(pair_query).tolist(), target))]
+    def _aligned(self, side: _QuerySide, mirror, pair_query, pair_target, algorithm,
+                 **carry) -> typing.Dict[str, typing.Any]:
+        """The "full" step behind a selection made on scores: the chosen (query, target) pairs in ONE pair-list call.
+        Returns its arrays - without "aln", the per-pair views - and what the selection ``carry`` over beside them."""
+        if len(pair_target):
+            out = side.align_pairs(mirror, pair_query, pair_target, "full", algorithm)
+            out.pop("aln", None)
+        else:
+            out = _empty_arrays("full")
+        out.update(carry)
+        return out
 
     def align_pairs_pssm(self, pssms, database: BaseDatabase, pairs, *, mode: str = "score", algorithm: str = "sw",
                          device: int = 0) -> typing.List[ScoreResult]:
@@ -888,42 +1042,7 @@ class Aligner:
         order, each equal to ``self.align_pssm(pssms[i], database, mode=mode, algorithm=algorithm, start=j,
         end=j + 1)[0]`` (``FullResult.query_length`` is ``len(pssms[i])``): a library of PSSMs against the
         survivors of a prefilter, the hits of a family scan. The gap penalties are the aligner's."""
-        if mode not in _OPAL_SEARCH_MODES:
-            raise ValueError(f"invalid search mode: {mode!r}")
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if not isinstance(database, BaseDatabase):
-            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
-                            f"got {type(database).__name__})")
-        pssms = list(pssms)
-        for pssm in pssms:
-            if not isinstance(pssm, Pssm):
-                raise TypeError(f"Argument 'pssms' has an item of incorrect type (expected Pssm, got {type(pssm).__name__})")
-            if pssm.alphabet != database.alphabet:
-                raise ValueError("database and PSSM have different alphabets")
-        pairs = np.asarray(pairs if len(pairs) else np.zeros((0, 2), dtype=np.int64))
-        if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
-            raise ValueError("pairs must be a sequence of (pssm_index, target_index) integers")
-        pairs = pairs.astype(np.int64, copy=False)
-        with database.lock.read:
-            size = database._get_size()
-            if len(pairs):
-                if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= len(pssms):
-                    raise IndexError("PSSM index of a pair outside the PSSMs")
-                if pairs[:, 1].min() < 0 or pairs[:, 1].max() >= size:
-                    raise IndexError("target index of a pair outside the database")
-            if len(pairs) == 0:
-                return []
-            if _capi.lib().miopalDeviceCount() < 1:
-                raise RuntimeError("no supported SIMD backend available")
-            mirror = database._device_mirror(device)
-            return self._pair_results_pssm(pssms, mirror, pairs[:, 0], pairs[:, 1], mode, algorithm)
-
-    def _pair_results_pssm(self, pssms, mirror, pair_pssm, pair_target, mode, algorithm):
-        """One `align_pairs_pssm` call on the mirror; its arrays as result objects, in pair order."""
-        out = mirror.align_pairs_pssm([p.scores for p in pssms], [p.consensus for p in pssms], pair_pssm, pair_target,
-                                      self.gap_open, self.gap_extend, mode, algorithm)
-        return self._pair_objects(out, mirror, [len(p) for p in pssms], pair_pssm, pair_target, mode)
+        return self._pair_list(_Profiles(self, pssms, True), database, pairs, mode, algorithm, device)
 
     def profile_columns(self, query, database: BaseDatabase, targets, *, algorithm: str = "sw", return_msa: bool = False,
                         device: int = 0) -> "ProfileColumns":
@@ -935,41 +1054,20 @@ class Aligner:
         letters per position are counted and weighted (Henikoff position-based weights) on the GPU in integers: only
         the columns and one weight per member come back. Returns a `ProfileColumns`; ``return_msa=True`` also brings
         the multiple alignment. An empty ``targets`` is the profile of the query alone and needs no device."""
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if not isinstance(database, BaseDatabase):
-            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
-                            f"got {type(database).__name__})")
-        if query is None:
-            raise TypeError("Argument 'query' must not be None")
-        if isinstance(query, Pssm):
-            if query.alphabet != database.alphabet:
-                raise ValueError("database and PSSM have different alphabets")
-            codes = query.consensus
-        else:
-            if database.alphabet != self.alphabet:
-                raise ValueError("database and score matrix have different alphabets")
-            codes = np.frombuffer(database.alphabet.encode(query), dtype=np.uint8)
+        side = (_Profiles if isinstance(query, Pssm) else _Sequences)(self, query, False)
+        request = _Request(side, database, None, algorithm, device=device)
         targets = np.asarray(targets if len(targets) else np.zeros(0, dtype=np.int64))
         if targets.ndim != 1 or not np.issubdtype(targets.dtype, np.integer):
             raise ValueError("targets must be a sequence of integer target indices")
         targets = targets.astype(np.int64, copy=False)
         alphabet = database.alphabet
-        with database.lock.read:
-            if len(targets) and (targets.min() < 0 or targets.max() >= database._get_size()):
-                raise IndexError("target index outside the database")
+        with request:
             if len(targets) == 0:
-                return ProfileColumns.of_query(codes, alphabet, return_msa)
-            if _capi.lib().miopalDeviceCount() < 1:
-                raise RuntimeError("no supported SIMD backend available")
-            mirror = database._device_mirror(device)
-            if isinstance(query, Pssm):
-                out = mirror.profile_columns_pssm(query.scores, codes, targets, self.gap_open, self.gap_extend, algorithm,
-                                                  return_msa)
-            else:
-                out = mirror.profile_columns(codes, _int_matrix_array(self._int_matrix), targets, self.gap_open,
-                                             self.gap_extend, algorithm, return_msa)
-        return ProfileColumns(out["counts"], out["weighted"], out["member_weights"], alphabet, codes, out["msa"])
+                return ProfileColumns.of_query(side.codes, alphabet, return_msa)
+            if targets.min() < 0 or targets.max() >= request.size:
+                raise IndexError("target index outside the database")
+            out = side.profile_columns(request.mirror(), targets, algorithm, return_msa)
+        return ProfileColumns(out["counts"], out["weighted"], out["member_weights"], alphabet, side.codes, out["msa"])
 
     def iterated_search(self, query, database: BaseDatabase, max_evalue: float, *, rounds: int = 3, algorithm: str = "sw",
                         background=None, pseudocount: float = 10.0, exclude_z: float = 5.0, device: int = 0):
@@ -1015,50 +1113,7 @@ class Aligner:
         key=lambda r: r.score, reverse=True) if min_score is None or r.score >= min_score][:k]``. ``mode="full"``
         selects on the scores, then aligns the chosen targets only, in one pair-list call (miopalAlignPairsPssm):
         the step an iterated profile search repeats."""
-        if not isinstance(pssm, Pssm):
-            raise TypeError(f"Argument 'pssm' has incorrect type (expected Pssm, got {type(pssm).__name__})")
-        if mode not in _OPAL_SEARCH_MODES:
-            raise ValueError(f"invalid search mode: {mode!r}")
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-            raise TypeError(f"k must be an integer, not {type(k).__name__}")
-        k = int(k)
-        if k < 0 or k > _capi.MIOPAL_MAX_TOP:
-            raise ValueError(f"k must be between 0 and {_capi.MIOPAL_MAX_TOP} (MIOPAL_MAX_TOP), got {k}")
-        if min_score is not None:
-            min_score = int(min_score)
-        if start < 0 or end < 0:
-            raise OverflowError("can't convert negative value to uint32_t")
-        if not isinstance(database, BaseDatabase):
-            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
-                            f"got {type(database).__name__})")
-        if pssm.alphabet != database.alphabet:
-            raise ValueError("database and PSSM have different alphabets")
-        with database.lock.read:
-            size = database._get_size()
-            if end < start:
-                raise IndexError("database slice end is lower than start")
-            end = min(end, size)
-            if start > size:
-                raise IndexError("database slice start is past the end of the database")
-            if end == start or k == 0:
-                return []
-            if _capi.lib().miopalDeviceCount() < 1:
-                raise RuntimeError("no supported SIMD backend available")
-            mirror = database._device_mirror(device)
-            out = mirror.search_pssm_top(pssm.scores, self.gap_open, self.gap_extend, "score" if mode == "full" else mode,
-                                         algorithm, start, end, k, min_score)
-            c = out["count"]
-            target = out["target"][:c]
-            if mode == "full":
-                if c == 0:
-                    return []
-                return self._pair_results_pssm([pssm], mirror, np.zeros(c, dtype=np.int32), target, "full", algorithm)
-            if mode == "score":
-                return [ScoreResult(int(t), int(s)) for t, s in zip(target, out["score"][:c])]
-            return [EndResult(int(t), int(s), int(qe), int(te)) for t, s, qe, te in
-                    zip(target, out["score"][:c], out["end_q"][:c], out["end_t"][:c])]
+        return self._top(_Profiles(self, pssm, False), database, k, mode, algorithm, min_score, start, end, device)[0]
 
     def top_hits(self, query, database: BaseDatabase, k: int = 10, *, mode: str = "score", algorithm: str = "sw",
                  min_score: typing.Optional[int] = None, start: int = 0, end: int = UINT32_MAX,
@@ -1068,7 +1123,7 @@ class Aligner:
         ``[r for r in sorted(self.align(query, database, mode=mode, ...), key=lambda r: r.score, reverse=True)
         if min_score is None or r.score >= min_score][:k]``. ``mode="full"`` selects on the scores, then aligns the
         chosen targets only, in one pair-list call (miopalAlignPairs)."""
-        return self._top(query, [query], database, k, mode, algorithm, min_score, start, end, device, False)[0]
+        return self._top(_Sequences(self, query, False), database, k, mode, algorithm, min_score, start, end, device)[0]
 
     def top_hits_many(self, queries, database: BaseDatabase, k: int = 10, *, mode: str = "score",
                       algorithm: str = "sw", min_score: typing.Optional[int] = None, start: int = 0,
@@ -1076,76 +1131,28 @@ class Aligner:
         """Extension: `top_hits` of every query of ``queries`` in one batched search
         (miopalSearchBatchTop); returns one list per query. ``mode="full"`` selects on the scores, then aligns
         all chosen (query, target) pairs in ONE pair-list call (miopalAlignPairs)."""
-        return self._top(None, queries, database, k, mode, algorithm, min_score, start, end, device, True)
+        return self._top(_Sequences(self, queries, True), database, k, mode, algorithm, min_score, start, end, device)
 
-    def _top(self, query, queries, database, k, mode, algorithm, min_score, start, end, device, many):
-        if mode not in _OPAL_SEARCH_MODES:
-            raise ValueError(f"invalid search mode: {mode!r}")
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-            raise TypeError(f"k must be an integer, not {type(k).__name__}")
-        k = int(k)
-        if k < 0 or k > _capi.MIOPAL_MAX_TOP:
-            raise ValueError(f"k must be between 0 and {_capi.MIOPAL_MAX_TOP} (MIOPAL_MAX_TOP), got {k}")
+    def _top(self, side: _QuerySide, database, k, mode, algorithm, min_score, start, end, device):
+        """`top_hits` and its forms: one list of result objects per query of ``side``, the device selection on the scores
+        (and end locations), and for "full" the chosen pairs aligned behind it."""
         if min_score is not None:
             min_score = int(min_score)
-        if start < 0 or end < 0:
-            raise OverflowError("can't convert negative value to uint32_t")
-        if not isinstance(database, BaseDatabase):
-            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
-                            f"got {type(database).__name__})")
-        if database.alphabet != self.alphabet:
-            raise ValueError("database and score matrix have different alphabets")
-        queries = list(queries)
-        for q in queries:
-            if q is None:
-                raise TypeError("Argument 'query' must not be None")
-        encoded = [database.alphabet.encode(q) for q in queries]
-        with database.lock.read:
-            size = database._get_size()
-            if end < start:
-                raise IndexError("database slice end is lower than start")
-            end = min(end, size)
-            if start > size:
-                raise IndexError("database slice start is past the end of the database")
-            if end == start or k == 0 or not encoded:
-                return [[] for _ in encoded]
-            if _capi.lib().miopalDeviceCount() < 1:
-                raise RuntimeError("no supported SIMD backend available")
-            mirror = database._device_mirror(device)
-            matrix = _int_matrix_array(self._int_matrix)
-            search_mode = "score" if mode == "full" else mode
-            arrays = [np.frombuffer(e, dtype=np.uint8) for e in encoded]
-            if many:
-                out = mirror.search_batch_top(arrays, matrix, self.gap_open, self.gap_extend, search_mode, algorithm,
-                                              start, end, k, min_score)
-                counts = [int(c) for c in out["count"]]
-                rows = [{key: out[key][i] for key in out if key != "count"} for i in range(len(encoded))]
-            else:
-                out = mirror.search_top(arrays[0], matrix, self.gap_open, self.gap_extend, search_mode, algorithm,
-                                        start, end, k, min_score)
-                counts = [out["count"]]
-                rows = [out]
-            if mode == "full":
-                # every chosen (query, target) pair in one pair-list call, cut back into one list per query
-                chosen = [row["target"][:c] for c, row in zip(counts, rows)]
-                pair_target = np.concatenate(chosen) if chosen else np.zeros(0, dtype=np.int64)
-                if len(pair_target) == 0:
-                    return [[] for _ in encoded]
-                pair_query = np.repeat(np.arange(len(encoded), dtype=np.int32), counts)
-                flat = self._pair_results(arrays, mirror, matrix, pair_query, pair_target, "full", algorithm)
-                bounds = np.concatenate(([0], np.cumsum(counts))).tolist()
-                return [flat[bounds[i]:bounds[i + 1]] for i in range(len(encoded))]
-            results = []
-            for q, c, row in zip(arrays, counts, rows):
-                target = row["target"][:c]
-                if mode == "score":
-                    results.append([ScoreResult(int(t), int(s)) for t, s in zip(target, row["score"][:c])])
-                elif mode == "end":
-                    results.append([EndResult(int(t), int(s), int(qe), int(te)) for t, s, qe, te in
-                                    zip(target, row["score"][:c], row["end_q"][:c], row["end_t"][:c])])
-            return results
+        with _Request(side, database, mode, algorithm, start, end, device,
+                      lambda: _count_argument("k", k, 0, _capi.MIOPAL_MAX_TOP, "MIOPAL_MAX_TOP")) as request:
+            k = request.checked
+            if request.end == start or k == 0 or not side.lengths:
+                return [[] for _ in side.lengths]
+            mirror = request.mirror()
+            counts, out = side.top(mirror, "score" if mode == "full" else mode, algorithm, start, request.end, k,
+                                   min_score)
+            rows = [{key: table[i, :c] for key, table in out.items()} for i, c in enumerate(counts)]
+            if mode != "full":
+                return [_result_objects(mode, row["target"], None, None, None, row) for row in rows]
+            target = np.concatenate([row["target"] for row in rows])
+            owner = np.repeat(np.arange(len(counts), dtype=np.int32), counts)
+            arrays = self._aligned(side, mirror, owner, target, algorithm)
+            return _cut(_result_objects(mode, target, owner, side.lengths, _target_lengths(mirror, mode), arrays), counts)
 
     def best_queries(self, queries, database: BaseDatabase, m: int = 1, *, mode: str = "score", algorithm: str = "sw",
                      min_score: typing.Optional[int] = None, start: int = 0, end: int = UINT32_MAX,
@@ -1157,22 +1164,14 @@ class Aligner:
         ``self.align(queries[query_index], database, mode=mode, ...)[target]``. ``min_score``: only queries scoring at
         least that many count. ``mode="full"`` selects on the scores, then aligns all chosen (query, target) pairs in
         ONE pair-list call (miopalAlignPairs)."""
-        out, query_lengths, mirror = self._best_queries(queries, database, m, mode, algorithm, min_score, start, end,
-                                                        device)
-        counts = out["count"].tolist()
-        chosen = np.arange(out["query"].shape[1])[None, :] < out["count"][:, None]
-        index = out["query"][chosen].tolist()
+        out, side, mirror = self._best_queries(queries, database, m, mode, algorithm, min_score, start, end, device)
+        counts = out.pop("count")
+        chosen = np.arange(out["query"].shape[1])[None, :] < counts[:, None]
         target = np.repeat(np.arange(start, start + len(counts), dtype=np.int64), counts)
-        if mode == "full":
-            flat = self._pair_objects(out["pairs"], mirror, query_lengths, index, target, mode) if index else []
-        elif mode == "score":
-            flat = [ScoreResult(t, s) for t, s in zip(target.tolist(), out["score"][chosen].tolist())]
-        else:
-            flat = [EndResult(t, s, qe, te) for t, s, qe, te in
-                    zip(target.tolist(), out["score"][chosen].tolist(), out["end_q"][chosen].tolist(),
-                        out["end_t"][chosen].tolist())]
-        bounds = np.concatenate(([0], np.cumsum(counts))).tolist()
-        return [list(zip(index[bounds[t]:bounds[t + 1]], flat[bounds[t]:bounds[t + 1]])) for t in range(len(counts))]
+        arrays = out["pairs"] if mode == "full" else {key: table[chosen] for key, table in out.items()}
+        index = out["query"][chosen].tolist()
+        flat = _result_objects(mode, target, index, side.lengths, _target_lengths(mirror, mode), arrays)
+        return _cut(list(zip(index, flat)), counts.tolist())
 
     def best_queries_arrays(self, queries, database: BaseDatabase, m: int = 1, *, mode: str = "score",
                             algorithm: str = "sw", min_score: typing.Optional[int] = None, start: int = 0,
@@ -1184,72 +1183,30 @@ class Aligner:
         return self._best_queries(queries, database, m, mode, algorithm, min_score, start, end, device)[0]
 
     def _best_queries(self, queries, database, m, mode, algorithm, min_score, start, end, device):
-        """The arrays of `best_queries_arrays`, the query lengths and the device mirror (None where none was needed):
-        `_top`'s checks, the device selection, and for "full" the pair list behind it."""
-        if mode not in _OPAL_SEARCH_MODES:
-            raise ValueError(f"invalid search mode: {mode!r}")
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
-            raise TypeError(f"m must be an integer, not {type(m).__name__}")
-        m = int(m)
-        if m < 1 or m > _capi.MIOPAL_MAX_TARGET_TOP:
-            raise ValueError(f"m must be between 1 and {_capi.MIOPAL_MAX_TARGET_TOP} (MIOPAL_MAX_TARGET_TOP), got {m}")
+        """The arrays of `best_queries_arrays`, the query side and the device mirror (None where none was needed): the
+        device selection, and for "full" the chosen pairs aligned behind it, row-major over (target, rank)."""
         if min_score is not None:
             min_score = int(min_score)
-        if start < 0 or end < 0:
-            raise OverflowError("can't convert negative value to uint32_t")
-        if not isinstance(database, BaseDatabase):
-            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
-                            f"got {type(database).__name__})")
-        if database.alphabet != self.alphabet:
-            raise ValueError("database and score matrix have different alphabets")
-        queries = list(queries)
-        for q in queries:
-            if q is None:
-                raise TypeError("Argument 'query' must not be None")
-        encoded = [database.alphabet.encode(q) for q in queries]
-        query_lengths = [len(e) for e in encoded]
-        with database.lock.read:
-            size = database._get_size()
-            if end < start:
-                raise IndexError("database slice end is lower than start")
-            end = min(end, size)
-            if start > size:
-                raise IndexError("database slice start is past the end of the database")
-            n = end - start
-            mirror = None
-            if n == 0 or not encoded:
-                out = {"count": np.zeros(n, dtype=np.int32), "query": np.full((n, m), -1, dtype=np.int32),
-                       "score": np.full((n, m), -1, dtype=np.int32)}
-                if mode == "end":
-                    out.update(end_q=np.full((n, m), -1, dtype=np.int32), end_t=np.full((n, m), -1, dtype=np.int32))
+        side = _Sequences(self, queries, True)
+        with _Request(side, database, mode, algorithm, start, end, device,
+                      lambda: _count_argument("m", m, 1, _capi.MIOPAL_MAX_TARGET_TOP, "MIOPAL_MAX_TARGET_TOP")) as request:
+            m = request.checked
+            n = request.end - start
+            search_mode = "score" if mode == "full" else mode
+            if n == 0 or not side.lengths:
+                mirror = None
+                out = dict(_empty_arrays(search_mode, (n, m), -1), count=np.zeros(n, dtype=np.int32),
+                           query=np.full((n, m), -1, dtype=np.int32))
             else:
-                if _capi.lib().miopalDeviceCount() < 1:
-                    raise RuntimeError("no supported SIMD backend available")
-                mirror = database._device_mirror(device)
-                matrix = _int_matrix_array(self._int_matrix)
-                arrays = [np.frombuffer(e, dtype=np.uint8) for e in encoded]
-                out = mirror.search_batch_target_top(arrays, matrix, self.gap_open, self.gap_extend,
-                                                     "score" if mode == "full" else mode, algorithm, start, end, m,
-                                                     min_score)
+                mirror = request.mirror()
+                out = mirror.search_batch_target_top(side.arrays, self._matrix, self.gap_open, self.gap_extend,
+                                                     search_mode, algorithm, start, request.end, m, min_score)
             if mode == "full":
-                # every chosen (query, target) pair in one pair-list call, row-major over (target, rank)
-                chosen = np.arange(m)[None, :] < out["count"][:, None]
-                pair_query = out["query"][chosen]
-                pair_target = np.repeat(np.arange(start, end, dtype=np.int64), out["count"])
-                if len(pair_query):
-                    pairs = mirror.align_pairs(arrays, pair_query, pair_target, matrix, self.gap_open, self.gap_extend,
-                                               "full", algorithm)
-                    pairs.pop("aln", None)
-                else:
-                    zeros = lambda: np.zeros(0, dtype=np.int32)   # noqa: E731
-                    pairs = {"score": zeros(), "end_q": zeros(), "end_t": zeros(), "start_q": zeros(), "start_t": zeros(),
-                             "aln_flat": np.zeros(0, dtype=np.uint8), "aln_off": np.zeros(1, dtype=np.int64)}
-                pairs.update(query=pair_query, target=pair_target)
-                out["pairs"] = pairs
-            return out, query_lengths, mirror
-
+                pair_query = out["query"][np.arange(m)[None, :] < out["count"][:, None]]
+                pair_target = np.repeat(np.arange(start, request.end, dtype=np.int64), out["count"])
+                out["pairs"] = self._aligned(side, mirror, pair_query, pair_target, algorithm, query=pair_query,
+                                             target=pair_target)
+            return out, side, mirror
 
     def hits(self, query, database: BaseDatabase, min_score: int, *, mode: str = "score", algorithm: str = "sw",
              start: int = 0, end: int = UINT32_MAX, device: int = 0, max_hits: typing.Optional[int] = None,
@@ -1260,16 +1217,18 @@ class Aligner:
         in database order; ``sort=True`` orders best first (score descending, index ascending: `top_hits`' order) on
         the host. ``mode="full"`` selects on the scores, then aligns the hits only, in one pair-list call
         (miopalAlignPairs). With more than ``max_hits`` hits: `_capi.TooManyHits`, its ``counts`` the number."""
-        return self._hit_objects(*self._hit_arrays([query], None, database, min_score, mode, algorithm, start, end,
-                                                   device, max_hits, sort, False), mode)[0]
+        arrays = self._hit_arrays(_Sequences(self, query, False), database, min_score, mode, algorithm, start, end, device,
+                                  max_hits, sort)
+        return self._hit_objects(*arrays, mode)[0]
 
     def hits_arrays(self, query, database: BaseDatabase, min_score: int, *, mode: str = "score", algorithm: str = "sw",
                     start: int = 0, end: int = UINT32_MAX, device: int = 0, max_hits: typing.Optional[int] = None,
                     sort: bool = False) -> typing.Dict[str, np.ndarray]:
         """`hits` without result objects: "target" (int64) and "score" - for "end" and "full" also "end_q" / "end_t",
         for "full" also "start_q" / "start_t", "aln_flat" / "aln_off" - one entry per hit (and "offsets": [0, hits])."""
-        return self._hit_arrays([query], None, database, min_score, mode, algorithm, start, end, device, max_hits, sort,
-                                False)[0]
+        arrays = self._hit_arrays(_Sequences(self, query, False), database, min_score, mode, algorithm, start, end, device,
+                                  max_hits, sort)
+        return arrays[0]
 
     def hits_many(self, queries, database: BaseDatabase, min_score, *, mode: str = "score", algorithm: str = "sw",
                   start: int = 0, end: int = UINT32_MAX, device: int = 0, max_hits: typing.Optional[int] = None,
@@ -1277,8 +1236,9 @@ class Aligner:
         """Extension: `hits` of every query of ``queries`` in one batched search (miopalSearchBatchHits); returns one
         list per query. ``min_score``: an integer, or one per query. ``max_hits`` bounds the total over all queries.
         ``mode="full"`` aligns all (query, hit) pairs in ONE pair-list call."""
-        return self._hit_objects(*self._hit_arrays(queries, None, database, min_score, mode, algorithm, start, end,
-                                                   device, max_hits, sort, True), mode)
+        arrays = self._hit_arrays(_Sequences(self, queries, True), database, min_score, mode, algorithm, start, end, device,
+                                  max_hits, sort)
+        return self._hit_objects(*arrays, mode)
 
     def hits_many_arrays(self, queries, database: BaseDatabase, min_score, *, mode: str = "score",
                          algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
@@ -1286,8 +1246,9 @@ class Aligner:
         """`hits_many` as a CSR, for callers that want no objects (the edge list of an all-against-all comparison):
         "offsets" (len(queries) + 1,), and `hits_arrays`' arrays with entries offsets[i]:offsets[i + 1] the hits of
         query i."""
-        return self._hit_arrays(queries, None, database, min_score, mode, algorithm, start, end, device, max_hits, sort,
-                                True)[0]
+        arrays = self._hit_arrays(_Sequences(self, queries, True), database, min_score, mode, algorithm, start, end, device,
+                                  max_hits, sort)
+        return arrays[0]
 
     def hits_pssm(self, pssm: "Pssm", database: BaseDatabase, min_score: int, *, mode: str = "score",
                   algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
@@ -1296,15 +1257,17 @@ class Aligner:
         equal to ``[r for r in self.align_pssm(pssm, database, mode=mode, ...) if r.score >= min_score]``.
         ``mode="full"`` aligns the hits in one pair-list call (miopalAlignPairsPssm): all targets above the inclusion
         threshold, the step an iterated profile search repeats."""
-        return self._hit_objects(*self._hit_arrays(None, pssm, database, min_score, mode, algorithm, start, end, device,
-                                                   max_hits, sort, False), mode)[0]
+        arrays = self._hit_arrays(_Profiles(self, pssm, False), database, min_score, mode, algorithm, start, end, device,
+                                  max_hits, sort)
+        return self._hit_objects(*arrays, mode)[0]
 
     def hits_pssm_arrays(self, pssm: "Pssm", database: BaseDatabase, min_score: int, *, mode: str = "score",
                          algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
                          max_hits: typing.Optional[int] = None, sort: bool = False) -> typing.Dict[str, np.ndarray]:
         """`hits_pssm` without result objects (`hits_arrays`' dict)."""
-        return self._hit_arrays(None, pssm, database, min_score, mode, algorithm, start, end, device, max_hits, sort,
-                                False)[0]
+        arrays = self._hit_arrays(_Profiles(self, pssm, False), database, min_score, mode, algorithm, start, end, device,
+                                  max_hits, sort)
+        return arrays[0]
 
     @staticmethod
     def _hit_thresholds(min_score, count, many):
@@ -1319,137 +1282,6 @@ class Aligner:
         if per_query and len(values) != count:
             raise ValueError(f"min_score must be an integer or hold one per query ({count}), got {len(values)}")
         return np.array([int(v) for v in values] if per_query else [int(min_score)] * count, dtype=np.int32)
-
-    def _hit_arrays(self, queries, pssm, database, min_score, mode, algorithm, start, end, device, max_hits, sort, many,
-                    significant=None):
-        """The CSR of `hits`, `hits_many` (queries) and `hits_pssm` (pssm): the checks of `_top` / `top_hits_pssm`, the
-        device selection, the host sort, and for "full" the pair list behind them. Returns (arrays, (query lengths,
-        target lengths or None)): what `_hit_objects` needs beside the arrays. ``significant``: (max_evalue,
-        exclude_z) of the `significant_hits` forms in the place of ``min_score`` - the arrays then hold "evalue",
-        "zscore" and "fits" (one `ScoreFit` per query) as well, and ``sort`` orders by E-value, then index."""
-        if pssm is not None or queries is None:
-            if not isinstance(pssm, Pssm):
-                raise TypeError(f"Argument 'pssm' has incorrect type (expected Pssm, got {type(pssm).__name__})")
-        if mode not in _OPAL_SEARCH_MODES:
-            raise ValueError(f"invalid search mode: {mode!r}")
-        if algorithm not in _OPAL_ALGORITHMS:
-            raise ValueError(f"invalid algorithm: {algorithm!r}")
-        if max_hits is not None:
-            if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
-                raise TypeError(f"max_hits must be an integer or None, not {type(max_hits).__name__}")
-            if max_hits < 0:
-                raise ValueError("max_hits must not be negative")
-            max_hits = int(max_hits)
-        if start < 0 or end < 0:
-            raise OverflowError("can't convert negative value to uint32_t")
-        if not isinstance(database, BaseDatabase):
-            raise TypeError(f"Argument 'database' has incorrect type (expected BaseDatabase, "
-                            f"got {type(database).__name__})")
-        if pssm is not None:
-            if pssm.alphabet != database.alphabet:
-                raise ValueError("database and PSSM have different alphabets")
-            count, encoded = 1, None
-        else:
-            if database.alphabet != self.alphabet:
-                raise ValueError("database and score matrix have different alphabets")
-            queries = list(queries)
-            for q in queries:
-                if q is None:
-                    raise TypeError("Argument 'query' must not be None")
-            encoded = [database.alphabet.encode(q) for q in queries]
-            count = len(encoded)
-        if significant is None:
-            thresholds = self._hit_thresholds(min_score, count, many)
-        else:
-            cuts, exclude_z = self._evalue_cuts(significant[0], count, many), self._exclude_z(significant[1])
-        query_lengths = [len(pssm)] if pssm is not None else [len(e) for e in encoded]
-        ends = mode != "score"
-        with database.lock.read:
-            size = database._get_size()
-            if end < start:
-                raise IndexError("database slice end is lower than start")
-            end = min(end, size)
-            if start > size:
-                raise IndexError("database slice start is past the end of the database")
-            if end == start or count == 0:
-                out = {"offsets": np.zeros(count + 1, dtype=np.int64), "target": np.zeros(0, dtype=np.int64),
-                       "score": np.zeros(0, dtype=np.int32)}
-                if ends:
-                    out.update(end_q=np.zeros(0, dtype=np.int32), end_t=np.zeros(0, dtype=np.int32))
-                if mode == "full":
-                    out.update(start_q=np.zeros(0, dtype=np.int32), start_t=np.zeros(0, dtype=np.int32),
-                               aln_flat=np.zeros(0, dtype=np.uint8), aln_off=np.zeros(1, dtype=np.int64))
-                if significant is not None:
-                    out.update(evalue=np.zeros(0, dtype=np.float64), zscore=np.zeros(0, dtype=np.float64),
-                               fits=[ScoreFit() for _ in range(count)])
-                return out, (query_lengths, None)
-            if _capi.lib().miopalDeviceCount() < 1:
-                raise RuntimeError("no supported SIMD backend available")
-            mirror = database._device_mirror(device)
-            search_mode = "score" if mode == "full" else mode
-            if significant is not None:
-                arrays, matrix = None, None
-                if pssm is not None:
-                    got = mirror.search_pssm_significant(pssm.scores, self.gap_open, self.gap_extend, search_mode,
-                                                         algorithm, start, end, float(cuts[0]), exclude_z, max_hits)
-                else:
-                    matrix = _int_matrix_array(self._int_matrix)
-                    arrays = [np.frombuffer(e, dtype=np.uint8) for e in encoded]
-                    if many:
-                        got = mirror.search_batch_significant(arrays, matrix, self.gap_open, self.gap_extend, search_mode,
-                                                              algorithm, start, end, cuts, exclude_z, max_hits)
-                        got.pop("_fits_owner", None)
-                    else:
-                        got = mirror.search_significant(arrays[0], matrix, self.gap_open, self.gap_extend, search_mode,
-                                                        algorithm, start, end, float(cuts[0]), exclude_z, max_hits)
-                if "fit" in got:
-                    got["offsets"] = np.array([0, got.pop("count")], dtype=np.int64)
-                    got["fits"] = [got.pop("fit")]
-                got["fits"] = [ScoreFit(f) for f in got["fits"]]
-            elif pssm is not None:
-                got = mirror.search_pssm_hits(pssm.scores, self.gap_open, self.gap_extend, search_mode, algorithm, start,
-                                              end, int(thresholds[0]), max_hits)
-                got["offsets"] = np.array([0, got.pop("count")], dtype=np.int64)
-                arrays, matrix = None, None
-            else:
-                matrix = _int_matrix_array(self._int_matrix)
-                arrays = [np.frombuffer(e, dtype=np.uint8) for e in encoded]
-                if many:
-                    got = mirror.search_batch_hits(arrays, matrix, self.gap_open, self.gap_extend, search_mode, algorithm,
-                                                   start, end, thresholds, max_hits)
-                else:
-                    got = mirror.search_hits(arrays[0], matrix, self.gap_open, self.gap_extend, search_mode, algorithm,
-                                             start, end, int(thresholds[0]), max_hits)
-                    got["offsets"] = np.array([0, got.pop("count")], dtype=np.int64)
-            offsets = got["offsets"]
-            owner = np.repeat(np.arange(count, dtype=np.int32), np.diff(offsets))
-            if sort and len(owner):
-                # best first inside every query: score descending, then index ascending (`top_hits`' order); the
-                # significant forms: E-value ascending, then index
-                first = got["evalue"] if significant is not None else -got["score"].astype(np.int64)
-                order = np.lexsort((got["target"], first, owner))
-                for key in ("target", "score", "end_q", "end_t", "evalue"):
-                    if key in got:
-                        got[key] = got[key][order]
-            if significant is not None:
-                lengths = np.diff(mirror.offsets)[got["target"]]
-                got["zscore"] = np.zeros(len(owner), dtype=np.float64)
-                for i, fit in enumerate(got["fits"]):
-                    span = slice(int(offsets[i]), int(offsets[i + 1]))
-                    got["zscore"][span] = fit.zscore(got["score"][span], lengths[span])
-            if mode == "full":
-                # every (query, hit) pair in one pair-list call, in the order chosen above
-                target = got["target"]
-                extra = {key: got[key] for key in ("evalue", "zscore", "fits") if key in got}
-                if pssm is not None:
-                    got = mirror.align_pairs_pssm([pssm.scores], [pssm.consensus], owner, target, self.gap_open,
-                                                  self.gap_extend, "full", algorithm)
-                else:
-                    got = mirror.align_pairs(arrays, owner, target, matrix, self.gap_open, self.gap_extend, "full",
-                                             algorithm)
-                got.pop("aln", None)
-                got.update(offsets=offsets, target=target, **extra)
-            return got, (query_lengths, np.diff(mirror.offsets) if mode == "full" else None)
 
     @staticmethod
     def _evalue_cuts(max_evalue, count, many):
@@ -1474,6 +1306,68 @@ class Aligner:
             raise ValueError("exclude_z must not be NaN")
         return float(exclude_z)
 
+    def _hit_arrays(self, side: _QuerySide, database, min_score, mode, algorithm, start, end, device, max_hits, sort,
+                    significant=None):
+        """The CSR of `hits` and its forms: the device selection, the host sort, and for "full" the hits aligned behind
+        them. Returns (arrays, (query lengths, target lengths or None)): what `_hit_objects` needs beside the arrays.
+        ``significant``: (max_evalue, exclude_z) of the `significant_hits` forms in the place of ``min_score`` - the
+        arrays then hold "evalue", "zscore" and "fits" (one `ScoreFit` per query) as well, and ``sort`` orders by
+        E-value, then index."""
+        request = _Request(side, database, mode, algorithm, start, end, device, lambda: _max_hits_argument(max_hits))
+        max_hits, count = request.checked, len(side.lengths)
+        if significant is None:
+            thresholds = self._hit_thresholds(min_score, count, side.many)
+        else:
+            cuts, exclude_z = self._evalue_cuts(significant[0], count, side.many), self._exclude_z(significant[1])
+        with request:
+            if request.end == start or count == 0:
+                out = dict(_empty_arrays(mode), offsets=np.zeros(count + 1, dtype=np.int64),
+                           target=np.zeros(0, dtype=np.int64))
+                if significant is not None:
+                    out.update(evalue=np.zeros(0, dtype=np.float64), zscore=np.zeros(0, dtype=np.float64),
+                               fits=[ScoreFit() for _ in range(count)])
+                return out, (side.lengths, None)
+            mirror = request.mirror()
+            search_mode = "score" if mode == "full" else mode
+            if significant is None:
+                got = side.hits(mirror, search_mode, algorithm, start, request.end, thresholds, max_hits)
+            else:
+                got = side.significant(mirror, search_mode, algorithm, start, request.end, cuts, exclude_z, max_hits)
+            offsets = got["offsets"]
+            owner = np.repeat(np.arange(count, dtype=np.int32), np.diff(offsets))
+            if sort and len(owner):
+                # best first inside every query: score descending, then index ascending (`top_hits`' order); the
+                # significant forms: E-value ascending, then index
+                first = got["evalue"] if significant is not None else -got["score"].astype(np.int64)
+                order = np.lexsort((got["target"], first, owner))
+                for key in ("target", "score", "end_q", "end_t", "evalue"):
+                    if key in got:
+                        got[key] = got[key][order]
+            if significant is not None:
+                lengths = np.diff(mirror.offsets)[got["target"]]
+                got["zscore"] = np.zeros(len(owner), dtype=np.float64)
+                for i, fit in enumerate(got["fits"]):
+                    span = slice(int(offsets[i]), int(offsets[i + 1]))
+                    got["zscore"][span] = fit.zscore(got["score"][span], lengths[span])
+            if mode == "full":
+                # every (query, hit) pair, in the order chosen above
+                carry = {key: got[key] for key in ("offsets", "target", "evalue", "zscore", "fits") if key in got}
+                got = self._aligned(side, mirror, owner, got["target"], algorithm, **carry)
+            return got, (side.lengths, _target_lengths(mirror, mode))
+
+    def _significant_objects(self, out, lengths, mode):
+        offsets = out["offsets"].tolist()
+        return [SignificantHits(results, out["evalue"][offsets[i]:offsets[i + 1]], out["zscore"][offsets[i]:offsets[i + 1]],
+                                out["fits"][i])
+                for i, results in enumerate(self._hit_objects(out, lengths, mode))]
+
+    @staticmethod
+    def _hit_objects(out, lengths, mode):
+        """The CSR of `_hit_arrays` as one list of result objects per query."""
+        counts = np.diff(out["offsets"])
+        owner = np.repeat(np.arange(len(counts)), counts) if mode == "full" else None
+        return _cut(_result_objects(mode, out["target"], owner, lengths[0], lengths[1], out), counts.tolist())
+
     def significant_hits(self, query, database: BaseDatabase, max_evalue: float, *, mode: str = "score",
                          algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
                          exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
@@ -1488,18 +1382,19 @@ class Aligner:
         ``.evalues`` / ``.zscores`` (float64) and ``.fit`` (a `ScoreFit`); iterating yields (result, evalue).
         ``sort=True``: E-value ascending, then index. ``mode="full"`` aligns the hits in one pair-list call. The
         z-score holds for any algorithm; the E-value is calibrated for local ("sw") scores."""
-        return self._significant_objects(self._hit_arrays([query], None, database, None, mode, algorithm, start, end,
-                                                          device, max_hits, sort, False, (max_evalue, exclude_z)), mode)[0]
+        arrays = self._hit_arrays(_Sequences(self, query, False), database, None, mode, algorithm, start, end, device,
+                                  max_hits, sort, (max_evalue, exclude_z))
+        return self._significant_objects(*arrays, mode)[0]
 
     def significant_hits_arrays(self, query, database: BaseDatabase, max_evalue: float, *, mode: str = "score",
                                 algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
                                 exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
                                 sort: bool = False) -> typing.Dict[str, typing.Any]:
         """`significant_hits` without result objects: `hits_arrays`' dict plus "evalue", "zscore" and "fit"."""
-        out = self._hit_arrays([query], None, database, None, mode, algorithm, start, end, device, max_hits, sort, False,
-                               (max_evalue, exclude_z))[0]
-        out["fit"] = out.pop("fits")[0]
-        return out
+        arrays = self._hit_arrays(_Sequences(self, query, False), database, None, mode, algorithm, start, end, device,
+                                  max_hits, sort, (max_evalue, exclude_z))
+        arrays[0]["fit"] = arrays[0].pop("fits")[0]
+        return arrays[0]
 
     def significant_hits_many(self, queries, database: BaseDatabase, max_evalue, *, mode: str = "score",
                               algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
@@ -1507,16 +1402,18 @@ class Aligner:
                               sort: bool = False) -> typing.List["SignificantHits"]:
         """Extension: `significant_hits` of every query in one batched search (miopalSearchBatchSignificant); one
         `SignificantHits` per query. ``max_evalue``: a number, or one per query."""
-        return self._significant_objects(self._hit_arrays(queries, None, database, None, mode, algorithm, start, end,
-                                                          device, max_hits, sort, True, (max_evalue, exclude_z)), mode)
+        arrays = self._hit_arrays(_Sequences(self, queries, True), database, None, mode, algorithm, start, end, device,
+                                  max_hits, sort, (max_evalue, exclude_z))
+        return self._significant_objects(*arrays, mode)
 
     def significant_hits_many_arrays(self, queries, database: BaseDatabase, max_evalue, *, mode: str = "score",
                                      algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
                                      exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
                                      sort: bool = False) -> typing.Dict[str, typing.Any]:
         """`significant_hits_many` as `hits_many_arrays`' CSR plus "evalue", "zscore" and "fits" (one per query)."""
-        return self._hit_arrays(queries, None, database, None, mode, algorithm, start, end, device, max_hits, sort, True,
-                                (max_evalue, exclude_z))[0]
+        arrays = self._hit_arrays(_Sequences(self, queries, True), database, None, mode, algorithm, start, end, device,
+                                  max_hits, sort, (max_evalue, exclude_z))
+        return arrays[0]
 
     def significant_hits_pssm(self, pssm: "Pssm", database: BaseDatabase, max_evalue: float, *, mode: str = "score",
                               algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
@@ -1524,47 +1421,19 @@ class Aligner:
                               sort: bool = False) -> "SignificantHits":
         """Extension: `significant_hits` with a `Pssm` in the place of the query and the aligner's matrix
         (miopalSearchPssmSignificant): the inclusion step of an iterated profile search."""
-        return self._significant_objects(self._hit_arrays(None, pssm, database, None, mode, algorithm, start, end, device,
-                                                          max_hits, sort, False, (max_evalue, exclude_z)), mode)[0]
+        arrays = self._hit_arrays(_Profiles(self, pssm, False), database, None, mode, algorithm, start, end, device,
+                                  max_hits, sort, (max_evalue, exclude_z))
+        return self._significant_objects(*arrays, mode)[0]
 
     def significant_hits_pssm_arrays(self, pssm: "Pssm", database: BaseDatabase, max_evalue: float, *,
                                      mode: str = "score", algorithm: str = "sw", start: int = 0, end: int = UINT32_MAX,
                                      device: int = 0, exclude_z: float = 5.0, max_hits: typing.Optional[int] = None,
                                      sort: bool = False) -> typing.Dict[str, typing.Any]:
         """`significant_hits_pssm` without result objects (`significant_hits_arrays`' dict)."""
-        out = self._hit_arrays(None, pssm, database, None, mode, algorithm, start, end, device, max_hits, sort, False,
-                               (max_evalue, exclude_z))[0]
-        out["fit"] = out.pop("fits")[0]
-        return out
-
-    def _significant_objects(self, arrays_and_lengths, mode):
-        out, lengths = arrays_and_lengths
-        offsets = out["offsets"].tolist()
-        return [SignificantHits(results, out["evalue"][offsets[i]:offsets[i + 1]], out["zscore"][offsets[i]:offsets[i + 1]],
-                                out["fits"][i])
-                for i, results in enumerate(self._hit_objects(out, lengths, mode))]
-
-    @staticmethod
-    def _hit_objects(out, lengths, mode):
-        """The CSR of `_hit_arrays` as one list of result objects per query."""
-        offsets = out["offsets"].tolist()
-        owner = np.repeat(np.arange(len(offsets) - 1), np.diff(out["offsets"])).tolist()
-        score, target = out["score"].tolist(), out["target"].tolist()
-        if mode == "score":
-            flat = [ScoreResult(t, s) for t, s in zip(target, score)]
-        else:
-            end_q, end_t = out["end_q"].tolist(), out["end_t"].tolist()
-            if mode == "end":
-                flat = [EndResult(t, s, qe, te) for t, s, qe, te in zip(target, score, end_q, end_t)]
-            else:
-                start_q, start_t = out["start_q"].tolist(), out["start_t"].tolist()
-                off = out["aln_off"].tolist()
-                text = out["aln_flat"].tobytes().translate(_OPS_TO_TEXT).decode("ascii")
-                qlen, tlen = lengths
-                flat = [FullResult(t, score[p], end_q[p], end_t[p], start_q[p], start_t[p], qlen[q], int(tlen[t]),
-                                   text[off[p]:off[p + 1]])
-                        for p, (q, t) in enumerate(zip(owner, target))]
-        return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+        arrays = self._hit_arrays(_Profiles(self, pssm, False), database, None, mode, algorithm, start, end, device,
+                                  max_hits, sort, (max_evalue, exclude_z))
+        arrays[0]["fit"] = arrays[0].pop("fits")[0]
+        return arrays[0]
 
 
 class ScoreFit:
