@@ -69,14 +69,18 @@ struct InterseqArgs {
     // sweeps an equal interval of the launch's chunks; a group cut by an interval's end is handed on
     int splitMode;             // 0 = off (groups handed out dynamically), 1 = on, 2 = on, consumers recompute from column 0
     int splitBlocks;           // workgroups of the launch (the plan below is made for splitBlocks * 12 wavefronts)
-    const int64_t* chunkPrefix;   // [groups of the view + 1] running number of chunks
+    const int64_t* chunkPrefix;   // (not read any more: the intervals come as splitPlan, below)
     uint4* splitState;         // [wavefront][splitStateQuads(rows)][64]: H, E and best at the cut that starts its interval
-    int* splitFlags;           // [wavefronts + 1], zeroed before the launch: 1 = the state is there
+    int* splitFlags;           // [wavefronts + 1]: == splitEpoch (below) = the state is there
     int stripSpinCap;          // strips kernels: polls (x s_sleep) before a unit gives up on the strip above; 0 = the default
     int faultUnit1;            // strips kernels, test hook: unit (this - 1) behaves as if it had died; 0 = none
     unsigned long long* stripTiming;   // diagnostic builds (-DMIOPAL_STRIP_TIMING=1, interseq_impl.h): six counters; else null
     uint2* boundary[2];        // ping-pong strip boundaries, same indexing as pack*4
     const int64_t* boundaryOff;
+    // column split, what the host prepares once and not per launch (interseq_impl.h, "the split form's prologue")
+    const int4* splitPlan;     // [wavefronts + 1] per interval boundary {group that holds its chunk (from groupBase), chunks
+                               // into that group, the chunk's number in the launch, 0}: no search through chunkPrefix
+    uint32_t splitEpoch;       // never 0: splitFlags[w] == splitEpoch = the state of THIS launch is there (no zeroing per launch)
 };
 
 // ---- batch forms of the one-strip pair-table kernels (interseq_batch_impl.h) ----
@@ -330,6 +334,13 @@ constexpr int kPairStripsFirst = 32;       // shortest strips of the multi-strip
 constexpr int kPairStripsMaxRows = 52, kPairStripsMaxRowsLoc = 48;   // tallest strips of the multi-strip pair-table kernel
 constexpr int kPairStripsMaxRowsKnown = 40;   // ... of an `end` search in two sweeps (scores, then the cell that holds them)
 constexpr int kPairWavesPerGroup = 12;     // = kPairWaves: wavefronts of a workgroup of the one-strip pair-table kernels
+// LDS of the one-strip biased kernels behind the table: 4 per-SIMD counters and the pacing words (= kPaceInts), and for
+// the column split the query profile (nSymbols x qPad int16; qPad is a multiple of 8) the table is built from
+constexpr int kPairTailInts = 4 + 20;
+constexpr size_t kCuLdsBytes = 160 * 1024;   // a compute unit's LDS, what allowFullLds (launch_layer.h) opens to a kernel
+__host__ __device__ constexpr size_t pairSplitLdsBytes(int rowsPerStrip, int nSymbols, int qPad) {
+    return pairLdsBytes(rowsPerStrip, nSymbols) + kPairTailInts * sizeof(int) + (((size_t)nSymbols * qPad * 2 + 15) & ~(size_t)15);
+}
 inline size_t splitStateBytes(int rows) { return (size_t)((2 * rows + 1 + 3) / 4) * kLanes * 16; }   // per wavefront
 constexpr int kBiasedScoreLimit = 25600;   // = kBiasedLimit: a best at or above it is recomputed
 constexpr int kBiasedMaxMagnitude = 1024;  // |score|, open - ext, ext - open

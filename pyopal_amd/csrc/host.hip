@@ -595,6 +595,41 @@ int miopalSelfTest(int which) {
             // traceback batches - against literals worked out from the expressions it replaced: full_plan_selftest.h
             return fullPlanSelfTest();
         }
+        if (which == 6) {
+            // The column split's host side. Its launch asks for the pair table, the counters behind it and the profile: within
+            // the CU's 160 KB for every row count at 24 symbols, and wherever the table alone passes interseqPairFits ...
+            for (int rows = 1; rows <= 64; ++rows) {
+                const int qPad = (rows + 7) / 8 * 8;
+                if (pairSplitLdsBytes(rows, 24, qPad) > kCuLdsBytes) return 1000 + rows;
+                for (int nSym = 2; nSym <= kMaxAlphabet + 1; ++nSym)
+                    if (interseqPairFits(rows, nSym) && pairSplitLdsBytes(rows, nSym, qPad) > kCuLdsBytes) return 2000 + rows;
+            }
+            // ... and its plan against the definition, chunk by chunk: interval w = chunks [w C / W, (w + 1) C / W) of the
+            // groups' chunk sequence - equal groups, ragged ones, an interval inside one group, one chunk per wavefront
+            const std::vector<std::vector<int>> cases = {{75, 75, 75, 75, 75}, {9, 7, 7, 5, 3, 3, 1, 1}, {40}, {3, 2, 1, 1, 5}};
+            for (const std::vector<int>& chunks : cases) {
+                std::vector<int> groupOfChunk, intoGroup;
+                for (size_t g = 0; g < chunks.size(); ++g)
+                    for (int c = 0; c < chunks[g]; ++c) {
+                        groupOfChunk.push_back((int)g);
+                        intoGroup.push_back(c);
+                    }
+                const int64_t C = (int64_t)groupOfChunk.size();
+                for (int W = 1; W <= C; ++W) {
+                    const std::vector<int4> plan = splitPlanOf(chunks.data(), (int)chunks.size(), W);
+                    if ((int)plan.size() != W + 1) return 3000;
+                    for (int w = 0; w <= W; ++w) {
+                        const int64_t x = w * (C / W) + w * (C % W) / W;
+                        const int4 e = plan[(size_t)w];
+                        if (e.z != x || e.w != 0) return 3001;
+                        if (x == C ? (e.x != (int)chunks.size() || e.y != 0)
+                                   : (e.x != groupOfChunk[(size_t)x] || e.y != intoGroup[(size_t)x])) return 3002;
+                        if (w > 0 && e.z <= plan[(size_t)w - 1].z) return 3003;   // (no empty interval)
+                    }
+                }
+            }
+            return 0;
+        }
         if (which != 1) return -1;
         // (no device call on the way: the handle is never filled, the builders are injected)
         std::unique_ptr<MiopalDb> db(new MiopalDb());

@@ -18,6 +18,24 @@ static inline void scoreExtremes(const int* entries, size_t count, int* maxScore
     *minScore = count ? *std::min_element(entries, entries + count) : 0;
 }
 
+// The column split's plan (interseq_impl.h): the launch's chunks - those of groupChunks[0 .. nGroups) in order, fewer
+// than 2^31 - cut into `wavefronts` equal intervals. Entry w = where interval w begins and w - 1 ends: the group that
+// holds that chunk (nGroups behind the last chunk), how many of the group's chunks lie in front of it, and its number.
+static std::vector<int4> splitPlanOf(const int* groupChunks, int nGroups, int wavefronts) {
+    int64_t total = 0;
+    for (int g = 0; g < nGroups; ++g) total += groupChunks[g];
+    const int64_t each = total / wavefronts, rest = total % wavefronts;
+    std::vector<int4> plan((size_t)wavefronts + 1);
+    int g = 0;
+    int64_t before = 0;   // chunks of the groups in front of g
+    for (int w = 0; w <= wavefronts; ++w) {
+        const int64_t x = w * each + w * rest / wavefronts;
+        while (g < nGroups && before + groupChunks[g] <= x) before += groupChunks[g++];
+        plan[(size_t)w] = make_int4(g, (int)(x - before), (int)x, 0);
+    }
+    return plan;
+}
+
 // ---- one search ----------------------------------------------------------------
 struct Search {
     MiopalDb* db;
@@ -873,6 +891,8 @@ struct Search {
         return 0;
     }
 
+    static bool oneStripPair(const ScorePlan& p) { return !p.pairStrips && (p.usePair || p.globalPair); }
+
     // step 8: the packed kernels' arguments, and the unit / boundary buffers of the launch that was planned
     int prepareLaunch(const View* view, const ScorePlan& p, const std::vector<int16_t>& prof, PassBuffers& b, InterseqArgs& ia) {
         void *pp, *vs;
@@ -880,7 +900,8 @@ struct Search {
         RC_TRY(ws->get(kViewScore, (size_t)view->nGroups * kGroupTargets * sizeof(int32_t), &vs));
         RC_TRY(ws->get(kViewOvf, (size_t)view->nGroups * kGroupTargets, &b.vo));
         RC_TRY(ws->get(kCounter, sizeof(int32_t), &b.ct));
-        RC_TRY(ws->stageUpload(pp, prof.data(), prof.size() * sizeof(prof[0]), stream));
+        // (the one-strip pair-table launch sends the profile itself, or has its kernel read the staged copy: planOneStripPair)
+        if (!oneStripPair(p)) RC_TRY(ws->stageUpload(pp, prof.data(), prof.size() * sizeof(prof[0]), stream));
         if (p.mayOverflow) HIP_TRY(hipMemsetAsync(b.ct, 0, sizeof(int32_t), stream));
         ia.pack = view->d_pack;
         ia.groupOff = view->d_groupOff;
@@ -1068,11 +1089,15 @@ struct Search {
     struct OneStripLaunch {
         hipError_t launch = hipSuccess;   // what the launch said
         bool directScatter = false;       // the kernel writes database order itself
+        int pairUnits = 0;                // CUs the launch may use
+        PairFlavour flavour = kPairSwInt16;
     };
-    int launchOneStripPair(const View* view, const ScorePlan& p, InterseqArgs& ia, int32_t* d_score, int32_t* d_endI, int32_t* d_endJ,
-                           bool forked, bool nothingElseWrites, OneStripLaunch* done) {
+    // ... what the launch needs, decided and enqueued in front of the pass's first timing event: the CUs, the column split
+    // with its flags and plan, where the results go, and the profile - so that the timed span is the kernel's, as it was
+    // when prepareLaunch sent the profile
+    int planOneStripPair(const View* view, const ScorePlan& p, const std::vector<int16_t>& prof, InterseqArgs& ia, int32_t* d_score,
+                         int32_t* d_endI, int32_t* d_endJ, bool forked, bool nothingElseWrites, OneStripLaunch* done) {
         bool directScatter = false;
-        void* wc = nullptr;   // (taken and zeroed below, with the column split's flags behind it)
         // The persistent workgroups fill every CU (LDS and registers): a kernel of another
         // stream - the collective that gathers the previous search's scores - would wait for
         // them to leave. MIOPAL_RESERVE_CUS keeps a few CUs out of the launch for it.
@@ -1093,6 +1118,62 @@ struct Search {
             const char* tt = tuned(Tune::TAIL_THROTTLE);
             ia.tailThrottle = (tt ? tt[0] == '1' : uniform) ? (ia.nGroups + blocks * 4 - 1) / (blocks * 4) : 0;
         }
+        const PairFlavour pf = p.globalPair ? kPairGlobalBiased : p.biased ? kPairSwBiased : p.halfFloat ? kPairSwHalf : kPairSwInt16;
+        // Column split (interseq_impl.h): groups of similar length, Smith-Waterman scores of one strip on the
+        // biased flavour, and at least a longest group's chunks for every resident wavefront - no group is cut
+        // twice - or the launch keeps the dynamic hand-out. The plan follows the CUs the launch may use.
+        // MIOPAL_COLUMN_SPLIT: 0 = off, n = forced on n workgroups, "recompute" = forced, nothing handed on.
+        if (pf == kPairSwBiased && !p.locate) {
+            const char* cs = tuned(Tune::COLUMN_SPLIT);
+            const bool recompute = cs && !strcmp(cs, "recompute");
+            const int forced = cs && !recompute ? std::max(0, atoi(cs)) : 0;
+            int64_t chunks = view->totalChunks;
+            for (int g = 0; g < p.firstGroup; ++g) chunks -= view->groupChunksHost[g];
+            // (no empty interval, forced or not: the state of a cut is left for the NEXT wavefront)
+            const int blocks = (int)std::min<int64_t>(forced > 0 ? std::min(forced, pairUnits) : std::max(1, std::min(pairUnits, ia.nGroups)),
+                                                      chunks / kPairWavesPerGroup);
+            const int64_t wavefronts = (int64_t)blocks * kPairWavesPerGroup;
+            // (... and the launch's LDS - table, counters, the profile's copy - within the CU's: true of every table the host
+            // accepts at all, miopalSelfTest(6); said here so that the launch's own refusal is never the one that decides)
+            const bool ldsFits = pairSplitLdsBytes(p.pairRows, p.nSym, p.qPad) <= kCuLdsBytes;
+            if (blocks >= 1 && ldsFits && (recompute || forced > 0 || (!cs && uniform && chunks / wavefronts >= longest))) {
+                void *st, *fl, *pl;
+                RC_TRY(ws->get(kSplitState, (size_t)(wavefronts + 1) * splitStateBytes(p.pairRows), &st));
+                RC_TRY(ws->get(kSplitFlags, (size_t)(wavefronts + 1) * sizeof(int), &fl));
+                RC_TRY(ws->get(kSplitPlan, (size_t)(wavefronts + 1) * sizeof(int4), &pl));
+                // Nothing of this is done per launch. The flags carry the launch's epoch, counted per workspace: zeroed
+                // when they are allocated (all of the allocation: a later, wider launch finds zeros too) and when the
+                // counter would wrap, so that no flag left by an earlier launch - of any plan - equals a new epoch.
+                // (MIOPAL_TEST_SPLIT_EPOCH: this launch's epoch, for the tests of the wrap)
+                if (const char* te = tuned(Tune::TEST_SPLIT_EPOCH)) ws->splitEpoch = (uint32_t)strtoull(te, nullptr, 10) - 1u;
+                if (ws->splitFlagsBorn != ws->born[kSplitFlags] || ws->splitEpoch == UINT32_MAX) {
+                    HIP_TRY(hipMemsetAsync(fl, 0, ws->cap[kSplitFlags], stream));
+                    ws->splitFlagsBorn = ws->born[kSplitFlags];
+                    ws->splitEpoch = 0;
+                }
+                // ... and the plan of the intervals stays on the device for as long as view and width are the same
+                if (ws->splitPlanBorn != ws->born[kSplitPlan] || ws->splitPlanView != view->serial ||
+                    ws->splitPlanFirstGroup != p.firstGroup || ws->splitPlanBlocks != blocks) {
+                    const std::vector<int4> plan = splitPlanOf(view->groupChunksHost.data() + p.firstGroup, ia.nGroups, (int)wavefronts);
+                    RC_TRY(ws->stageUpload(pl, plan.data(), plan.size() * sizeof(int4), stream));
+                    ws->splitPlanBorn = ws->born[kSplitPlan];
+                    ws->splitPlanView = view->serial;
+                    ws->splitPlanFirstGroup = p.firstGroup;
+                    ws->splitPlanBlocks = blocks;
+                }
+                ia.splitMode = recompute ? 2 : 1;
+                ia.splitBlocks = blocks;
+                ia.splitState = (uint4*)st;
+                ia.splitFlags = (int*)fl;
+                ia.splitPlan = (const int4*)pl;
+                ia.splitEpoch = ++ws->splitEpoch;
+            }
+        }
+        // The profile goes into the staging buffer BEFORE the results' place is decided: should staging it (or the plan
+        // above) ever drain the buffer, the generation check below sees that and the scores take the device array -
+        // bindHostOutputs leaves 1 MB of room behind the host scores for these 50 KB, so it does not happen.
+        const void* staged;
+        RC_TRY(ws->stage(prof.data(), prof.size() * sizeof(prof[0]), &staged));
         // Headline fast path: one strip, Smith-Waterman scores, no lane can leave its range, nothing
         // else writes the results (no side jobs, no skipped groups, no windows): the kernel writes
         // database order itself - into the caller's device buffer, or for miopalSearch into the
@@ -1118,39 +1199,33 @@ struct Search {
             ia.overflow = nullptr;
             directScatter = true;
         }
-        const PairFlavour pf = p.globalPair ? kPairGlobalBiased : p.biased ? kPairSwBiased : p.halfFloat ? kPairSwHalf : kPairSwInt16;
-        // Column split (interseq_impl.h): groups of similar length, Smith-Waterman scores of one strip on the
-        // biased flavour, and at least a longest group's chunks for every resident wavefront - no group is cut
-        // twice - or the launch keeps the dynamic hand-out. The plan follows the CUs the launch may use.
-        // MIOPAL_COLUMN_SPLIT: 0 = off, n = forced on n workgroups, "recompute" = forced, nothing handed on.
-        size_t splitFlags = 0;
-        if (pf == kPairSwBiased && !p.locate) {
-            const char* cs = tuned(Tune::COLUMN_SPLIT);
-            const bool recompute = cs && !strcmp(cs, "recompute");
-            const int forced = cs && !recompute ? std::max(0, atoi(cs)) : 0;
-            int64_t chunks = view->totalChunks;
-            for (int g = 0; g < p.firstGroup; ++g) chunks -= view->groupChunksHost[g];
-            // (no empty interval, forced or not: the state of a cut is left for the NEXT wavefront)
-            const int blocks = (int)std::min<int64_t>(forced > 0 ? std::min(forced, pairUnits) : std::max(1, std::min(pairUnits, ia.nGroups)),
-                                                      chunks / kPairWavesPerGroup);
-            const int64_t wavefronts = (int64_t)blocks * kPairWavesPerGroup;
-            if (blocks >= 1 && (recompute || forced > 0 || (!cs && uniform && chunks / wavefronts >= longest))) {
-                void* st;
-                RC_TRY(ws->get(kSplitState, (size_t)(wavefronts + 1) * splitStateBytes(p.pairRows), &st));
-                ia.splitMode = recompute ? 2 : 1;
-                ia.splitBlocks = blocks;
-                ia.chunkPrefix = view->d_chunkPrefix;
-                ia.splitState = (uint4*)st;
-                splitFlags = (size_t)wavefronts + 1;
-            }
+        // On the column split's fast path the kernel reads the staged copy itself, once per workgroup into LDS - no copy
+        // in front of the launch. The staging buffer is not drained before the launch's stream has been waited for
+        // (Workspace::stage), on the asynchronous entry points neither. Every other launch gets its copy on the device.
+        if (ia.splitMode && directScatter) ia.profile = (const int16_t*)staged;
+        else HIP_TRY(hipMemcpyAsync(const_cast<int16_t*>(ia.profile), staged, prof.size() * sizeof(prof[0]), hipMemcpyHostToDevice, stream));
+        done->directScatter = directScatter;
+        done->pairUnits = pairUnits;
+        done->flavour = pf;
+        return 0;
+    }
+
+    // ... and the launch itself
+    int launchOneStripPair(const ScorePlan& p, InterseqArgs& ia, OneStripLaunch* done) {
+        const int pairUnits = done->pairUnits;
+        const PairFlavour pf = done->flavour;
+        if (!ia.splitMode) {
+            // (the dynamic hand-out's counter; the column split takes nothing from it)
+            void* wc;
+            RC_TRY(ws->get(kWorkCounter, sizeof(int), &wc));
+            HIP_TRY(hipMemsetAsync(wc, 0, sizeof(int), stream));
+            ia.workCounter = (int*)wc;
         }
-        RC_TRY(ws->get(kWorkCounter, (1 + splitFlags) * sizeof(int), &wc));
-        HIP_TRY(hipMemsetAsync(wc, 0, (1 + splitFlags) * sizeof(int), stream));
-        ia.workCounter = (int*)wc;
-        if (splitFlags) ia.splitFlags = (int*)wc + 1;
         // (diagnostic builds of the Smith-Waterman kernel, -DMIOPAL_HEADLINE_TIMING=1: the SIMDs' finish times)
         unsigned long long* simdFinish = nullptr;
-        const int finishSlots = 1 + 4 * pairUnits;
+        // (behind the SIMDs of the launch's workgroups: when the pair table stood, latest and sum)
+        const int blocks = ia.splitMode ? ia.splitBlocks : std::max(1, std::min(pairUnits, ia.nGroups));
+        const int finishSlots = 1 + 4 * blocks + 2;
         if (pf == kPairSwBiased && tuned(Tune::STRIP_TIMING)) {
             void* tb;
             RC_TRY(ws->get(kStripTiming, finishSlots * sizeof(unsigned long long), &tb));
@@ -1170,7 +1245,7 @@ struct Search {
             HIP_TRY(hipStreamSynchronize(stream));
             double sum = 0, last = 0, first = 1e30;
             int n = 0;
-            for (int i = 1; i < finishSlots; ++i) {
+            for (int i = 1; i < finishSlots - 2; ++i) {
                 if (t[i] == 0) continue;   // (a build without stamps, or a SIMD the launch left alone)
                 const double us = (double)(t[i] - t[0]) / 100.0;   // 100 MHz ticks -> us
                 sum += us;
@@ -1182,8 +1257,11 @@ struct Search {
                 fprintf(stderr, "[miopal] headline timing (%d SIMDs, %d groups, %d rows): finish mean %.1f us  first %.1f  last %.1f  "
                                 "last - mean %.1f us\n",
                         n, ia.nGroups, p.pairRows, sum / n, first, last, last - sum / n);
+            if (t[finishSlots - 2] != 0)
+                fprintf(stderr, "[miopal] headline prologue (%d workgroups): pair table ready %.2f us after the first wavefront's start "
+                                "(mean), %.2f us (last)\n",
+                        blocks, ((double)t[finishSlots - 1] / blocks - (double)t[0]) / 100.0, (double)(t[finishSlots - 2] - t[0]) / 100.0);
         }
-        done->directScatter = directScatter;
         done->launch = pe;
         return 0;
     }
@@ -1271,6 +1349,10 @@ struct Search {
             RC_TRY(forkSideJobs(p, sideJobs, d_score, d_endI, d_endJ, &forked, spt));
             InterseqArgs ia{};
             RC_TRY(prepareLaunch(view.get(), p, prof, b, ia));
+            const int16_t* const profileDevice = ia.profile;
+            OneStripLaunch done;
+            if (oneStripPair(p))
+                RC_TRY(planOneStripPair(view.get(), p, prof, ia, d_score, d_endI, d_endJ, forked, sideJobs.empty() && jobs.empty(), &done));
             const bool timed = db->profiling.load() != 0;
             EventPair ev;
             if (timed) {
@@ -1312,8 +1394,7 @@ struct Search {
                 else if (p.locate)
                     HIP_TRY(launchDecodeStripKeys(ia.stripKeys, view->nGroups * kGroupTargets, ia.score, ia.endI, ia.endJ, stream));
             } else if (p.usePair || p.globalPair) {
-                OneStripLaunch done;
-                RC_TRY(launchOneStripPair(view.get(), p, ia, d_score, d_endI, d_endJ, forked, sideJobs.empty() && jobs.empty(), &done));
+                RC_TRY(launchOneStripPair(p, ia, &done));
                 directScatter = done.directScatter;
                 const hipError_t pe = done.launch;
                 if (pe != hipSuccess) {
@@ -1335,6 +1416,10 @@ struct Search {
                         directScatter = wroteHost = false;
                         ia.directOut = nullptr;
                         ia.overflow = (uint8_t*)b.vo;
+                    }
+                    if (ia.profile != profileDevice) {   // (... and reads the profile from the device)
+                        ia.profile = profileDevice;
+                        RC_TRY(ws->stageUpload(const_cast<int16_t*>(profileDevice), prof.data(), prof.size() * sizeof(prof[0]), stream));
                     }
                     HIP_TRY(launchInterseq(ia, p.rows, p.waves, p.flavour, p.locate, stream));
                 }

@@ -26,6 +26,12 @@ struct View {
     bool packPending = false;        // lists built and uploaded, residues not packed yet (prefetched view)
     PackArgs pendingPack{};
     size_t packCap = 0, metaCap = 0; // sizes of the two allocations (a refilled handle re-uses them)
+    // one number per view ever built (never 0): what a workspace derived from a view's lists - the column split's plan -
+    // is recognised by it, where an address may come back for another view
+    const uint64_t serial = [] {
+        static std::atomic<uint64_t> last{0};
+        return ++last;
+    }();
     ~View() {
         if (d_pack) (void)hipFree(d_pack);
         if (d_meta) (void)hipFree(d_meta);

@@ -25,6 +25,8 @@ enum Slot {
     // miopalProfileColumns (host_profile.inc): the multiple alignment and the tables, in the workspace the call holds
     // throughout; a chunk's member indices, in the workspace that produced the chunk
     kProfileMsa, kProfileTables, kProfileMember,
+    // column split: the flags of the cuts (epochs: zeroed when allocated, not per launch) and the intervals' plan
+    kSplitFlags, kSplitPlan,
     kSlots
 };
 
@@ -300,6 +302,15 @@ struct Workspace {
     // which lease last asked for a slot (trimTo frees what the search that has just ended did NOT use first)
     uint64_t usedBy[kSlots] = {};
     uint64_t leaseStamp = 0;
+    // which allocation a slot holds (never 0 once allocated): what a search left in a slot for later searches - the column
+    // split's flags and plan - is still there when the number is the one it saw
+    uint64_t born[kSlots] = {};
+    uint64_t allocations = 0;
+    // column split of the one-strip Smith-Waterman kernel (host_search.inc: launchOneStripPair). The flags carry the epoch
+    // of the launch that set them, one counter per workspace; the plan in kSplitPlan was made for this view and width
+    uint32_t splitEpoch = 0;
+    uint64_t splitFlagsBorn = 0, splitPlanBorn = 0, splitPlanView = 0;
+    int splitPlanFirstGroup = 0, splitPlanBlocks = 0;
     std::mutex busy;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timings;  // dominant-kernel launches
     // side stream for the intra-sequence recompute that runs beside the inter-sequence kernel
@@ -462,10 +473,19 @@ struct Workspace {
     // as soon as the call returns
     int stageUpload(void* deviceDst, const void* src, size_t bytes, hipStream_t on) {
         if (bytes == 0) return 0;
+        const void* staged;
+        RC_TRY(stage(src, bytes, &staged));
+        HIP_TRY(hipMemcpyAsync(deviceDst, staged, bytes, hipMemcpyHostToDevice, on));
+        return 0;
+    }
+    // The first half of stageUpload alone: `src` copied into the staging buffer. *staged is device-visible (pinned,
+    // mapped) and stays as it is until the buffer is drained - finishDownloads(), which waits for `stream` first, on
+    // every entry point, the asynchronous ones included - so a kernel enqueued on `stream` before that may read it.
+    int stage(const void* src, size_t bytes, const void** staged) {
         const size_t aligned = (bytes + 255) & ~(size_t)255;
         RC_TRY(reserveStaging(aligned));
         memcpy((char*)pinned + pinnedUsed, src, bytes);
-        HIP_TRY(hipMemcpyAsync(deviceDst, (const char*)pinned + pinnedUsed, bytes, hipMemcpyHostToDevice, on));
+        *staged = (const char*)pinned + pinnedUsed;
         pinnedUsed += aligned;
         return 0;
     }
@@ -503,6 +523,7 @@ struct Workspace {
             size_t want = bytes + bytes / 8 + 256;
             HIP_TRY(hipMalloc(&buf[slot], want));
             cap[slot] = want;
+            born[slot] = ++allocations;
             if (want > (512u << 20) && tuned(Tune::VERBOSE))
                 fprintf(stderr, "miopal: workspace slot %d grows to %zu MiB\n", slot, want >> 20);
         }
@@ -529,6 +550,7 @@ struct Workspace {
             return false;
         }
         cap[slot] = bytes;
+        born[slot] = ++allocations;
         if (bytes > (512u << 20) && tuned(Tune::VERBOSE))
             fprintf(stderr, "miopal: workspace slot %d grows to %zu MiB\n", slot, bytes >> 20);
         *out = buf[slot];

@@ -1141,6 +1141,7 @@ struct StripTimer {
 #endif
 };
 constexpr int kPaceInts = 20;   // 4 SIMDs x 4 slots of progress + 4 slot counters
+static_assert(kPairTailInts == 4 + kPaceInts, "common.h mirrors this");
 struct SimdPace {
     int* mine = nullptr;        // this wavefront's progress word
     const int4* simdRow = nullptr;
@@ -1183,7 +1184,9 @@ struct SimdPace {
 //   -DMIOPAL_HEADLINE_TIMING=1   every wavefront stamps s_memrealtime (100 MHz, one clock for the whole device)
 //                                when it starts and when it leaves; with MIOPAL_STRIP_TIMING=1 the host hands over
 //                                InterseqArgs::stripTiming: [0] the earliest start (min), [1 + 4 * block + simd] the
-//                                last exit on that SIMD (max), and prints how the SIMDs' finish times spread
+//                                last exit on that SIMD (max), and prints how the SIMDs' finish times spread; behind
+//                                them (from slot 1 + 4 * gridDim.x) when the pair table stood: the latest
+//                                workgroup (max) and the sum over the workgroups - the prologue, launch to first column
 #ifndef MIOPAL_HEADLINE_TIMING
 #define MIOPAL_HEADLINE_TIMING 0
 #endif
@@ -1191,14 +1194,17 @@ struct SimdPace {
 // Column split (SPLIT; scores only). The dynamic hand-out's unit is a whole group, so a launch of G groups on S
 // SIMDs lasts ceil(G / S) group-times whatever G is. With SPLIT the chunk sequence of all the launch's groups is
 // cut into W = gridDim.x * kPairWaves equal intervals, one per resident wavefront: wavefront w owns the chunks
-// [w C / W, (w + 1) C / W) of a.chunkPrefix. A group cut by an interval's end is BEGUN by that wavefront (the
+// [w C / W, (w + 1) C / W) of that sequence, and the host says where each interval begins (a.splitPlan: group, chunks
+// into it, chunk number - no search on the device). A group cut by an interval's end is BEGUN by that wavefront (the
 // producer, first thing it does) and FINISHED by the next one (the consumer, last thing it does); between the two
 // the whole groups of the interval. At the cut the producer leaves H[R], E[R] and the running best - rebased to
 // shift 0, so that no scalar state travels - in a.splitState (slot w + 1: [quad][lane] x 16 bytes, the sc1 buffer
-// stores of StripRows) and publishes a.splitFlags[w + 1] (stripPublish / stripPoll, common.h); only the wavefront
-// that reaches the group's last chunk writes its scores. The host takes this mode when an interval is at least as
-// long as the longest group (no group is cut twice, and a consumer arrives nearly a whole interval after its
-// producer has left); forced on smaller launches (MIOPAL_COLUMN_SPLIT) an interval may lie inside one group, whose
+// stores of StripRows) and publishes a.splitFlags[w + 1] (stripPublish / stripPoll, common.h) with the launch's
+// epoch a.splitEpoch, which no flag of an earlier launch or plan can equal: the host zeroes the flags when it
+// allocates them and when its counter wraps, never per launch. Only the wavefront that reaches the group's last chunk
+// writes its scores. The host takes this mode when an interval is at least as long as the longest group (no group is
+// cut twice, and a consumer arrives nearly a whole interval after its producer has left); forced on smaller launches
+// (MIOPAL_COLUMN_SPLIT) an interval may lie inside one group, whose
 // wavefront then consumes and produces. A consumer polls kSplitPolls times at most, then - or at once with
 // a.splitMode == 2 - sweeps the group from column 0 itself: always correct, no launch can hang on a flag.
 // The wavefronts of a SIMD are paced by what is left of their INTERVALS: equal shares that end together.
@@ -1244,7 +1250,45 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
     const uint32_t zero2 = both(LOC ? kLocZero : kBiasedZero);
 
     // build the table: one thread per (pair row, query row); profile = true scores as int16
-    {
+    if constexpr (SPLIT) {
+        // The split form's prologue: the profile comes into LDS with one coalesced load per thread (it may lie in the
+        // host's pinned staging buffer: read once, no copy in front of the launch), then wavefront w builds the pair
+        // rows w, w + 12, ... with lane = query row - two LDS reads and one LDS write per entry, (tA, tB) stepped
+        // along, no division. Same table bytes as the loop below.
+        uint32_t* pw = reinterpret_cast<uint32_t*>(pairs);
+        uint32_t* lw = pw + nSym * nSym * (SLOTS * 4) + kPairTailInts;
+        const uint32_t* gw = reinterpret_cast<const uint32_t*>(a.profile);
+        const int words = nSym * a.qPad / 2;
+#pragma unroll 1
+        for (int idx = threadIdx.x; idx < words; idx += kPairWaves * kLanes) lw[idx] = gw[idx];
+        __syncthreads();
+        const int16_t* lp = reinterpret_cast<const int16_t*>(lw);
+        const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        // (four pair rows at a time: their eight reads are in flight together - one row at a time the loop is a chain of
+        // LDS round trips)
+        constexpr int kAtOnce = 4;
+        const int nRows = nSym * nSym;
+        int tA = 0, tB = w;
+        for (int row = w; row < nRows; row += kPairWaves * kAtOnce) {
+            int vA[kAtOnce], vB[kAtOnce];
+#pragma unroll
+            for (int k = 0; k < kAtOnce; ++k) {
+                for (; tB >= nSym; tB -= nSym) ++tA;
+                // (rows behind the table's end and lanes behind the query's rows: entry 0, not used)
+                const bool on = lane < R && row + k * kPairWaves < nRows;
+                vA[k] = lp[on ? tA * a.qPad + lane : 0];
+                vB[k] = lp[on ? tB * a.qPad + lane : 0];
+                tB += kPairWaves;
+            }
+#pragma unroll
+            for (int k = 0; k < kAtOnce; ++k) {
+                // (scores only: no row bits, and the padding score is its own pattern)
+                const int sA = vA[k] + ext, sB = vB[k] + ext;
+                if (lane < R && row + k * kPairWaves < nRows)
+                    pw[(row + k * kPairWaves) * (SLOTS * 4) + lane] = (uint32_t)(sB * 65536 + sA);
+            }
+        }
+    } else {
         const int16_t* gp = a.profile;
         uint32_t* pw = reinterpret_cast<uint32_t*>(pairs);
         const int total = nSym * nSym * R;
@@ -1263,6 +1307,14 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
     int* simdTaken = reinterpret_cast<int*>(pairs + nSym * nSym * SLOTS);
     if (threadIdx.x < 4) simdTaken[threadIdx.x] = 0;
     __syncthreads();
+#if MIOPAL_HEADLINE_TIMING
+    // (the table stands: the latest workgroup, and the sum over the workgroups for their mean)
+    if (a.stripTiming && threadIdx.x == 0) {
+        const unsigned long long built = __builtin_amdgcn_s_memrealtime();
+        atomicMax(a.stripTiming + 1 + 4 * gridDim.x, built);
+        atomicAdd(a.stripTiming + 2 + 4 * gridDim.x, built);
+    }
+#endif
     // (the wavefronts of a SIMD paced by what is left of their groups: MIOPAL_HEADLINE_PACE above)
     SimdPace pace;
     if (MIOPAL_HEADLINE_PACE) pace.init(simdTaken + 4, lane);
@@ -1280,29 +1332,18 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
     // 2 = the piece that finishes gLo
     int splitW = 0, gLo = 0, gHi = 0, cutLo = 0, cutHi = 0, gWhole = 0, phase = 0, paceAfter = 0;
     if constexpr (SPLIT) {
-        const int64_t* pre = a.chunkPrefix + a.groupBase;
-        // (the launch's chunks are fewer than 2^31 and its wavefronts fewer than 2^15: 32-bit arithmetic throughout)
-        const uint32_t C = (uint32_t)(pre[a.nGroups] - pre[0]);
-        const uint32_t W = kPairWaves * gridDim.x, each = C / W, rest = C % W;
+        // the host's plan (host_search.inc, splitPlanOf; made once per view and launch width, for the forced test
+        // plans too): the two boundaries of the interval, {group, chunks into it, chunk number}
         splitW = kPairWaves * (int)blockIdx.x + wave;
-        const uint32_t lo = splitW * each + splitW * rest / W, hi = (splitW + 1) * each + (splitW + 1) * rest / W;
-        // (groups of similar length: the proportional guess is a step or two off at most)
-        const float groupsPerChunk = (float)a.nGroups / (float)(C > 0 ? C : 1);
-        auto groupOf = [&](uint32_t x) {
-            int k = (int)((float)x * groupsPerChunk);
-            k = k < 0 ? 0 : k > a.nGroups ? a.nGroups : k;
-            while (k > 0 && (uint32_t)(pre[k] - pre[0]) > x) --k;
-            while (k < a.nGroups && (uint32_t)(pre[k + 1] - pre[0]) <= x) ++k;
-            return k;
-        };
+        const int4 from = a.splitPlan[splitW], to = a.splitPlan[splitW + 1];
         // (wave-uniform, and said so: what a vector load returns would keep all that follows in VGPRs)
-        gLo = __builtin_amdgcn_readfirstlane(groupOf(lo));
-        gHi = __builtin_amdgcn_readfirstlane(groupOf(hi));
-        cutLo = __builtin_amdgcn_readfirstlane((int)(lo - (uint32_t)(pre[gLo] - pre[0])));
-        cutHi = __builtin_amdgcn_readfirstlane((int)(hi - (uint32_t)(pre[gHi] - pre[0])));
+        gLo = __builtin_amdgcn_readfirstlane(from.x);
+        gHi = __builtin_amdgcn_readfirstlane(to.x);
+        cutLo = __builtin_amdgcn_readfirstlane(from.y);
+        cutHi = __builtin_amdgcn_readfirstlane(to.y);
         gWhole = cutLo > 0 ? gLo + 1 : gLo;
-        paceAfter = __builtin_amdgcn_readfirstlane((int)(hi - lo));
-        if (lo == hi) phase = 3;
+        paceAfter = __builtin_amdgcn_readfirstlane(to.z - from.z);
+        if (paceAfter == 0) phase = 3;
     }
     for (;;) {
         int g;
@@ -1381,7 +1422,7 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
                 bool there = false;
                 if (a.splitMode != 2) {
                     for (int poll = 0; poll < kSplitPolls && !there; ++poll) {
-                        there = stripPoll(a.splitFlags + splitW) != 0;
+                        there = stripPoll(a.splitFlags + splitW) == (int)a.splitEpoch;   // (a flag of an earlier launch never is)
                         if (!there) __builtin_amdgcn_s_sleep(16);
                     }
                 }
@@ -1546,7 +1587,7 @@ __global__ __launch_bounds__(kPairWaves * kLanes) void interseq_pair_biased_kern
                     };
                     next.store(q, lane, StripU4{word(4 * q), word(4 * q + 1), word(4 * q + 2), word(4 * q + 3)});
                 }
-                stripPublish(a.splitFlags + splitW + 1, 1, lane);
+                stripPublish(a.splitFlags + splitW + 1, (int)a.splitEpoch, lane);
                 continue;                   // (the consumer writes the group's scores)
             }
         }
@@ -1613,9 +1654,11 @@ static hipError_t launchPairBiasedR(const InterseqArgs& a, int computeUnits, hip
 // (flags, state slots, the interval's length) was made for
 template <int R>
 static hipError_t launchPairBiasedSplitR(const InterseqArgs& a, hipStream_t stream) {
-    const size_t lds = PairLayout<R>::bytes(a.nSymbols) + 16 + kPaceInts * sizeof(int);
+    // (table + per-SIMD counters + pacing as above, and the profile the table is built from)
+    const size_t lds = pairSplitLdsBytes(R, a.nSymbols, a.qPad);
+    if (lds > kCuLdsBytes || a.qPad < R || (a.qPad & 7)) return hipErrorInvalidValue;
     if (const hipError_t e = allowFullLds<&interseq_pair_biased_kernel<R, false, true>>(); e != hipSuccess) return e;
-    if (a.splitBlocks < 1 || !a.chunkPrefix || !a.splitState || !a.splitFlags) return hipErrorInvalidValue;
+    if (a.splitBlocks < 1 || !a.splitState || !a.splitFlags || !a.splitPlan || a.splitEpoch == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL((interseq_pair_biased_kernel<R, false, true>), dim3(a.splitBlocks), dim3(kPairWaves * kLanes), lds, stream, a);
     return hipGetLastError();
 }
