@@ -381,8 +381,8 @@ int miopalSearchBatchHits(MiopalDb* db, const unsigned char* queries, const int6
  * strips, within 2 GB: against a handle whose longest target has more than 4 194 304 (HW) or 2 097 152 (SW) residues such
  * a query is refused with MIOPAL_ERR_BAD_ARGUMENT and a message that states the limit, after the range check and before
  * any device call. Queries of at most 64 rows have no such limit.
- * Not part of this call: the start locations and operations of an occurrence, a batch of queries, opalSearchDatabase
- * and the multi-GPU driver. Thread safety as miopalSearch.
+ * Not part of this call: a batch of queries, opalSearchDatabase and the multi-GPU driver (the start locations and
+ * operations of an occurrence: miopalSearchOccurrencesAligned below). Thread safety as miopalSearch.
  */
 int miopalSearchOccurrences(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                             const int* scoreMatrix, int alphabetLength, int mode,
@@ -411,6 +411,77 @@ int miopalSearchPssmOccurrences(MiopalDb* db, const int* rowScores, int queryLen
  * strips per sweep, ceil(queryLength / 64). All 0 for an empty slice.
  */
 void miopalLastOccurrenceRouting(int64_t counts[4]);
+
+/*
+ * miopalSearchOccurrences with the other end of every occurrence: where it starts and, when asked for, its operations
+ * - an adapter is trimmed at the column where it begins, a repeated domain is cut out from start to end, occurrences
+ * are filtered by identity.
+ *
+ * The first five outputs (*count, *targetIndex, *score, *endTarget, *endQuery) are miopalSearchOccurrences' outputs to
+ * the letter: same rule, same order, same bytes. maxHits is honoured before any alignment work
+ * (MIOPAL_ERR_TOO_MANY_HITS with *count filled and nothing allocated).
+ *
+ * Start of the occurrence (v, r, j) of target t: the start rule at the head of oracle/opal_oracle.c, applied to the
+ * occurrence's end cell (r, j) in the place of the target's best. The scan runs over the reversed prefixes q[0..r],
+ * t[0..j] under NW borders; the region is the last row for OPAL_MODE_HW and all cells for OPAL_MODE_SW; candidates are
+ * scanned column by column, row by row inside a column, and a candidate replaces the best only when strictly greater.
+ * The cell (a, b) found gives (*startQuery)[k] = r - a and (*startTarget)[k] = j - b. The degenerate HW optimum is the
+ * checker's: when v equals the border gap over q[0..r] and no real alignment reaches it, the target span is empty,
+ * startTarget = j + 1, startQuery = 0, and the alignment is all query-consuming gaps (OPAL_ALIGN_DEL).
+ * For the target's best occurrence (miopalSearchOccurrences' anchor property) start and operations are those of
+ * miopalSearch(..., OPAL_SEARCH_ALIGNMENT) on that target.
+ *
+ * Operations: the checker's traceback of the global alignment of q[startQuery..r] with t[startTarget..j], one byte
+ * per operation as miopalAlignPairs encodes them; the operations of occurrence k lie in
+ * (*alignments)[(*alignmentOffsets)[k] .. (*alignmentOffsets)[k + 1]); *alignmentOffsets has *count + 1 entries.
+ * alignments == NULL and alignmentOffsets == NULL together: starts only - the reversed scan and the start cells run,
+ * and no direction pass, no walk and no operation traffic follow. Exactly one of the two NULL is
+ * MIOPAL_ERR_BAD_ARGUMENT.
+ *
+ * Outputs: all malloc'ed by the library, sized on the device, freed by the caller; NULL with *count = 0, except
+ * *alignmentOffsets, which then holds the single 0. On any error every output is as it was (MIOPAL_ERR_TOO_MANY_HITS
+ * fills *count). Two calls return the same bytes.
+ * Checks and their order: miopalSearchOccurrences', then null startTarget / startQuery, then the pair alignments /
+ * alignmentOffsets.
+ * On the device: the occurrences stay where the write sweep left them; their target origins are gathered from the
+ * handle's offsets (occurrence_pair_inputs_kernel), and the later passes of a miopalAlignPairs `full` list - the
+ * reversed-prefix scan with the stop rule, the start cells, the direction pass, the walk, the gather - run on them
+ * chunk by chunk in occurrence order, chunks sized as that call sizes them. Nothing of the occurrence list goes up
+ * over PCIe; starts, lengths and operations come down per chunk.
+ * Not part of this call: a batch of queries, opalSearchDatabase and the multi-GPU driver. Thread safety as
+ * miopalSearch.
+ */
+int miopalSearchOccurrencesAligned(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                                   const int* scoreMatrix, int alphabetLength, int mode,
+                                   int64_t start, int64_t end, int minScore, int window, int64_t maxHits,
+                                   int64_t* count, int64_t** targetIndex, int** score, int** endTarget, int** endQuery,
+                                   int** startTarget, int** startQuery,
+                                   unsigned char** alignments, int64_t** alignmentOffsets);
+
+/*
+ * miopalSearchOccurrencesAligned with a position-specific scoring matrix in the place of (query, scoreMatrix):
+ * rowScores and consensus as in miopalSearchPssm. The consensus tells OPAL_ALIGN_MATCH from OPAL_ALIGN_MISMATCH; it is
+ * required when operations are asked for (queryLength > 0), as miopalAlignPairsPssm requires it, and may be NULL for
+ * starts only. The first five outputs are miopalSearchPssmOccurrences'; the later passes are the row-indexed ones of
+ * miopalAlignPairsPssm with this one PSSM in the table. The height limit of the sweep stays.
+ * Checked before any device call in miopalSearchPssmOccurrences' order, with the new null outputs behind its own and
+ * the consensus (missing; a residue out of range) behind them, before the PSSM's height.
+ */
+int miopalSearchPssmOccurrencesAligned(MiopalDb* db, const int* rowScores, const unsigned char* consensus,
+                                       int queryLength, int gapOpen, int gapExt, int alphabetLength, int mode,
+                                       int64_t start, int64_t end, int minScore, int window, int64_t maxHits,
+                                       int64_t* count, int64_t** targetIndex, int** score, int** endTarget,
+                                       int** endQuery, int** startTarget, int** startQuery,
+                                       unsigned char** alignments, int64_t** alignmentOffsets);
+
+/*
+ * What the alignment stage of the calling thread's last miopalSearchOccurrencesAligned / ...PssmOccurrencesAligned
+ * did: counts[0] = occurrences whose direction pass ran one lane each, counts[1] = one wavefront each (both 0 for
+ * starts only: no direction work), counts[2] = chunks of the stage, counts[3] = the longest target window
+ * (endTarget - startTarget + 1) of the call. All 0 without occurrences. miopalLastOccurrenceRouting keeps reporting
+ * the sweeps.
+ */
+void miopalLastOccurrenceAlignRouting(int64_t counts[4]);
 
 /*
  * The significant hits of a query: miopalSearchHits with the cut stated as an E-value, the statistics gathered on the

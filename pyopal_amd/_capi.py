@@ -88,6 +88,7 @@ EXPORTS = [
     "miopalSetTuning", "miopalGetTuning", "miopalDbSetOption", "miopalDbReleaseWorkspaces",
     "miopalProfileColumns", "miopalProfileColumnsPssm",
     "miopalSearchOccurrences", "miopalSearchPssmOccurrences", "miopalLastOccurrenceRouting",
+    "miopalSearchOccurrencesAligned", "miopalSearchPssmOccurrencesAligned", "miopalLastOccurrenceAlignRouting",
     # test hooks
     "miopalTestProfileColumns",
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
@@ -164,6 +165,7 @@ def lib() -> ctypes.CDLL:
             "miopalLastFullRouting": (c_int, []),
             "miopalLastRouting": (None, [p_i64]), "miopalLastPairRouting": (None, [p_i64]),
             "miopalLastBatchRouting": (None, [p_i64]), "miopalLastOccurrenceRouting": (None, [p_i64]),
+            "miopalLastOccurrenceAlignRouting": (None, [p_i64]),
             "miopalLastKernelTime": (c_int, [c_vp, ctypes.POINTER(ctypes.c_float)]),
             "miopalSearch": (c_int, one + middle + [c_vp] * 7),
             "miopalSearchFlat": (c_int, one + middle + flat + [c_vp]),
@@ -201,6 +203,9 @@ def lib() -> ctypes.CDLL:
         # occurrences: no search type; minScore, window, maxHits, one count
         for side, head in (("", one), ("Pssm", pssm)):
             table[f"miopalSearch{side}Occurrences"] = (c_int, head + middle[1:] + [c_int, c_int, c_i64, p_i64] + found)
+        # ... aligned: the PSSM with its consensus; behind the occurrences startT, startQ, operations, their offsets
+        for side, head in (("", one), ("Pssm", pssm_full)):
+            table[f"miopalSearch{side}OccurrencesAligned"] = (c_int, head + middle[1:] + [c_int, c_int, c_i64, p_i64] + found + [pp] * 4)
         for name, (restype, argtypes) in table.items():
             getattr(L, name).restype = restype
             getattr(L, name).argtypes = argtypes
@@ -424,10 +429,28 @@ def pick_occurrences_rows(value: np.ndarray, length, min_score: int, window: int
             "score": _take_malloced(score, total, np.int32), "row": _take_malloced(row, total, np.int32)}
 
 
+def _check_occurrence_rule(algorithm, min_score, window) -> None:
+    """what the C side refuses of an occurrence search's rule, refused before it is reached"""
+    if algorithm not in ("hw", "sw"):
+        raise ValueError(f"occurrences are defined for the algorithms 'hw' and 'sw', not {algorithm!r}")
+    if window is not None and window < 0:
+        raise ValueError("window must not be negative")
+    if algorithm == "sw" and min_score < 1:
+        raise ValueError("min_score must be at least 1 with algorithm 'sw'")
+
+
 def last_occurrence_routing() -> typing.List[int]:
     """miopalLastOccurrenceRouting: [targets of the count sweep, targets of the write sweep, chunks, strips per sweep]"""
     counts = (ctypes.c_int64 * 4)()
     lib().miopalLastOccurrenceRouting(counts)
+    return list(counts)
+
+
+def last_occurrence_align_routing() -> typing.List[int]:
+    """miopalLastOccurrenceAlignRouting: [occurrences aligned one lane each, one wavefront each, chunks of the alignment
+    stage, the longest target window] of the calling thread's last `search_occurrence_alignments` call"""
+    counts = (ctypes.c_int64 * 4)()
+    lib().miopalLastOccurrenceAlignRouting(counts)
     return list(counts)
 
 
@@ -959,13 +982,7 @@ class DeviceDatabase:
     select_hits_rows = staticmethod(select_hits_rows)
 
     def _search_occurrences(self, side: _QuerySide, algorithm, start, end, min_score, window, max_hits):
-        # what the C side refuses, refused before it is reached
-        if algorithm not in ("hw", "sw"):
-            raise ValueError(f"occurrences are defined for the algorithms 'hw' and 'sw', not {algorithm!r}")
-        if window is not None and window < 0:
-            raise ValueError("window must not be negative")
-        if algorithm == "sw" and min_score < 1:
-            raise ValueError("min_score must be at least 1 with algorithm 'sw'")
+        _check_occurrence_rule(algorithm, min_score, window)
         counts = ctypes.c_int64(-1)
         ptrs = _HitPointers()
         rc = getattr(lib(), f"miopalSearch{side.name}Occurrences")(
@@ -997,8 +1014,55 @@ class DeviceDatabase:
         return self._search_occurrences(self._pssm_side(row_scores, None, gap_open, gap_extend), algorithm, start, end,
                                         min_score, window, max_hits)
 
+    def _search_occurrence_alignments(self, side: _QuerySide, algorithm, start, end, min_score, window, max_hits,
+                                      operations):
+        _check_occurrence_rule(algorithm, min_score, window)
+        counts = ctypes.c_int64(-1)
+        ptrs = _HitPointers()
+        start_t, start_q, ops, ops_off = (ctypes.c_void_p() for _ in range(4))
+        rc = getattr(lib(), f"miopalSearch{side.name}OccurrencesAligned")(
+            self._h, *side.queries, *side.scoring, MODE[algorithm], start, self._clamp(end), min_score,
+            side.length if window is None else window, _bound(max_hits), ctypes.byref(counts), *ptrs.refs(),
+            ctypes.byref(start_t), ctypes.byref(start_q), ctypes.byref(ops) if operations else None,
+            ctypes.byref(ops_off) if operations else None)
+        out = self._found(rc, counts, ptrs, "end")
+        n = out["count"]
+        out.update(start_t=_take_malloced(start_t, n, np.int32), start_q=_take_malloced(start_q, n, np.int32))
+        if operations:
+            aoff = _take_malloced(ops_off, n + 1, np.int64)
+            flat = _take_malloced(ops, int(aoff[-1]), np.uint8)
+            out.update(aln_flat=flat, aln_off=aoff, aln=_LazyAlignments(flat, aoff))
+        return out
+
+    def search_occurrence_alignments(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
+                                     algorithm: str = "hw", start: int = 0, end: typing.Optional[int] = None,
+                                     min_score: int = 1, window: typing.Optional[int] = None,
+                                     max_hits: typing.Optional[int] = None,
+                                     operations: bool = True) -> typing.Dict[str, typing.Any]:
+        """miopalSearchOccurrencesAligned: `search_occurrences` with the other end of every occurrence. Returns
+        `search_occurrences`' dict - the same arrays, byte for byte - plus "start_t" and "start_q" (where occurrence k
+        begins in its target and in the query; the checker's start rule applied to the occurrence's end cell) and, with
+        ``operations``, "aln_flat", "aln_off" and "aln": the operations of occurrence k are
+        ``aln_flat[aln_off[k]:aln_off[k + 1]]``, encoded as `align_pairs` encodes them. ``operations=False``: starts
+        only - no direction pass, no walk, no operation traffic - and no "aln*" keys."""
+        return self._search_occurrence_alignments(self._query_side(query, matrix, gap_open, gap_extend), algorithm, start,
+                                                  end, min_score, window, max_hits, operations)
+
+    def search_occurrence_alignments_pssm(self, row_scores: np.ndarray, consensus: typing.Optional[np.ndarray] = None,
+                                          gap_open: int = 3, gap_extend: int = 1, algorithm: str = "hw", start: int = 0,
+                                          end: typing.Optional[int] = None, min_score: int = 1,
+                                          window: typing.Optional[int] = None, max_hits: typing.Optional[int] = None,
+                                          operations: bool = True) -> typing.Dict[str, typing.Any]:
+        """miopalSearchPssmOccurrencesAligned: `search_occurrence_alignments` with a position-specific scoring matrix
+        (``row_scores`` and ``consensus`` as in `search_pssm`) in the place of (query, matrix). The consensus tells
+        matches from mismatches and is required with ``operations`` (the C side refuses a call without one)."""
+        return self._search_occurrence_alignments(
+            self._pssm_side(row_scores, consensus, gap_open, gap_extend, with_consensus=True), algorithm, start, end,
+            min_score, window, max_hits, operations)
+
     pick_occurrences_rows = staticmethod(pick_occurrences_rows)
     last_occurrence_routing = staticmethod(last_occurrence_routing)
+    last_occurrence_align_routing = staticmethod(last_occurrence_align_routing)
 
     def search_significant(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
                            mode: str = "score", algorithm: str = "sw", start: int = 0,

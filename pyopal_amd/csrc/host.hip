@@ -38,6 +38,7 @@
 #include "full_plan_selftest.h"
 #include "launch_layer_selftest.h"
 #include "occurrences.h"
+#include "occurrence_align.h"
 #include "profile_columns.h"
 #include "score_ranges_selftest.h"
 #include "select_columns.h"
@@ -744,6 +745,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_pairs.inc"
 #include "host_profile.inc"
 #include "host_occurrences.inc"
+#include "host_occurrence_align.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                  int64_t end, int* score, int* endTarget, int* endQuery, int* startTarget,
@@ -1008,6 +1010,69 @@ int miopalSearchPssmOccurrences(MiopalDb* db, const int* rowScores, int queryLen
 void miopalLastOccurrenceRouting(int64_t counts[4]) {
     if (!counts) return;
     for (int k = 0; k < 4; ++k) counts[k] = g_lastOccurrenceRouting[k];
+}
+
+// the outputs the aligned forms add: the starts always, the operations and their offsets together or not at all
+static int checkOccurrenceAlignOutputs(int** startTarget, int** startQuery, unsigned char** alignments,
+                                       int64_t** alignmentOffsets) {
+    if (!startTarget || !startQuery) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null start-location outputs");
+    if ((alignments == nullptr) != (alignmentOffsets == nullptr))
+        return fail(MIOPAL_ERR_BAD_ARGUMENT, "alignments and alignmentOffsets: both, or neither (starts only)");
+    return 0;
+}
+
+// miopalSearchOccurrencesAligned: miopalSearchOccurrences' checks in its order, then the new null outputs; the sweeps,
+// and behind them the later passes of a `full` pair list on the occurrences (host_occurrence_align.inc)
+int miopalSearchOccurrencesAligned(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
+                                   const int* scoreMatrix, int alphabetLength, int mode, int64_t start, int64_t end,
+                                   int minScore, int window, int64_t maxHits, int64_t* count, int64_t** targetIndex,
+                                   int** score, int** endTarget, int** endQuery, int** startTarget, int** startQuery,
+                                   unsigned char** alignments, int64_t** alignmentOffsets) {
+    return guarded([&]() -> int {
+    RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, OPAL_SEARCH_SCORE_END, mode, start, end));
+    RC_TRY(checkOccurrenceRule(mode, minScore, window));
+    RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, count, targetIndex, score, endTarget, endQuery));
+    RC_TRY(checkOccurrenceAlignOutputs(startTarget, startQuery, alignments, alignmentOffsets));
+    return searchOccurrencesAlignedImpl(db, query, queryLength, gapOpen, gapExt, scoreMatrix, nullptr, alphabetLength, mode,
+                                        start, end, minScore, window, maxHits, count, targetIndex, score, endTarget,
+                                        endQuery, startTarget, startQuery, alignments, alignmentOffsets);
+    });
+}
+
+// miopalSearchPssmOccurrencesAligned: miopalSearchPssmOccurrences' checks in its order, the new null outputs behind
+// its own and, with operations, the consensus as miopalAlignPairsPssm requires it; then the same
+int miopalSearchPssmOccurrencesAligned(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
+                                       int gapOpen, int gapExt, int alphabetLength, int mode, int64_t start, int64_t end,
+                                       int minScore, int window, int64_t maxHits, int64_t* count, int64_t** targetIndex,
+                                       int** score, int** endTarget, int** endQuery, int** startTarget, int** startQuery,
+                                       unsigned char** alignments, int64_t** alignmentOffsets) {
+    return guarded([&]() -> int {
+    const int Q = queryLength, A = alphabetLength;
+    RC_TRY(PssmQuery::checkBeforeHandle(mode, OPAL_SEARCH_SCORE_END, Q, rowScores, A));
+    RC_TRY(checkOccurrenceRule(mode, minScore, window));
+    RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, count, targetIndex, score, endTarget, endQuery));
+    RC_TRY(checkOccurrenceAlignOutputs(startTarget, startQuery, alignments, alignmentOffsets));
+    if (alignments && Q > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
+    if (consensus)
+        for (int i = 0; i < Q; ++i)
+            if (consensus[i] >= A && consensus[i] != 255)
+                return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %d", consensus[i], i);
+    if (perPairPssmBytes(Q, A) == 0)
+        return fail(MIOPAL_ERR_BAD_ARGUMENT, "a PSSM of %d rows at %d letters does not fit the occurrence sweep's LDS table: "
+                    "(rows + 1) x (letters + 1) x 4 bytes within 64 KB less 256, %d rows at most", Q, A,
+                    (64 * 1024 - 256) / (4 * (A + 1)) - 1);
+    RC_TRY(PssmQuery::checkHandle(db, A, start, end));
+    if (end > start) RC_TRY(checkPssmRange(db, rowScores, Q, A, gapOpen, gapExt));
+    const PssmQuery pssm(rowScores, consensus, Q);
+    return searchOccurrencesAlignedImpl(db, pssm.consensus(), Q, gapOpen, gapExt, nullptr, pssm.rows(), A, mode, start, end,
+                                        minScore, window, maxHits, count, targetIndex, score, endTarget, endQuery,
+                                        startTarget, startQuery, alignments, alignmentOffsets);
+    });
+}
+
+void miopalLastOccurrenceAlignRouting(int64_t counts[4]) {
+    if (!counts) return;
+    for (int k = 0; k < 4; ++k) counts[k] = g_lastOccurrenceAlignRouting[k];
 }
 
 int miopalTestPickOccurrences(const int* value, const int* valueRow, int rows, int64_t stride, const int32_t* length,

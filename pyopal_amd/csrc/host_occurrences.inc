@@ -38,6 +38,19 @@ int checkOccurrenceRule(int mode, int minScore, int window) {
     return 0;
 }
 
+// The occurrences where the write sweep left them, for a stage that goes on with them on the device
+// (host_occurrence_align.inc): entry k is (target[k], score[k], row[k], column[k]), `total` entries each in the
+// workspace of `s`; `hits` holds the same arrays on the host, already down.
+struct OccurrencesOnDevice {
+    Search* s;
+    int64_t total;
+    const int64_t* target;
+    const int32_t *score, *row, *column;
+    const HitArrays* hits;
+    int region;
+};
+using OccurrenceStage = std::function<int(const OccurrencesOnDevice&)>;
+
 }  // namespace
 
 // One sweep (count: list == null, every target of the slice; write: the `listed` targets of `list`), chunk by chunk
@@ -77,11 +90,12 @@ static int occurrenceSweep(Search& s, OccurrenceArgs a, int region, bool write, 
 }
 
 // Behind the entry points' checks. `matrix` or `pssmRows` is the score source (the other null; with rows, `query` is
-// the filler consensus). Nothing is written to the outputs before the last step that can fail.
+// the filler consensus). Nothing is written to the outputs before the last step that can fail. `stage`: what
+// miopalSearchOccurrencesAligned runs behind the download of the occurrences; the two entry points of this file pass none.
 static int searchOccurrencesImpl(MiopalDb* db, const unsigned char* query, int Q, int open, int ext, const int* matrix,
                                  const int* pssmRows, int A, int mode, int64_t start, int64_t end, int minScore,
                                  int window, int64_t maxHits, int64_t* count, int64_t** targetIndex, int** score,
-                                 int** endTarget, int** endQuery) {
+                                 int** endTarget, int** endQuery, const OccurrenceStage* stage = nullptr) {
     for (int k = 0; k < 4; ++k) g_lastOccurrenceRouting[k] = 0;
     const int64_t n = end - start;
     auto nothing = [&] {
@@ -162,6 +176,8 @@ static int searchOccurrencesImpl(MiopalDb* db, const unsigned char* query, int Q
     RC_TRY(ws->stageDownload(hits.endQ, a.outRow, sizeof(int) * (size_t)total));
     RC_TRY(ws->stageDownload(hits.endT, a.outColumn, sizeof(int) * (size_t)total));
     RC_TRY(ws->finishDownloads());
+    // (a stage behind the sweeps takes the occurrences where they are, in the workspace this call holds)
+    if (stage) RC_TRY((*stage)(OccurrencesOnDevice{&s, total, a.outTarget, a.outScore, a.outRow, a.outColumn, &hits, region}));
     *count = total;
     hits.release(targetIndex, score, endTarget, endQuery);
     return 0;

@@ -26,6 +26,9 @@
 // A `full` list may be given a consumer (PairChunkConsumer below; miopalProfileColumns, host_profile.inc): per chunk it
 // is handed what the walk left on the device in the place of gather + download, and the operations never reach the
 // host. Without one the function runs the statements it always ran.
+//
+// The passes behind the forward pass are runLaterPasses below, which the aligned occurrence search
+// (host_occurrence_align.inc) shares: its end cells are the occurrences the write sweep left on the device.
 namespace {
 
 constexpr int64_t kPairChunkMax = int64_t(1) << 22;   // pairs per chunk at most (56-byte jobs, twice)
@@ -75,7 +78,231 @@ struct PairChunkConsumer {
     std::function<int(const PairChunk&)> chunk;
 };
 
+// The later passes of a chunk of end cells that lie on the device - the `full` pair list's and the aligned occurrence
+// search's (host_occurrence_align.inc): what they read, and what they leave on the host. Entry k of the chunk has the
+// score / end cell score[k], endI[k] (query row), endJ[k] (target column); its target begins at residue tOff[k] and
+// its query at qBase[k] of the query buffer (null: 0).
+struct LaterPasses {
+    MiopalDb* db;
+    Search* s;
+    int mode, open, ext, A, totalQuery;
+    int nc, maxL;              // entries; the longest target (prefix) of the chunk
+    bool oneStrip;             // no query (prefix) of the chunk has more than 64 rows
+    int64_t fwdWsStride;       // strip-boundary columns per job of the wavefront-per-pair scan (0: one strip)
+    bool lane, lanePossible, forceLane;   // the scan one lane per entry; the lane kernels may be used at all (then
+                                          // `sorted`, `bins` and `head` are there)
+    const int32_t *score, *endI, *endJ;
+    const int64_t* tOff;
+    const int32_t* qBase;
+    PairJob *jobs, *sorted;
+    int *bins, *head;
+    bool startsOnly;           // stop after the start cells: no direction pass, no walk, no operations
+    bool endsOnHost;           // hs / hi / hj hold the chunk's scores and end cells already: not downloaded again
+    const PairChunkConsumer* consumer;
+    const int64_t* pairs;      // the consumer's view of the entries' positions in the caller's list
+    std::function<long long(int)> idOf;   // what the messages call entry k
+    const char* noun;
+    // host side: nc entries each
+    int32_t *hs, *hi, *hj;
+    std::vector<int32_t>*hsq, *hst, *hlen, *hts;
+    HostBytes* outOps;         // the chunk's operations are appended
+    // what the passes did: the longest target window; the direction pass one lane per entry, and the wavefronts at
+    // the head of its sorted list that went one wavefront per entry (read back only when asked for)
+    int64_t maxWindow = 0;
+    bool traceLane = false;
+    int* traceHeadWaves = nullptr;
+};
+
 }  // namespace
+
+// From the start cells to the chunk's download: reversed-prefix scan with the stop rule -> start cells -> [direction
+// pass -> walk -> gather (or the consumer)] -> one download.
+static int runLaterPasses(LaterPasses& c) {
+    MiopalDb* const db = c.db;
+    Search& s = *c.s;
+    Workspace* const ws = s.ws;
+    hipStream_t const stream = s.stream;
+    const int nc = c.nc, mode = c.mode, open = c.open, ext = c.ext, totalQuery = c.totalQuery;
+    const int64_t nc64 = roundLanes(nc);
+    const bool lane = c.lane, lanePossible = c.lanePossible, forceLane = c.forceLane, oneStrip = c.oneStrip;
+    const int64_t fwdWsStride = c.fwdWsStride;
+    const PairChunkConsumer* const consumer = c.consumer;
+    const void *ps = c.score, *pi = c.endI, *pj = c.endJ, *ptoff = c.tOff, *pqbase = c.qBase;
+    void *pjobs = c.jobs, *psorted = c.sorted, *pbins = c.bins, *phead = c.head;
+    DpRules fr{};
+    rulesForMode(mode, &fr);
+    const PerPairArgs perPair = perPairCommon(db, s, totalQuery, c.A, open, ext);
+    // ---- start cells: reversed prefixes anchored on the end cells -----------------------------------
+    void *rs = nullptr, *ri = nullptr, *rj = nullptr, *psq, *pst, *pmis, *plen, *pts;
+    RC_TRY(ws->get(kStartQ, (size_t)nc * sizeof(int32_t), &psq));
+    RC_TRY(ws->get(kStartT, (size_t)nc * sizeof(int32_t), &pst));
+    RC_TRY(ws->get(kMismatch, 4 * sizeof(int), &pmis));
+    RC_TRY(ws->get(kOpsLen, (size_t)nc * sizeof(int32_t), &plen));
+    RC_TRY(ws->get(kTraceScore, (size_t)nc * sizeof(int32_t), &pts));
+    HIP_TRY(hipMemsetAsync(pmis, 0, 4 * sizeof(int), stream));
+    if (mode != OPAL_MODE_NW) {
+        RC_TRY(ws->get(kRScore, (size_t)nc * sizeof(int32_t), &rs));
+        RC_TRY(ws->get(kRI, (size_t)nc * sizeof(int32_t), &ri));
+        RC_TRY(ws->get(kRJ, (size_t)nc * sizeof(int32_t), &rj));
+        const DpRules rr{1, 1, 0, fr.region};
+        if (lane) {
+            HIP_TRY(launchReverseJobs(nc, (const int32_t*)ps, (const int32_t*)pi, (const int32_t*)pj, (const int64_t*)ptoff,
+                                      packRules(rr), 0, (PairJob*)pjobs, stream, (const int32_t*)pqbase));
+            PerPairArgs pa = perPair;
+            pa.jobs = (const PairJob*)pjobs;
+            if (!oneStrip) {
+                // prefixes of similar length share a wavefront
+                HIP_TRY(launchSortJobsByLength((const PairJob*)pjobs, nc, c.maxL, (int*)pbins, (PairJob*)psorted, stream));
+                pa.jobs = (const PairJob*)psorted;
+                void* pb;
+                RC_TRY(ws->get(kPairListBoundary, boundaryBytes(nc, c.maxL), &pb));
+                pa.boundary = (int2*)pb;
+                pa.boundaryStride = c.maxL;
+            }
+            pa.nJobs = nc;
+            pa.score = (int32_t*)rs;
+            pa.endI = (int32_t*)ri;
+            pa.endJ = (int32_t*)rj;
+            pa.reversed = 1;
+            HIP_TRY(launchPerPair(pa, fr.region, stream));
+        } else {
+            HIP_TRY(launchReverseJobs(nc, (const int32_t*)ps, (const int32_t*)pi, (const int32_t*)pj, (const int64_t*)ptoff,
+                                      packRules(rr), fwdWsStride, (PairJob*)pjobs, stream, (const int32_t*)pqbase));
+            RC_TRY(s.runDeviceJobs((const PairJob*)pjobs, nc, (int32_t*)rs, (int32_t*)ri, (int32_t*)rj, false, nullptr, fwdWsStride));
+        }
+    }
+    HIP_TRY(launchStartCells(nc, mode, open, ext, (const int32_t*)ps, (const int32_t*)pi, (const int32_t*)pj,
+                             (const int32_t*)rs, (const int32_t*)ri, (const int32_t*)rj, (int32_t*)psq, (int32_t*)pst,
+                             (int*)pmis, stream));
+    // the traceback's slots are sized by the chunk's longest target window and tallest query window
+    int checks[3] = {0, 0, 0};
+    RC_TRY(ws->stageDownload(checks, pmis, sizeof checks));
+    if (c.startsOnly) {
+        // ... and nothing follows the start cells: they come down with the checks
+        c.hsq->resize((size_t)nc); c.hst->resize((size_t)nc);
+        RC_TRY(ws->stageDownload(c.hsq->data(), psq, (size_t)nc * sizeof(int32_t)));
+        RC_TRY(ws->stageDownload(c.hst->data(), pst, (size_t)nc * sizeof(int32_t)));
+        if (!c.endsOnHost) {
+            RC_TRY(ws->stageDownload(c.hs, ps, (size_t)nc * sizeof(int32_t)));
+            RC_TRY(ws->stageDownload(c.hi, pi, (size_t)nc * sizeof(int32_t)));
+            RC_TRY(ws->stageDownload(c.hj, pj, (size_t)nc * sizeof(int32_t)));
+        }
+    }
+    RC_TRY(ws->finishDownloads());
+    if (checks[0])
+        return fail(MIOPAL_ERR_INTERNAL, "reverse pass disagrees with the forward score for %s %lld", c.noun, c.idOf(checks[0] - 1));
+    const int64_t maxWindow = std::max(checks[1], 1), windowRows = std::max(checks[2], 1);
+    c.maxWindow = maxWindow;
+    if (c.startsOnly) return 0;
+    const int64_t windowStrips = (windowRows + kLanes - 1) / kLanes;
+    const int64_t slotDir = miopal::slotDir(windowStrips, maxWindow);
+    const int64_t slotOps = miopal::slotOps(windowRows, maxWindow);
+    const int64_t traceWsStride = windowStrips > 1 ? maxWindow : 0;
+    // ---- directions: one lane or one wavefront per pair (full_plan.h; ms; the chunk is one batch) ------
+    const double cells = traceCells(windowStrips, maxWindow);
+    const bool traceLane = lanePossible && (forceLane || traceLaneMs(1, (double)nc, cells) <= traceWaveMs(1, (double)nc, cells));
+    c.traceLane = traceLane;
+    void *pd, *pslots, *pcompact = nullptr, *pblock, *ptotals;
+    RC_TRY(ws->get(kOps, (size_t)(nc * slotOps), &pslots));
+    if (!consumer) RC_TRY(ws->get(kCompactOps, (size_t)(nc * slotOps), &pcompact));
+    RC_TRY(ws->get(kOpsOff, (size_t)((nc + 255) / 256) * sizeof(int64_t), &pblock));
+    RC_TRY(ws->get(kOpsTotals, 2 * sizeof(int64_t), &ptotals));
+    HIP_TRY(hipMemsetAsync(ptotals, 0, 2 * sizeof(int64_t), stream));
+    HIP_TRY(launchTraceJobs(nc, packRules(DpRules{1, 1, 0, kLastCell}), (const int32_t*)psq, (const int32_t*)pst,
+                            (const int32_t*)pi, (const int32_t*)pj, (const int64_t*)ptoff, slotDir, traceWsStride,
+                            (PairJob*)pjobs, stream, (const int32_t*)pqbase));
+    WalkArgs wa{};
+    bool headUsed = false;
+    if (traceLane) {
+        const int64_t slotDirUsed = miopal::slotDirUsed(kDirLane, windowStrips, maxWindow);   // two rows per byte
+        if (!ws->tryGet(kDirs, (size_t)(nc64 * slotDirUsed), &pd))
+            return fail(MIOPAL_ERR_HIP, "out of device memory for the traceback workspace");
+        int64_t maxHead = std::min<int64_t>((1ll << 30) / slotDir / kLanes, nc64 / kLanes);
+        void* pheadDirs = nullptr;
+        if (maxHead > 0 && !ws->tryGet(kHeadDirs, (size_t)(maxHead * kLanes * slotDir), &pheadDirs)) maxHead = 0;
+        HIP_TRY(hipMemsetAsync(phead, 0, sizeof(int), stream));
+        HIP_TRY(launchSortJobsByLength((const PairJob*)pjobs, nc, (int)maxWindow, (int*)pbins, (PairJob*)psorted, stream,
+                                       maxHead > 0 ? (int*)phead : nullptr, (int)maxHead, (int)windowRows));
+        PerPairArgs pa = perPair;
+        if (maxHead > 0) {
+            // outliers at the head of the sorted list: one wavefront per pair
+            const int nh = (int)std::min<int64_t>(nc, maxHead * kLanes);
+            RC_TRY(s.runDeviceJobs((const PairJob*)psorted, nh, (int32_t*)pts, nullptr, nullptr, true, (uint8_t*)pheadDirs,
+                                   traceWsStride, (const int*)phead, slotDir));
+            pa.skipWaves = (const int*)phead;
+            wa.headWaves = (const int*)phead;
+            wa.headDirs = (const uint8_t*)pheadDirs;
+            wa.headDirStride = slotDir;
+            headUsed = true;
+        }
+        pa.jobs = (const PairJob*)psorted;
+        pa.nJobs = nc;
+        pa.dirs = (uint8_t*)pd;
+        pa.score = (int32_t*)pts;
+        pa.dirWaveStride = slotDirUsed * kLanes;
+        pa.dirStripColumns = dirStripColumns(false, maxWindow);
+        if (windowStrips > 1) {
+            void* pb;
+            RC_TRY(ws->get(kPairListBoundary, boundaryBytes(nc, maxWindow), &pb));
+            pa.boundary = (int2*)pb;
+            pa.boundaryStride = maxWindow;
+        }
+        HIP_TRY(launchPerPair(pa, kPerPairTrace, stream));
+        wa.slotByOut = 1;
+        wa.dirWaveStride = pa.dirWaveStride;
+        wa.dirStripColumns = pa.dirStripColumns;
+    } else {
+        if (!ws->tryGet(kDirs, (size_t)(nc * slotDir), &pd))
+            return fail(MIOPAL_ERR_HIP, "out of device memory for the traceback workspace");
+        RC_TRY(s.runDeviceJobs((const PairJob*)pjobs, nc, (int32_t*)pts, nullptr, nullptr, true, (uint8_t*)pd, traceWsStride));
+    }
+    fillWalk(&wa, (const PairJob*)(traceLane ? psorted : pjobs), nc, db, s, totalQuery, pd, pslots, slotOps, plen);
+    HIP_TRY(launchWalk(wa, stream));
+    if (consumer) {
+        // (the operations stay where the walk left them: the consumer's kernels read the slots)
+        RC_TRY(consumer->chunk(PairChunk{ws, nc, c.pairs, (const uint8_t*)pslots, slotOps,
+                                         (const int32_t*)plen, (const int32_t*)psq, (const int32_t*)pst,
+                                         (const int64_t*)ptoff}));
+    } else {
+        HIP_TRY(launchGatherOps(nc, (const uint8_t*)pslots, slotOps, (const int32_t*)plen, (int64_t*)pblock,
+                                (const int64_t*)ptotals, (int64_t*)ptotals + 1, (uint8_t*)pcompact, stream));
+    }
+    // ---- one download: the small arrays (they carry the total), then the operations ---------------------
+    std::vector<int32_t>&hsq = *c.hsq, &hst = *c.hst, &hlen = *c.hlen, &hts = *c.hts;
+    hsq.resize((size_t)nc); hst.resize((size_t)nc); hlen.resize((size_t)nc); hts.resize((size_t)nc);
+    int64_t total = 0;
+    if (!consumer) RC_TRY(ws->stageDownload(&total, (const int64_t*)ptotals + 1, sizeof(int64_t)));
+    if (!c.endsOnHost) {
+        RC_TRY(ws->stageDownload(c.hs, ps, (size_t)nc * sizeof(int32_t)));
+        RC_TRY(ws->stageDownload(c.hi, pi, (size_t)nc * sizeof(int32_t)));
+        RC_TRY(ws->stageDownload(c.hj, pj, (size_t)nc * sizeof(int32_t)));
+    }
+    RC_TRY(ws->stageDownload(hsq.data(), psq, (size_t)nc * sizeof(int32_t)));
+    RC_TRY(ws->stageDownload(hst.data(), pst, (size_t)nc * sizeof(int32_t)));
+    RC_TRY(ws->stageDownload(hlen.data(), plen, (size_t)nc * sizeof(int32_t)));
+    RC_TRY(ws->stageDownload(hts.data(), pts, (size_t)nc * sizeof(int32_t)));
+    if (c.traceHeadWaves) {
+        *c.traceHeadWaves = 0;
+        if (headUsed) RC_TRY(ws->stageDownload(c.traceHeadWaves, phead, sizeof(int)));
+    }
+    RC_TRY(ws->finishDownloads());
+    if (!consumer) {
+        if (total < 0 || total > nc * slotOps) return fail(MIOPAL_ERR_INTERNAL, "bad operation count");
+        const size_t at = c.outOps->size;
+        if (!c.outOps->resize(at + (size_t)total)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+        RC_TRY(ws->stageDownload(c.outOps->data + at, pcompact, (size_t)total));
+        RC_TRY(ws->finishDownloads());
+    }
+    int64_t sum = 0;
+    for (int k = 0; k < nc; ++k) {
+        if (c.hi[k] >= 0 && c.hj[k] >= 0 && hts[(size_t)k] != c.hs[k])
+            return fail(MIOPAL_ERR_INTERNAL, "traceback score %d differs from search score %d for %s %lld",
+                        hts[(size_t)k], c.hs[k], c.noun, c.idOf(k));
+        sum += hlen[(size_t)k];
+    }
+    if (!consumer && sum != total) return fail(MIOPAL_ERR_INTERNAL, "operation offsets disagree with the device");
+    return 0;
+}
 
 static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
                           const int32_t* pairQuery, const int64_t* pairTarget, int64_t nPairs, int open, int ext,
@@ -338,157 +565,26 @@ static int alignPairsImpl(MiopalDb* db, const unsigned char* queries, const int6
                 }
                 RC_TRY(ws->finishDownloads());
             } else {
-                // ---- start cells: reversed prefixes anchored on the end cells -----------------------------------
-                void *rs = nullptr, *ri = nullptr, *rj = nullptr, *psq, *pst, *pmis, *plen, *pts;
-                RC_TRY(ws->get(kStartQ, (size_t)nc * sizeof(int32_t), &psq));
-                RC_TRY(ws->get(kStartT, (size_t)nc * sizeof(int32_t), &pst));
-                RC_TRY(ws->get(kMismatch, 4 * sizeof(int), &pmis));
-                RC_TRY(ws->get(kOpsLen, (size_t)nc * sizeof(int32_t), &plen));
-                RC_TRY(ws->get(kTraceScore, (size_t)nc * sizeof(int32_t), &pts));
-                HIP_TRY(hipMemsetAsync(pmis, 0, 4 * sizeof(int), stream));
-                if (mode != OPAL_MODE_NW) {
-                    RC_TRY(ws->get(kRScore, (size_t)nc * sizeof(int32_t), &rs));
-                    RC_TRY(ws->get(kRI, (size_t)nc * sizeof(int32_t), &ri));
-                    RC_TRY(ws->get(kRJ, (size_t)nc * sizeof(int32_t), &rj));
-                    const DpRules rr{1, 1, 0, fr.region};
-                    if (lane) {
-                        HIP_TRY(launchReverseJobs(nc, (const int32_t*)ps, (const int32_t*)pi, (const int32_t*)pj, (const int64_t*)ptoff,
-                                                  packRules(rr), 0, (PairJob*)pjobs, stream, (const int32_t*)pqbase));
-                        PerPairArgs pa = perPair;
-                        pa.jobs = (const PairJob*)pjobs;
-                        if (!oneStrip) {
-                            // prefixes of similar length share a wavefront
-                            HIP_TRY(launchSortJobsByLength((const PairJob*)pjobs, nc, ch.maxL, (int*)pbins, (PairJob*)psorted, stream));
-                            pa.jobs = (const PairJob*)psorted;
-                            void* pb;
-                            RC_TRY(ws->get(kPairListBoundary, boundaryBytes(nc, ch.maxL), &pb));
-                            pa.boundary = (int2*)pb;
-                            pa.boundaryStride = ch.maxL;
-                        }
-                        pa.nJobs = nc;
-                        pa.score = (int32_t*)rs;
-                        pa.endI = (int32_t*)ri;
-                        pa.endJ = (int32_t*)rj;
-                        pa.reversed = 1;
-                        HIP_TRY(launchPerPair(pa, fr.region, stream));
-                    } else {
-                        HIP_TRY(launchReverseJobs(nc, (const int32_t*)ps, (const int32_t*)pi, (const int32_t*)pj, (const int64_t*)ptoff,
-                                                  packRules(rr), fwdWsStride, (PairJob*)pjobs, stream, (const int32_t*)pqbase));
-                        RC_TRY(s.runDeviceJobs((const PairJob*)pjobs, nc, (int32_t*)rs, (int32_t*)ri, (int32_t*)rj, false, nullptr, fwdWsStride));
-                    }
-                }
-                HIP_TRY(launchStartCells(nc, mode, open, ext, (const int32_t*)ps, (const int32_t*)pi, (const int32_t*)pj,
-                                         (const int32_t*)rs, (const int32_t*)ri, (const int32_t*)rj, (int32_t*)psq, (int32_t*)pst,
-                                         (int*)pmis, stream));
-                // the traceback's slots are sized by the chunk's longest target window and tallest query window
-                int checks[3] = {0, 0, 0};
-                RC_TRY(ws->stageDownload(checks, pmis, sizeof checks));
-                RC_TRY(ws->finishDownloads());
-                if (checks[0])
-                    return fail(MIOPAL_ERR_INTERNAL, "reverse pass disagrees with the forward score for pair %lld",
-                                (long long)order[(size_t)(ch.first + checks[0] - 1)]);
-                const int64_t maxWindow = std::max(checks[1], 1), windowRows = std::max(checks[2], 1);
-                const int64_t windowStrips = (windowRows + kLanes - 1) / kLanes;
-                const int64_t slotDir = miopal::slotDir(windowStrips, maxWindow);
-                const int64_t slotOps = miopal::slotOps(windowRows, maxWindow);
-                const int64_t traceWsStride = windowStrips > 1 ? maxWindow : 0;
-                // ---- directions: one lane or one wavefront per pair (full_plan.h; ms; the chunk is one batch) ------
-                const double cells = traceCells(windowStrips, maxWindow);
-                const bool traceLane = lanePossible && (forceLane || traceLaneMs(1, (double)nc, cells) <= traceWaveMs(1, (double)nc, cells));
-                void *pd, *pslots, *pcompact = nullptr, *pblock, *ptotals;
-                RC_TRY(ws->get(kOps, (size_t)(nc * slotOps), &pslots));
-                if (!consumer) RC_TRY(ws->get(kCompactOps, (size_t)(nc * slotOps), &pcompact));
-                RC_TRY(ws->get(kOpsOff, (size_t)((nc + 255) / 256) * sizeof(int64_t), &pblock));
-                RC_TRY(ws->get(kOpsTotals, 2 * sizeof(int64_t), &ptotals));
-                HIP_TRY(hipMemsetAsync(ptotals, 0, 2 * sizeof(int64_t), stream));
-                HIP_TRY(launchTraceJobs(nc, packRules(DpRules{1, 1, 0, kLastCell}), (const int32_t*)psq, (const int32_t*)pst,
-                                        (const int32_t*)pi, (const int32_t*)pj, (const int64_t*)ptoff, slotDir, traceWsStride,
-                                        (PairJob*)pjobs, stream, (const int32_t*)pqbase));
-                WalkArgs wa{};
-                if (traceLane) {
-                    const int64_t slotDirUsed = miopal::slotDirUsed(kDirLane, windowStrips, maxWindow);   // two rows per byte
-                    if (!ws->tryGet(kDirs, (size_t)(nc64 * slotDirUsed), &pd))
-                        return fail(MIOPAL_ERR_HIP, "out of device memory for the traceback workspace");
-                    int64_t maxHead = std::min<int64_t>((1ll << 30) / slotDir / kLanes, nc64 / kLanes);
-                    void* pheadDirs = nullptr;
-                    if (maxHead > 0 && !ws->tryGet(kHeadDirs, (size_t)(maxHead * kLanes * slotDir), &pheadDirs)) maxHead = 0;
-                    HIP_TRY(hipMemsetAsync(phead, 0, sizeof(int), stream));
-                    HIP_TRY(launchSortJobsByLength((const PairJob*)pjobs, nc, (int)maxWindow, (int*)pbins, (PairJob*)psorted, stream,
-                                                   maxHead > 0 ? (int*)phead : nullptr, (int)maxHead, (int)windowRows));
-                    PerPairArgs pa = perPair;
-                    if (maxHead > 0) {
-                        // outliers at the head of the sorted list: one wavefront per pair
-                        const int nh = (int)std::min<int64_t>(nc, maxHead * kLanes);
-                        RC_TRY(s.runDeviceJobs((const PairJob*)psorted, nh, (int32_t*)pts, nullptr, nullptr, true, (uint8_t*)pheadDirs,
-                                               traceWsStride, (const int*)phead, slotDir));
-                        pa.skipWaves = (const int*)phead;
-                        wa.headWaves = (const int*)phead;
-                        wa.headDirs = (const uint8_t*)pheadDirs;
-                        wa.headDirStride = slotDir;
-                    }
-                    pa.jobs = (const PairJob*)psorted;
-                    pa.nJobs = nc;
-                    pa.dirs = (uint8_t*)pd;
-                    pa.score = (int32_t*)pts;
-                    pa.dirWaveStride = slotDirUsed * kLanes;
-                    pa.dirStripColumns = dirStripColumns(false, maxWindow);
-                    if (windowStrips > 1) {
-                        void* pb;
-                        RC_TRY(ws->get(kPairListBoundary, boundaryBytes(nc, maxWindow), &pb));
-                        pa.boundary = (int2*)pb;
-                        pa.boundaryStride = maxWindow;
-                    }
-                    HIP_TRY(launchPerPair(pa, kPerPairTrace, stream));
-                    wa.slotByOut = 1;
-                    wa.dirWaveStride = pa.dirWaveStride;
-                    wa.dirStripColumns = pa.dirStripColumns;
-                } else {
-                    if (!ws->tryGet(kDirs, (size_t)(nc * slotDir), &pd))
-                        return fail(MIOPAL_ERR_HIP, "out of device memory for the traceback workspace");
-                    RC_TRY(s.runDeviceJobs((const PairJob*)pjobs, nc, (int32_t*)pts, nullptr, nullptr, true, (uint8_t*)pd, traceWsStride));
-                }
-                fillWalk(&wa, (const PairJob*)(traceLane ? psorted : pjobs), nc, db, s, totalQuery, pd, pslots, slotOps, plen);
-                HIP_TRY(launchWalk(wa, stream));
-                if (consumer) {
-                    // (the operations stay where the walk left them: the consumer's kernels read the slots)
-                    RC_TRY(consumer->chunk(PairChunk{ws, nc, order.data() + ch.first, (const uint8_t*)pslots, slotOps,
-                                                     (const int32_t*)plen, (const int32_t*)psq, (const int32_t*)pst,
-                                                     (const int64_t*)ptoff}));
-                } else {
-                    HIP_TRY(launchGatherOps(nc, (const uint8_t*)pslots, slotOps, (const int32_t*)plen, (int64_t*)pblock,
-                                            (const int64_t*)ptotals, (int64_t*)ptotals + 1, (uint8_t*)pcompact, stream));
-                }
-                // ---- one download: the small arrays (they carry the total), then the operations ---------------------
-                hsq.resize((size_t)nc); hst.resize((size_t)nc); hlen.resize((size_t)nc); hts.resize((size_t)nc);
-                int64_t total = 0;
-                if (!consumer) RC_TRY(ws->stageDownload(&total, (const int64_t*)ptotals + 1, sizeof(int64_t)));
-                RC_TRY(ws->stageDownload(hs.data(), ps, (size_t)nc * sizeof(int32_t)));
-                RC_TRY(ws->stageDownload(hi.data(), pi, (size_t)nc * sizeof(int32_t)));
-                RC_TRY(ws->stageDownload(hj.data(), pj, (size_t)nc * sizeof(int32_t)));
-                RC_TRY(ws->stageDownload(hsq.data(), psq, (size_t)nc * sizeof(int32_t)));
-                RC_TRY(ws->stageDownload(hst.data(), pst, (size_t)nc * sizeof(int32_t)));
-                RC_TRY(ws->stageDownload(hlen.data(), plen, (size_t)nc * sizeof(int32_t)));
-                RC_TRY(ws->stageDownload(hts.data(), pts, (size_t)nc * sizeof(int32_t)));
-                RC_TRY(ws->finishDownloads());
-                if (!consumer) {
-                    if (total < 0 || total > nc * slotOps) return fail(MIOPAL_ERR_INTERNAL, "bad operation count");
-                    const size_t at = outOps->size;
-                    if (!outOps->resize(at + (size_t)total)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
-                    RC_TRY(ws->stageDownload(outOps->data + at, pcompact, (size_t)total));
-                    RC_TRY(ws->finishDownloads());
-                }
-                int64_t sum = 0;
+                // ---- the later passes, from the start cells to the chunk's download (runLaterPasses) -------------
+                LaterPasses lp{};
+                lp.db = db; lp.s = &s;
+                lp.mode = mode; lp.open = open; lp.ext = ext; lp.A = A; lp.totalQuery = totalQuery;
+                lp.nc = nc; lp.maxL = ch.maxL; lp.oneStrip = oneStrip; lp.fwdWsStride = fwdWsStride;
+                lp.lane = lane; lp.lanePossible = lanePossible; lp.forceLane = forceLane;
+                lp.score = (const int32_t*)ps; lp.endI = (const int32_t*)pi; lp.endJ = (const int32_t*)pj;
+                lp.tOff = (const int64_t*)ptoff; lp.qBase = (const int32_t*)pqbase;
+                lp.jobs = (PairJob*)pjobs; lp.sorted = (PairJob*)psorted; lp.bins = (int*)pbins; lp.head = (int*)phead;
+                lp.consumer = consumer; lp.pairs = order.data() + ch.first; lp.noun = "pair";
+                lp.idOf = [&](int k) { return (long long)order[(size_t)(ch.first + k)]; };
+                lp.hs = hs.data(); lp.hi = hi.data(); lp.hj = hj.data();
+                lp.hsq = &hsq; lp.hst = &hst; lp.hlen = &hlen; lp.hts = &hts; lp.outOps = outOps;
+                RC_TRY(runLaterPasses(lp));
                 for (int k = 0; k < nc; ++k) {
                     const int64_t p = order[(size_t)(ch.first + k)];
-                    if (hi[(size_t)k] >= 0 && hj[(size_t)k] >= 0 && hts[(size_t)k] != hs[(size_t)k])
-                        return fail(MIOPAL_ERR_INTERNAL, "traceback score %d differs from search score %d for pair %lld",
-                                    hts[(size_t)k], hs[(size_t)k], (long long)p);
                     startQuery[p] = hsq[(size_t)k];
                     startTarget[p] = hst[(size_t)k];
                     lensByPair[(size_t)p] = hlen[(size_t)k];
-                    sum += hlen[(size_t)k];
                 }
-                if (!consumer && sum != total) return fail(MIOPAL_ERR_INTERNAL, "operation offsets disagree with the device");
             }
             for (int k = 0; k < nc; ++k) {
                 const int64_t p = order[(size_t)(ch.first + k)];
