@@ -21,6 +21,14 @@ constexpr int kNegInf = INT32_MIN / 4;
 constexpr int kJobsPerBlock = 4;
 constexpr int kMatStride = kMaxAlphabet + 1;  // odd stride: rows fall on different LDS banks
 
+// The top border of the first strip is kept as two running sums, one gap of k + 1 residues (open + k ext) and k + 1
+// one-residue gaps ((k + 1) open), and the border cell is the cheaper of the two (common.h borderGap). The second sum
+// only ever wins when open < ext, and (k + 1) open leaves 32 bits after 2^31 / open steps - eight columns at the
+// largest open the range check admits, where it came back negative and won the min. What the second sum grows by per
+// column: open when it can win (then (k + 1) open < (k + 1) ext, within the range check), else ext, which keeps it
+// equal to the first.
+static __device__ __forceinline__ int topManyStep(int open, int ext) { return open < ext ? open : ext; }
+
 // ---- the row-indexed forms (PSSM: a position-specific scoring matrix, miopalSearchPssm) -----------------------
 // The plain kernels stage the [A][A] matrix once per workgroup and a lane reads the matrix row of its query residue,
 // srow = smat + qres * kMatStride. With a.rows the score of row i is a.rows[i][.] - there is no residue to index a
@@ -84,6 +92,7 @@ __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_kernel(Intras
     const int hFloor = floor0 ? 0 : INT32_MIN;   // Smith-Waterman floor as a max that is always there
     const int region = (job.rules >> 4) & 3;
     const int open = a.gapOpen, ext = a.gapExt;
+    const int manyStep = topManyStep(open, ext);
 
     int best = floor0 ? 0 : INT32_MIN;
     int bi = -1, bj = -1;
@@ -178,7 +187,7 @@ __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_kernel(Intras
                             hTop = topGap ? -min(topOne, topMany) : 0;
                             fTop = kNegInf;
                             topOne += ext;
-                            topMany += open;
+                            topMany += manyStep;
                         } else {
                             bH = __builtin_amdgcn_update_dpp(bH, bH, kRol1, 0xf, 0xf, false);
                             bF = __builtin_amdgcn_update_dpp(bF, bF, kRol1, 0xf, 0xf, false);
@@ -301,6 +310,7 @@ __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_wide_kernel(I
     const int hFloor = floor0 ? 0 : INT32_MIN;
     const int region = (job.rules >> 4) & 3;
     const int open = a.gapOpen, ext = a.gapExt;
+    const int manyStep = topManyStep(open, ext);
     int best = floor0 ? 0 : INT32_MIN;
     int bi = -1, bj = -1;
     if (Q > 0 && L > 0) {
@@ -360,9 +370,9 @@ __global__ __launch_bounds__(kJobsPerBlock * kLanes) void intraseq_wide_kernel(I
                 tres = tnext;
                 // the row above (lane 0: the top border of columns 2 k and 2 k + 1)
                 const int hTop0 = topGap ? -min(topOne, topMany) : 0;
-                const int hTop1 = topGap ? -min(topOne + ext, topMany + open) : 0;
+                const int hTop1 = topGap ? -min(topOne + ext, topMany + manyStep) : 0;
                 topOne += 2 * ext;
-                topMany += 2 * open;
+                topMany += 2 * manyStep;
                 const int hUp0 = __builtin_amdgcn_update_dpp(hTop0, hA, kShr1, 0xf, 0xf, false);
                 const int fUp0 = __builtin_amdgcn_update_dpp(kNegInf, fA, kShr1, 0xf, 0xf, false);
                 const int hUp1 = __builtin_amdgcn_update_dpp(hTop1, hB, kShr1, 0xf, 0xf, false);
@@ -480,6 +490,7 @@ __global__ __launch_bounds__(PSSM_WAVES ? PSSM_WAVES * kLanes : 1024) void intra
     const int hFloor = floor0 ? 0 : INT32_MIN;
     const int region = (job.rules >> 4) & 3;
     const int open = a.gapOpen, ext = a.gapExt;
+    const int manyStep = topManyStep(open, ext);
     const uint8_t* tptr = a.residues + job.tOff;
     [[maybe_unused]] const uint8_t* qptr = a.query + job.qOff;
     const int jobStrips = (Q + kLanes - 1) / kLanes;
@@ -558,7 +569,7 @@ __global__ __launch_bounds__(PSSM_WAVES ? PSSM_WAVES * kLanes : 1024) void intra
                     hTop = topGap ? -min(topOne, topMany) : 0;
                     fTop = kNegInf;
                     topOne += ext;
-                    topMany += open;
+                    topMany += manyStep;
                 } else {
                     bH = __builtin_amdgcn_update_dpp(bH, bH, kRol1, 0xf, 0xf, false);
                     bF = __builtin_amdgcn_update_dpp(bF, bF, kRol1, 0xf, 0xf, false);

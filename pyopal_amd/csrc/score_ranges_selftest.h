@@ -69,6 +69,18 @@ inline int scoreRangesSelfTest() {
     if (int32Bound({0, 1, 0, 0}, 1, (1ll << 29) - 1) != kInt32Safe) return 52;
     // |min S| counts where it is the larger: 6 + 20 + 10 x 30 + 30
     if (int32Bound({3, 1, 11, -30}, 10, 10) != 356) return 53;
+    // every other term of the bound alone, one unit inside and one outside (52 is ext's row), Q = 1, L = 1:
+    //   2 open: 2 x (2^28 - 1) = 2^29 - 2 fits, 2 x 2^28 does not
+    if (!int32Fits(int32Bound({(1 << 28) - 1, 0, 0, 0}, 1, 1)) || int32Fits(int32Bound({1 << 28, 0, 0, 0}, 1, 1))) return 54;
+    //   min(Q, L) mag + mag, the largest score: 2 x (2^28 - 1) fits, 2 x 2^28 does not; and the lowest, by its magnitude
+    if (!int32Fits(int32Bound({0, 0, (1 << 28) - 1, 0}, 1, 1)) || int32Fits(int32Bound({0, 0, 1 << 28, 0}, 1, 1))) return 55;
+    if (!int32Fits(int32Bound({0, 0, 0, -(1 << 28) + 1}, 1, 1)) || int32Fits(int32Bound({0, 0, 0, -(1 << 28)}, 1, 1))) return 56;
+    //   min(Q, L) counts the shorter side: mag 2^19 at Q = 1023 against L = 2000 is 2^29 exactly, at Q = 1022 2^19 less;
+    //   and it is the target that is the shorter side when the query is long
+    if (int32Bound({0, 0, 1 << 19, 0}, 1023, 2000) != kInt32Safe || !int32Fits(int32Bound({0, 0, 1 << 19, 0}, 1022, 2000))) return 57;
+    if (int32Bound({0, 0, 1 << 19, 0}, 2000, 1023) != kInt32Safe || !int32Fits(int32Bound({0, 0, 1 << 19, 0}, 2000, 1022))) return 58;
+    //   (Q + L) ext counts both sides: ext 2^19, Q + L = 1024 is 2^29 exactly, one row less fits
+    if (int32Bound({0, 1 << 19, 0, 0}, 24, 1000) != kInt32Safe || !int32Fits(int32Bound({0, 1 << 19, 0, 0}, 23, 1000))) return 59;
     // ---- (e) NW / HW / OV in the general kernel, Q = 53 ----
     // plain: 9 + 53 + L < 32000: L <= 31937 (53 x 11 = 583 is far below)
     if (!fitsPlain(b62, 53, 31937) || fitsPlain(b62, 53, 31938) || fitsPlain(b62, 53, 0)) return 60;

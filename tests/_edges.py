@@ -1,4 +1,5 @@
-"""Inputs for the tests at the edges of the static range rules (test_range_edges_cpu.py, test_gpu_range_edges.py).
+"""Inputs for the tests at the edges of the static range rules (test_range_edges_cpu.py, test_gpu_range_edges.py) and
+of the 32-bit rule behind them (test_int32_edges_cpu.py, test_gpu_int32_edges.py: INT32_AXES and what follows it).
 
 NW, HW and OV run on 16-bit patterns when inequalities over the scoring model say so (score_ranges.h:
 globalOneStripFits, globalStripsFit, fitsPlain, fitsDiag, fitsUnsigned; perpair_packed.hip: packedScanFits,
@@ -143,6 +144,52 @@ def axis_model(axis, v, base=BASE):
     for name in AXES[axis][0]:
         m[name] = -v if name == "low" else v
     return m
+
+
+# ---- the edge of the 32-bit rule (test_int32_edges_cpu.py, test_gpu_int32_edges.py) ----------------------------------
+# Every entry point refuses a model with int32Bound >= 2^29 (score_ranges.h):
+#   2 |open| + (Q + longest) |ext| + min(Q, longest) mag + mag,   mag = the largest absolute substitution score.
+# Each axis takes one term of that bound (`mixed`: all of them) to the last value that is admitted; the other
+# parameters stay at BASE. axis -> (model of v, low end of the probe). There is no axis of ext alone: with open < ext
+# the borders are made of openings and the extension is never used.
+INT32_AXES = {
+    "match": (lambda v: dict(BASE, match=v), BASE["match"]),                      # the top of the range, Q * match
+    "low": (lambda v: dict(BASE, low=-v), -BASE["low"]),                          # transient diag + score sums only
+    "open": (lambda v: dict(BASE, open=v, ext=1), BASE["open"]),                  # borders less open beside minus infinity
+    "open=ext": (lambda v: dict(BASE, open=v, ext=v), BASE["ext"]),               # deep true values, the column scale j * ext
+    "mixed": (lambda v: dict(BASE, match=v, low=-v, open=16 * v, ext=max(v // 8, 1)), BASE["match"]),
+}
+INT32_HIGH = 1 << 29      # refused on every axis
+INT32_Q = (1, 33, 64, 65, 130)   # one row, one strip, the edge of a strip, two strips, three strips
+INT32_LONG = 300
+
+
+def int32_model(axis, v):
+    return INT32_AXES[axis][0](int(v))
+
+
+def int32_forms(axis):
+    """the query forms an axis runs with: all one letter as well where the lowest score is at its far end"""
+    return ("random", "one") if axis in ("low", "mixed") else ("random",)
+
+
+def int32_family(form, Q):
+    """(query, targets): about 55 targets of at most INT32_LONG + Q residues (4 Q where that is more) - the smallest family that still has a
+    copy of the query, runs of the low letter on every side of it, an empty target, and lanes shorter than the
+    longest target of their wavefront"""
+    q = edge_query(form, Q)
+    return q, family(q, long=INT32_LONG, n_random=40)
+
+
+def int32_formula(model, Q, longest):
+    """int32Bound of score_ranges.h, for the CPU tier (which has no router to ask); the GPU tier probes the router"""
+    mag = max(abs(model["match"]), abs(model["mild"]), abs(model["low"]))
+    return 2 * abs(model["open"]) + (Q + longest) * abs(model["ext"]) + min(Q, longest) * mag + mag
+
+
+def int32_formula_last(axis, Q, longest):
+    """the largest v of `axis` with the formula's bound below 2^29"""
+    return last_admitted(lambda v: int32_formula(int32_model(axis, v), Q, longest) < (1 << 29), INT32_AXES[axis][1], INT32_HIGH)
 
 
 ONE_STRIP_Q = (2, 33, 60)

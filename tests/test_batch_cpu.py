@@ -3,6 +3,7 @@ the C ABI declares and exports it, and the Python layer validates its arguments 
 answers an empty query list or an empty slice without a device."""
 import os
 import re
+import threading
 
 import numpy as np
 import pytest
@@ -24,8 +25,13 @@ def test_batch_entry_points_are_declared_and_exported():
 
 
 def test_last_batch_routing_starts_at_zero():
-    # (a thread that never ran a batch: the thread-local counters are zero)
-    assert _capi.DeviceDatabase.last_batch_routing() == (0, 0, 0, 0)
+    # (a thread that never ran a batch: the thread-local counters are zero - asked from a fresh thread, whatever this
+    # one has run before)
+    seen = []
+    fresh = threading.Thread(target=lambda: seen.append(_capi.DeviceDatabase.last_batch_routing()))
+    fresh.start()
+    fresh.join()
+    assert seen == [(0, 0, 0, 0)]
 
 
 def test_align_many_argument_validation():

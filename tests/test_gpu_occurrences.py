@@ -32,18 +32,19 @@ def capi():
 
 # ---- the recurrence, one numpy lane per target ----------------------------------------------------------------------
 
-def column_values(rows, targets, gap_open, gap_extend, algorithm):
+def column_values(rows, targets, gap_open, gap_extend, algorithm, neg=-(10 ** 9)):
     """-> (v, r), both [targets][longest]: column j of target k holds, for "hw", H[Q - 1][j] under HW's borders (the top
     row free, the left column one gap of i + 1 residues or i + 1 openings, whichever is cheaper) and r = Q - 1; for
     "sw" the column's maximum with the floor at 0 and the smallest row that reaches it. rows[i][t]: the score of query
-    position i against residue t. Columns behind a target hold nothing meaningful."""
+    position i against residue t. Columns behind a target hold nothing meaningful. ``neg``: the witness's minus
+    infinity, below every true value of the scoring model (test_gpu_int32_edges.py passes -2^60)."""
     rows = np.asarray(rows, dtype=np.int64)
     hw, Q, n = algorithm == "hw", len(rows), len(targets)
     longest = max(max((len(t) for t in targets), default=0), 1)
     T = np.zeros((n, longest), dtype=np.int64)
     for k, t in enumerate(targets):
         T[k, :len(t)] = t
-    NEG = -(10 ** 9)
+    NEG = neg
     left = [-min(gap_open + i * gap_extend, (i + 1) * gap_open) if hw else 0 for i in range(Q)]
     Hprev = np.repeat(np.array(left, dtype=np.int64)[:, None], n, axis=1)   # column -1
     Eprev = np.full((Q, n), NEG, dtype=np.int64)

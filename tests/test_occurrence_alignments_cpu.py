@@ -8,6 +8,7 @@ import ctypes
 import os
 import re
 import subprocess
+import threading
 
 import numpy as np
 import pytest
@@ -65,8 +66,13 @@ def test_library_exports_the_entry_points():
         assert getattr(lib, name).argtypes is not None, name
     assert len(lib.miopalSearchOccurrencesAligned.argtypes) == 22
     assert len(lib.miopalSearchPssmOccurrencesAligned.argtypes) == 22
-    # the routing of a thread that has searched nothing
-    assert _capi.last_occurrence_align_routing() == [0, 0, 0, 0]
+    # the routing of a thread that has searched nothing (the counters are thread_local: asked from a fresh thread,
+    # whatever this one has searched before)
+    seen = []
+    fresh = threading.Thread(target=lambda: seen.append(_capi.last_occurrence_align_routing()))
+    fresh.start()
+    fresh.join()
+    assert seen == [[0, 0, 0, 0]]
     lib.miopalLastOccurrenceAlignRouting(None)
 
 

@@ -8,6 +8,7 @@ import ctypes
 import os
 import re
 import subprocess
+import threading
 
 import numpy as np
 import pytest
@@ -56,8 +57,13 @@ def test_library_exports_the_entry_points():
     lib = _capi.lib()
     for name in NAMES:
         assert getattr(lib, name).argtypes is not None, name
-    # the routing of a thread that has searched nothing
-    assert _capi.last_occurrence_routing() == [0, 0, 0, 0]
+    # the routing of a thread that has searched nothing (the counters are thread_local: asked from a fresh thread,
+    # whatever this one has searched before)
+    seen = []
+    fresh = threading.Thread(target=lambda: seen.append(_capi.last_occurrence_routing()))
+    fresh.start()
+    fresh.join()
+    assert seen == [[0, 0, 0, 0]]
     lib.miopalLastOccurrenceRouting(None)
 
 
