@@ -12,8 +12,10 @@ The start rule for the occurrence (v, r, j) of a target t under a query of rows 
   - the cell (a, b) gives startQuery = r - a, startTarget = j - b;
   - the degenerate optimum of "hw": when the maximum is not v and v is the border gap over q[0 .. r], the target span
     is empty - startQuery = 0, startTarget = j + 1.
-The recurrence is written one numpy lane per occurrence and one vector of rows per lane; the gap consuming the query
-inside a column (F) is the running maximum it is when opening costs at least extending, which `starts` requires.
+The recurrence is written one numpy lane per occurrence and one vector of rows per lane. The gap consuming the query
+inside a column (F) comes in two forms: the running maximum that it is when opening costs at least extending, and
+the checker's own statement, row by row, for any non-negative gap costs; `starts` takes the first where it is valid
+and the second elsewhere, and tests/test_cases_cpu.py holds the two to each other and both to the C checker.
 """
 import numpy as np
 
@@ -28,11 +30,37 @@ def border(k, gap_open, gap_extend):
     return -min(gap_open + k * gap_extend, (k + 1) * gap_open)
 
 
-def starts(rows, targets, occurrences, gap_open, gap_extend, algorithm):
+def column_running(h0, top, gap_open, gap_extend):
+    """H of one column from h0 = max(diagonal, E) ([lanes][rows]) and the border cell above it. Valid for
+    open >= extend only: F[a] = max over the rows above, the border row included, of H - open - (rows between) x ext,
+    where h0 stands in for H because a gap opened from a cell that is itself the end of such a gap never beats that gap
+    extended."""
+    step = (np.arange(h0.shape[1]) - 1) * gap_extend
+    above = np.concatenate([np.full((len(h0), 1), top, dtype=np.int64), h0[:, :-1]], axis=1) + step[None, :]
+    F = np.maximum.accumulate(above, axis=1) - gap_open - step[None, :]
+    return np.maximum(h0, F)
+
+
+def column_by_rows(h0, top, gap_open, gap_extend):
+    """the same column as oracle/opal_oracle.c's dp_pass states it, for any gap costs:
+    F[a] = max(F[a - 1] - ext, H[a - 1] - open), H[a] = max(h0[a], F[a]), the border cell above row 0"""
+    H = np.empty_like(h0.T)
+    f, up = np.full(len(h0), NEG, dtype=np.int64), np.full(len(h0), top, dtype=np.int64)
+    for a, h in enumerate(np.ascontiguousarray(h0.T)):
+        f = np.maximum(f - gap_extend, up - gap_open)
+        up = H[a] = np.maximum(h, f)
+    return H.T
+
+
+def starts(rows, targets, occurrences, gap_open, gap_extend, algorithm, by_rows=None):
     """rows[i][t]: the score of query position i against residue t ([Q][A]); targets: a list of uint8 arrays;
     occurrences: (target, score, end_t, end_q) per occurrence. -> (start_t, start_q) int32 arrays. Raises when an
-    occurrence's score is neither the reversed maximum nor ("hw") the border gap: such a cell is no occurrence."""
-    assert gap_open >= gap_extend and algorithm in ("hw", "sw")
+    occurrence's score is neither the reversed maximum nor ("hw") the border gap: such a cell is no occurrence.
+    Any non-negative gap costs; ``by_rows``: the form of F (None: the running maximum where open >= extend)."""
+    assert gap_open >= 0 and gap_extend >= 0 and algorithm in ("hw", "sw")
+    by_rows = gap_open < gap_extend if by_rows is None else by_rows
+    assert by_rows or gap_open >= gap_extend
+    column = column_by_rows if by_rows else column_running
     rows = np.asarray(rows, dtype=np.int64)
     occ = np.asarray(occurrences, dtype=np.int64).reshape(-1, 4)
     n = len(occ)
@@ -54,7 +82,6 @@ def starts(rows, targets, occurrences, gap_open, gap_extend, algorithm):
     best = np.full(n, NEG, dtype=np.int64)
     best_a = np.full(n, -1, dtype=np.int64)
     best_b = np.full(n, -1, dtype=np.int64)
-    step = (a - 1) * gap_extend
     for b in range(width):
         s = rows[row_of, T[:, b][:, None]]
         top = border(b, gap_open, gap_extend)
@@ -62,10 +89,7 @@ def starts(rows, targets, occurrences, gap_open, gap_extend, algorithm):
         E = np.maximum(Eprev - gap_extend, Hprev - gap_open)
         diag = np.concatenate([np.full((n, 1), top_prev, dtype=np.int64), Hprev[:, :-1]], axis=1)
         h0 = np.maximum(diag + s, E)
-        # F[a] = max over the rows above, the border row included, of H - open - (rows between) x ext
-        above = np.concatenate([np.full((n, 1), top, dtype=np.int64), h0[:, :-1]], axis=1) + step[None, :]
-        F = np.maximum.accumulate(above, axis=1) - gap_open - step[None, :]
-        H = np.maximum(h0, F)
+        H = column(h0, top, gap_open, gap_extend)
         seen = np.where(candidate, H, NEG)
         column_best = seen.max(axis=1)
         first = seen.argmax(axis=1)
