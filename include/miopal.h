@@ -381,8 +381,9 @@ int miopalSearchBatchHits(MiopalDb* db, const unsigned char* queries, const int6
  * strips, within 2 GB: against a handle whose longest target has more than 4 194 304 (HW) or 2 097 152 (SW) residues such
  * a query is refused with MIOPAL_ERR_BAD_ARGUMENT and a message that states the limit, after the range check and before
  * any device call. Queries of at most 64 rows have no such limit.
- * Not part of this call: a batch of queries, opalSearchDatabase and the multi-GPU driver (the start locations and
- * operations of an occurrence: miopalSearchOccurrencesAligned below). Thread safety as miopalSearch.
+ * Not part of this call: opalSearchDatabase and the multi-GPU driver (the start locations and operations of an
+ * occurrence: miopalSearchOccurrencesAligned below; a panel of queries: miopalSearchBatchOccurrences). Thread safety as
+ * miopalSearch.
  */
 int miopalSearchOccurrences(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                             const int* scoreMatrix, int alphabetLength, int mode,
@@ -411,6 +412,60 @@ int miopalSearchPssmOccurrences(MiopalDb* db, const int* rowScores, int queryLen
  * strips per sweep, ceil(queryLength / 64). All 0 for an empty slice.
  */
 void miopalLastOccurrenceRouting(int64_t counts[4]);
+
+/*
+ * miopalSearchOccurrences for a whole panel of queries in one call - 96 barcodes, a primer panel, a kit's adapters
+ * with their reverse complements - against the targets [start, end). queries / queryOffsets / nQueries are
+ * miopalSearchBatch's; minScore[nQueries] and window[nQueries] hold one cut and one suppression window per query. Gap
+ * model, matrix, modes (OPAL_MODE_HW and OPAL_MODE_SW only) and the picking rule are miopalSearchOccurrences' to the
+ * letter.
+ *
+ * Output: a CSR as miopalSearchBatchHits returns it. hitOffsets is the caller's array of nQueries + 1 entries,
+ * hitOffsets[0] = 0; *targetIndex, *score, *endTarget and *endQuery are malloc'ed, hitOffsets[nQueries] entries each,
+ * freed by the caller, NULL without occurrences. Entries hitOffsets[i] .. hitOffsets[i + 1] are byte for byte what
+ * miopalSearchOccurrences returns for query i alone with minScore[i] and window[i]: targets absolute and ascending,
+ * columns ascending inside a target; two calls return the same bytes. maxHits bounds the TOTAL over all queries
+ * (< 0: no bound): with more, MIOPAL_ERR_TOO_MANY_HITS with hitOffsets filled and nothing allocated. On any other
+ * error every output is as it was. nQueries = 0 or an empty slice: checked, hitOffsets all 0, NULL arrays, nothing
+ * launched.
+ * Checks and their order, all before any device work: the query list, then every query with miopalSearch's checks
+ * (one failing query refuses the call); the mode; every window[i] >= 0; under OPAL_MODE_SW every minScore[i] >= 1; NULL
+ * minScore / window with nQueries > 0; null outputs; miopalSearch's 32-bit range check for every query
+ * (OPAL_ERR_OVERFLOW).
+ * On the device: queries of 1 .. 64 rows share launches. A chunk of them (queries x targets of the slice within 2^25
+ * entries, 32 768 queries at most) costs one count sweep - the slice's jobs built and sorted once, the rows of a group
+ * of queries side by side in a compute unit's LDS, a lane walking its target once per query of the group - one scan,
+ * one small download, one write sweep over the (query, target) pairs that have occurrences only, and the download of
+ * the occurrences: two host round trips per chunk, not per query. A group is as many consecutive queries as fit the
+ * 160 KB of LDS, except where that would leave the count sweep fewer than 32 workgroups per compute unit (targets / 256
+ * x groups): then the queries are spread over more, smaller groups, down to one query a group. The figure 32 rests on
+ * one measured panel and is the switch BATCH_OCCURRENCE_WORKGROUPS_PER_CU (0: groups only as the LDS
+ * makes them); the answer does not depend on it. An empty query has no occurrences. A query of more than 64 rows
+ * runs through miopalSearchOccurrences' own path inside the call (its strip-workspace refusal included) and its
+ * stretch is spliced into the CSR at its place; what miopalLastOccurrenceRouting reports is left as it was. Once the
+ * total has passed maxHits the remaining queries are still counted - hitOffsets is complete - but nothing is written.
+ * Not part of this call: panels of PSSMs, the start locations and operations of a panel's occurrences,
+ * opalSearchDatabase and the multi-GPU driver. Thread safety as miopalSearch.
+ */
+int miopalSearchBatchOccurrences(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                                 int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int mode,
+                                 int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
+                                 int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery);
+
+/*
+ * What the last miopalSearchBatchOccurrences of the calling thread did: counts[0] = queries on the panel kernels,
+ * counts[1] = queries on the single-query path, counts[2] = chunks (one count sweep + scan + download + write sweep
+ * each), counts[3] = (query, target) pairs the write sweeps took - those that have occurrences. All 0 for an empty
+ * slice or an empty list.
+ */
+void miopalLastBatchOccurrenceRouting(int64_t counts[4]);
+
+/*
+ * How the last miopalSearchBatchOccurrences of the calling thread grouped its panel queries: counts[0] = groups over
+ * all chunks (the rows of a group share a workgroup's LDS in the count sweep), counts[1] = the most queries in one
+ * group, counts[2] = the bytes of LDS of the largest group's rows. All 0 when no panel kernel ran.
+ */
+void miopalLastBatchOccurrenceGroups(int64_t counts[3]);
 
 /*
  * miopalSearchOccurrences with the other end of every occurrence: where it starts and, when asked for, its operations

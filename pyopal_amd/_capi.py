@@ -89,6 +89,7 @@ EXPORTS = [
     "miopalProfileColumns", "miopalProfileColumnsPssm",
     "miopalSearchOccurrences", "miopalSearchPssmOccurrences", "miopalLastOccurrenceRouting",
     "miopalSearchOccurrencesAligned", "miopalSearchPssmOccurrencesAligned", "miopalLastOccurrenceAlignRouting",
+    "miopalSearchBatchOccurrences", "miopalLastBatchOccurrenceRouting", "miopalLastBatchOccurrenceGroups",
     # test hooks
     "miopalTestProfileColumns",
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
@@ -166,6 +167,7 @@ def lib() -> ctypes.CDLL:
             "miopalLastRouting": (None, [p_i64]), "miopalLastPairRouting": (None, [p_i64]),
             "miopalLastBatchRouting": (None, [p_i64]), "miopalLastOccurrenceRouting": (None, [p_i64]),
             "miopalLastOccurrenceAlignRouting": (None, [p_i64]),
+            "miopalLastBatchOccurrenceRouting": (None, [p_i64]), "miopalLastBatchOccurrenceGroups": (None, [p_i64]),
             "miopalLastKernelTime": (c_int, [c_vp, ctypes.POINTER(ctypes.c_float)]),
             "miopalSearch": (c_int, one + middle + [c_vp] * 7),
             "miopalSearchFlat": (c_int, one + middle + flat + [c_vp]),
@@ -203,6 +205,8 @@ def lib() -> ctypes.CDLL:
         # occurrences: no search type; minScore, window, maxHits, one count
         for side, head in (("", one), ("Pssm", pssm)):
             table[f"miopalSearch{side}Occurrences"] = (c_int, head + middle[1:] + [c_int, c_int, c_i64, p_i64] + found)
+        # ... of a panel: one cut and one window per query, maxHits over all of them, the CSR's offsets
+        table["miopalSearchBatchOccurrences"] = (c_int, batch + middle[1:] + [c_vp, c_vp, c_i64, c_vp] + found)
         # ... aligned: the PSSM with its consensus; behind the occurrences startT, startQ, operations, their offsets
         for side, head in (("", one), ("Pssm", pssm_full)):
             table[f"miopalSearch{side}OccurrencesAligned"] = (c_int, head + middle[1:] + [c_int, c_int, c_i64, p_i64] + found + [pp] * 4)
@@ -444,6 +448,33 @@ def last_occurrence_routing() -> typing.List[int]:
     counts = (ctypes.c_int64 * 4)()
     lib().miopalLastOccurrenceRouting(counts)
     return list(counts)
+
+
+def last_batch_occurrence_routing() -> typing.List[int]:
+    """miopalLastBatchOccurrenceRouting: [queries on the panel kernels, queries on the single-query path, chunks, (query,
+    target) pairs the write sweeps took] of the calling thread's last `search_batch_occurrences` call"""
+    counts = (ctypes.c_int64 * 4)()
+    lib().miopalLastBatchOccurrenceRouting(counts)
+    return list(counts)
+
+
+def last_batch_occurrence_groups() -> typing.List[int]:
+    """miopalLastBatchOccurrenceGroups: [groups of panel queries over all chunks, the most queries in one group, the bytes
+    of LDS of the largest group's rows] of the calling thread's last `search_batch_occurrences` call"""
+    counts = (ctypes.c_int64 * 3)()
+    lib().miopalLastBatchOccurrenceGroups(counts)
+    return list(counts)
+
+
+def _per_query(values, lengths, name) -> np.ndarray:
+    """a cut or a window of a panel as the C ABI takes it: one int32 per query from a scalar or one value per query
+    (None, as the scalar or as an entry: the query's own length)"""
+    if values is None or np.ndim(values) == 0:
+        values = [values] * len(lengths)
+    values = list(values)
+    if len(values) != len(lengths):
+        raise ValueError(f"{name} must be one value or one per query ({len(lengths)}), got {len(values)}")
+    return np.array([n if v is None else int(v) for v, n in zip(values, lengths)], dtype=np.int64)
 
 
 def last_occurrence_align_routing() -> typing.List[int]:
@@ -1060,8 +1091,40 @@ class DeviceDatabase:
             self._pssm_side(row_scores, consensus, gap_open, gap_extend, with_consensus=True), algorithm, start, end,
             min_score, window, max_hits, operations)
 
+    def search_batch_occurrences(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
+                                 gap_extend: int = 1, algorithm: str = "hw", start: int = 0,
+                                 end: typing.Optional[int] = None, min_score=1, window=None,
+                                 max_hits: typing.Optional[int] = None) -> typing.Dict[str, np.ndarray]:
+        """miopalSearchBatchOccurrences: `search_occurrences` of every query of a panel in one call. ``min_score`` and
+        ``window``: one value or one per query; a window of None is that query's length. Returns a CSR: "offsets"
+        (len(queries) + 1,) and "target", "score", "end_t", "end_q" of offsets[-1] entries; entries
+        offsets[i]:offsets[i + 1] equal search_occurrences(queries[i], ...) byte for byte. ``max_hits`` bounds the
+        total; TooManyHits carries the offsets in ``counts``. The rule's faults raise ValueError before any device
+        call, as `search_occurrences`' do."""
+        side = self._batch_side(queries, matrix, gap_open, gap_extend)
+        lengths = np.diff(side.keep[1]).tolist()
+        cuts, windows = _per_query(min_score, lengths, "min_score"), _per_query(window, lengths, "window")
+        if algorithm not in ("hw", "sw"):
+            raise ValueError(f"occurrences are defined for the algorithms 'hw' and 'sw', not {algorithm!r}")
+        if np.any(windows < 0):
+            raise ValueError("window must not be negative")
+        if algorithm == "sw" and np.any(cuts < 1):
+            raise ValueError("min_score must be at least 1 with algorithm 'sw'")
+        if len(cuts) and (cuts.min() < -(2 ** 31) or cuts.max() >= 2 ** 31 or windows.max() >= 2 ** 31):
+            raise OverflowError("min_score / window does not fit a 32-bit integer")
+        cuts, windows = cuts.astype(np.int32), windows.astype(np.int32)
+        offsets = np.zeros(side.rows + 1, dtype=np.int64)
+        ptrs = _HitPointers()
+        rc = lib().miopalSearchBatchOccurrences(
+            self._h, *side.queries, *side.scoring, MODE[algorithm], start, self._clamp(end),
+            _ptr(cuts) if side.rows else None, _ptr(windows) if side.rows else None, _bound(max_hits), _ptr(offsets),
+            *ptrs.refs())
+        return self._found(rc, offsets, ptrs, "end")
+
     pick_occurrences_rows = staticmethod(pick_occurrences_rows)
     last_occurrence_routing = staticmethod(last_occurrence_routing)
+    last_batch_occurrence_routing = staticmethod(last_batch_occurrence_routing)
+    last_batch_occurrence_groups = staticmethod(last_batch_occurrence_groups)
     last_occurrence_align_routing = staticmethod(last_occurrence_align_routing)
 
     def search_significant(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,

@@ -38,6 +38,7 @@
 #include "full_plan_selftest.h"
 #include "launch_layer_selftest.h"
 #include "occurrences.h"
+#include "occurrences_batch.h"
 #include "occurrence_align.h"
 #include "profile_columns.h"
 #include "score_ranges_selftest.h"
@@ -746,6 +747,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_profile.inc"
 #include "host_occurrences.inc"
 #include "host_occurrence_align.inc"
+#include "host_batch_occurrences.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
                  int64_t end, int* score, int* endTarget, int* endQuery, int* startTarget,
@@ -1010,6 +1012,29 @@ int miopalSearchPssmOccurrences(MiopalDb* db, const int* rowScores, int queryLen
 void miopalLastOccurrenceRouting(int64_t counts[4]) {
     if (!counts) return;
     for (int k = 0; k < 4; ++k) counts[k] = g_lastOccurrenceRouting[k];
+}
+
+// miopalSearchBatchOccurrences: miopalSearchOccurrences' checks for every query of the list, in its order, before any
+// device work; then the panel kernels and, for queries of more than 64 rows, the single-query search
+// (host_batch_occurrences.inc)
+int miopalSearchBatchOccurrences(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                                 int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int mode,
+                                 int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
+                                 int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery) {
+    return guarded([&]() -> int {
+    return searchBatchOccurrencesImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength, mode,
+                                      start, end, minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery);
+    });
+}
+
+void miopalLastBatchOccurrenceRouting(int64_t counts[4]) {
+    if (!counts) return;
+    for (int k = 0; k < 4; ++k) counts[k] = g_lastBatchOccurrenceRouting[k];
+}
+
+void miopalLastBatchOccurrenceGroups(int64_t counts[3]) {
+    if (!counts) return;
+    for (int k = 0; k < 3; ++k) counts[k] = g_lastBatchOccurrenceGroups[k];
 }
 
 // the outputs the aligned forms add: the starts always, the operations and their offsets together or not at all

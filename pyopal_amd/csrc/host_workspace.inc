@@ -30,6 +30,9 @@ enum Slot {
     // miopalSearchOccurrences (host_occurrences.inc): per-target counts, offsets and the list of the targets that have
     // occurrences; the written occurrences, sized to their number
     kOccurrenceScratch, kOccurrenceOut,
+    // miopalSearchBatchOccurrences (host_batch_occurrences.inc): a chunk's queries and groups; where each query's
+    // stretch of the scan's list begins, and the offsets and totals that come down
+    kBatchOccurrenceMeta, kBatchOccurrenceBounds,
     kSlots
 };
 

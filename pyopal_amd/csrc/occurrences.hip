@@ -25,6 +25,7 @@
 // supplies, through the same launchers. The offsets are a three-kernel exclusive scan that also lists, in ascending
 // order, the entries that have occurrences: the write sweep runs over those alone.
 #include "occurrences.h"
+#include "occurrence_picker.h"   // OccurrencePicker: the rule, shared with occurrences_batch.hip
 #include "launch_layer.h"
 
 namespace miopal {
@@ -42,32 +43,6 @@ constexpr bool kPssmUnit = true;
 #else
 constexpr bool kPssmUnit = false;
 #endif
-
-// Greedy peak picking with a suppression window, left to right over one target's columns: the candidate is the
-// first column of the highest value seen since the last emission; it is emitted once a column more than `window`
-// behind it is reached, or at the end.
-struct OccurrencePicker {
-    int minScore, window;
-    int cj = -1, cv = 0, cr = 0;   // the candidate (cj < 0: none)
-    __device__ OccurrencePicker(int minScore_, int window_) : minScore(minScore_), window(window_) {}
-    template <typename Emit>
-    __device__ void feed(int j, int v, int r, Emit&& emit) {
-        if (cj >= 0 && j - cj > window) {
-            emit(cj, cv, cr);
-            cj = -1;
-        }
-        if (v >= minScore && (cj < 0 || v > cv)) {
-            cj = j;
-            cv = v;
-            cr = r;
-        }
-    }
-    template <typename Emit>
-    __device__ void finish(Emit&& emit) {
-        if (cj >= 0) emit(cj, cv, cr);
-        cj = -1;
-    }
-};
 
 template <int REGION, bool WRITE, bool PSSM>
 __global__ __launch_bounds__(kBlock) void occurrences_sweep_kernel(OccurrenceArgs a) {

@@ -12,6 +12,7 @@
 namespace miopal {
 
 #define MIOPAL_TUNING_SWITCHES(X)                                                                          \
+    X(BATCH_OCCURRENCE_ENTRIES) X(BATCH_OCCURRENCE_WORKGROUPS_PER_CU)                                      \
     X(COLUMN_SPLIT) X(DEVICE) X(FORCE_LANE_PER_PAIR) X(HOST_THREADS) X(HOST_TRACEBACK) X(NO_ASYNC_SHARES) X(NO_BIASED)     \
     X(NO_CALLER_PINNED) X(NO_DIAG_SHIFT) X(NO_DIRECT_SCATTER) X(NO_EARLY_HOST_SHARE) X(NO_GLOBAL_STRIPS)   \
     X(NO_HOST_SCATTER) X(NO_HUGEPAGE) X(NO_HYBRID_TRACE) X(NO_JOBS_AHEAD) X(NO_ONE_LAUNCH)                 \

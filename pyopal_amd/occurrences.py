@@ -8,6 +8,8 @@ plus a fixed table of extensions.
     sites = find_occurrences(aligner, "ETSEEES", database, 25)          # FullResult, several per target
     ends = find_occurrences(aligner, "ETSEEES", database, 25, mode="end")
 
+    panel = find_occurrences_many(aligner, barcodes, database, 25)        # one list of EndResult per query
+
 ``mode="end"`` is served by the occurrence search alone (EndResult: score and end cell); ``mode="full"`` by the aligned
 form, whose start cells follow the checker's rule applied to each occurrence's end cell, and whose operations are the
 global alignment of the rectangle between start and end.
@@ -114,3 +116,68 @@ def find_occurrences_arrays(aligner: Aligner, query, database: BaseDatabase, min
     "full", "start_q" / "start_t", "aln_flat" / "aln_off" - one entry per occurrence."""
     side = _Sequences(aligner, query, False)
     return _arrays(side, database, min_score, window, algorithm, mode, start, end, device, max_hits)[0]
+
+
+# --- a panel of queries in one call (miopalSearchBatchOccurrences) ----------------------------------------------------
+
+def _panel_values(values, name, none_allowed):
+    """one cut or window, or one per query, as a list (their number is checked once the queries are known)"""
+    many = not (values is None or isinstance(values, (int, np.integer, bool)))
+    items = list(values) if many else [values]
+    for v in items:
+        if v is None and none_allowed:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            what = "an integer or None" if none_allowed else "an integer"
+            raise TypeError(f"{name} must be {what}, or one per query, not {type(v).__name__}")
+    return items, many
+
+
+def _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits):
+    if mode not in _MODES:
+        raise ValueError(f"occurrences are reported with mode 'end' or 'full', not {mode!r}")
+    if mode == "full":
+        raise ValueError("the alignments of a panel's occurrences are not available yet: find_occurrences_many reports "
+                         "mode 'end'; find_occurrences(..., mode='full') aligns one query's occurrences")
+    cuts, many_cuts = _panel_values(min_score, "min_score", False)
+    windows, many_windows = _panel_values(window, "window", True)
+    for cut in cuts or [1]:
+        _rule(mode, algorithm, cut, None)
+    for w in windows:
+        _rule(mode, algorithm, 1, w)
+    side = _Sequences(aligner, queries, True)
+    request = _Request(side, database, mode, algorithm, start, end, device, lambda: _max_hits_argument(max_hits))
+    for items, many, name in ((cuts, many_cuts, "min_score"), (windows, many_windows, "window")):
+        if many and len(items) != len(side.lengths):
+            raise ValueError(f"{name} must be one value or one per query ({len(side.lengths)}), got {len(items)}")
+    rows = len(side.lengths)
+    with request:
+        if request.end == start or rows == 0 or max(side.lengths) == 0:
+            # (nothing to search, or nothing to search with: answered without a device)
+            return dict(_empty_arrays(mode), offsets=np.zeros(rows + 1, dtype=np.int64), target=np.zeros(0, dtype=np.int64))
+        return request.mirror().search_batch_occurrences(
+            side.arrays, aligner._matrix, aligner.gap_open, aligner.gap_extend, algorithm, start, request.end,
+            cuts if many_cuts else cuts[0], windows if many_windows else windows[0], request.checked)
+
+
+def find_occurrences_many(aligner: Aligner, queries, database: BaseDatabase, min_score, *, window=None,
+                          algorithm: str = "hw", mode: str = "end", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                          max_hits: typing.Optional[int] = None) -> typing.List[typing.List[ScoreResult]]:
+    """`find_occurrences` for a whole panel of queries - barcodes, primers, a kit's adapters - in one device call: a
+    list with one list of `EndResult` per query, each what ``find_occurrences(aligner, query, ..., mode="end")``
+    returns for that query. ``min_score`` and ``window``: one value or one per query (a window of None: that query's
+    length). ``max_hits`` bounds the total over all queries; `_capi.TooManyHits` carries the CSR offsets in
+    ``counts``. ``mode="full"`` raises ValueError: the alignments of a panel's occurrences are not available yet. That
+    and the other rule faults raise before any device call; an empty panel or slice is answered without a device."""
+    out = _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits)
+    flat = _result_objects(mode, out["target"], None, None, None, out)
+    offsets = out["offsets"].tolist()
+    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+
+
+def find_occurrences_many_arrays(aligner: Aligner, queries, database: BaseDatabase, min_score, *, window=None,
+                                 algorithm: str = "hw", mode: str = "end", start: int = 0, end: int = UINT32_MAX,
+                                 device: int = 0, max_hits: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+    """`find_occurrences_many` without result objects: a CSR - "offsets" (one entry per query plus one), "target"
+    (int64), "score", "end_q" and "end_t"; entries offsets[i]:offsets[i + 1] belong to query i."""
+    return _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits)
