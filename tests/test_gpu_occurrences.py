@@ -1,6 +1,7 @@
 """Every occurrence of a query in each target, picked on the device (miopalSearchOccurrences,
 miopalSearchPssmOccurrences; DeviceDatabase.search_occurrences / search_occurrences_pssm). Three witnesses: a numpy
-statement of the recurrence, written out below, that returns every column's value and row; the project's CPU checker on prefixes and on whole targets; and tests/_occurrences.pick, the rule itself."""
+statement of the recurrence (tests/_occurrences.column_values) that returns every column's value and row; the project's
+CPU checker on prefixes and on whole targets; and tests/_occurrences.pick, the rule itself."""
 import ctypes
 import functools
 
@@ -10,7 +11,7 @@ import pytest
 import _data
 import _oracle
 import _pssm
-from _occurrences import INT_MIN, pick
+from _occurrences import INT_MIN, column_values, pick   # noqa: F401 (column_values: other modules import it from here)
 from pyopal_amd.matrices import ScoringMatrix
 
 pytestmark = pytest.mark.gpu
@@ -28,45 +29,6 @@ def capi():
     from pyopal_amd import _capi
     assert _capi.lib().miopalDeviceCount() >= 1, "no gfx950 device visible"
     return _capi
-
-
-# ---- the recurrence, one numpy lane per target ----------------------------------------------------------------------
-
-def column_values(rows, targets, gap_open, gap_extend, algorithm, neg=-(10 ** 9)):
-    """-> (v, r), both [targets][longest]: column j of target k holds, for "hw", H[Q - 1][j] under HW's borders (the top
-    row free, the left column one gap of i + 1 residues or i + 1 openings, whichever is cheaper) and r = Q - 1; for
-    "sw" the column's maximum with the floor at 0 and the smallest row that reaches it. rows[i][t]: the score of query
-    position i against residue t. Columns behind a target hold nothing meaningful. ``neg``: the witness's minus
-    infinity, below every true value of the scoring model (test_gpu_int32_edges.py passes -2^60)."""
-    rows = np.asarray(rows, dtype=np.int64)
-    hw, Q, n = algorithm == "hw", len(rows), len(targets)
-    longest = max(max((len(t) for t in targets), default=0), 1)
-    T = np.zeros((n, longest), dtype=np.int64)
-    for k, t in enumerate(targets):
-        T[k, :len(t)] = t
-    NEG = neg
-    left = [-min(gap_open + i * gap_extend, (i + 1) * gap_open) if hw else 0 for i in range(Q)]
-    Hprev = np.repeat(np.array(left, dtype=np.int64)[:, None], n, axis=1)   # column -1
-    Eprev = np.full((Q, n), NEG, dtype=np.int64)
-    V = np.zeros((n, longest), dtype=np.int64)
-    R = np.zeros((n, longest), dtype=np.int64)
-    for j in range(longest):
-        s = rows[:, T[:, j]]
-        E = np.maximum(Hprev - gap_open, Eprev - gap_extend)
-        H = np.empty((Q, n), dtype=np.int64)
-        up_h, up_f, diag = np.zeros(n, dtype=np.int64), np.full(n, NEG), np.zeros(n, dtype=np.int64)   # the free top row
-        for i in range(Q):
-            f = np.maximum(up_h - gap_open, up_f - gap_extend)
-            h = np.maximum(np.maximum(diag + s[i], E[i]), f)
-            if not hw:
-                h = np.maximum(h, 0)
-            diag, H[i], up_h, up_f = Hprev[i], h, h, f
-        if hw:
-            V[:, j], R[:, j] = H[Q - 1], Q - 1
-        else:
-            V[:, j], R[:, j] = H.max(axis=0), H.argmax(axis=0)   # (argmax: the first, the smallest row)
-        Hprev, Eprev = H, E
-    return V, R
 
 
 def expected(V, R, lengths, min_score, window, start=0):

@@ -15,7 +15,9 @@ import pytest
 
 from pyopal_amd import _capi
 
-from _occurrences import INT_MAX, INT_MIN, pick, pick_rows
+import _oracle
+from _occurrences import INT_MAX, INT_MIN, column_values, expected_flat, flat_columns, pick, pick_rows, row_values
+from pyopal_amd.matrices import ScoringMatrix
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BAD = 101   # MIOPAL_ERR_BAD_ARGUMENT (include/opal.h)
@@ -236,6 +238,78 @@ def test_pick_rows_is_a_csr():
     got = pick_rows(value, [4, 4, 2], 1, 0)
     assert got["offsets"].tolist() == [0, 2, 2, 4]
     assert got["column"].tolist() == [0, 2, 0, 1] and got["score"].tolist() == [5, 5, 1, 2] and got["row"].tolist() == [-1] * 4
+
+
+# ---- the recurrence row by row: the witness of the long-target tests ------------------------------------------------
+
+@pytest.mark.parametrize("alphabet", [2, 4, 24])
+@pytest.mark.parametrize("gaps", [(3, 1), (11, 1), (2, 2), (5, 0), (0, 0), (1, 1)])
+def test_row_values_is_column_values(gaps, alphabet):
+    """values and rows, "hw" and "sw", queries of one row to three strips, targets of 0 .. 90 residues (0, 1 and a
+    two-letter one among them)"""
+    rng = np.random.default_rng(alphabet * 100 + gaps[0] * 10 + gaps[1])
+    matrix = rng.integers(-6, 9, size=(alphabet, alphabet))
+    lengths = [0, 1, 2, 63, 64, 65, 90] + rng.integers(0, 91, size=5).tolist()
+    targets = [rng.integers(0, alphabet, size=n).astype(np.uint8) for n in lengths]
+    targets.append(rng.integers(0, 2, size=80).astype(np.uint8))
+    for q in (1, 7, 64, 65, 130):
+        rows = matrix[rng.integers(0, alphabet, size=q)]
+        for algorithm in ("hw", "sw"):
+            V, R = column_values(rows, targets, gaps[0], gaps[1], algorithm)
+            for k, t in enumerate(targets):
+                v, r = row_values(rows, t, gaps[0], gaps[1], algorithm)
+                assert v.shape == r.shape == (len(t),)
+                assert np.array_equal(v, V[k, :len(t)]) and np.array_equal(r, R[k, :len(t)]), (q, algorithm, k)
+
+
+def test_row_values_marks_the_ties_between_strips():
+    """a column's maximum reached in two strips of 64 rows: worked by hand (every score 0 under "sw": every cell is 0,
+    the smallest row 0, and every later strip ties), and none where the query is one strip"""
+    target = np.zeros(9, dtype=np.uint8)
+    for q, want in ((64, False), (65, True), (130, True)):
+        tied = np.ones(9, dtype=bool)
+        v, r = row_values(np.zeros((q, 2), dtype=np.int64), target, 3, 1, "sw", tied=tied)
+        assert np.all(v == 0) and np.all(r == 0) and np.all(tied == want), q
+    # a maximum that a later strip passes is no tie: row 70 alone scores
+    rows = np.zeros((130, 2), dtype=np.int64)
+    rows[70] = 5
+    tied = np.ones(9, dtype=bool)
+    v, r = row_values(rows, target, 3, 1, "sw", tied=tied)
+    assert np.all(v == 5) and np.all(r == 70) and not tied.any()
+    with pytest.raises(AssertionError):
+        row_values(rows, target, 1, 2, "sw")
+
+
+def test_flat_answers_are_the_per_target_rule():
+    rng = np.random.default_rng(3)
+    values = [rng.integers(-5, 6, size=n) for n in (7, 0, 1, 30)]
+    rows = [rng.integers(0, 9, size=len(v)) for v in values]
+    V, R, offsets = flat_columns(values, rows)
+    assert offsets.tolist() == [0, 7, 7, 8, 38]
+    for cut, window, first, last in ((0, 0, 0, 4), (-5, 0, 1, 4), (2, 3, 0, 4), (2, 0, 3, 4), (9, 0, 0, 4)):
+        got = expected_flat(V, R, offsets, cut, window, first=first, last=last)
+        want = [(k, v, j, r) for k in range(first, last) for j, v, r in pick(values[k], cut, window, rows[k])]
+        assert list(zip(*(got[key].tolist() for key in ("target", "score", "end_t", "end_q")))) == want, (cut, window)
+        assert got["target"].dtype == np.int64 and got["score"].dtype == np.int32
+
+
+@pytest.mark.parametrize("q", [7, 65, 130])
+def test_row_values_against_the_checker_at_read_length(q):
+    """two targets of 5000 and 20 000 residues: the largest value, the first column that reaches it and its row are the
+    C checker's score, end_t and end_q"""
+    B62 = np.array(ScoringMatrix.from_name("BLOSUM62").int_array(), dtype=np.int32)
+    rng = np.random.default_rng(50 + q)
+    query = rng.integers(0, 20, size=q).astype(np.uint8)
+    targets = [rng.integers(0, 20, size=n).astype(np.uint8) for n in (5000, 20000)]
+    residues, offsets = _oracle.flatten(targets)
+    for gaps in ((11, 1), (2, 2)):
+        for algorithm in ("hw", "sw"):
+            want = _oracle.search(query, residues, offsets, B62, gaps[0], gaps[1], "end", algorithm)
+            for k, t in enumerate(targets):
+                v, r = row_values(B62.reshape(24, 24)[query], t, gaps[0], gaps[1], algorithm)
+                j = int(np.argmax(v))   # (the first column that holds the maximum)
+                assert (int(v[j]), j, int(r[j])) == (int(want["score"][k]), int(want["end_t"][k]), int(want["end_q"][k])), (
+                    q, gaps, algorithm, k)
 
 
 # ---- the Python layer -----------------------------------------------------------------------------------------------
