@@ -218,6 +218,21 @@ int miopalLastKernelTime(MiopalDb* db, float* ms);
 void miopalLastRouting(int64_t counts[4]);
 
 /*
+ * The windows of the calling thread's most recent score pass (diagnostics for tests; no reference counterpart).
+ * Smith-Waterman and HW searches may cut long targets into overlapping windows [k stride, k stride + stride +
+ * overlap) that are merged on the device; all four fields are reset when a score pass starts:
+ *   out[0] the overlap of the windows in columns; 0: no windows (the small-search route included)
+ *   out[1] the stride of the view the pass ran on - read from the view itself, not from what the plan asked for.
+ *          The two agree: views are cached by (slice, overlap, stride), and a view whose lists were built ahead of
+ *          the upload is only taken for a request of its own overlap AND stride (such views are whole-target views,
+ *          overlap 0 and stride 0, today).
+ *   out[2] the entries of that view: windows, plus one for every target that is not cut
+ *   out[3] 1 when the windows were merged by (score, column, row) keys - end locations were wanted -, 0 when the
+ *          scores alone were merged
+ */
+void miopalLastWindowPlan(int64_t out[4]);
+
+/*
  * Many queries against one slice [start, end) of a resident handle in one call (no reference counterpart:
  * the batch form of pyopal's thread-pool loop of searches). Query k is
  * queries[queryOffsets[k] .. queryOffsets[k + 1]) (nQueries + 1 offsets); outputs are row-major

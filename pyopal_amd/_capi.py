@@ -80,7 +80,7 @@ EXPORTS = [
     "miopalDeviceCount", "miopalLastError", "miopalDbCreate", "miopalDbCreateFlat", "miopalDbCreateSubset",
     "miopalDbDestroy", "miopalDbCount", "miopalDbTotalLength", "miopalDbDeviceBytes",
     "miopalSearch", "miopalSearchFlat", "miopalSearchFlatInto", "miopalSearchPssm", "miopalSearchDeviceScores", "miopalSetProfiling", "miopalLastKernelTime",
-    "miopalLastRouting", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
+    "miopalLastRouting", "miopalLastWindowPlan", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
     "miopalSearchBatch", "miopalLastBatchRouting", "miopalSearchTop", "miopalSearchBatchTop",
     "miopalAlignPairs", "miopalLastPairRouting", "miopalSearchPssmTop", "miopalAlignPairsPssm",
     "miopalSearchHits", "miopalSearchPssmHits", "miopalSearchBatchHits", "miopalSearchBatchTargetTop",
@@ -164,7 +164,7 @@ def lib() -> ctypes.CDLL:
             "miopalSetProfiling": (None, [c_vp, c_int]),
             "miopalReleaseCaches": (None, []),
             "miopalLastFullRouting": (c_int, []),
-            "miopalLastRouting": (None, [p_i64]), "miopalLastPairRouting": (None, [p_i64]),
+            "miopalLastRouting": (None, [p_i64]), "miopalLastWindowPlan": (None, [p_i64]), "miopalLastPairRouting": (None, [p_i64]),
             "miopalLastBatchRouting": (None, [p_i64]), "miopalLastOccurrenceRouting": (None, [p_i64]),
             "miopalLastOccurrenceAlignRouting": (None, [p_i64]),
             "miopalLastBatchOccurrenceRouting": (None, [p_i64]), "miopalLastBatchOccurrenceGroups": (None, [p_i64]),
@@ -1326,6 +1326,15 @@ class DeviceDatabase:
         counts = (ctypes.c_int64 * 4)()
         lib().miopalLastRouting(counts)
         return tuple(int(c) for c in counts)
+
+    @staticmethod
+    def last_window_plan() -> typing.Tuple[int, int, int, int]:
+        """(overlap - 0: no windows -, stride of the view that was used, entries of that view, 1 when the windows
+        were merged by key for end locations) for the score pass of the calling thread's most recent search
+        (include/miopal.h, miopalLastWindowPlan)."""
+        out = (ctypes.c_int64 * 4)()
+        lib().miopalLastWindowPlan(out)
+        return tuple(int(c) for c in out)
 
     @staticmethod
     def last_full_routing() -> int:

@@ -413,6 +413,14 @@ struct Search {
             const double balancedColumns = (double)db->total * share / ((double)kGroupTargets * 12.0 * db->computeUnits);
             const int64_t want = (int64_t)(1.5 * balancedColumns) - p.overlap;
             if (want > p.stride) p.stride = (int)std::min<int64_t>((want + 255) / 256 * 256, 8192);
+            // (MIOPAL_TEST_WINDOW_STRIDE: the stride of a search that is cut anyway, for the tests of the strides
+            // that only databases of 1e8 .. 2e9 residues reach: a multiple of 256 between the shortest stride of
+            // this overlap and 8192, anything else is ignored; it never turns windows on or off)
+            if (const char* ts = tuned(Tune::TEST_WINDOW_STRIDE)) {
+                char* rest = nullptr;
+                const long v = strtol(ts, &rest, 10);
+                if (rest != ts && *rest == 0 && v % 256 == 0 && v >= segmentStride(p.overlap) && v <= 8192) p.stride = (int)v;
+            }
         }
     }
 
@@ -1306,6 +1314,7 @@ struct Search {
         wroteHost = false;
 
         g_lastRouting[0] = g_lastRouting[1] = g_lastRouting[2] = g_lastRouting[3] = 0;
+        g_lastWindowPlan[0] = g_lastWindowPlan[1] = g_lastWindowPlan[2] = g_lastWindowPlan[3] = 0;
         if (!interseqUsable() || (smallSearch() && smallSearchAllowed(db))) {
             g_lastRouting[0] = n;
             jobs.reserve((size_t)n);
@@ -1327,6 +1336,12 @@ struct Search {
         // are never negative); whole-target results of the int32 kernel are plain stores of the
         // final value, in either order the maximum is that value
         p.keyed = p.overlap > 0 && searchType != OPAL_SEARCH_SCORE;  // with end locations
+        if (view->overlap > 0) {   // miopalLastWindowPlan: what the view holds, not what the plan wished for
+            g_lastWindowPlan[0] = view->overlap;
+            g_lastWindowPlan[1] = view->stride;
+            g_lastWindowPlan[2] = view->nPacked;
+            g_lastWindowPlan[3] = p.keyed ? 1 : 0;
+        }
         if (p.keyed) {
             RC_TRY(ws->get(kKeys, (size_t)n * sizeof(unsigned long long), &b.keys));
             HIP_TRY(hipMemsetAsync(b.keys, 0, (size_t)n * sizeof(unsigned long long), stream));

@@ -78,7 +78,8 @@ int buildView(MiopalDb* db, int64_t start, int64_t end, int overlap, std::shared
         {
             std::lock_guard<std::mutex> g(db->viewMutex);
             for (auto it = db->prefetched.begin(); it != db->prefetched.end(); ++it)
-                if (*it && (*it)->start == start && (*it)->end == end && (*it)->overlap == overlap) {
+                if (*it && (*it)->start == start && (*it)->end == end && (*it)->overlap == overlap &&
+                    (*it)->stride == (overlap > 0 ? (strideWanted > 0 ? strideWanted : segmentStride(overlap)) : 0)) {
                     ready = std::move(*it);
                     db->prefetched.erase(it);
                     break;

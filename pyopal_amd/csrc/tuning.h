@@ -22,7 +22,7 @@ namespace miopal {
     X(NO_SW_SHIFT) X(NO_TWO_PASS_ENDS) X(NO_UNPACK_CREW) X(NO_VIEW_PREFETCH) X(ONE_LAUNCH_GROUP)           \
     X(PAIR_STRIPS) X(PARKED_WORKSPACE_MB) X(PHASE_TIMING) X(RESERVE_CUS) X(SEARCH_UNDER_UPLOAD)            \
     X(SPARE_HANDLE_MB) X(STRIPS) X(STRIP_TIMING) X(TAIL_THROTTLE) X(TEST_REFUSE_PAIR_LAUNCH)               \
-    X(TEST_SPLIT_EPOCH)                                                                                    \
+    X(TEST_SPLIT_EPOCH) X(TEST_WINDOW_STRIDE)                                                              \
     X(TWO_PASS_ENDS) X(UNITS) X(UPLOAD_PIECE_KB) X(UPLOAD_STREAMS) X(UPLOAD_THREADS) X(VERBOSE)            \
     X(VIEW_CACHE_MB)
 
