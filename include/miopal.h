@@ -459,8 +459,8 @@ void miopalLastOccurrenceRouting(int64_t counts[4]);
  * runs through miopalSearchOccurrences' own path inside the call (its strip-workspace refusal included) and its
  * stretch is spliced into the CSR at its place; what miopalLastOccurrenceRouting reports is left as it was. Once the
  * total has passed maxHits the remaining queries are still counted - hitOffsets is complete - but nothing is written.
- * Not part of this call: panels of PSSMs, the start locations and operations of a panel's occurrences,
- * opalSearchDatabase and the multi-GPU driver. Thread safety as miopalSearch.
+ * Not part of this call: panels of PSSMs, opalSearchDatabase and the multi-GPU driver (the start locations and
+ * operations of a panel's occurrences: miopalSearchBatchOccurrencesAligned below). Thread safety as miopalSearch.
  */
 int miopalSearchBatchOccurrences(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
                                  int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int mode,
@@ -518,8 +518,8 @@ void miopalLastBatchOccurrenceGroups(int64_t counts[3]);
  * reversed-prefix scan with the stop rule, the start cells, the direction pass, the walk, the gather - run on them
  * chunk by chunk in occurrence order, chunks sized as that call sizes them. Nothing of the occurrence list goes up
  * over PCIe; starts, lengths and operations come down per chunk.
- * Not part of this call: a batch of queries, opalSearchDatabase and the multi-GPU driver. Thread safety as
- * miopalSearch.
+ * Not part of this call: opalSearchDatabase and the multi-GPU driver (a panel of queries in one call:
+ * miopalSearchBatchOccurrencesAligned below). Thread safety as miopalSearch.
  */
 int miopalSearchOccurrencesAligned(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                                    const int* scoreMatrix, int alphabetLength, int mode,
@@ -552,6 +552,59 @@ int miopalSearchPssmOccurrencesAligned(MiopalDb* db, const int* rowScores, const
  * the sweeps.
  */
 void miopalLastOccurrenceAlignRouting(int64_t counts[4]);
+
+/*
+ * miopalSearchBatchOccurrences with the other end of every occurrence - miopalSearchOccurrencesAligned for a whole
+ * panel of queries in one call: the user who demultiplexes on 96 barcodes is the one who trims at their starts.
+ *
+ * The first outputs (hitOffsets, *targetIndex, *score, *endTarget, *endQuery) are miopalSearchBatchOccurrences' to the
+ * letter: same rule, same order, same bytes. *startTarget, *startQuery, *alignments and *alignmentOffsets are one CSR
+ * with them: entries hitOffsets[i] .. hitOffsets[i + 1] of the starts, and the operations
+ * (*alignments)[(*alignmentOffsets)[k] .. (*alignmentOffsets)[k + 1]) of those occurrences k, are byte for byte what
+ * miopalSearchOccurrencesAligned returns for query i alone with minScore[i] and window[i], the alignment offsets
+ * rebased: *alignmentOffsets has hitOffsets[nQueries] + 1 entries, entry 0 is 0 and the operations concatenate in CSR
+ * order. alignments == NULL and alignmentOffsets == NULL together: starts only, no direction pass, no walk and no
+ * operation traffic. Exactly one of the two NULL is MIOPAL_ERR_BAD_ARGUMENT.
+ *
+ * Outputs: all malloc'ed by the library, freed by the caller; with no occurrences the pointers are NULL, except
+ * *alignmentOffsets, which then holds the single 0 (nQueries = 0 and an empty slice included). On any error every
+ * output is as it was, hitOffsets under MIOPAL_ERR_TOO_MANY_HITS excepted. Two calls return the same bytes.
+ * maxHits bounds the TOTAL over all queries (< 0: no bound). Unlike miopalSearchOccurrencesAligned, which honours it
+ * before any alignment work, the panel learns its total chunk by chunk: once the running total passes maxHits no
+ * further alignment stage runs and the remaining queries are only counted, what earlier chunks aligned is discarded,
+ * hitOffsets is filled for every query, nothing else is allocated or written, and the call returns
+ * MIOPAL_ERR_TOO_MANY_HITS.
+ * Checks and their order, all before any device work: miopalSearchBatchOccurrences' up to its null outputs, then null
+ * startTarget / startQuery, then the pair alignments / alignmentOffsets, then its 32-bit range check for every query
+ * (one failing query refuses the call).
+ * On the device: miopalSearchBatchOccurrences' sweeps, and behind the write sweep of every panel chunk that has
+ * occurrences the alignment stage, in the workspace the chunk holds. The chunk's queries go up once more, end to end,
+ * with their origins; the occurrences stay where the write sweep left them and are taken in output order, in
+ * sub-chunks sized as miopalAlignPairs sizes its chunks (from the tallest query of the chunk and the longest target
+ * that has an occurrence). Per sub-chunk one gather (batch_occurrence_origins_kernel) finds each occurrence's
+ * target origin in the handle's offsets and its query's origin from the occurrence's position - a binary search in the
+ * chunk's per-query offsets, which the scan left on the device - and the later passes of a miopalAlignPairs `full`
+ * list run on them. Nothing of the occurrence list goes up over PCIe; starts, lengths and operations come down per
+ * sub-chunk. A query of more than 64 rows runs through miopalSearchOccurrencesAligned's own path inside the call and
+ * its stretch is spliced into the CSR at its place; an empty query has no occurrences. What
+ * miopalLastOccurrenceRouting and miopalLastOccurrenceAlignRouting report is left as it was.
+ * Not part of this call: panels of PSSMs, opalSearchDatabase and the multi-GPU driver. Thread safety as miopalSearch.
+ */
+int miopalSearchBatchOccurrencesAligned(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets,
+                                        int nQueries, int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength,
+                                        int mode, int64_t start, int64_t end, const int* minScore, const int* window,
+                                        int64_t maxHits, int64_t* hitOffsets, int64_t** targetIndex, int** score,
+                                        int** endTarget, int** endQuery, int** startTarget, int** startQuery,
+                                        unsigned char** alignments, int64_t** alignmentOffsets);
+
+/*
+ * What the alignment stages of the calling thread's last miopalSearchBatchOccurrencesAligned did: counts[0] =
+ * occurrences whose direction pass ran one lane each, counts[1] = one wavefront each (both 0 for starts only),
+ * counts[2] = sub-chunks of the stage, counts[3] = the longest target window (endTarget - startTarget + 1) of the
+ * call; the first three summed, the last the maximum, over panel chunks and long queries. All 0 without occurrences.
+ * miopalLastBatchOccurrenceRouting and miopalLastBatchOccurrenceGroups keep reporting the sweeps.
+ */
+void miopalLastBatchOccurrenceAlignRouting(int64_t counts[4]);
 
 /*
  * The significant hits of a query: miopalSearchHits with the cut stated as an E-value, the statistics gathered on the

@@ -90,6 +90,7 @@ EXPORTS = [
     "miopalSearchOccurrences", "miopalSearchPssmOccurrences", "miopalLastOccurrenceRouting",
     "miopalSearchOccurrencesAligned", "miopalSearchPssmOccurrencesAligned", "miopalLastOccurrenceAlignRouting",
     "miopalSearchBatchOccurrences", "miopalLastBatchOccurrenceRouting", "miopalLastBatchOccurrenceGroups",
+    "miopalSearchBatchOccurrencesAligned", "miopalLastBatchOccurrenceAlignRouting",
     # test hooks
     "miopalTestProfileColumns",
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
@@ -168,6 +169,7 @@ def lib() -> ctypes.CDLL:
             "miopalLastBatchRouting": (None, [p_i64]), "miopalLastOccurrenceRouting": (None, [p_i64]),
             "miopalLastOccurrenceAlignRouting": (None, [p_i64]),
             "miopalLastBatchOccurrenceRouting": (None, [p_i64]), "miopalLastBatchOccurrenceGroups": (None, [p_i64]),
+            "miopalLastBatchOccurrenceAlignRouting": (None, [p_i64]),
             "miopalLastKernelTime": (c_int, [c_vp, ctypes.POINTER(ctypes.c_float)]),
             "miopalSearch": (c_int, one + middle + [c_vp] * 7),
             "miopalSearchFlat": (c_int, one + middle + flat + [c_vp]),
@@ -210,6 +212,7 @@ def lib() -> ctypes.CDLL:
         # ... aligned: the PSSM with its consensus; behind the occurrences startT, startQ, operations, their offsets
         for side, head in (("", one), ("Pssm", pssm_full)):
             table[f"miopalSearch{side}OccurrencesAligned"] = (c_int, head + middle[1:] + [c_int, c_int, c_i64, p_i64] + found + [pp] * 4)
+        table["miopalSearchBatchOccurrencesAligned"] = (c_int, table["miopalSearchBatchOccurrences"][1] + [pp] * 4)
         for name, (restype, argtypes) in table.items():
             getattr(L, name).restype = restype
             getattr(L, name).argtypes = argtypes
@@ -482,6 +485,15 @@ def last_occurrence_align_routing() -> typing.List[int]:
     stage, the longest target window] of the calling thread's last `search_occurrence_alignments` call"""
     counts = (ctypes.c_int64 * 4)()
     lib().miopalLastOccurrenceAlignRouting(counts)
+    return list(counts)
+
+
+def last_batch_occurrence_align_routing() -> typing.List[int]:
+    """miopalLastBatchOccurrenceAlignRouting: [occurrences aligned one lane each, one wavefront each, sub-chunks of the
+    alignment stage, the longest target window] of the calling thread's last `search_batch_occurrence_alignments`
+    call, over its panel chunks and long queries"""
+    counts = (ctypes.c_int64 * 4)()
+    lib().miopalLastBatchOccurrenceAlignRouting(counts)
     return list(counts)
 
 
@@ -1101,6 +1113,15 @@ class DeviceDatabase:
         offsets[i]:offsets[i + 1] equal search_occurrences(queries[i], ...) byte for byte. ``max_hits`` bounds the
         total; TooManyHits carries the offsets in ``counts``. The rule's faults raise ValueError before any device
         call, as `search_occurrences`' do."""
+        rc, offsets, ptrs = self._call_batch_occurrences("miopalSearchBatchOccurrences", queries, matrix, gap_open,
+                                                         gap_extend, algorithm, start, end, min_score, window, max_hits)
+        return self._found(rc, offsets, ptrs, "end")
+
+    def _call_batch_occurrences(self, entry, queries, matrix, gap_open, gap_extend, algorithm, start, end, min_score,
+                                window, max_hits, more=()):
+        """The preamble of the panel occurrence searches - the query side, the per-query cuts and windows, the rule's
+        faults - and the call of the entry point named ``entry``, with ``more`` arguments behind the four result
+        pointers. Returns (the code, the offsets, the result pointers)."""
         side = self._batch_side(queries, matrix, gap_open, gap_extend)
         lengths = np.diff(side.keep[1]).tolist()
         cuts, windows = _per_query(min_score, lengths, "min_score"), _per_query(window, lengths, "window")
@@ -1115,16 +1136,42 @@ class DeviceDatabase:
         cuts, windows = cuts.astype(np.int32), windows.astype(np.int32)
         offsets = np.zeros(side.rows + 1, dtype=np.int64)
         ptrs = _HitPointers()
-        rc = lib().miopalSearchBatchOccurrences(
-            self._h, *side.queries, *side.scoring, MODE[algorithm], start, self._clamp(end),
-            _ptr(cuts) if side.rows else None, _ptr(windows) if side.rows else None, _bound(max_hits), _ptr(offsets),
-            *ptrs.refs())
-        return self._found(rc, offsets, ptrs, "end")
+        rc = getattr(lib(), entry)(self._h, *side.queries, *side.scoring, MODE[algorithm], start, self._clamp(end),
+                   _ptr(cuts) if side.rows else None, _ptr(windows) if side.rows else None, _bound(max_hits),
+                   _ptr(offsets), *ptrs.refs(), *more)
+        return rc, offsets, ptrs
+
+    def search_batch_occurrence_alignments(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray,
+                                           gap_open: int = 3, gap_extend: int = 1, algorithm: str = "hw", start: int = 0,
+                                           end: typing.Optional[int] = None, min_score=1, window=None,
+                                           max_hits: typing.Optional[int] = None,
+                                           operations: bool = True) -> typing.Dict[str, typing.Any]:
+        """miopalSearchBatchOccurrencesAligned: `search_occurrence_alignments` of every query of a panel in one call.
+        Returns `search_batch_occurrences`' dict - the same arrays, byte for byte - plus "start_t" and "start_q" and,
+        with ``operations``, "aln_flat", "aln_off" (offsets[-1] + 1 entries, rebased to start at 0) and "aln": entries
+        offsets[i]:offsets[i + 1] equal search_occurrence_alignments(queries[i], ...). ``operations=False``: starts
+        only, and no "aln*" keys. ``max_hits`` bounds the total; TooManyHits carries the offsets in ``counts``, and
+        what had been aligned by then is discarded."""
+        start_t, start_q, ops, ops_off = (ctypes.c_void_p() for _ in range(4))
+        more = (ctypes.byref(start_t), ctypes.byref(start_q), ctypes.byref(ops) if operations else None,
+                ctypes.byref(ops_off) if operations else None)
+        rc, offsets, ptrs = self._call_batch_occurrences("miopalSearchBatchOccurrencesAligned", queries, matrix,
+                                                         gap_open, gap_extend, algorithm, start, end, min_score, window,
+                                                         max_hits, more)
+        out = self._found(rc, offsets, ptrs, "end")
+        n = int(offsets[-1])
+        out.update(start_t=_take_malloced(start_t, n, np.int32), start_q=_take_malloced(start_q, n, np.int32))
+        if operations:
+            aoff = _take_malloced(ops_off, n + 1, np.int64)
+            flat = _take_malloced(ops, int(aoff[-1]), np.uint8)
+            out.update(aln_flat=flat, aln_off=aoff, aln=_LazyAlignments(flat, aoff))
+        return out
 
     pick_occurrences_rows = staticmethod(pick_occurrences_rows)
     last_occurrence_routing = staticmethod(last_occurrence_routing)
     last_batch_occurrence_routing = staticmethod(last_batch_occurrence_routing)
     last_batch_occurrence_groups = staticmethod(last_batch_occurrence_groups)
+    last_batch_occurrence_align_routing = staticmethod(last_batch_occurrence_align_routing)
     last_occurrence_align_routing = staticmethod(last_occurrence_align_routing)
 
     def search_significant(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,

@@ -40,6 +40,7 @@
 #include "occurrences.h"
 #include "occurrences_batch.h"
 #include "occurrence_align.h"
+#include "occurrence_align_batch.h"
 #include "profile_columns.h"
 #include "score_ranges_selftest.h"
 #include "select_columns.h"
@@ -753,6 +754,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_profile.inc"
 #include "host_occurrences.inc"
 #include "host_occurrence_align.inc"
+#include "host_batch_occurrence_align.inc"
 #include "host_batch_occurrences.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
@@ -1044,6 +1046,7 @@ void miopalLastBatchOccurrenceGroups(int64_t counts[3]) {
 }
 
 // the outputs the aligned forms add: the starts always, the operations and their offsets together or not at all
+// (declared in host_batch_occurrences.inc, whose panel form makes the check among its own)
 static int checkOccurrenceAlignOutputs(int** startTarget, int** startQuery, unsigned char** alignments,
                                        int64_t** alignmentOffsets) {
     if (!startTarget || !startQuery) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null start-location outputs");
@@ -1104,6 +1107,27 @@ int miopalSearchPssmOccurrencesAligned(MiopalDb* db, const int* rowScores, const
 void miopalLastOccurrenceAlignRouting(int64_t counts[4]) {
     if (!counts) return;
     for (int k = 0; k < 4; ++k) counts[k] = g_lastOccurrenceAlignRouting[k];
+}
+
+// miopalSearchBatchOccurrencesAligned: miopalSearchBatchOccurrences' checks in its order with the new null outputs
+// behind its own; the panel's sweeps with the alignment stage behind every write sweep
+// (host_batch_occurrence_align.inc), a long query's through miopalSearchOccurrencesAligned's own path
+int miopalSearchBatchOccurrencesAligned(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets,
+                                        int nQueries, int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength,
+                                        int mode, int64_t start, int64_t end, const int* minScore, const int* window,
+                                        int64_t maxHits, int64_t* hitOffsets, int64_t** targetIndex, int** score,
+                                        int** endTarget, int** endQuery, int** startTarget, int** startQuery,
+                                        unsigned char** alignments, int64_t** alignmentOffsets) {
+    return guarded([&]() -> int {
+    return searchBatchOccurrencesImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength, mode,
+                                      start, end, minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery,
+                                      true, startTarget, startQuery, alignments, alignmentOffsets);
+    });
+}
+
+void miopalLastBatchOccurrenceAlignRouting(int64_t counts[4]) {
+    if (!counts) return;
+    for (int k = 0; k < 4; ++k) counts[k] = g_lastBatchOccurrenceAlignRouting[k];
 }
 
 int miopalTestPickOccurrences(const int* value, const int* valueRow, int rows, int64_t stride, const int32_t* length,

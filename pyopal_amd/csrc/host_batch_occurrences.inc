@@ -9,6 +9,13 @@
 // A query of more than 64 rows runs through searchOccurrencesImpl inside the same call (what miopalSearchBatch does
 // with its long queries); an empty query has no occurrences. The pieces are spliced into the CSR at the end: nothing
 // is written to the outputs before the last step that can fail.
+//
+// miopalSearchBatchOccurrencesAligned is the same call with an alignment stage behind every write sweep
+// (host_batch_occurrence_align.inc for the panel chunks, host_occurrence_align.inc's for a long query): every piece
+// then carries its occurrences' starts and operations, and the splice puts those together as well.
+static int checkOccurrenceAlignOutputs(int** startTarget, int** startQuery, unsigned char** alignments,
+                                       int64_t** alignmentOffsets);   // (host.hip, with the entry points)
+
 namespace {
 
 thread_local int64_t g_lastBatchOccurrenceRouting[4] = {0, 0, 0, 0};   // miopalLastBatchOccurrenceRouting
@@ -36,21 +43,31 @@ int64_t batchOccurrenceWorkgroupsPerCu() {
     return kBatchOccurrenceWorkgroupsPerCu;
 }
 
-// where a query's occurrences lie until the CSR is put together
+// where a query's occurrences lie until the CSR is put together; aligned (the aligned call): the starts of the piece
+// `from`, entry for entry, and its operations - those of the stretch are opsOff[first] .. opsOff[first + count]
 struct OccurrenceStretch {
     const HitArrays* from = nullptr;
     int64_t first = 0, count = 0;
+    const OccurrenceAlignment* aligned = nullptr;
+};
+
+// the aligned call: whether operations are asked for, and where the pieces' alignments are kept until the splice
+struct BatchOccurrenceAlign {
+    bool operations;
+    std::vector<std::unique_ptr<OccurrenceAlignment>> pieces;
 };
 
 }  // namespace
 
 // The panel queries `panel` (indices into the call's list, ascending, 1 .. 64 rows each), chunk by chunk. counts[i]
 // and stretch[i] are filled for every one of them; once *running passes maxHits (*over) the chunks are only counted.
+// `align` (null: the plain call): the alignment stage runs behind every write sweep, and never once *over is set.
 static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets,
                                 const std::vector<int>& panel, int open, int ext, const int* matrix, int A, int mode,
                                 int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
                                 int64_t* running, bool* over, std::vector<int64_t>* counts,
-                                std::vector<OccurrenceStretch>* stretch, std::vector<std::unique_ptr<HitArrays>>* pieces) {
+                                std::vector<OccurrenceStretch>* stretch, std::vector<std::unique_ptr<HitArrays>>* pieces,
+                                BatchOccurrenceAlign* align) {
     const int64_t n = end - start;
     const int region = mode == OPAL_MODE_HW ? kLastRow : kAllCells;
     const int64_t maxL = db->maxLen;
@@ -201,19 +218,38 @@ static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, cons
         RC_TRY(ws->stageDownload(hits.endQ, a.outRow, sizeof(int) * (size_t)total));
         RC_TRY(ws->stageDownload(hits.endT, a.outColumn, sizeof(int) * (size_t)total));
         RC_TRY(ws->finishDownloads());
+        const OccurrenceAlignment* aligned = nullptr;
+        if (align) {
+            // the stage, on the occurrences where they are (head[0 .. cq] still lies behind dHead). It takes kJobs,
+            // kSortedJobs and kSortBins: the next chunk's count sweep builds the slice's sorted jobs again.
+            align->pieces.emplace_back(new OccurrenceAlignment());
+            RC_TRY(alignBatchOccurrencesStage(
+                BatchOccurrencesOnDevice{db, ws, queries, queryOffsets, panel.data() + p0, cq, open, ext, matrix, A, mode, total,
+                                         a.outTarget, a.outScore, a.outRow, a.outColumn, dHead, &hits},
+                align->operations, align->pieces.back().get()));
+            aligned = align->pieces.back().get();
+            jobsOf = -1;
+            psorted = nullptr;
+        }
         for (int q = 0; q < cq; ++q)
-            (*stretch)[(size_t)panel[p0 + (size_t)q]] = OccurrenceStretch{&hits, head[(size_t)q], head[(size_t)q + 1] - head[(size_t)q]};
+            (*stretch)[(size_t)panel[p0 + (size_t)q]] =
+                OccurrenceStretch{&hits, head[(size_t)q], head[(size_t)q + 1] - head[(size_t)q], aligned};
     }
     return 0;
 }
 
-// Behind nothing: the checks of miopalSearchOccurrences over the whole list, in its order, come first
+// Behind nothing: the checks of miopalSearchOccurrences over the whole list, in its order, come first.
+// wantAligned: miopalSearchBatchOccurrencesAligned - the four outputs behind endQuery are checked and written too.
 static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
                                       int open, int ext, const int* matrix, int A, int mode, int64_t start, int64_t end,
                                       const int* minScore, const int* window, int64_t maxHits, int64_t* hitOffsets,
-                                      int64_t** targetIndex, int** score, int** endTarget, int** endQuery) {
+                                      int64_t** targetIndex, int** score, int** endTarget, int** endQuery,
+                                      bool wantAligned = false, int** startTarget = nullptr, int** startQuery = nullptr,
+                                      unsigned char** alignments = nullptr, int64_t** alignmentOffsets = nullptr) {
     for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceRouting[k] = 0;
     for (int k = 0; k < 3; ++k) g_lastBatchOccurrenceGroups[k] = 0;
+    if (wantAligned)
+        for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceAlignRouting[k] = 0;
     RC_TRY(validateBatch(db, queries, queryOffsets, nQueries, matrix, A, OPAL_SEARCH_SCORE_END, mode, start, end));
     if (mode != OPAL_MODE_HW && mode != OPAL_MODE_SW)
         return fail(OPAL_ERR_INVALID_MODE, "occurrences are defined for OPAL_MODE_HW and OPAL_MODE_SW, not for mode %d", mode);
@@ -226,6 +262,10 @@ static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries
                 return fail(MIOPAL_ERR_BAD_ARGUMENT, "minScore = %d at query %d: OPAL_MODE_SW needs a cut of at least 1", minScore[i], i);
     if (nQueries > 0 && (!minScore || !window)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null minScore / window list");
     RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, hitOffsets, targetIndex, score, endTarget, endQuery));
+    if (wantAligned) RC_TRY(checkOccurrenceAlignOutputs(startTarget, startQuery, alignments, alignmentOffsets));
+    const bool operations = wantAligned && alignments != nullptr;
+    BatchOccurrenceAlign alignState{operations, {}};
+    BatchOccurrenceAlign* const align = wantAligned ? &alignState : nullptr;
     const int64_t n = end - start;
     std::vector<int64_t> counts((size_t)nQueries, 0);
     std::vector<OccurrenceStretch> stretch((size_t)nQueries);
@@ -251,31 +291,73 @@ static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries
         // filled for every query also when there are too many hits, and nothing is written or downloaded for them.
         int64_t singleRouting[4];
         for (int k = 0; k < 4; ++k) singleRouting[k] = g_lastOccurrenceRouting[k];
+        // (the same for what miopalLastOccurrenceAlignRouting reports, which a long query's stage counts in)
+        int64_t singleAlignRouting[4];
+        for (int k = 0; k < 4; ++k) singleAlignRouting[k] = g_lastOccurrenceAlignRouting[k];
         struct PutBack {
-            const int64_t* saved;
-            ~PutBack() { for (int k = 0; k < 4; ++k) g_lastOccurrenceRouting[k] = saved[k]; }
-        } putBack{singleRouting};
+            const int64_t *saved, *savedAlign;
+            ~PutBack() {
+                for (int k = 0; k < 4; ++k) g_lastOccurrenceRouting[k] = saved[k];
+                for (int k = 0; k < 4; ++k) g_lastOccurrenceAlignRouting[k] = savedAlign[k];
+            }
+        } putBack{singleRouting, singleAlignRouting};
         for (int i : single) {
             int64_t found = 0;
             const int64_t room = over ? 0 : maxHits < 0 ? -1 : maxHits - running;
             pieces.emplace_back(new HitArrays());
             HitArrays& hits = *pieces.back();
+            // (aligned: the single-query stage behind its write sweep - it does not run when the bound is passed)
+            OccurrenceAlignment* got = nullptr;
+            if (align) {
+                align->pieces.emplace_back(new OccurrenceAlignment());
+                got = align->pieces.back().get();
+                for (int k = 0; k < 4; ++k) g_lastOccurrenceAlignRouting[k] = 0;
+            }
+            const OccurrenceStage stage = [&](const OccurrencesOnDevice& o) { return alignOccurrencesStage(o, operations, got); };
             const int rc = searchOccurrencesImpl(db, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open,
                                                  ext, matrix, nullptr, A, mode, start, end, minScore[i], window[i], room, &found,
-                                                 &hits.target, &hits.score, &hits.endT, &hits.endQ);
+                                                 &hits.target, &hits.score, &hits.endT, &hits.endQ, align ? &stage : nullptr);
             if (rc == MIOPAL_ERR_TOO_MANY_HITS) over = true;
             else if (rc) return rc;
+            if (align) {
+                for (int k = 0; k < 3; ++k) g_lastBatchOccurrenceAlignRouting[k] += g_lastOccurrenceAlignRouting[k];
+                g_lastBatchOccurrenceAlignRouting[3] = std::max(g_lastBatchOccurrenceAlignRouting[3], g_lastOccurrenceAlignRouting[3]);
+            }
             counts[(size_t)i] = found;
             running += found;
-            if (!over) stretch[(size_t)i] = OccurrenceStretch{&hits, 0, found};
+            if (!over) stretch[(size_t)i] = OccurrenceStretch{&hits, 0, found, found > 0 ? got : nullptr};
         }
         if (!panel.empty() && db->maxLen > 0)
             RC_TRY(batchOccurrencePanel(db, queries, queryOffsets, panel, open, ext, matrix, A, mode, start, end, minScore, window,
-                                        maxHits, &running, &over, &counts, &stretch, &pieces));
+                                        maxHits, &running, &over, &counts, &stretch, &pieces, align));
     }
-    // nothing failed: the outputs are written from here on
     HitArrays all;
     if (!over) RC_TRY(all.alloc(running, true));
+    // (aligned: the starts, the rebased offsets - the single 0 without occurrences - and room for the operations)
+    OccurrenceAlignment joined;
+    if (align && !over) {
+        if (running > 0) {
+            joined.startT = (int*)malloc(sizeof(int) * (size_t)running);
+            joined.startQ = (int*)malloc(sizeof(int) * (size_t)running);
+            if (!joined.startT || !joined.startQ) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+        }
+        if (operations) {
+            joined.opsOff = (int64_t*)malloc(sizeof(int64_t) * (size_t)(running + 1));
+            if (!joined.opsOff) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+            joined.opsOff[0] = 0;
+            int64_t at = 0, nOps = 0;
+            for (int i = 0; i < nQueries; ++i) {
+                const OccurrenceStretch& s = stretch[(size_t)i];
+                for (int64_t k = 0; k < s.count; ++k, ++at) {
+                    nOps += s.aligned->opsOff[s.first + k + 1] - s.aligned->opsOff[s.first + k];
+                    joined.opsOff[at + 1] = nOps;
+                }
+            }
+            if (at != running) return fail(MIOPAL_ERR_INTERNAL, "panel occurrence stretches hold %lld of %lld", (long long)at, (long long)running);
+            if (running > 0 && !joined.ops.resize((size_t)nOps)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+        }
+    }
+    // nothing failed: the outputs are written from here on
     hitOffsets[0] = 0;
     for (int i = 0; i < nQueries; ++i) hitOffsets[i + 1] = hitOffsets[i] + counts[(size_t)i];
     if (over) return fail(MIOPAL_ERR_TOO_MANY_HITS, "%lld occurrences, maxHits = %lld", (long long)running, (long long)maxHits);
@@ -287,7 +369,23 @@ static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries
         memcpy(all.score + at, s.from->score + s.first, sizeof(int) * len);
         memcpy(all.endT + at, s.from->endT + s.first, sizeof(int) * len);
         memcpy(all.endQ + at, s.from->endQ + s.first, sizeof(int) * len);
+        if (!align) continue;
+        memcpy(joined.startT + at, s.aligned->startT + s.first, sizeof(int) * len);
+        memcpy(joined.startQ + at, s.aligned->startQ + s.first, sizeof(int) * len);
+        if (operations)
+            memcpy(joined.ops.data + joined.opsOff[at], s.aligned->ops.data + s.aligned->opsOff[s.first],
+                   (size_t)(joined.opsOff[at + len] - joined.opsOff[at]));
     }
     all.release(targetIndex, score, endTarget, endQuery);
+    if (align) {
+        *startTarget = joined.startT;
+        *startQuery = joined.startQ;
+        joined.startT = joined.startQ = nullptr;
+        if (operations) {
+            *alignments = joined.ops.release();
+            *alignmentOffsets = joined.opsOff;
+            joined.opsOff = nullptr;
+        }
+    }
     return 0;
 }

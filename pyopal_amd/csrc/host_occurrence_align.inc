@@ -33,13 +33,19 @@ struct OccurrenceAlignment {
 
 }  // namespace
 
-static int alignOccurrencesStage(const OccurrencesOnDevice& o, bool operations, OccurrenceAlignment* out) {
-    Search& s = *o.s;
+// The stage itself, shared with the panel form (host_batch_occurrence_align.inc): the `total` occurrences whose arrays
+// dScore / dRow / dColumn lie in the workspace of `s` and whose host copies are `hits`, chunk by chunk in output order.
+// `s` holds the query buffer (ensurePairInputs has run or runs here): the call's one query, or a panel chunk's queries
+// end to end; Q = its tallest query, which sizes the chunks. gather(c0, nc, targetOff, &qBase) enqueues what fills
+// targetOff[0 .. nc) for the occurrences c0 .. c0 + nc and names their query origins (null: all at 0). What the
+// chunks did is added to `routing` (the figures of miopalLastOccurrenceAlignRouting).
+using OccurrenceGather = std::function<int(int64_t c0, int nc, int64_t* targetOff, const int32_t** qBase)>;
+
+static int alignOccurrenceChunks(Search& s, int64_t total, const HitArrays& hits, const int32_t* dScore, const int32_t* dRow,
+                                 const int32_t* dColumn, int Q, bool operations, const OccurrenceGather& gather,
+                                 int64_t* routing, OccurrenceAlignment* out) {
     MiopalDb* const db = s.db;
     Workspace* const ws = s.ws;
-    const int64_t total = o.total;
-    const int Q = s.Q;
-    const HitArrays& hits = *o.hits;
     out->startT = (int*)malloc(sizeof(int) * (size_t)total);
     out->startQ = (int*)malloc(sizeof(int) * (size_t)total);
     if (operations) out->opsOff = (int64_t*)malloc(sizeof(int64_t) * (size_t)(total + 1));
@@ -77,15 +83,16 @@ static int alignOccurrencesStage(const OccurrencesOnDevice& o, bool operations, 
             RC_TRY(ws->get(kSortedJobs, (size_t)nc * sizeof(PairJob), &psorted));
             RC_TRY(ws->get(kHeadWaves, sizeof(int), &phead));
         }
-        HIP_TRY(launchOccurrencePairInputs(nc, o.target + c0, db->d_offsets, db->count, (int64_t*)ptoff, s.stream));
+        const int32_t* pqbase = nullptr;
+        RC_TRY(gather(c0, nc, (int64_t*)ptoff, &pqbase));
         int headWaves = 0;
         LaterPasses lp{};
         lp.db = db; lp.s = &s;
-        lp.mode = s.mode; lp.open = s.open; lp.ext = s.ext; lp.A = s.A; lp.totalQuery = Q;
+        lp.mode = s.mode; lp.open = s.open; lp.ext = s.ext; lp.A = s.A; lp.totalQuery = s.Q;
         lp.nc = nc; lp.maxL = chunkL; lp.oneStrip = oneStrip; lp.fwdWsStride = oneStrip ? 0 : chunkL;
         lp.lane = lane; lp.lanePossible = lanePossible; lp.forceLane = forceLane;
-        lp.score = o.score + c0; lp.endI = o.row + c0; lp.endJ = o.column + c0;
-        lp.tOff = (const int64_t*)ptoff; lp.qBase = nullptr;
+        lp.score = dScore + c0; lp.endI = dRow + c0; lp.endJ = dColumn + c0;
+        lp.tOff = (const int64_t*)ptoff; lp.qBase = pqbase;
         lp.jobs = (PairJob*)pjobs; lp.sorted = (PairJob*)psorted; lp.bins = (int*)pbins; lp.head = (int*)phead;
         lp.startsOnly = !operations; lp.endsOnHost = true;
         lp.consumer = nullptr; lp.pairs = nullptr; lp.noun = "occurrence";
@@ -101,16 +108,26 @@ static int alignOccurrencesStage(const OccurrencesOnDevice& o, bool operations, 
         }
         if (operations) {
             const int64_t toWave = lp.traceLane ? std::min<int64_t>(nc, (int64_t)headWaves * kLanes) : nc;
-            g_lastOccurrenceAlignRouting[0] += nc - toWave;
-            g_lastOccurrenceAlignRouting[1] += toWave;
+            routing[0] += nc - toWave;
+            routing[1] += toWave;
         }
-        g_lastOccurrenceAlignRouting[2] += 1;
-        g_lastOccurrenceAlignRouting[3] = std::max(g_lastOccurrenceAlignRouting[3], lp.maxWindow);
+        routing[2] += 1;
+        routing[3] = std::max(routing[3], lp.maxWindow);
     }
     if (operations && (size_t)out->opsOff[total] != out->ops.size)
         return fail(MIOPAL_ERR_INTERNAL, "operation offsets disagree with the device");
     if (operations && !out->ops.data && !out->ops.resize(0)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
     return 0;
+}
+
+static int alignOccurrencesStage(const OccurrencesOnDevice& o, bool operations, OccurrenceAlignment* out) {
+    Search& s = *o.s;
+    const OccurrenceGather gather = [&](int64_t c0, int nc, int64_t* targetOff, const int32_t**) {
+        HIP_TRY(launchOccurrencePairInputs(nc, o.target + c0, s.db->d_offsets, s.db->count, targetOff, s.stream));
+        return 0;
+    };
+    return alignOccurrenceChunks(s, o.total, *o.hits, o.score, o.row, o.column, s.Q, operations, gather,
+                                 g_lastOccurrenceAlignRouting, out);
 }
 
 // Behind the entry points' checks: the sweeps with the stage behind them, then the outputs - all of them, or none.

@@ -9,6 +9,7 @@ plus a fixed table of extensions.
     ends = find_occurrences(aligner, "ETSEEES", database, 25, mode="end")
 
     panel = find_occurrences_many(aligner, barcodes, database, 25)        # one list of EndResult per query
+    trims = find_occurrence_alignments_many(aligner, barcodes, database, 25)   # ... of FullResult per query
 
 ``mode="end"`` is served by the occurrence search alone (EndResult: score and end cell); ``mode="full"`` by the aligned
 form, whose start cells follow the checker's rule applied to each occurrence's end cell, and whose operations are the
@@ -133,12 +134,15 @@ def _panel_values(values, name, none_allowed):
     return items, many
 
 
-def _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits):
+def _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits,
+                  operations=None):
+    """(the CSR of the request, the query side, the target lengths or None). ``operations`` None: the panel search
+    (`find_occurrences_many`, mode "end"); a bool: the aligned form, with or without the operations."""
     if mode not in _MODES:
         raise ValueError(f"occurrences are reported with mode 'end' or 'full', not {mode!r}")
-    if mode == "full":
-        raise ValueError("the alignments of a panel's occurrences are not available yet: find_occurrences_many reports "
-                         "mode 'end'; find_occurrences(..., mode='full') aligns one query's occurrences")
+    if mode == "full" and operations is None:
+        raise ValueError("the alignments of a panel's occurrences are not available yet from find_occurrences_many, "
+                         "which reports mode 'end': find_occurrence_alignments_many aligns a panel's occurrences")
     cuts, many_cuts = _panel_values(min_score, "min_score", False)
     windows, many_windows = _panel_values(window, "window", True)
     for cut in cuts or [1]:
@@ -154,10 +158,18 @@ def _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode
     with request:
         if request.end == start or rows == 0 or max(side.lengths) == 0:
             # (nothing to search, or nothing to search with: answered without a device)
-            return dict(_empty_arrays(mode), offsets=np.zeros(rows + 1, dtype=np.int64), target=np.zeros(0, dtype=np.int64))
-        return request.mirror().search_batch_occurrences(
-            side.arrays, aligner._matrix, aligner.gap_open, aligner.gap_extend, algorithm, start, request.end,
-            cuts if many_cuts else cuts[0], windows if many_windows else windows[0], request.checked)
+            out = dict(_empty_arrays(mode), offsets=np.zeros(rows + 1, dtype=np.int64), target=np.zeros(0, dtype=np.int64))
+            if operations is False:
+                del out["aln_flat"], out["aln_off"]
+            return out, side, None
+        mirror = request.mirror()
+        rule = (side.arrays, aligner._matrix, aligner.gap_open, aligner.gap_extend, algorithm, start, request.end,
+                cuts if many_cuts else cuts[0], windows if many_windows else windows[0], request.checked)
+        if operations is None:
+            return mirror.search_batch_occurrences(*rule), side, None
+        out = mirror.search_batch_occurrence_alignments(*rule, operations)
+        out.pop("aln", None)
+        return out, side, _target_lengths(mirror, mode)
 
 
 def find_occurrences_many(aligner: Aligner, queries, database: BaseDatabase, min_score, *, window=None,
@@ -167,9 +179,10 @@ def find_occurrences_many(aligner: Aligner, queries, database: BaseDatabase, min
     list with one list of `EndResult` per query, each what ``find_occurrences(aligner, query, ..., mode="end")``
     returns for that query. ``min_score`` and ``window``: one value or one per query (a window of None: that query's
     length). ``max_hits`` bounds the total over all queries; `_capi.TooManyHits` carries the CSR offsets in
-    ``counts``. ``mode="full"`` raises ValueError: the alignments of a panel's occurrences are not available yet. That
-    and the other rule faults raise before any device call; an empty panel or slice is answered without a device."""
-    out = _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits)
+    ``counts``. ``mode="full"`` raises ValueError - the alignments of a panel's occurrences are not available yet
+    under this name: `find_occurrence_alignments_many` returns them. That and the other rule faults raise before any
+    device call; an empty panel or slice is answered without a device."""
+    out = _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits)[0]
     flat = _result_objects(mode, out["target"], None, None, None, out)
     offsets = out["offsets"].tolist()
     return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
@@ -180,4 +193,36 @@ def find_occurrences_many_arrays(aligner: Aligner, queries, database: BaseDataba
                                  device: int = 0, max_hits: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
     """`find_occurrences_many` without result objects: a CSR - "offsets" (one entry per query plus one), "target"
     (int64), "score", "end_q" and "end_t"; entries offsets[i]:offsets[i + 1] belong to query i."""
-    return _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits)
+    return _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits)[0]
+
+
+# --- ... with where every occurrence starts and how it aligns (miopalSearchBatchOccurrencesAligned) ------------------
+# (names of their own: find_occurrences_many(..., mode="full") keeps raising, which its tests pin)
+
+def find_occurrence_alignments_many(aligner: Aligner, queries, database: BaseDatabase, min_score, *, window=None,
+                                    algorithm: str = "hw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                                    max_hits: typing.Optional[int] = None) -> typing.List[typing.List[ScoreResult]]:
+    """`find_occurrences(..., mode="full")` for a whole panel of queries in one device call: a list with one list of
+    `FullResult` per query, each what ``find_occurrences(aligner, query, ..., mode="full")`` returns for that query -
+    the occurrence's start, so that a read is trimmed at ``target_start``, and its alignment. ``min_score``,
+    ``window`` and ``max_hits`` as in `find_occurrences_many`; once the total passes ``max_hits`` nothing more is
+    aligned and `_capi.TooManyHits` carries the CSR offsets. The rule's faults raise before any device call; an empty
+    panel or slice is answered without a device."""
+    out, side, target_lengths = _panel_arrays(aligner, queries, database, min_score, window, algorithm, "full", start, end,
+                                              device, max_hits, True)
+    offsets = out["offsets"]
+    owner = np.repeat(np.arange(len(offsets) - 1, dtype=np.int64), np.diff(offsets))
+    flat = _result_objects("full", out["target"], owner, side.lengths, target_lengths, out)
+    offsets = offsets.tolist()
+    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+
+
+def find_occurrence_alignments_many_arrays(aligner: Aligner, queries, database: BaseDatabase, min_score, *, window=None,
+                                           algorithm: str = "hw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                                           max_hits: typing.Optional[int] = None,
+                                           operations: bool = True) -> typing.Dict[str, typing.Any]:
+    """`find_occurrence_alignments_many` without result objects: `find_occurrences_many_arrays`' CSR plus "start_q" /
+    "start_t" and, with ``operations``, "aln_flat" / "aln_off" (one entry per occurrence plus one, starting at 0);
+    entries offsets[i]:offsets[i + 1] belong to query i. ``operations=False``: starts only."""
+    return _panel_arrays(aligner, queries, database, min_score, window, algorithm, "full", start, end, device, max_hits,
+                         bool(operations))[0]
