@@ -142,7 +142,8 @@ int miopalSearchFlat(MiopalDb* db, const unsigned char* query, int queryLength, 
  * the strip at hand in LDS instead of the matrix ("Position-specific scoring matrices").
  * The k best hits and pair lists take a PSSM too: miopalSearchPssmTop and miopalAlignPairsPssm, below.
  * Out of scope: PSSM forms of miopalSearchBatch and miopalSearchBatchTop (their kernels take queries of at
- * most 64 rows, which few PSSMs are), of opalSearchDatabase and of the multi-GPU shard driver. The columns a PSSM
+ * most 64 rows, which few PSSMs are - motifs are: miopalSearchPssmBatchOccurrences takes a panel of them), of
+ * opalSearchDatabase and of the multi-GPU shard driver. The columns a PSSM
  * is built from come from miopalProfileColumns, below; the pseudocounts and log-odds on top of them are the
  * caller's (Pssm.from_columns in the Python layer). Still out of scope there: per-column reduced alignments as
  * PSI-BLAST weights them, composition-based statistics, insertion-aware profiles.
@@ -459,8 +460,9 @@ void miopalLastOccurrenceRouting(int64_t counts[4]);
  * runs through miopalSearchOccurrences' own path inside the call (its strip-workspace refusal included) and its
  * stretch is spliced into the CSR at its place; what miopalLastOccurrenceRouting reports is left as it was. Once the
  * total has passed maxHits the remaining queries are still counted - hitOffsets is complete - but nothing is written.
- * Not part of this call: panels of PSSMs, opalSearchDatabase and the multi-GPU driver (the start locations and
- * operations of a panel's occurrences: miopalSearchBatchOccurrencesAligned below). Thread safety as miopalSearch.
+ * Not part of this call: opalSearchDatabase and the multi-GPU driver (the start locations and operations of a
+ * panel's occurrences: miopalSearchBatchOccurrencesAligned below; a panel of PSSMs: miopalSearchPssmBatchOccurrences
+ * below). Thread safety as miopalSearch.
  */
 int miopalSearchBatchOccurrences(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
                                  int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int mode,
@@ -468,7 +470,7 @@ int miopalSearchBatchOccurrences(MiopalDb* db, const unsigned char* queries, con
                                  int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery);
 
 /*
- * What the last miopalSearchBatchOccurrences of the calling thread did: counts[0] = queries on the panel kernels,
+ * What the last panel occurrence search of the calling thread, plain or PSSM, did: counts[0] = queries on the panel kernels,
  * counts[1] = queries on the single-query path, counts[2] = chunks (one count sweep + scan + download + write sweep
  * each), counts[3] = (query, target) pairs the write sweeps took - those that have occurrences. All 0 for an empty
  * slice or an empty list.
@@ -476,7 +478,7 @@ int miopalSearchBatchOccurrences(MiopalDb* db, const unsigned char* queries, con
 void miopalLastBatchOccurrenceRouting(int64_t counts[4]);
 
 /*
- * How the last miopalSearchBatchOccurrences of the calling thread grouped its panel queries: counts[0] = groups over
+ * How the last panel occurrence search of the calling thread, plain or PSSM, grouped its panel queries: counts[0] = groups over
  * all chunks (the rows of a group share a workgroup's LDS in the count sweep), counts[1] = the most queries in one
  * group, counts[2] = the bytes of LDS of the largest group's rows. All 0 when no panel kernel ran.
  */
@@ -588,7 +590,8 @@ void miopalLastOccurrenceAlignRouting(int64_t counts[4]);
  * sub-chunk. A query of more than 64 rows runs through miopalSearchOccurrencesAligned's own path inside the call and
  * its stretch is spliced into the CSR at its place; an empty query has no occurrences. What
  * miopalLastOccurrenceRouting and miopalLastOccurrenceAlignRouting report is left as it was.
- * Not part of this call: panels of PSSMs, opalSearchDatabase and the multi-GPU driver. Thread safety as miopalSearch.
+ * Not part of this call: opalSearchDatabase and the multi-GPU driver (a panel of PSSMs:
+ * miopalSearchPssmBatchOccurrencesAligned below). Thread safety as miopalSearch.
  */
 int miopalSearchBatchOccurrencesAligned(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets,
                                         int nQueries, int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength,
@@ -598,13 +601,88 @@ int miopalSearchBatchOccurrencesAligned(MiopalDb* db, const unsigned char* queri
                                         unsigned char** alignments, int64_t** alignmentOffsets);
 
 /*
- * What the alignment stages of the calling thread's last miopalSearchBatchOccurrencesAligned did: counts[0] =
+ * What the alignment stages of the last panel occurrence search of the calling thread, plain or PSSM, did
+ * (miopalSearchBatchOccurrencesAligned, miopalSearchPssmBatchOccurrencesAligned): counts[0] =
  * occurrences whose direction pass ran one lane each, counts[1] = one wavefront each (both 0 for starts only),
  * counts[2] = sub-chunks of the stage, counts[3] = the longest target window (endTarget - startTarget + 1) of the
  * call; the first three summed, the last the maximum, over panel chunks and long queries. All 0 without occurrences.
  * miopalLastBatchOccurrenceRouting and miopalLastBatchOccurrenceGroups keep reporting the sweeps.
  */
 void miopalLastBatchOccurrenceAlignRouting(int64_t counts[4]);
+
+/*
+ * miopalSearchBatchOccurrences with a panel of position-specific scoring matrices in the place of (queries,
+ * scoreMatrix) - a library of transcription-factor weight matrices over promoters, degenerate primers written as
+ * weights, barcodes with per-position quality weights - each with its reverse complement where both strands count.
+ * The list is passed as miopalAlignPairsPssm passes it: rowScores holds alphabetLength ints per row, row r at
+ * rowScores[r * alphabetLength]; rowOffsets[nPssms + 1] delimits the PSSMs in rows; minScore[nPssms] and
+ * window[nPssms] hold one cut and one window per PSSM.
+ *
+ * Output: miopalSearchBatchOccurrences' CSR. Entries hitOffsets[i] .. hitOffsets[i + 1] of every output are byte for
+ * byte what miopalSearchPssmOccurrences returns for PSSM i alone with minScore[i] and window[i]. The CSR layout,
+ * maxHits bounding the TOTAL and the behaviour under MIOPAL_ERR_TOO_MANY_HITS (hitOffsets filled, nothing allocated),
+ * the result with no occurrences, with nPssms = 0, with an empty PSSM and with an empty slice, every output left as it
+ * was on any other error, two calls returning the same bytes, OPAL_MODE_HW and OPAL_MODE_SW only: all as
+ * miopalSearchBatchOccurrences states them.
+ * Checks and their order, all before any device work. First what needs no handle: the mode; the list (nPssms < 0, NULL
+ * rowOffsets, an offset that is negative or decreases, more than 2^31 - 65 rows in all - miopalAlignPairsPssm's bound);
+ * NULL rowScores with rows present; alphabetLength outside 1 .. 32; every window[i] >= 0; under OPAL_MODE_SW every
+ * minScore[i] >= 1; NULL minScore / window with nPssms > 0; null outputs; then the height of every PSSM of more than
+ * 64 rows against the single sweep's LDS table (miopalSearchPssmOccurrences' limit: 493 rows at 32 letters, 651 at
+ * 24) - one PSSM that is too tall refuses the whole call with that call's message, naming the PSSM. Then the null
+ * handle, alphabetLength against the handle's, the slice, and miopalSearch's 32-bit range check of every PSSM with the
+ * extreme entries of its own rows: one failing PSSM refuses the call with OPAL_ERR_OVERFLOW.
+ * On the device: PSSMs of 1 .. 64 rows take the panel kernels, chunked and grouped exactly as
+ * miopalSearchBatchOccurrences chunks and groups queries of those heights (the same bounds and switches). The sweep is
+ * that call's cell for cell; what differs is where a group's LDS table comes from: a chunk's rows go up once, end to
+ * end (4 x alphabetLength bytes a row), with one int per table row that names the row it holds, and a workgroup fills
+ * its table with rows[r][t] + gapOpen, the pad score in the pad column and in the pad rows behind each PSSM. No
+ * matrix and no residue list are involved. An empty PSSM has no occurrences. A PSSM of more than 64 rows runs through
+ * miopalSearchPssmOccurrences' own path inside the call and its stretch is spliced into the CSR at its place; what
+ * miopalLastOccurrenceRouting reports is left as it was. miopalLastBatchOccurrenceRouting and
+ * miopalLastBatchOccurrenceGroups report this call as they report the plain one.
+ * Not part of this call: PSSM forms of miopalSearchBatch and miopalSearchBatchTop, PSSMs taller than the single
+ * sweep's table, opalSearchDatabase and the multi-GPU driver, statistics for motif scores. Thread safety as miopalSearch.
+ */
+int miopalSearchPssmBatchOccurrences(MiopalDb* db, const int* rowScores, const int64_t* rowOffsets, int nPssms,
+                                     int gapOpen, int gapExt, int alphabetLength, int mode, int64_t start, int64_t end,
+                                     const int* minScore, const int* window, int64_t maxHits,
+                                     int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget,
+                                     int** endQuery);
+
+/*
+ * miopalSearchPssmBatchOccurrences with the other end of every occurrence - miopalSearchPssmOccurrencesAligned for a
+ * whole panel of PSSMs in one call. consensus holds one residue (or 255) per row, in rowOffsets' row coordinates; it
+ * tells OPAL_ALIGN_MATCH from OPAL_ALIGN_MISMATCH, is required when operations are asked for and rows are present,
+ * and may be NULL for starts only - miopalSearchPssmOccurrencesAligned's rule.
+ *
+ * Output: miopalSearchBatchOccurrencesAligned's. Entries hitOffsets[i] .. hitOffsets[i + 1] of every output, and the
+ * operations of those occurrences, are byte for byte what miopalSearchPssmOccurrencesAligned returns for PSSM i alone
+ * with minScore[i] and window[i], the alignment offsets rebased as miopalSearchBatchOccurrencesAligned rebases them.
+ * Starts only, the outputs without occurrences and on error, and maxHits - once the running total passes it no further
+ * stage runs, what was aligned is discarded, hitOffsets is filled - are that call's.
+ * Checks and their order: miopalSearchPssmBatchOccurrences' up to its null outputs, then null startTarget /
+ * startQuery, the pair alignments / alignmentOffsets, the consensus (missing; a residue out of range), then the
+ * heights, the handle and the range checks as there.
+ * On the device: miopalSearchPssmBatchOccurrences' sweeps, and behind the write sweep of every panel chunk that has
+ * occurrences the alignment stage with the row-indexed later passes of miopalAlignPairsPssm. Their lane-per-pair
+ * kernels keep the whole row table in LDS (64 KB less 256 bytes: 493 rows at 32 letters), and a chunk of motifs has
+ * more rows than that. A chunk's occurrences lie PSSM after PSSM, so a run of consecutive PSSMs owns a contiguous
+ * stretch of them: the chunk's PSSMs are split into runs whose rows fit the table, and the stage runs once per run
+ * that has occurrences, with that run's rows - a window of the rows the sweeps read, not uploaded again - as the
+ * table, its consensus and its PSSMs' row origins going up. No occurrence goes to the wavefront-per-pair kernels
+ * because the chunk as a whole is large. Sub-chunks inside a run are sized as the plain stage sizes them. A PSSM of
+ * more than 64 rows runs through miopalSearchPssmOccurrencesAligned's own path inside the call.
+ * miopalLastBatchOccurrenceAlignRouting reports the stages (counts[2]: sub-chunks over all runs).
+ * Not part of this call: what miopalSearchPssmBatchOccurrences leaves out. Thread safety as miopalSearch.
+ */
+int miopalSearchPssmBatchOccurrencesAligned(MiopalDb* db, const int* rowScores, const unsigned char* consensus,
+                                            const int64_t* rowOffsets, int nPssms, int gapOpen, int gapExt,
+                                            int alphabetLength, int mode, int64_t start, int64_t end,
+                                            const int* minScore, const int* window, int64_t maxHits,
+                                            int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget,
+                                            int** endQuery, int** startTarget, int** startQuery,
+                                            unsigned char** alignments, int64_t** alignmentOffsets);
 
 /*
  * The significant hits of a query: miopalSearchHits with the cut stated as an E-value, the statistics gathered on the

@@ -91,6 +91,7 @@ EXPORTS = [
     "miopalSearchOccurrencesAligned", "miopalSearchPssmOccurrencesAligned", "miopalLastOccurrenceAlignRouting",
     "miopalSearchBatchOccurrences", "miopalLastBatchOccurrenceRouting", "miopalLastBatchOccurrenceGroups",
     "miopalSearchBatchOccurrencesAligned", "miopalLastBatchOccurrenceAlignRouting",
+    "miopalSearchPssmBatchOccurrences", "miopalSearchPssmBatchOccurrencesAligned",
     # test hooks
     "miopalTestProfileColumns",
     "miopalSelfTest", "miopalTestInjectFault", "miopalTestSetLogicalDevices", "miopalTestSelectTop",
@@ -213,6 +214,10 @@ def lib() -> ctypes.CDLL:
         for side, head in (("", one), ("Pssm", pssm_full)):
             table[f"miopalSearch{side}OccurrencesAligned"] = (c_int, head + middle[1:] + [c_int, c_int, c_i64, p_i64] + found + [pp] * 4)
         table["miopalSearchBatchOccurrencesAligned"] = (c_int, table["miopalSearchBatchOccurrences"][1] + [pp] * 4)
+        # ... of a panel of PSSMs: db, rows, [consensus,] row offsets, n, gapOpen, gapExt, A where `batch` stands
+        for name, consensus in (("miopalSearchPssmBatchOccurrences", []), ("miopalSearchPssmBatchOccurrencesAligned", [c_vp])):
+            table[name] = (c_int, [c_vp, c_vp] + consensus + [c_vp, c_int, c_int, c_int, c_int]
+                           + table[name.replace("Pssm", "")][1][len(batch):])
         for name, (restype, argtypes) in table.items():
             getattr(L, name).restype = restype
             getattr(L, name).argtypes = argtypes
@@ -676,10 +681,10 @@ def _pssm_rows(row_scores, alphabet_length, shape):
 
 class _QuerySide(typing.NamedTuple):
     """What a call searches with, as the C ABI takes it: a query with a matrix, a PSSM, or a list of queries with a
-    matrix (`DeviceDatabase._query_side`, `_pssm_side`, `_batch_side`)."""
-    name: str                       # "", "Pssm", "Batch": the C functions that take it are miopalSearch<name>...
+    matrix, or a list of PSSMs (`DeviceDatabase._query_side`, `_pssm_side`, `_batch_side`, `_pssm_batch_side`)."""
+    name: str                       # "", "Pssm", "Batch", "PssmBatch": the C functions that take it are miopalSearch<name>...
     queries: tuple                  # their arguments after the handle: (query, length) / (rows, [consensus,] length) /
-                                    # (queries, offsets, n) ...
+                                    # (queries, offsets, n) / (rows, [consensus,] row offsets, n) ...
     scoring: tuple                  # ... and (gapOpen, gapExt, [matrix,] alphabet length)
     rows: typing.Optional[int]      # None: one query, one row of outputs; else the queries: a row each, or a CSR
     length: typing.Optional[int]    # of the one query
@@ -984,6 +989,20 @@ class DeviceDatabase:
         `search_pssm` gives for ``target[i]``."""
         return self._search_top(self._pssm_side(row_scores, None, gap_open, gap_extend), mode, algorithm, start, end, k, min_score)
 
+    def _pssm_batch_side(self, pssm_rows, consensus, gap_open, gap_extend, with_consensus=False) -> _QuerySide:
+        """a list of PSSMs as miopalAlignPairsPssm takes it: the rows end to end, [the consensus,] the row offsets"""
+        rows = [_pssm_rows(r, self.alphabet_length, "every PSSM must have shape (rows") for r in pssm_rows]
+        flat, offsets = _packed(rows, None)
+        cons = None
+        if consensus is not None:
+            cs = [np.ascontiguousarray(c, dtype=np.uint8).ravel() for c in consensus]
+            if [len(c) for c in cs] != [len(r) for r in rows]:
+                raise ValueError("consensus must have one entry per row of every PSSM")
+            cons = np.concatenate(cs) if offsets[-1] else None
+        pointers = (_ptr(flat),) + ((_ptr(cons),) if with_consensus else ()) + (_ptr(offsets), len(rows))
+        return _QuerySide("PssmBatch", pointers, (gap_open, gap_extend, self.alphabet_length), len(rows), None,
+                          (flat, offsets, cons))
+
     def search_batch_top(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray, gap_open: int = 3,
                          gap_extend: int = 1, mode: str = "score", algorithm: str = "sw", start: int = 0,
                          end: typing.Optional[int] = None, k: int = 10,
@@ -1113,16 +1132,28 @@ class DeviceDatabase:
         offsets[i]:offsets[i + 1] equal search_occurrences(queries[i], ...) byte for byte. ``max_hits`` bounds the
         total; TooManyHits carries the offsets in ``counts``. The rule's faults raise ValueError before any device
         call, as `search_occurrences`' do."""
-        rc, offsets, ptrs = self._call_batch_occurrences("miopalSearchBatchOccurrences", queries, matrix, gap_open,
-                                                         gap_extend, algorithm, start, end, min_score, window, max_hits)
+        rc, offsets, ptrs = self._call_batch_occurrences(self._batch_side(queries, matrix, gap_open, gap_extend),
+                                                         algorithm, start, end, min_score, window, max_hits)
         return self._found(rc, offsets, ptrs, "end")
 
-    def _call_batch_occurrences(self, entry, queries, matrix, gap_open, gap_extend, algorithm, start, end, min_score,
-                                window, max_hits, more=()):
-        """The preamble of the panel occurrence searches - the query side, the per-query cuts and windows, the rule's
-        faults - and the call of the entry point named ``entry``, with ``more`` arguments behind the four result
-        pointers. Returns (the code, the offsets, the result pointers)."""
-        side = self._batch_side(queries, matrix, gap_open, gap_extend)
+    def search_batch_occurrences_pssm(self, row_scores: typing.Sequence[np.ndarray], gap_open: int = 3,
+                                      gap_extend: int = 1, algorithm: str = "hw", start: int = 0,
+                                      end: typing.Optional[int] = None, min_score=1, window=None,
+                                      max_hits: typing.Optional[int] = None) -> typing.Dict[str, np.ndarray]:
+        """miopalSearchPssmBatchOccurrences: `search_batch_occurrences` with a panel of position-specific scoring
+        matrices (``row_scores[m]``: integers of shape (rows of PSSM m, alphabet length)) in the place of (queries,
+        matrix). Returns `search_batch_occurrences`' dict; entries offsets[i]:offsets[i + 1] equal
+        search_occurrences_pssm(row_scores[i], ...) byte for byte. A window of None is that PSSM's height."""
+        rc, offsets, ptrs = self._call_batch_occurrences(self._pssm_batch_side(row_scores, None, gap_open, gap_extend),
+                                                         algorithm, start, end, min_score, window, max_hits)
+        return self._found(rc, offsets, ptrs, "end")
+
+    def _call_batch_occurrences(self, side: _QuerySide, algorithm, start, end, min_score, window, max_hits, aligned=None):
+        """The preamble of the panel occurrence searches, plain and PSSM - the per-query cuts and windows, the rule's
+        faults - and the call of miopalSearch<side>Occurrences or, with ``aligned`` (the four arguments behind the
+        result pointers), ...OccurrencesAligned. Returns (the code, the offsets, the result pointers)."""
+        entry = f"miopalSearch{side.name}Occurrences" + ("" if aligned is None else "Aligned")
+        more = aligned or ()
         lengths = np.diff(side.keep[1]).tolist()
         cuts, windows = _per_query(min_score, lengths, "min_score"), _per_query(window, lengths, "window")
         if algorithm not in ("hw", "sw"):
@@ -1152,12 +1183,28 @@ class DeviceDatabase:
         offsets[i]:offsets[i + 1] equal search_occurrence_alignments(queries[i], ...). ``operations=False``: starts
         only, and no "aln*" keys. ``max_hits`` bounds the total; TooManyHits carries the offsets in ``counts``, and
         what had been aligned by then is discarded."""
+        return self._batch_occurrence_alignments(self._batch_side(queries, matrix, gap_open, gap_extend), algorithm, start,
+                                                 end, min_score, window, max_hits, operations)
+
+    def search_batch_occurrence_alignments_pssm(self, row_scores: typing.Sequence[np.ndarray],
+                                                consensus: typing.Optional[typing.Sequence[np.ndarray]] = None,
+                                                gap_open: int = 3, gap_extend: int = 1, algorithm: str = "hw",
+                                                start: int = 0, end: typing.Optional[int] = None, min_score=1,
+                                                window=None, max_hits: typing.Optional[int] = None,
+                                                operations: bool = True) -> typing.Dict[str, typing.Any]:
+        """miopalSearchPssmBatchOccurrencesAligned: `search_batch_occurrence_alignments` with a panel of PSSMs
+        (``row_scores`` as in `search_batch_occurrences_pssm`; ``consensus[m]``: one residue or 255 per row of PSSM m,
+        required with ``operations``) in the place of (queries, matrix). Entries offsets[i]:offsets[i + 1] equal
+        search_occurrence_alignments_pssm(row_scores[i], consensus[i], ...)."""
+        side = self._pssm_batch_side(row_scores, consensus, gap_open, gap_extend, with_consensus=True)
+        return self._batch_occurrence_alignments(side, algorithm, start, end, min_score, window, max_hits, operations)
+
+    def _batch_occurrence_alignments(self, side: _QuerySide, algorithm, start, end, min_score, window, max_hits,
+                                     operations) -> typing.Dict[str, typing.Any]:
         start_t, start_q, ops, ops_off = (ctypes.c_void_p() for _ in range(4))
         more = (ctypes.byref(start_t), ctypes.byref(start_q), ctypes.byref(ops) if operations else None,
                 ctypes.byref(ops_off) if operations else None)
-        rc, offsets, ptrs = self._call_batch_occurrences("miopalSearchBatchOccurrencesAligned", queries, matrix,
-                                                         gap_open, gap_extend, algorithm, start, end, min_score, window,
-                                                         max_hits, more)
+        rc, offsets, ptrs = self._call_batch_occurrences(side, algorithm, start, end, min_score, window, max_hits, more)
         out = self._found(rc, offsets, ptrs, "end")
         n = int(offsets[-1])
         out.update(start_t=_take_malloced(start_t, n, np.int32), start_q=_take_malloced(start_q, n, np.int32))
@@ -1254,17 +1301,10 @@ class DeviceDatabase:
         one residue (or 255) per row of PSSM m - required for mode "full", may be None otherwise. Pair p aligns PSSM
         ``pair_pssm[p]`` with target ``pair_target[p]``; returns `align_pairs`' dict, entry p equal to
         ``search_pssm(pssm_rows[i], consensus[i], ..., start=j, end=j + 1)``."""
-        rows = [_pssm_rows(r, self.alphabet_length, "every PSSM must have shape (rows") for r in pssm_rows]
-        flat, offsets = _packed(rows, None)
-        cons = None
-        if consensus is not None:
-            cs = [np.ascontiguousarray(c, dtype=np.uint8).ravel() for c in consensus]
-            if [len(c) for c in cs] != [len(r) for r in rows]:
-                raise ValueError("consensus must have one entry per row of every PSSM")
-            cons = np.concatenate(cs) if offsets[-1] else None
+        side = self._pssm_batch_side(pssm_rows, consensus, gap_open, gap_extend, with_consensus=True)
 
         def call(st, pq, pt, n, score, et, eq, s_t, s_q, ops_ptr, aoff):
-            return lib().miopalAlignPairsPssm(self._h, _ptr(flat), _ptr(cons), _ptr(offsets), len(rows), pq, pt, n,
+            return lib().miopalAlignPairsPssm(self._h, *side.queries, pq, pt, n,
                                               gap_open, gap_extend, self.alphabet_length, st, MODE[algorithm], score,
                                               et, eq, s_t, s_q, ctypes.byref(ops_ptr), aoff)
         return self._pair_list(call, pair_pssm, pair_target, mode)

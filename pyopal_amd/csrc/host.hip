@@ -755,6 +755,7 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_occurrences.inc"
 #include "host_occurrence_align.inc"
 #include "host_batch_occurrence_align.inc"
+#include "host_batch_occurrence_align_pssm.inc"
 #include "host_batch_occurrences.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
@@ -1122,6 +1123,32 @@ int miopalSearchBatchOccurrencesAligned(MiopalDb* db, const unsigned char* queri
     return searchBatchOccurrencesImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength, mode,
                                       start, end, minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery,
                                       true, startTarget, startQuery, alignments, alignmentOffsets);
+    });
+}
+
+// miopalSearchPssmBatchOccurrences, miopalSearchPssmBatchOccurrencesAligned: the panel calls with a list of PSSMs, passed
+// as miopalAlignPairsPssm takes it (host_batch_occurrences.inc: searchPssmBatchOccurrencesImpl, its checks and their order)
+int miopalSearchPssmBatchOccurrences(MiopalDb* db, const int* rowScores, const int64_t* rowOffsets, int nPssms, int gapOpen,
+                                     int gapExt, int alphabetLength, int mode, int64_t start, int64_t end,
+                                     const int* minScore, const int* window, int64_t maxHits, int64_t* hitOffsets,
+                                     int64_t** targetIndex, int** score, int** endTarget, int** endQuery) {
+    return guarded([&]() -> int {
+    return searchPssmBatchOccurrencesImpl(db, rowScores, nullptr, rowOffsets, nPssms, gapOpen, gapExt, alphabetLength, mode, start,
+                                          end, minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery,
+                                          false, nullptr, nullptr, nullptr, nullptr);
+    });
+}
+
+int miopalSearchPssmBatchOccurrencesAligned(MiopalDb* db, const int* rowScores, const unsigned char* consensus,
+                                            const int64_t* rowOffsets, int nPssms, int gapOpen, int gapExt,
+                                            int alphabetLength, int mode, int64_t start, int64_t end, const int* minScore,
+                                            const int* window, int64_t maxHits, int64_t* hitOffsets, int64_t** targetIndex,
+                                            int** score, int** endTarget, int** endQuery, int** startTarget,
+                                            int** startQuery, unsigned char** alignments, int64_t** alignmentOffsets) {
+    return guarded([&]() -> int {
+    return searchPssmBatchOccurrencesImpl(db, rowScores, consensus, rowOffsets, nPssms, gapOpen, gapExt, alphabetLength, mode,
+                                          start, end, minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget,
+                                          endQuery, true, startTarget, startQuery, alignments, alignmentOffsets);
     });
 }
 

@@ -19,7 +19,9 @@ thread_local int64_t g_lastBatchOccurrenceAlignRouting[4] = {0, 0, 0, 0};   // m
 
 // A panel chunk's occurrences where the write sweep left them: entry k is (target[k], score[k], row[k], column[k]),
 // `total` entries each in `ws`; head[0 .. cq] on the device (see above); `hits` holds the four arrays on the host.
-// The chunk's queries are panel[0 .. cq) of the call's list.
+// The chunk's queries are panel[0 .. cq) of the call's list. A PSSM panel (rowScores: the call's rows, else null;
+// host_batch_occurrence_align_pssm.inc): `queries` is the consensus in the offsets' row coordinates, dRows the chunk's
+// rows end to end where the sweeps read them, hostHead the host's copy of head[0 .. cq].
 struct BatchOccurrencesOnDevice {
     MiopalDb* db;
     Workspace* ws;
@@ -35,6 +37,9 @@ struct BatchOccurrencesOnDevice {
     const int32_t *score, *row, *column;
     const int64_t* head;
     const HitArrays* hits;
+    const int* rowScores = nullptr;
+    const int32_t* dRows = nullptr;
+    const int64_t* hostHead = nullptr;
 };
 
 }  // namespace

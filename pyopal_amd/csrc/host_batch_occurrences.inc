@@ -13,6 +13,12 @@
 // miopalSearchBatchOccurrencesAligned is the same call with an alignment stage behind every write sweep
 // (host_batch_occurrence_align.inc for the panel chunks, host_occurrence_align.inc's for a long query): every piece
 // then carries its occurrences' starts and operations, and the splice puts those together as well.
+//
+// miopalSearchPssmBatchOccurrences and its aligned form are the same calls with a list of position-specific scoring
+// matrices where the queries and the matrix stand (PanelSide): their own checks, in the single PSSM calls' order, then
+// the same routing, chunks, groups and splice. A chunk's PSSM rows go up once, end to end ([rows][A] ints, kPssmRows),
+// with one int per TABLE row that names its source row (-1: a pad row) where the plain form uploads the residue list;
+// the sweeps are occurrences_batch_pssm.hip's, the stage host_batch_occurrence_align_pssm.inc's. No matrix goes up.
 static int checkOccurrenceAlignOutputs(int** startTarget, int** startQuery, unsigned char** alignments,
                                        int64_t** alignmentOffsets);   // (host.hip, with the entry points)
 
@@ -43,6 +49,17 @@ int64_t batchOccurrenceWorkgroupsPerCu() {
     return kBatchOccurrenceWorkgroupsPerCu;
 }
 
+// The score source of a panel. Plain: `residues` / `offsets` are the queries, `matrix` [A][A], rowScores null. PSSM:
+// rowScores holds A ints per row, `offsets` delimits the PSSMs in rows, `residues` is the consensus (never null here:
+// a filler of 255s where the caller gave none) in the same row coordinates; matrix is null.
+struct PanelSide {
+    const unsigned char* residues;
+    const int64_t* offsets;
+    const int* matrix;
+    const int* rowScores;
+    bool pssm() const { return rowScores != nullptr; }
+};
+
 // where a query's occurrences lie until the CSR is put together; aligned (the aligned call): the starts of the piece
 // `from`, entry for entry, and its operations - those of the stretch are opsOff[first] .. opsOff[first + count]
 struct OccurrenceStretch {
@@ -62,8 +79,8 @@ struct BatchOccurrenceAlign {
 // The panel queries `panel` (indices into the call's list, ascending, 1 .. 64 rows each), chunk by chunk. counts[i]
 // and stretch[i] are filled for every one of them; once *running passes maxHits (*over) the chunks are only counted.
 // `align` (null: the plain call): the alignment stage runs behind every write sweep, and never once *over is set.
-static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets,
-                                const std::vector<int>& panel, int open, int ext, const int* matrix, int A, int mode,
+static int batchOccurrencePanel(MiopalDb* db, const PanelSide& side,
+                                const std::vector<int>& panel, int open, int ext, int A, int mode,
                                 int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
                                 int64_t* running, bool* over, std::vector<int64_t>* counts,
                                 std::vector<OccurrenceStretch>* stretch, std::vector<std::unique_ptr<HitArrays>>* pieces,
@@ -76,9 +93,14 @@ static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, cons
     RC_TRY(lease.acquireInternal());
     Workspace* ws = lease.ws;
     hipStream_t stream = ws->stream;
-    void* pmatrix;
-    RC_TRY(ws->get(kMatrix, (size_t)A * A * sizeof(int32_t), &pmatrix));
-    RC_TRY(ws->stageUpload(pmatrix, matrix, (size_t)A * A * sizeof(int32_t), stream));
+    const unsigned char* const queries = side.residues;
+    const int64_t* const queryOffsets = side.offsets;
+    const bool pssm = side.pssm();
+    void* pmatrix = nullptr;
+    if (!pssm) {
+        RC_TRY(ws->get(kMatrix, (size_t)A * A * sizeof(int32_t), &pmatrix));
+        RC_TRY(ws->stageUpload(pmatrix, side.matrix, (size_t)A * A * sizeof(int32_t), stream));
+    }
 
     const int64_t perChunk = std::max<int64_t>(1, std::min<int64_t>(kBatchOccurrenceChunkQueries, batchOccurrenceEntries() / n));
     // A group is as many consecutive queries as fit the LDS - unless that leaves the count sweep fewer than
@@ -94,16 +116,29 @@ static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, cons
         const int cq = (int)std::min<int64_t>(perChunk, (int64_t)(panel.size() - p0));
         const int64_t N = (int64_t)cq * n;
         // the chunk's row list, its queries and its groups
+        // (PSSM panel: the chunk's rows end to end, unpadded, and per table row the row it holds)
         std::vector<uint8_t> rowResidue;
+        std::vector<int32_t> rowSource;
+        std::vector<int> chunkRows;
         std::vector<int4> meta;   // [cq] queries, then the groups
         meta.reserve((size_t)cq + 16);
         int tallest = 0;
         for (int q = 0; q < cq; ++q) {
             const int i = panel[p0 + (size_t)q];
             const int Q = (int)(queryOffsets[i + 1] - queryOffsets[i]);
-            meta.push_back(make_int4((int)rowResidue.size(), Q, minScore[i], window[i]));
-            rowResidue.insert(rowResidue.end(), queries + queryOffsets[i], queries + queryOffsets[i + 1]);
-            rowResidue.resize(rowResidue.size() + (size_t)(batchOccurrenceRows(Q) - Q), (uint8_t)kBatchOccurrencePadRow);
+            const size_t pad = (size_t)(batchOccurrenceRows(Q) - Q);
+            if (pssm) {
+                meta.push_back(make_int4((int)rowSource.size(), Q, minScore[i], window[i]));
+                const int32_t origin = (int32_t)(chunkRows.size() / (size_t)A);
+                for (int r = 0; r < Q; ++r) rowSource.push_back(origin + r);
+                rowSource.resize(rowSource.size() + pad, -1);
+                chunkRows.insert(chunkRows.end(), side.rowScores + (size_t)queryOffsets[i] * A,
+                                 side.rowScores + (size_t)queryOffsets[i + 1] * A);
+            } else {
+                meta.push_back(make_int4((int)rowResidue.size(), Q, minScore[i], window[i]));
+                rowResidue.insert(rowResidue.end(), queries + queryOffsets[i], queries + queryOffsets[i + 1]);
+                rowResidue.resize(rowResidue.size() + pad, (uint8_t)kBatchOccurrencePadRow);
+            }
             tallest = std::max(tallest, batchOccurrenceRows(Q));
         }
         const int64_t perGroup = std::max<int64_t>(1, (cq + wantGroups - 1) / wantGroups);
@@ -125,23 +160,35 @@ static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, cons
         }
         g_lastBatchOccurrenceGroups[0] += groups;
         g_lastBatchOccurrenceGroups[2] = std::max<int64_t>(g_lastBatchOccurrenceGroups[2], (int64_t)batchOccurrenceLdsBytes(widest, A));
-        void *prows, *pmeta, *pbounds, *pscratch;
-        RC_TRY(ws->get(kQuery, rowResidue.size(), &prows));
+        void *prows, *pmeta, *pbounds, *pscratch, *pscores = nullptr;
+        if (pssm) {
+            RC_TRY(ws->get(kBatchOccurrenceRowSource, rowSource.size() * sizeof(int32_t), &prows));
+            RC_TRY(ws->get(kPssmRows, chunkRows.size() * sizeof(int32_t), &pscores));
+        } else {
+            RC_TRY(ws->get(kQuery, rowResidue.size(), &prows));
+        }
         RC_TRY(ws->get(kBatchOccurrenceMeta, meta.size() * sizeof(int4), &pmeta));
         RC_TRY(ws->get(kBatchOccurrenceBounds, ((size_t)cq + 3) * sizeof(int64_t) + ((size_t)cq + 1) * sizeof(int32_t), &pbounds));
         RC_TRY(ws->get(kOccurrenceScratch, occurrenceScratchBytes(N), &pscratch));
-        RC_TRY(ws->stageUpload(prows, rowResidue.data(), rowResidue.size(), stream));
+        if (pssm) {
+            RC_TRY(ws->stageUpload(prows, rowSource.data(), rowSource.size() * sizeof(int32_t), stream));
+            RC_TRY(ws->stageUpload(pscores, chunkRows.data(), chunkRows.size() * sizeof(int32_t), stream));
+        } else {
+            RC_TRY(ws->stageUpload(prows, rowResidue.data(), rowResidue.size(), stream));
+        }
         RC_TRY(ws->stageUpload(pmeta, meta.data(), meta.size() * sizeof(int4), stream));
         const OccurrenceScratch sc = occurrenceScratchLayout(pscratch, N);
         int64_t* dHead = (int64_t*)pbounds;
         int32_t* dFirst = (int32_t*)(dHead + cq + 3);
         BatchOccurrenceArgs a{};
         a.residues = db->d_residues;
-        a.rowResidue = (const uint8_t*)prows;
+        if (pssm) a.rowSource = (const int32_t*)prows;
+        else a.rowResidue = (const uint8_t*)prows;
         a.query = (const int4*)pmeta;
         a.group = a.query + cq;
         a.nQueries = cq;
-        a.matrix = (const int32_t*)pmatrix;
+        if (pssm) a.rows = (const int32_t*)pscores;
+        else a.matrix = (const int32_t*)pmatrix;
         a.alphabet = A;
         a.gapOpen = open;
         a.gapExt = ext;
@@ -162,7 +209,8 @@ static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, cons
             }
             a.jobs = (const PairJob*)psorted;
             a.nJobs = nc;
-            const hipError_t e = launchBatchOccurrencesCount(a, region, groups, batchOccurrenceLdsBytes(widest, A), stream);
+            const hipError_t e = (pssm ? launchBatchOccurrencesCountPssm : launchBatchOccurrencesCount)(
+                a, region, groups, batchOccurrenceLdsBytes(widest, A), stream);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 return fail(MIOPAL_ERR_HIP, "panel occurrence sweep launch (count): %s", hipGetErrorString(e));
@@ -206,7 +254,8 @@ static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, cons
         a.outRow = (int32_t*)(base + slot.offEndQ);
         a.outColumn = (int32_t*)(base + slot.offEndT);
         {
-            const hipError_t e = launchBatchOccurrencesWrite(a, region, listed, batchOccurrenceLdsBytes(tallest, A), stream);
+            const hipError_t e = (pssm ? launchBatchOccurrencesWritePssm : launchBatchOccurrencesWrite)(
+                a, region, listed, batchOccurrenceLdsBytes(tallest, A), stream);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 return fail(MIOPAL_ERR_HIP, "panel occurrence sweep launch (write): %s", hipGetErrorString(e));
@@ -223,10 +272,12 @@ static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, cons
             // the stage, on the occurrences where they are (head[0 .. cq] still lies behind dHead). It takes kJobs,
             // kSortedJobs and kSortBins: the next chunk's count sweep builds the slice's sorted jobs again.
             align->pieces.emplace_back(new OccurrenceAlignment());
-            RC_TRY(alignBatchOccurrencesStage(
-                BatchOccurrencesOnDevice{db, ws, queries, queryOffsets, panel.data() + p0, cq, open, ext, matrix, A, mode, total,
-                                         a.outTarget, a.outScore, a.outRow, a.outColumn, dHead, &hits},
-                align->operations, align->pieces.back().get()));
+            // (PSSM panel: the chunk's rows stay where they are, kPssmRows, and the stage reads them there)
+            const BatchOccurrencesOnDevice on{db, ws, queries, queryOffsets, panel.data() + p0, cq, open, ext, side.matrix, A,
+                                              mode, total, a.outTarget, a.outScore, a.outRow, a.outColumn, dHead, &hits,
+                                              side.rowScores, (const int32_t*)pscores, head.data()};
+            RC_TRY((pssm ? alignPssmBatchOccurrencesStage : alignBatchOccurrencesStage)(on, align->operations,
+                                                                                        align->pieces.back().get()));
             aligned = align->pieces.back().get();
             jobsOf = -1;
             psorted = nullptr;
@@ -238,6 +289,20 @@ static int batchOccurrencePanel(MiopalDb* db, const unsigned char* queries, cons
     return 0;
 }
 
+static int batchOccurrencesCore(MiopalDb* db, const PanelSide& side, int nQueries, int open, int ext, int A, int mode,
+                                int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
+                                int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery,
+                                bool wantAligned, int** startTarget, int** startQuery, unsigned char** alignments,
+                                int64_t** alignmentOffsets);
+
+// what the reporters of the panel occurrence searches say starts over with every call, plain or PSSM
+static void resetBatchOccurrenceReports(bool wantAligned) {
+    for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceRouting[k] = 0;
+    for (int k = 0; k < 3; ++k) g_lastBatchOccurrenceGroups[k] = 0;
+    if (wantAligned)
+        for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceAlignRouting[k] = 0;
+}
+
 // Behind nothing: the checks of miopalSearchOccurrences over the whole list, in its order, come first.
 // wantAligned: miopalSearchBatchOccurrencesAligned - the four outputs behind endQuery are checked and written too.
 static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
@@ -246,10 +311,7 @@ static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries
                                       int64_t** targetIndex, int** score, int** endTarget, int** endQuery,
                                       bool wantAligned = false, int** startTarget = nullptr, int** startQuery = nullptr,
                                       unsigned char** alignments = nullptr, int64_t** alignmentOffsets = nullptr) {
-    for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceRouting[k] = 0;
-    for (int k = 0; k < 3; ++k) g_lastBatchOccurrenceGroups[k] = 0;
-    if (wantAligned)
-        for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceAlignRouting[k] = 0;
+    resetBatchOccurrenceReports(wantAligned);
     RC_TRY(validateBatch(db, queries, queryOffsets, nQueries, matrix, A, OPAL_SEARCH_SCORE_END, mode, start, end));
     if (mode != OPAL_MODE_HW && mode != OPAL_MODE_SW)
         return fail(OPAL_ERR_INVALID_MODE, "occurrences are defined for OPAL_MODE_HW and OPAL_MODE_SW, not for mode %d", mode);
@@ -263,6 +325,81 @@ static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries
     if (nQueries > 0 && (!minScore || !window)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null minScore / window list");
     RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, hitOffsets, targetIndex, score, endTarget, endQuery));
     if (wantAligned) RC_TRY(checkOccurrenceAlignOutputs(startTarget, startQuery, alignments, alignmentOffsets));
+    return batchOccurrencesCore(db, PanelSide{queries, queryOffsets, matrix, nullptr}, nQueries, open, ext, A, mode, start, end,
+                                minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery, wantAligned,
+                                startTarget, startQuery, alignments, alignmentOffsets);
+}
+
+// miopalSearchPssmBatchOccurrences(Aligned): what needs no handle first, in the single PSSM calls' order with the plain
+// panel's per-query checks among it, then the handle and what depends on it; the range check of every PSSM, with the
+// extreme entries of its own rows, is the core's.
+static int searchPssmBatchOccurrencesImpl(MiopalDb* db, const int* rowScores, const unsigned char* consensus,
+                                          const int64_t* rowOffsets, int nPssms, int open, int ext, int A, int mode,
+                                          int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
+                                          int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget,
+                                          int** endQuery, bool wantAligned, int** startTarget, int** startQuery,
+                                          unsigned char** alignments, int64_t** alignmentOffsets) {
+    resetBatchOccurrenceReports(wantAligned);
+    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
+    if (mode != OPAL_MODE_HW && mode != OPAL_MODE_SW)
+        return fail(OPAL_ERR_INVALID_MODE, "occurrences are defined for OPAL_MODE_HW and OPAL_MODE_SW, not for mode %d", mode);
+    if (nPssms < 0 || (nPssms > 0 && !rowOffsets)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad PSSM list");
+    for (int m = 0; m < nPssms; ++m)
+        if (rowOffsets[m] < 0 || rowOffsets[m + 1] < rowOffsets[m]) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad row offsets at %d", m);
+    const int64_t first = nPssms > 0 ? rowOffsets[0] : 0, totalRows = nPssms > 0 ? rowOffsets[nPssms] - first : 0;
+    if (totalRows > INT32_MAX - 64) return fail(MIOPAL_ERR_BAD_ARGUMENT, "the PSSMs of a panel hold 2^31 - 65 rows at most");
+    if (totalRows > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
+    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    if (window)
+        for (int i = 0; i < nPssms; ++i)
+            if (window[i] < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "negative window %d at PSSM %d", window[i], i);
+    if (minScore && mode == OPAL_MODE_SW)
+        for (int i = 0; i < nPssms; ++i)
+            if (minScore[i] < 1)
+                return fail(MIOPAL_ERR_BAD_ARGUMENT, "minScore = %d at PSSM %d: OPAL_MODE_SW needs a cut of at least 1", minScore[i], i);
+    if (nPssms > 0 && (!minScore || !window)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null minScore / window list");
+    RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, hitOffsets, targetIndex, score, endTarget, endQuery));
+    if (wantAligned) {
+        RC_TRY(checkOccurrenceAlignOutputs(startTarget, startQuery, alignments, alignmentOffsets));
+        if (alignments && totalRows > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
+        if (consensus)
+            for (int64_t i = first; i < first + totalRows; ++i)
+                if (consensus[i] >= A && consensus[i] != 255)
+                    return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %lld", consensus[i], (long long)i);
+    }
+    // (a PSSM of more than 64 rows takes the single sweep, which keeps its rows in LDS)
+    for (int i = 0; i < nPssms; ++i) {
+        const int64_t Q = rowOffsets[i + 1] - rowOffsets[i];
+        if (Q > kLanes && (Q > INT32_MAX || perPairPssmBytes((int)Q, A) == 0))
+            return fail(MIOPAL_ERR_BAD_ARGUMENT, "PSSM %d of the panel: a PSSM of %lld rows at %d letters does not fit the occurrence "
+                        "sweep's LDS table: (rows + 1) x (letters + 1) x 4 bytes within 64 KB less 256, %d rows at most", i,
+                        (long long)Q, A, (64 * 1024 - 256) / (4 * (A + 1)) - 1);
+    }
+    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
+    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
+    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
+    // (without a consensus - the plain form, starts only - every position is "no residue": the kernels never read it)
+    std::vector<unsigned char> none;
+    if (!wantAligned || !consensus) {
+        none.assign((size_t)(first + std::max<int64_t>(totalRows, 1)), 255);   // (indexed in the offsets' coordinates)
+        consensus = none.data();
+    }
+    static const int64_t kNoPssms[1] = {0};
+    static const int kNoPanelRows[1] = {0};   // (no rows: the score source still says "position-specific")
+    return batchOccurrencesCore(db, PanelSide{consensus, nPssms > 0 ? rowOffsets : kNoPssms, nullptr, totalRows > 0 ? rowScores : kNoPanelRows},
+                                nPssms, open, ext, A, mode, start, end, minScore, window, maxHits, hitOffsets, targetIndex, score,
+                                endTarget, endQuery, wantAligned, startTarget, startQuery, alignments, alignmentOffsets);
+}
+
+// Behind the checks of either form: the range check of every query, the routing, the pieces and the splice.
+static int batchOccurrencesCore(MiopalDb* db, const PanelSide& side, int nQueries, int open, int ext, int A, int mode,
+                                int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
+                                int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery,
+                                bool wantAligned, int** startTarget, int** startQuery, unsigned char** alignments,
+                                int64_t** alignmentOffsets) {
+    const unsigned char* const queries = side.residues;
+    const int64_t* const queryOffsets = side.offsets;
+    const int* const matrix = side.matrix;
     const bool operations = wantAligned && alignments != nullptr;
     BatchOccurrenceAlign alignState{operations, {}};
     BatchOccurrenceAlign* const align = wantAligned ? &alignState : nullptr;
@@ -273,13 +410,15 @@ static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries
     int64_t running = 0;
     bool over = false;
     if (n > 0 && nQueries > 0) {
-        // miopalSearch's range check (32-bit arithmetic only), for every query before any device work
+        // miopalSearch's range check (32-bit arithmetic only), for every query before any device work (a PSSM: with
+        // the extreme entries of its own rows)
         ScoreModel model{open, ext, 0, 0};
-        scoreExtremes(matrix, (size_t)A * A, &model.maxScore, &model.minScore);
+        if (!side.pssm()) scoreExtremes(matrix, (size_t)A * A, &model.maxScore, &model.minScore);
         std::vector<int> panel, single;
         for (int i = 0; i < nQueries; ++i) {
             const int Q = (int)(queryOffsets[i + 1] - queryOffsets[i]);
-            RC_TRY(checkInt32Range(model, Q, db->maxLen));
+            if (side.pssm()) RC_TRY(checkPssmRange(db, side.rowScores + (size_t)queryOffsets[i] * A, Q, A, open, ext));
+            else RC_TRY(checkInt32Range(model, Q, db->maxLen));
             if (Q > kLanes) single.push_back(i);
             else if (Q > 0) panel.push_back(i);
         }
@@ -315,7 +454,8 @@ static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries
             }
             const OccurrenceStage stage = [&](const OccurrencesOnDevice& o) { return alignOccurrencesStage(o, operations, got); };
             const int rc = searchOccurrencesImpl(db, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open,
-                                                 ext, matrix, nullptr, A, mode, start, end, minScore[i], window[i], room, &found,
+                                                 ext, matrix, side.pssm() ? side.rowScores + (size_t)queryOffsets[i] * A : nullptr, A,
+                                                 mode, start, end, minScore[i], window[i], room, &found,
                                                  &hits.target, &hits.score, &hits.endT, &hits.endQ, align ? &stage : nullptr);
             if (rc == MIOPAL_ERR_TOO_MANY_HITS) over = true;
             else if (rc) return rc;
@@ -328,7 +468,7 @@ static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries
             if (!over) stretch[(size_t)i] = OccurrenceStretch{&hits, 0, found, found > 0 ? got : nullptr};
         }
         if (!panel.empty() && db->maxLen > 0)
-            RC_TRY(batchOccurrencePanel(db, queries, queryOffsets, panel, open, ext, matrix, A, mode, start, end, minScore, window,
+            RC_TRY(batchOccurrencePanel(db, side, panel, open, ext, A, mode, start, end, minScore, window,
                                         maxHits, &running, &over, &counts, &stretch, &pieces, align));
     }
     HitArrays all;

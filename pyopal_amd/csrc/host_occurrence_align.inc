@@ -41,27 +41,34 @@ struct OccurrenceAlignment {
 // chunks did is added to `routing` (the figures of miopalLastOccurrenceAlignRouting).
 using OccurrenceGather = std::function<int(int64_t c0, int nc, int64_t* targetOff, const int32_t** qBase)>;
 
-static int alignOccurrenceChunks(Search& s, int64_t total, const HitArrays& hits, const int32_t* dScore, const int32_t* dRow,
-                                 const int32_t* dColumn, int Q, bool operations, const OccurrenceGather& gather,
-                                 int64_t* routing, OccurrenceAlignment* out) {
-    MiopalDb* const db = s.db;
-    Workspace* const ws = s.ws;
+// ... in three steps, so that the PSSM panel can run the chunks over one stretch of the occurrences after another, each
+// with a query buffer of its own (host_batch_occurrence_align_pssm.inc): the arrays for all `total` occurrences,
+static int allocOccurrenceAlignment(int64_t total, bool operations, OccurrenceAlignment* out) {
     out->startT = (int*)malloc(sizeof(int) * (size_t)total);
     out->startQ = (int*)malloc(sizeof(int) * (size_t)total);
     if (operations) out->opsOff = (int64_t*)malloc(sizeof(int64_t) * (size_t)(total + 1));
     if (!out->startT || !out->startQ || (operations && !out->opsOff)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
     if (operations) out->opsOff[0] = 0;
+    return 0;
+}
 
+// the chunks of the occurrences first .. last (stretches are taken in ascending order, none left out: the operations
+// are appended and opsOff[first] is the stretch before's last entry),
+static int alignOccurrenceRange(Search& s, int64_t first, int64_t last, const HitArrays& hits, const int32_t* dScore,
+                                const int32_t* dRow, const int32_t* dColumn, int Q, bool operations,
+                                const OccurrenceGather& gather, int64_t* routing, OccurrenceAlignment* out) {
+    MiopalDb* const db = s.db;
+    Workspace* const ws = s.ws;
     int64_t maxL = 1;
-    for (int64_t k = 0; k < total; ++k) maxL = std::max<int64_t>(maxL, dbLen(db, hits.target[k]));
+    for (int64_t k = first; k < last; ++k) maxL = std::max<int64_t>(maxL, dbLen(db, hits.target[k]));
     const int64_t cap = pairChunkCapacity(Q, maxL, operations);
     const bool waveOnly = Q > kPairLaneMaxQuery || cap < kLanes;
     const bool forceLane = tuned(Tune::FORCE_LANE_PER_PAIR) != nullptr;
-    const bool tableFits = !s.pssmRows || perPairPssmBytes(Q, s.A) != 0;
+    const bool tableFits = !s.pssmRows || perPairPssmBytes(s.Q, s.A) != 0;   // (the whole buffer's rows are the table)
     const bool oneStrip = Q <= kLanes;
     std::vector<int32_t> hsq, hst, hlen, hts;
-    for (int64_t c0 = 0; c0 < total; c0 += cap) {
-        const int nc = (int)std::min(cap, total - c0);
+    for (int64_t c0 = first; c0 < last; c0 += cap) {
+        const int nc = (int)std::min(cap, last - c0);
         // the reversed prefixes of the chunk, in 64-row column steps (full_plan.h's estimates)
         double laneCols = 0, waveCols = 0, laneChain = 0, waveChain = 0;
         int chunkL = 1;
@@ -114,10 +121,23 @@ static int alignOccurrenceChunks(Search& s, int64_t total, const HitArrays& hits
         routing[2] += 1;
         routing[3] = std::max(routing[3], lp.maxWindow);
     }
+    return 0;
+}
+
+// and what is checked behind the last stretch.
+static int finishOccurrenceAlignment(int64_t total, bool operations, OccurrenceAlignment* out) {
     if (operations && (size_t)out->opsOff[total] != out->ops.size)
         return fail(MIOPAL_ERR_INTERNAL, "operation offsets disagree with the device");
     if (operations && !out->ops.data && !out->ops.resize(0)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
     return 0;
+}
+
+static int alignOccurrenceChunks(Search& s, int64_t total, const HitArrays& hits, const int32_t* dScore, const int32_t* dRow,
+                                 const int32_t* dColumn, int Q, bool operations, const OccurrenceGather& gather,
+                                 int64_t* routing, OccurrenceAlignment* out) {
+    RC_TRY(allocOccurrenceAlignment(total, operations, out));
+    RC_TRY(alignOccurrenceRange(s, 0, total, hits, dScore, dRow, dColumn, Q, operations, gather, routing, out));
+    return finishOccurrenceAlignment(total, operations, out);
 }
 
 static int alignOccurrencesStage(const OccurrencesOnDevice& o, bool operations, OccurrenceAlignment* out) {

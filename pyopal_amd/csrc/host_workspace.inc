@@ -33,6 +33,8 @@ enum Slot {
     // miopalSearchBatchOccurrences (host_batch_occurrences.inc): a chunk's queries and groups; where each query's
     // stretch of the scan's list begins, and the offsets and totals that come down
     kBatchOccurrenceMeta, kBatchOccurrenceBounds,
+    // miopalSearchPssmBatchOccurrences: which row of the chunk's PSSM rows (kPssmRows) each table row holds
+    kBatchOccurrenceRowSource,
     kSlots
 };
 

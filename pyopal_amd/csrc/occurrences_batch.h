@@ -53,11 +53,19 @@ struct BatchOccurrenceArgs {
     // the chunk's queries: rowResidue[r] = the residue of table row r (kBatchOccurrencePadRow: a pad row), every
     // query's rows padded to a multiple of eight; query[q] = {first row, rows of the query, minScore, window};
     // group[g] = {first query, queries, first row, rows} (count sweep: blockIdx.y = g)
-    const uint8_t* rowResidue;
+    // PSSM form (occurrences_batch_pssm.hip): rowSource[r] = the row of `rows` that table row r holds (-1: a pad row),
+    // rows = the chunk's PSSM rows end to end, [rows][alphabet]; query[] and group[] as above
+    union {
+        const uint8_t* rowResidue;
+        const int32_t* rowSource;
+    };
     const int4* query;
     const int4* group;
     int nQueries;
-    const int32_t* matrix;     // [A][A]
+    union {
+        const int32_t* matrix; // [A][A]
+        const int32_t* rows;   // PSSM form
+    };
     int alphabet, gapOpen, gapExt;
     int64_t n;                 // targets of the slice: the stride of the count array
     int32_t* count;            // count sweep: [nQueries][n]
@@ -75,6 +83,9 @@ struct BatchOccurrenceArgs {
 // table (count) / the tallest query's (write); listed: the scan's total of entries with occurrences.
 hipError_t launchBatchOccurrencesCount(const BatchOccurrenceArgs& a, int region, int groups, size_t ldsBytes, hipStream_t stream);
 hipError_t launchBatchOccurrencesWrite(const BatchOccurrenceArgs& a, int region, int64_t listed, size_t ldsBytes, hipStream_t stream);
+// the same sweeps with the table filled from PSSM rows (occurrences_batch_pssm.hip)
+hipError_t launchBatchOccurrencesCountPssm(const BatchOccurrenceArgs& a, int region, int groups, size_t ldsBytes, hipStream_t stream);
+hipError_t launchBatchOccurrencesWritePssm(const BatchOccurrenceArgs& a, int region, int64_t listed, size_t ldsBytes, hipStream_t stream);
 // first[q] (q = 0 .. nQueries) and head[q] = offsets[q * n] - the occurrences in front of query q, the chunk's total
 // at nQueries - then head[nQueries + 1 ..] = the scan's totals {occurrences, listed entries}: one small download
 hipError_t launchBatchOccurrencesBounds(const OccurrenceScratch& sc, int64_t n, int nQueries, int32_t* first, int64_t* head,

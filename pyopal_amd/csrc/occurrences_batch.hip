@@ -16,6 +16,11 @@
 //     them beyond the lanes of a wavefront's last, ragged piece.
 // The arithmetic, cell by cell and column by column, is occurrences_sweep_kernel's first strip: the answers are the
 // single-query search's byte for byte.
+//
+// PSSM form (miopalSearchPssmBatchOccurrences; occurrences_batch_pssm.hip defines MIOPAL_OCCURRENCES_BATCH_PSSM and
+// includes this file, as occurrences_pssm.hip includes occurrences.hip): the same sweep under the name
+// occurrences_batch_pssm_sweep_kernel, cell for cell. Only the table's source differs: table row r is row
+// rowSource[r] of the chunk's PSSM rows (-1: a pad row) + open - no residue list, no matrix.
 #include "occurrences_batch.h"
 #include "occurrence_picker.h"
 #include "launch_layer.h"
@@ -27,9 +32,16 @@ namespace {
 constexpr int kNegInf = INT32_MIN / 4;
 constexpr int kPadScore = -(1 << 28);
 constexpr int kBlock = 256;
+#ifdef MIOPAL_OCCURRENCES_BATCH_PSSM
+constexpr bool kPssmUnit = true;
+#define MIOPAL_BATCH_SWEEP_KERNEL occurrences_batch_pssm_sweep_kernel
+#else
+constexpr bool kPssmUnit = false;
+#define MIOPAL_BATCH_SWEEP_KERNEL occurrences_batch_sweep_kernel
+#endif
 
 template <int REGION, bool WRITE>
-__global__ __launch_bounds__(kBlock) void occurrences_batch_sweep_kernel(BatchOccurrenceArgs a) {
+__global__ __launch_bounds__(kBlock) void MIOPAL_BATCH_SWEEP_KERNEL(BatchOccurrenceArgs a) {
     static_assert(REGION == kLastRow || REGION == kAllCells, "HW or SW");
     constexpr bool SW = REGION == kAllCells;
     constexpr bool ROWS = SW && WRITE;   // the row of a column's maximum: only the write pass stores it
@@ -90,8 +102,13 @@ __global__ __launch_bounds__(kBlock) void occurrences_batch_sweep_kernel(BatchOc
     }
     for (int k = threadIdx.x; k < rowCount * rowInts; k += blockDim.x) {
         const int r = k / rowInts, t = k - r * rowInts;
-        const int residue = a.rowResidue[rowBase + r];
-        table[k] = (residue != kBatchOccurrencePadRow && t < A) ? a.matrix[residue * A + t] + open : kPadScore;
+        if constexpr (kPssmUnit) {
+            const int source = a.rowSource[rowBase + r];
+            table[k] = (source >= 0 && t < A) ? a.rows[(int64_t)source * A + t] + open : kPadScore;
+        } else {
+            const int residue = a.rowResidue[rowBase + r];
+            table[k] = (residue != kBatchOccurrencePadRow && t < A) ? a.matrix[residue * A + t] + open : kPadScore;
+        }
     }
     __syncthreads();
 
@@ -182,6 +199,7 @@ __global__ __launch_bounds__(kBlock) void occurrences_batch_sweep_kernel(BatchOc
     }
 }
 
+#ifndef MIOPAL_OCCURRENCES_BATCH_PSSM
 // first[q] = the position in the scan's list of the first entry >= q * n, head[q] = the occurrences in front of it
 __global__ __launch_bounds__(kBlock) void occurrences_batch_bounds_kernel(OccurrenceScratch sc, int64_t n, int nQueries,
                                                                           int32_t* first, int64_t* head) {
@@ -203,22 +221,34 @@ __global__ __launch_bounds__(kBlock) void occurrences_batch_bounds_kernel(Occurr
     }
 }
 
+#endif
+
 template <int REGION, bool WRITE>
 hipError_t launchSweep(const BatchOccurrenceArgs& a, dim3 grid, dim3 block, size_t ldsBytes, hipStream_t stream) {
-    if (const hipError_t e = allowFullLds<&occurrences_batch_sweep_kernel<REGION, WRITE>>(); e != hipSuccess) return e;
-    hipLaunchKernelGGL((occurrences_batch_sweep_kernel<REGION, WRITE>), grid, block, ldsBytes, stream, a);
+    if (const hipError_t e = allowFullLds<&MIOPAL_BATCH_SWEEP_KERNEL<REGION, WRITE>>(); e != hipSuccess) return e;
+    hipLaunchKernelGGL((MIOPAL_BATCH_SWEEP_KERNEL<REGION, WRITE>), grid, block, ldsBytes, stream, a);
     return hipGetLastError();
 }
 
 bool sweepArgsOk(const BatchOccurrenceArgs& a, int region, size_t ldsBytes) {
     if (region != kLastRow && region != kAllCells) return false;
+    // (the PSSM unit: rowSource and rows lie where rowResidue and matrix do)
     if (!a.residues || !a.rowResidue || !a.query || !a.matrix || a.nQueries < 1 || a.n < 1) return false;
     return a.alphabet >= 1 && a.alphabet <= kMaxAlphabet && ldsBytes >= 1 && ldsBytes <= kCuLdsBytes;
 }
 
 }  // namespace
 
-hipError_t launchBatchOccurrencesCount(const BatchOccurrenceArgs& a, int region, int groups, size_t ldsBytes, hipStream_t stream) {
+// the sweeps of this unit: occurrences_batch.o the plain form, occurrences_batch_pssm.o the row-filled one
+#ifdef MIOPAL_OCCURRENCES_BATCH_PSSM
+#define MIOPAL_BATCH_COUNT launchBatchOccurrencesCountPssm
+#define MIOPAL_BATCH_WRITE launchBatchOccurrencesWritePssm
+#else
+#define MIOPAL_BATCH_COUNT launchBatchOccurrencesCount
+#define MIOPAL_BATCH_WRITE launchBatchOccurrencesWrite
+#endif
+
+hipError_t MIOPAL_BATCH_COUNT(const BatchOccurrenceArgs& a, int region, int groups, size_t ldsBytes, hipStream_t stream) {
     if (a.nJobs <= 0) return hipSuccess;
     if (!sweepArgsOk(a, region, ldsBytes) || !a.jobs || !a.group || !a.count || groups < 1 || groups > 65535) return hipErrorInvalidValue;
     const dim3 grid((a.nJobs + kBlock - 1) / kBlock, groups), block(kBlock);
@@ -226,7 +256,7 @@ hipError_t launchBatchOccurrencesCount(const BatchOccurrenceArgs& a, int region,
                               : launchSweep<kAllCells, false>(a, grid, block, ldsBytes, stream);
 }
 
-hipError_t launchBatchOccurrencesWrite(const BatchOccurrenceArgs& a, int region, int64_t listed, size_t ldsBytes, hipStream_t stream) {
+hipError_t MIOPAL_BATCH_WRITE(const BatchOccurrenceArgs& a, int region, int64_t listed, size_t ldsBytes, hipStream_t stream) {
     if (listed <= 0) return hipSuccess;
     if (!sweepArgsOk(a, region, ldsBytes) || !a.offsets || !a.list || !a.first || !a.dbOffsets || !a.outTarget || !a.outScore ||
         !a.outColumn || !a.outRow || listed > a.n * a.nQueries)
@@ -237,6 +267,7 @@ hipError_t launchBatchOccurrencesWrite(const BatchOccurrenceArgs& a, int region,
                               : launchSweep<kAllCells, true>(a, grid, block, ldsBytes, stream);
 }
 
+#ifndef MIOPAL_OCCURRENCES_BATCH_PSSM
 hipError_t launchBatchOccurrencesBounds(const OccurrenceScratch& sc, int64_t n, int nQueries, int32_t* first, int64_t* head,
                                         hipStream_t stream) {
     if (n < 1 || nQueries < 1 || !first || !head) return hipErrorInvalidValue;
@@ -244,5 +275,6 @@ hipError_t launchBatchOccurrencesBounds(const OccurrenceScratch& sc, int64_t n, 
                        nQueries, first, head);
     return hipGetLastError();
 }
+#endif
 
 }  // namespace miopal

@@ -704,6 +704,10 @@ class _Profiles(_QuerySide):
     def on(self, mirror):
         return mirror._pssm_side(self.pssms[0].scores, None, self.aligner.gap_open, self.aligner.gap_extend)
 
+    @property
+    def arrays(self) -> typing.List[np.ndarray]:
+        return [p.scores for p in self.pssms]
+
     def search(self, mirror, mode, algorithm, start, end):
         pssm = self.pssms[0]
         return mirror.search_pssm(pssm.scores, pssm.consensus, self.aligner.gap_open, self.aligner.gap_extend, mode,
@@ -1569,6 +1573,39 @@ class Pssm:
         codes = np.frombuffer(alphabet.encode(sequence), dtype=np.uint8)
         table = _int_matrix_array(matrix.int_array()).reshape(len(alphabet), len(alphabet))
         return cls(table[codes], alphabet, codes)
+
+    def reverse_complement(self, complement=None) -> "Pssm":
+        """The PSSM of the other strand: the rows in reverse order, their columns and the consensus permuted by
+        ``complement``, a mapping over the alphabet's letters (letters it leaves out map to themselves). Default:
+        A and T, C and G are exchanged, U is mapped like T where the alphabet has it, every other letter stays; an
+        alphabet that holds none of these pairs raises ValueError, and so does one with a letter that is no IUPAC
+        nucleotide code - the protein alphabet has A, C, G and T, and exchanging those amino acids without being asked
+        to would be a wrong answer, not a default. ``NO_RESIDUE`` in the consensus stays. A motif
+        library is scanned on both strands by putting each PSSM and its reverse complement into the panel
+        (`find_occurrences_pssm_many`). Host-only."""
+        letters = self.alphabet.letters
+        if complement is None:
+            pairs = [(a, b) for a, b in (("A", "T"), ("C", "G"), ("A", "U")) if a in letters and b in letters]
+            if not pairs:
+                raise ValueError("the alphabet holds none of the pairs A/T, C/G, A/U: pass a complement mapping")
+            if any(x not in "ACGTUNRYSWKMBDHV*" for x in letters):
+                raise ValueError("the alphabet holds letters that are no nucleotide codes: pass a complement mapping")
+            complement = {}
+            for a, b in pairs:
+                complement[b] = a
+                complement.setdefault(a, b)   # (A goes to T where both T and U stand)
+        elif not isinstance(complement, typing.Mapping):
+            raise TypeError(f"complement must be a mapping of letters, not {type(complement).__name__}")
+        to = np.arange(len(letters), dtype=np.int64)
+        for a, b in complement.items():
+            if not (isinstance(a, str) and isinstance(b, str) and len(a) == 1 and len(b) == 1 and a in letters and b in letters):
+                raise ValueError(f"complement maps {a!r} to {b!r}: both must be letters of the alphabet")
+            to[letters.index(a)] = letters.index(b)
+        # a residue t of the other strand stands opposite to[t] of this one: scores'[i, t] = scores[Q - 1 - i, to[t]]
+        scores = self.scores[::-1][:, to]
+        lookup = np.arange(256, dtype=np.uint8)
+        lookup[:len(to)] = to
+        return Pssm(scores, self.alphabet, lookup[self.consensus[::-1]])
 
     @classmethod
     def from_columns(cls, columns: "ProfileColumns", prior: "Pssm", background, lam: float, *,

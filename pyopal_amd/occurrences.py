@@ -135,21 +135,24 @@ def _panel_values(values, name, none_allowed):
 
 
 def _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits,
-                  operations=None):
+                  operations=None, pssm=False):
     """(the CSR of the request, the query side, the target lengths or None). ``operations`` None: the panel search
-    (`find_occurrences_many`, mode "end"); a bool: the aligned form, with or without the operations."""
+    (`find_occurrences_many`, mode "end"); a bool: the aligned form, with or without the operations. ``pssm``: the
+    panel is a list of `Pssm` (the `..._pssm_many` functions)."""
+    many, aligned = ("find_occurrences_pssm_many", "find_occurrence_alignments_pssm_many") if pssm else \
+                    ("find_occurrences_many", "find_occurrence_alignments_many")
     if mode not in _MODES:
         raise ValueError(f"occurrences are reported with mode 'end' or 'full', not {mode!r}")
     if mode == "full" and operations is None:
-        raise ValueError("the alignments of a panel's occurrences are not available yet from find_occurrences_many, "
-                         "which reports mode 'end': find_occurrence_alignments_many aligns a panel's occurrences")
+        raise ValueError(f"the alignments of a panel's occurrences are not available yet from {many}, "
+                         f"which reports mode 'end': {aligned} aligns a panel's occurrences")
     cuts, many_cuts = _panel_values(min_score, "min_score", False)
     windows, many_windows = _panel_values(window, "window", True)
     for cut in cuts or [1]:
         _rule(mode, algorithm, cut, None)
     for w in windows:
         _rule(mode, algorithm, 1, w)
-    side = _Sequences(aligner, queries, True)
+    side = (_Profiles if pssm else _Sequences)(aligner, queries, True)
     request = _Request(side, database, mode, algorithm, start, end, device, lambda: _max_hits_argument(max_hits))
     for items, many, name in ((cuts, many_cuts, "min_score"), (windows, many_windows, "window")):
         if many and len(items) != len(side.lengths):
@@ -163,11 +166,16 @@ def _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode
                 del out["aln_flat"], out["aln_off"]
             return out, side, None
         mirror = request.mirror()
-        rule = (side.arrays, aligner._matrix, aligner.gap_open, aligner.gap_extend, algorithm, start, request.end,
+        rule = (aligner.gap_open, aligner.gap_extend, algorithm, start, request.end,
                 cuts if many_cuts else cuts[0], windows if many_windows else windows[0], request.checked)
         if operations is None:
-            return mirror.search_batch_occurrences(*rule), side, None
-        out = mirror.search_batch_occurrence_alignments(*rule, operations)
+            ends = mirror.search_batch_occurrences_pssm if pssm else mirror.search_batch_occurrences
+            return ends(side.arrays, *(() if pssm else (aligner._matrix,)), *rule), side, None
+        if pssm:
+            out = mirror.search_batch_occurrence_alignments_pssm(side.arrays, [p.consensus for p in side.pssms], *rule,
+                                                                 operations)
+        else:
+            out = mirror.search_batch_occurrence_alignments(side.arrays, aligner._matrix, *rule, operations)
         out.pop("aln", None)
         return out, side, _target_lengths(mirror, mode)
 
@@ -226,3 +234,59 @@ def find_occurrence_alignments_many_arrays(aligner: Aligner, queries, database: 
     entries offsets[i]:offsets[i + 1] belong to query i. ``operations=False``: starts only."""
     return _panel_arrays(aligner, queries, database, min_score, window, algorithm, "full", start, end, device, max_hits,
                          bool(operations))[0]
+
+
+# --- a panel of PSSMs in one call (miopalSearchPssmBatchOccurrences, ...Aligned) --------------------------------------
+# (the four functions above with a list of `Pssm` where the queries stand: a motif library, each PSSM beside its
+# `Pssm.reverse_complement()` where both strands count)
+
+def find_occurrences_pssm_many(aligner: Aligner, pssms, database: BaseDatabase, min_score, *, window=None,
+                               algorithm: str = "hw", mode: str = "end", start: int = 0, end: int = UINT32_MAX,
+                               device: int = 0,
+                               max_hits: typing.Optional[int] = None) -> typing.List[typing.List[ScoreResult]]:
+    """`find_occurrences_many` with a list of `Pssm` in the place of the queries and the aligner's matrix: one list of
+    `EndResult` per PSSM, each what ``find_occurrences_pssm(aligner, pssm, ..., mode="end")`` returns for that PSSM. A
+    window of None is that PSSM's height. ``mode="full"`` raises ValueError: `find_occurrence_alignments_pssm_many`
+    returns the alignments."""
+    out = _panel_arrays(aligner, pssms, database, min_score, window, algorithm, mode, start, end, device, max_hits,
+                        pssm=True)[0]
+    flat = _result_objects(mode, out["target"], None, None, None, out)
+    offsets = out["offsets"].tolist()
+    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+
+
+def find_occurrences_pssm_many_arrays(aligner: Aligner, pssms, database: BaseDatabase, min_score, *, window=None,
+                                      algorithm: str = "hw", mode: str = "end", start: int = 0, end: int = UINT32_MAX,
+                                      device: int = 0,
+                                      max_hits: typing.Optional[int] = None) -> typing.Dict[str, typing.Any]:
+    """`find_occurrences_pssm_many` without result objects: `find_occurrences_many_arrays`' CSR, entries
+    offsets[i]:offsets[i + 1] belonging to PSSM i."""
+    return _panel_arrays(aligner, pssms, database, min_score, window, algorithm, mode, start, end, device, max_hits,
+                         pssm=True)[0]
+
+
+def find_occurrence_alignments_pssm_many(aligner: Aligner, pssms, database: BaseDatabase, min_score, *, window=None,
+                                         algorithm: str = "hw", start: int = 0, end: int = UINT32_MAX, device: int = 0,
+                                         max_hits: typing.Optional[int] = None
+                                         ) -> typing.List[typing.List[ScoreResult]]:
+    """`find_occurrence_alignments_many` with a list of `Pssm`: one list of `FullResult` per PSSM, each what
+    ``find_occurrences_pssm(aligner, pssm, ..., mode="full")`` returns for that PSSM; the PSSMs' consensus tells
+    matches from mismatches."""
+    out, side, target_lengths = _panel_arrays(aligner, pssms, database, min_score, window, algorithm, "full", start, end,
+                                              device, max_hits, True, pssm=True)
+    offsets = out["offsets"]
+    owner = np.repeat(np.arange(len(offsets) - 1, dtype=np.int64), np.diff(offsets))
+    flat = _result_objects("full", out["target"], owner, side.lengths, target_lengths, out)
+    offsets = offsets.tolist()
+    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+
+
+def find_occurrence_alignments_pssm_many_arrays(aligner: Aligner, pssms, database: BaseDatabase, min_score, *,
+                                                window=None, algorithm: str = "hw", start: int = 0,
+                                                end: int = UINT32_MAX, device: int = 0,
+                                                max_hits: typing.Optional[int] = None,
+                                                operations: bool = True) -> typing.Dict[str, typing.Any]:
+    """`find_occurrence_alignments_pssm_many` without result objects: `find_occurrence_alignments_many_arrays`' CSR,
+    entries offsets[i]:offsets[i + 1] belonging to PSSM i. ``operations=False``: starts only."""
+    return _panel_arrays(aligner, pssms, database, min_score, window, algorithm, "full", start, end, device, max_hits,
+                         bool(operations), pssm=True)[0]
