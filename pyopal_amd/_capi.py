@@ -382,6 +382,27 @@ class _HitPointers:
         return out
 
 
+class _AlignedPointers:
+    """An aligned occurrence search's four outputs behind `_HitPointers`' (with ``operations``: all four) and their arrays."""
+
+    def __init__(self, operations: bool):
+        self.operations = operations
+        self.start_t, self.start_q = ctypes.c_void_p(), ctypes.c_void_p()
+        self.ops, self.ops_off = ctypes.c_void_p(), ctypes.c_void_p()
+
+    def refs(self):
+        return (ctypes.byref(self.start_t), ctypes.byref(self.start_q),
+                ctypes.byref(self.ops) if self.operations else None, ctypes.byref(self.ops_off) if self.operations else None)
+
+    def arrays(self, total: int) -> typing.Dict[str, typing.Any]:
+        out = {"start_t": _take_malloced(self.start_t, total, np.int32), "start_q": _take_malloced(self.start_q, total, np.int32)}
+        if self.operations:
+            aoff = _take_malloced(self.ops_off, total + 1, np.int64)
+            flat = _take_malloced(self.ops, int(aoff[-1]), np.uint8)
+            out.update(aln_flat=flat, aln_off=aoff, aln=_LazyAlignments(flat, aoff))
+        return out
+
+
 def select_hits_rows(score: np.ndarray, min_score, end_q: typing.Optional[np.ndarray] = None,
                      end_t: typing.Optional[np.ndarray] = None, start: int = 0) -> typing.Dict[str, np.ndarray]:
     """miopalTestSelectHits (test hook): the device compaction alone on the rows of ``score`` (int32, (rows, stride); a
@@ -442,7 +463,8 @@ def pick_occurrences_rows(value: np.ndarray, length, min_score: int, window: int
 
 
 def _check_occurrence_rule(algorithm, min_score, window) -> None:
-    """what the C side refuses of an occurrence search's rule, refused before it is reached"""
+    """what the C side refuses of an occurrence search's rule, refused before it is reached. ``min_score`` and
+    ``window``: the one value each of a single search (a window of None is the query's length), or a panel's smallest"""
     if algorithm not in ("hw", "sw"):
         raise ValueError(f"occurrences are defined for the algorithms 'hw' and 'sw', not {algorithm!r}")
     if window is not None and window < 0:
@@ -1052,6 +1074,19 @@ class DeviceDatabase:
             side.length if window is None else window, _bound(max_hits), ctypes.byref(counts), *ptrs.refs())
         return self._found(rc, counts, ptrs, "end")
 
+    def _search_occurrence_alignments(self, side: _QuerySide, algorithm, start, end, min_score, window, max_hits,
+                                      operations):
+        _check_occurrence_rule(algorithm, min_score, window)
+        counts = ctypes.c_int64(-1)
+        ptrs = _HitPointers()
+        more = _AlignedPointers(operations)
+        rc = getattr(lib(), f"miopalSearch{side.name}OccurrencesAligned")(
+            self._h, *side.queries, *side.scoring, MODE[algorithm], start, self._clamp(end), min_score,
+            side.length if window is None else window, _bound(max_hits), ctypes.byref(counts), *ptrs.refs(), *more.refs())
+        out = self._found(rc, counts, ptrs, "end")
+        out.update(more.arrays(out["count"]))
+        return out
+
     def search_occurrences(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
                            algorithm: str = "hw", start: int = 0, end: typing.Optional[int] = None, min_score: int = 1,
                            window: typing.Optional[int] = None,
@@ -1075,26 +1110,6 @@ class DeviceDatabase:
         in `search_pssm`) in the place of (query, matrix); PSSMs too tall for the sweep's LDS table are refused."""
         return self._search_occurrences(self._pssm_side(row_scores, None, gap_open, gap_extend), algorithm, start, end,
                                         min_score, window, max_hits)
-
-    def _search_occurrence_alignments(self, side: _QuerySide, algorithm, start, end, min_score, window, max_hits,
-                                      operations):
-        _check_occurrence_rule(algorithm, min_score, window)
-        counts = ctypes.c_int64(-1)
-        ptrs = _HitPointers()
-        start_t, start_q, ops, ops_off = (ctypes.c_void_p() for _ in range(4))
-        rc = getattr(lib(), f"miopalSearch{side.name}OccurrencesAligned")(
-            self._h, *side.queries, *side.scoring, MODE[algorithm], start, self._clamp(end), min_score,
-            side.length if window is None else window, _bound(max_hits), ctypes.byref(counts), *ptrs.refs(),
-            ctypes.byref(start_t), ctypes.byref(start_q), ctypes.byref(ops) if operations else None,
-            ctypes.byref(ops_off) if operations else None)
-        out = self._found(rc, counts, ptrs, "end")
-        n = out["count"]
-        out.update(start_t=_take_malloced(start_t, n, np.int32), start_q=_take_malloced(start_q, n, np.int32))
-        if operations:
-            aoff = _take_malloced(ops_off, n + 1, np.int64)
-            flat = _take_malloced(ops, int(aoff[-1]), np.uint8)
-            out.update(aln_flat=flat, aln_off=aoff, aln=_LazyAlignments(flat, aoff))
-        return out
 
     def search_occurrence_alignments(self, query: np.ndarray, matrix: np.ndarray, gap_open: int = 3, gap_extend: int = 1,
                                      algorithm: str = "hw", start: int = 0, end: typing.Optional[int] = None,
@@ -1132,9 +1147,8 @@ class DeviceDatabase:
         offsets[i]:offsets[i + 1] equal search_occurrences(queries[i], ...) byte for byte. ``max_hits`` bounds the
         total; TooManyHits carries the offsets in ``counts``. The rule's faults raise ValueError before any device
         call, as `search_occurrences`' do."""
-        rc, offsets, ptrs = self._call_batch_occurrences(self._batch_side(queries, matrix, gap_open, gap_extend),
-                                                         algorithm, start, end, min_score, window, max_hits)
-        return self._found(rc, offsets, ptrs, "end")
+        return self._search_batch_occurrences(self._batch_side(queries, matrix, gap_open, gap_extend), algorithm, start, end,
+                                              min_score, window, max_hits)
 
     def search_batch_occurrences_pssm(self, row_scores: typing.Sequence[np.ndarray], gap_open: int = 3,
                                       gap_extend: int = 1, algorithm: str = "hw", start: int = 0,
@@ -1144,33 +1158,29 @@ class DeviceDatabase:
         matrices (``row_scores[m]``: integers of shape (rows of PSSM m, alphabet length)) in the place of (queries,
         matrix). Returns `search_batch_occurrences`' dict; entries offsets[i]:offsets[i + 1] equal
         search_occurrences_pssm(row_scores[i], ...) byte for byte. A window of None is that PSSM's height."""
-        rc, offsets, ptrs = self._call_batch_occurrences(self._pssm_batch_side(row_scores, None, gap_open, gap_extend),
-                                                         algorithm, start, end, min_score, window, max_hits)
-        return self._found(rc, offsets, ptrs, "end")
+        return self._search_batch_occurrences(self._pssm_batch_side(row_scores, None, gap_open, gap_extend), algorithm, start,
+                                              end, min_score, window, max_hits)
 
-    def _call_batch_occurrences(self, side: _QuerySide, algorithm, start, end, min_score, window, max_hits, aligned=None):
-        """The preamble of the panel occurrence searches, plain and PSSM - the per-query cuts and windows, the rule's
-        faults - and the call of miopalSearch<side>Occurrences or, with ``aligned`` (the four arguments behind the
-        result pointers), ...OccurrencesAligned. Returns (the code, the offsets, the result pointers)."""
-        entry = f"miopalSearch{side.name}Occurrences" + ("" if aligned is None else "Aligned")
-        more = aligned or ()
+    def _search_batch_occurrences(self, side: _QuerySide, algorithm, start, end, min_score, window, max_hits, operations=None):
+        """The panel occurrence searches, plain and PSSM: the per-query cuts and windows, the rule's faults, and the call of
+        miopalSearch<side>Occurrences or, with ``operations`` (a bool: the aligned outputs with or without the operations), ...OccurrencesAligned."""
+        more = None if operations is None else _AlignedPointers(operations)
         lengths = np.diff(side.keep[1]).tolist()
         cuts, windows = _per_query(min_score, lengths, "min_score"), _per_query(window, lengths, "window")
-        if algorithm not in ("hw", "sw"):
-            raise ValueError(f"occurrences are defined for the algorithms 'hw' and 'sw', not {algorithm!r}")
-        if np.any(windows < 0):
-            raise ValueError("window must not be negative")
-        if algorithm == "sw" and np.any(cuts < 1):
-            raise ValueError("min_score must be at least 1 with algorithm 'sw'")
+        _check_occurrence_rule(algorithm, cuts.min(initial=1), windows.min(initial=0))   # (a panel's smallest decide)
         if len(cuts) and (cuts.min() < -(2 ** 31) or cuts.max() >= 2 ** 31 or windows.max() >= 2 ** 31):
             raise OverflowError("min_score / window does not fit a 32-bit integer")
         cuts, windows = cuts.astype(np.int32), windows.astype(np.int32)
         offsets = np.zeros(side.rows + 1, dtype=np.int64)
         ptrs = _HitPointers()
-        rc = getattr(lib(), entry)(self._h, *side.queries, *side.scoring, MODE[algorithm], start, self._clamp(end),
-                   _ptr(cuts) if side.rows else None, _ptr(windows) if side.rows else None, _bound(max_hits),
-                   _ptr(offsets), *ptrs.refs(), *more)
-        return rc, offsets, ptrs
+        rc = getattr(lib(), f"miopalSearch{side.name}Occurrences" + ("Aligned" if more else ""))(
+            self._h, *side.queries, *side.scoring, MODE[algorithm], start, self._clamp(end),
+            _ptr(cuts) if side.rows else None, _ptr(windows) if side.rows else None, _bound(max_hits),
+            _ptr(offsets), *ptrs.refs(), *(more.refs() if more else ()))
+        out = self._found(rc, offsets, ptrs, "end")
+        if more:
+            out.update(more.arrays(int(offsets[-1])))
+        return out
 
     def search_batch_occurrence_alignments(self, queries: typing.Sequence[np.ndarray], matrix: np.ndarray,
                                            gap_open: int = 3, gap_extend: int = 1, algorithm: str = "hw", start: int = 0,
@@ -1183,8 +1193,8 @@ class DeviceDatabase:
         offsets[i]:offsets[i + 1] equal search_occurrence_alignments(queries[i], ...). ``operations=False``: starts
         only, and no "aln*" keys. ``max_hits`` bounds the total; TooManyHits carries the offsets in ``counts``, and
         what had been aligned by then is discarded."""
-        return self._batch_occurrence_alignments(self._batch_side(queries, matrix, gap_open, gap_extend), algorithm, start,
-                                                 end, min_score, window, max_hits, operations)
+        return self._search_batch_occurrences(self._batch_side(queries, matrix, gap_open, gap_extend), algorithm, start, end,
+                                              min_score, window, max_hits, operations)
 
     def search_batch_occurrence_alignments_pssm(self, row_scores: typing.Sequence[np.ndarray],
                                                 consensus: typing.Optional[typing.Sequence[np.ndarray]] = None,
@@ -1197,22 +1207,7 @@ class DeviceDatabase:
         required with ``operations``) in the place of (queries, matrix). Entries offsets[i]:offsets[i + 1] equal
         search_occurrence_alignments_pssm(row_scores[i], consensus[i], ...)."""
         side = self._pssm_batch_side(row_scores, consensus, gap_open, gap_extend, with_consensus=True)
-        return self._batch_occurrence_alignments(side, algorithm, start, end, min_score, window, max_hits, operations)
-
-    def _batch_occurrence_alignments(self, side: _QuerySide, algorithm, start, end, min_score, window, max_hits,
-                                     operations) -> typing.Dict[str, typing.Any]:
-        start_t, start_q, ops, ops_off = (ctypes.c_void_p() for _ in range(4))
-        more = (ctypes.byref(start_t), ctypes.byref(start_q), ctypes.byref(ops) if operations else None,
-                ctypes.byref(ops_off) if operations else None)
-        rc, offsets, ptrs = self._call_batch_occurrences(side, algorithm, start, end, min_score, window, max_hits, more)
-        out = self._found(rc, offsets, ptrs, "end")
-        n = int(offsets[-1])
-        out.update(start_t=_take_malloced(start_t, n, np.int32), start_q=_take_malloced(start_q, n, np.int32))
-        if operations:
-            aoff = _take_malloced(ops_off, n + 1, np.int64)
-            flat = _take_malloced(ops, int(aoff[-1]), np.uint8)
-            out.update(aln_flat=flat, aln_off=aoff, aln=_LazyAlignments(flat, aoff))
-        return out
+        return self._search_batch_occurrences(side, algorithm, start, end, min_score, window, max_hits, operations)
 
     pick_occurrences_rows = staticmethod(pick_occurrences_rows)
     last_occurrence_routing = staticmethod(last_occurrence_routing)

@@ -41,6 +41,7 @@
 #include "occurrences_batch.h"
 #include "occurrence_align.h"
 #include "occurrence_align_batch.h"
+#include "occurrence_plan_selftest.h"
 #include "profile_columns.h"
 #include "score_ranges_selftest.h"
 #include "select_columns.h"
@@ -635,6 +636,11 @@ int miopalSelfTest(int which) {
             }
             return 0;
         }
+        if (which == 7) {
+            // the chunk plan of the panel occurrence searches - chunk sizes, groups, row lists and entries - against
+            // literals worked out by hand from occurrences_batch.h's rules: occurrence_plan_selftest.h
+            return occurrencePlanSelfTest();
+        }
         if (which != 1) return -1;
         // (no device call on the way: the handle is never filled, the builders are injected)
         std::unique_ptr<MiopalDb> db(new MiopalDb());
@@ -754,8 +760,6 @@ int miopalSearchDeviceScores(MiopalDb* db, const unsigned char* query, int query
 #include "host_profile.inc"
 #include "host_occurrences.inc"
 #include "host_occurrence_align.inc"
-#include "host_batch_occurrence_align.inc"
-#include "host_batch_occurrence_align_pssm.inc"
 #include "host_batch_occurrences.inc"
 int miopalSearch(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                  const int* scoreMatrix, int alphabetLength, int searchType, int mode, int64_t start,
@@ -898,11 +902,7 @@ int miopalSearchPssm(MiopalDb* db, const int* rowScores, const unsigned char* co
     const int Q = queryLength, A = alphabetLength;
     RC_TRY(PssmQuery::checkBeforeHandle(mode, searchType, Q, rowScores, A));
     const bool full = searchType == OPAL_SEARCH_ALIGNMENT;
-    if (full && Q > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
-    if (consensus)
-        for (int i = 0; i < Q; ++i)
-            if (consensus[i] >= A && consensus[i] != 255)
-                return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %d", consensus[i], i);
+    RC_TRY(checkConsensus(consensus, 0, Q, A, full));
     RC_TRY(PssmQuery::checkHandle(db, A, start, end));
     if (full && !operations) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null alignment outputs");
     if (operations) *operations = nullptr;
@@ -986,133 +986,87 @@ int miopalSearchOccurrences(MiopalDb* db, const unsigned char* query, int queryL
                             int window, int64_t maxHits, int64_t* count, int64_t** targetIndex, int** score,
                             int** endTarget, int** endQuery) {
     return guarded([&]() -> int {
+    const OccurrenceOutputs out{count, targetIndex, score, endTarget, endQuery};
     RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, OPAL_SEARCH_SCORE_END, mode, start, end));
-    RC_TRY(checkOccurrenceRule(mode, minScore, window));
-    RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, count, targetIndex, score, endTarget, endQuery));
-    return searchOccurrencesImpl(db, query, queryLength, gapOpen, gapExt, scoreMatrix, nullptr, alphabetLength, mode, start,
-                                 end, minScore, window, maxHits, count, targetIndex, score, endTarget, endQuery);
+    RC_TRY(checkOccurrenceRule(mode, 1, &minScore, &window, nullptr));
+    RC_TRY(out.check());
+    return searchOccurrencesCall(OccurrenceRequest{db, gapOpen, gapExt, alphabetLength, mode, start, end, maxHits},
+                                 OccurrenceQuery{query, queryLength, scoreMatrix, nullptr, minScore, window}, out);
     });
 }
 
-// miopalSearchPssmOccurrences: miopalSearchPssmHits' checks in its order - what needs no handle first, the occurrence
-// rule where that function refuses alignments, the outputs and the PSSM's height among it - then the same
-int miopalSearchPssmOccurrences(MiopalDb* db, const int* rowScores, int queryLength, int gapOpen, int gapExt,
-                                int alphabetLength, int mode, int64_t start, int64_t end, int minScore, int window,
-                                int64_t maxHits, int64_t* count, int64_t** targetIndex, int** score, int** endTarget,
-                                int** endQuery) {
-    return guarded([&]() -> int {
-    const int Q = queryLength, A = alphabetLength;
-    RC_TRY(PssmQuery::checkBeforeHandle(mode, OPAL_SEARCH_SCORE_END, Q, rowScores, A));
-    RC_TRY(checkOccurrenceRule(mode, minScore, window));
-    RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, count, targetIndex, score, endTarget, endQuery));
-    // (the sweep keeps the rows in LDS, as the lane-per-pair kernels of a PSSM pair list do)
-    if (perPairPssmBytes(Q, A) == 0)
-        return fail(MIOPAL_ERR_BAD_ARGUMENT, "a PSSM of %d rows at %d letters does not fit the occurrence sweep's LDS table: "
-                    "(rows + 1) x (letters + 1) x 4 bytes within 64 KB less 256, %d rows at most", Q, A,
-                    (64 * 1024 - 256) / (4 * (A + 1)) - 1);
-    RC_TRY(PssmQuery::checkHandle(db, A, start, end));
-    if (end > start) RC_TRY(checkPssmRange(db, rowScores, Q, A, gapOpen, gapExt));
-    const PssmQuery pssm(rowScores, nullptr, Q);
-    return searchOccurrencesImpl(db, pssm.consensus(), Q, gapOpen, gapExt, nullptr, pssm.rows(), A, mode, start, end, minScore,
-                                 window, maxHits, count, targetIndex, score, endTarget, endQuery);
-    });
-}
-
-void miopalLastOccurrenceRouting(int64_t counts[4]) {
-    if (!counts) return;
-    for (int k = 0; k < 4; ++k) counts[k] = g_lastOccurrenceRouting[k];
-}
-
-// miopalSearchBatchOccurrences: miopalSearchOccurrences' checks for every query of the list, in its order, before any
-// device work; then the panel kernels and, for queries of more than 64 rows, the single-query search
-// (host_batch_occurrences.inc)
-int miopalSearchBatchOccurrences(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
-                                 int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int mode,
-                                 int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
-                                 int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery) {
-    return guarded([&]() -> int {
-    return searchBatchOccurrencesImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength, mode,
-                                      start, end, minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery);
-    });
-}
-
-void miopalLastBatchOccurrenceRouting(int64_t counts[4]) {
-    if (!counts) return;
-    for (int k = 0; k < 4; ++k) counts[k] = g_lastBatchOccurrenceRouting[k];
-}
-
-void miopalLastBatchOccurrenceGroups(int64_t counts[3]) {
-    if (!counts) return;
-    for (int k = 0; k < 3; ++k) counts[k] = g_lastBatchOccurrenceGroups[k];
-}
-
-// the outputs the aligned forms add: the starts always, the operations and their offsets together or not at all
-// (declared in host_batch_occurrences.inc, whose panel form makes the check among its own)
-static int checkOccurrenceAlignOutputs(int** startTarget, int** startQuery, unsigned char** alignments,
-                                       int64_t** alignmentOffsets) {
-    if (!startTarget || !startQuery) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null start-location outputs");
-    if ((alignments == nullptr) != (alignmentOffsets == nullptr))
-        return fail(MIOPAL_ERR_BAD_ARGUMENT, "alignments and alignmentOffsets: both, or neither (starts only)");
-    return 0;
-}
-
-// miopalSearchOccurrencesAligned: miopalSearchOccurrences' checks in its order, then the new null outputs; the sweeps,
-// and behind them the later passes of a `full` pair list on the occurrences (host_occurrence_align.inc)
+// miopalSearchOccurrencesAligned: miopalSearchOccurrences' checks in its order, the new null outputs with the others;
+// the sweeps, and behind them the later passes of a `full` pair list on the occurrences (host_occurrence_align.inc)
 int miopalSearchOccurrencesAligned(MiopalDb* db, const unsigned char* query, int queryLength, int gapOpen, int gapExt,
                                    const int* scoreMatrix, int alphabetLength, int mode, int64_t start, int64_t end,
                                    int minScore, int window, int64_t maxHits, int64_t* count, int64_t** targetIndex,
                                    int** score, int** endTarget, int** endQuery, int** startTarget, int** startQuery,
                                    unsigned char** alignments, int64_t** alignmentOffsets) {
     return guarded([&]() -> int {
+    const OccurrenceOutputs out{count, targetIndex, score, endTarget, endQuery, true, startTarget, startQuery, alignments, alignmentOffsets};
     RC_TRY(validate(db, query, queryLength, scoreMatrix, alphabetLength, OPAL_SEARCH_SCORE_END, mode, start, end));
-    RC_TRY(checkOccurrenceRule(mode, minScore, window));
-    RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, count, targetIndex, score, endTarget, endQuery));
-    RC_TRY(checkOccurrenceAlignOutputs(startTarget, startQuery, alignments, alignmentOffsets));
-    return searchOccurrencesAlignedImpl(db, query, queryLength, gapOpen, gapExt, scoreMatrix, nullptr, alphabetLength, mode,
-                                        start, end, minScore, window, maxHits, count, targetIndex, score, endTarget,
-                                        endQuery, startTarget, startQuery, alignments, alignmentOffsets);
+    RC_TRY(checkOccurrenceRule(mode, 1, &minScore, &window, nullptr));
+    RC_TRY(out.check());
+    return searchOccurrencesCall(OccurrenceRequest{db, gapOpen, gapExt, alphabetLength, mode, start, end, maxHits},
+                                 OccurrenceQuery{query, queryLength, scoreMatrix, nullptr, minScore, window}, out);
     });
 }
 
-// miopalSearchPssmOccurrencesAligned: miopalSearchPssmOccurrences' checks in its order, the new null outputs behind
-// its own and, with operations, the consensus as miopalAlignPairsPssm requires it; then the same
+// miopalSearchPssmOccurrences(Aligned): miopalSearchPssmHits' checks in its order - what needs no handle first, the
+// occurrence rule where that function refuses alignments, the outputs, in the aligned form the consensus as
+// miopalAlignPairsPssm requires it, and the PSSM's height among it - then the same
+static int searchPssmOccurrencesEntry(const OccurrenceRequest& rq, const int* rowScores, const unsigned char* consensus, int Q,
+                                      int minScore, int window, const OccurrenceOutputs& out) {
+    RC_TRY(PssmQuery::checkBeforeHandle(rq.mode, OPAL_SEARCH_SCORE_END, Q, rowScores, rq.A));
+    RC_TRY(checkOccurrenceRule(rq.mode, 1, &minScore, &window, nullptr));
+    RC_TRY(out.check());
+    if (out.aligned) RC_TRY(checkConsensus(consensus, 0, Q, rq.A, out.alignments != nullptr));
+    RC_TRY(checkOccurrenceTableFits(Q, rq.A));
+    RC_TRY(PssmQuery::checkHandle(rq.db, rq.A, rq.start, rq.end));
+    if (rq.end > rq.start) RC_TRY(checkPssmRange(rq.db, rowScores, Q, rq.A, rq.open, rq.ext));
+    const PssmQuery pssm(rowScores, out.aligned ? consensus : nullptr, Q);
+    return searchOccurrencesCall(rq, OccurrenceQuery{pssm.consensus(), Q, nullptr, pssm.rows(), minScore, window}, out);
+}
+
+int miopalSearchPssmOccurrences(MiopalDb* db, const int* rowScores, int queryLength, int gapOpen, int gapExt,
+                                int alphabetLength, int mode, int64_t start, int64_t end, int minScore, int window,
+                                int64_t maxHits, int64_t* count, int64_t** targetIndex, int** score, int** endTarget,
+                                int** endQuery) {
+    return guarded([&]() -> int {
+    return searchPssmOccurrencesEntry(OccurrenceRequest{db, gapOpen, gapExt, alphabetLength, mode, start, end, maxHits}, rowScores,
+                                      nullptr, queryLength, minScore, window,
+                                      OccurrenceOutputs{count, targetIndex, score, endTarget, endQuery});
+    });
+}
+
 int miopalSearchPssmOccurrencesAligned(MiopalDb* db, const int* rowScores, const unsigned char* consensus, int queryLength,
                                        int gapOpen, int gapExt, int alphabetLength, int mode, int64_t start, int64_t end,
                                        int minScore, int window, int64_t maxHits, int64_t* count, int64_t** targetIndex,
                                        int** score, int** endTarget, int** endQuery, int** startTarget, int** startQuery,
                                        unsigned char** alignments, int64_t** alignmentOffsets) {
     return guarded([&]() -> int {
-    const int Q = queryLength, A = alphabetLength;
-    RC_TRY(PssmQuery::checkBeforeHandle(mode, OPAL_SEARCH_SCORE_END, Q, rowScores, A));
-    RC_TRY(checkOccurrenceRule(mode, minScore, window));
-    RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, count, targetIndex, score, endTarget, endQuery));
-    RC_TRY(checkOccurrenceAlignOutputs(startTarget, startQuery, alignments, alignmentOffsets));
-    if (alignments && Q > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
-    if (consensus)
-        for (int i = 0; i < Q; ++i)
-            if (consensus[i] >= A && consensus[i] != 255)
-                return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %d", consensus[i], i);
-    if (perPairPssmBytes(Q, A) == 0)
-        return fail(MIOPAL_ERR_BAD_ARGUMENT, "a PSSM of %d rows at %d letters does not fit the occurrence sweep's LDS table: "
-                    "(rows + 1) x (letters + 1) x 4 bytes within 64 KB less 256, %d rows at most", Q, A,
-                    (64 * 1024 - 256) / (4 * (A + 1)) - 1);
-    RC_TRY(PssmQuery::checkHandle(db, A, start, end));
-    if (end > start) RC_TRY(checkPssmRange(db, rowScores, Q, A, gapOpen, gapExt));
-    const PssmQuery pssm(rowScores, consensus, Q);
-    return searchOccurrencesAlignedImpl(db, pssm.consensus(), Q, gapOpen, gapExt, nullptr, pssm.rows(), A, mode, start, end,
-                                        minScore, window, maxHits, count, targetIndex, score, endTarget, endQuery,
-                                        startTarget, startQuery, alignments, alignmentOffsets);
+    return searchPssmOccurrencesEntry(OccurrenceRequest{db, gapOpen, gapExt, alphabetLength, mode, start, end, maxHits}, rowScores,
+                                      consensus, queryLength, minScore, window,
+                                      OccurrenceOutputs{count, targetIndex, score, endTarget, endQuery, true, startTarget, startQuery,
+                                                        alignments, alignmentOffsets});
     });
 }
 
-void miopalLastOccurrenceAlignRouting(int64_t counts[4]) {
-    if (!counts) return;
-    for (int k = 0; k < 4; ++k) counts[k] = g_lastOccurrenceAlignRouting[k];
+// miopalSearchBatchOccurrences(Aligned): miopalSearchOccurrences' checks for every query of the list, in its order,
+// before any device work, the aligned form's null outputs behind its own; then the panel kernels - in the aligned form
+// with the alignment stage behind every write sweep (host_batch_occurrence_align.inc) - and, for queries of more than
+// 64 rows, the single-query search (host_batch_occurrences.inc)
+int miopalSearchBatchOccurrences(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
+                                 int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength, int mode,
+                                 int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
+                                 int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery) {
+    return guarded([&]() -> int {
+    return searchBatchOccurrencesImpl(OccurrenceRequest{db, gapOpen, gapExt, alphabetLength, mode, start, end, maxHits},
+                                      PanelSide{queries, queryOffsets, nQueries, scoreMatrix, nullptr, minScore, window},
+                                      OccurrenceOutputs{hitOffsets, targetIndex, score, endTarget, endQuery});
+    });
 }
 
-// miopalSearchBatchOccurrencesAligned: miopalSearchBatchOccurrences' checks in its order with the new null outputs
-// behind its own; the panel's sweeps with the alignment stage behind every write sweep
-// (host_batch_occurrence_align.inc), a long query's through miopalSearchOccurrencesAligned's own path
 int miopalSearchBatchOccurrencesAligned(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets,
                                         int nQueries, int gapOpen, int gapExt, const int* scoreMatrix, int alphabetLength,
                                         int mode, int64_t start, int64_t end, const int* minScore, const int* window,
@@ -1120,9 +1074,10 @@ int miopalSearchBatchOccurrencesAligned(MiopalDb* db, const unsigned char* queri
                                         int** endTarget, int** endQuery, int** startTarget, int** startQuery,
                                         unsigned char** alignments, int64_t** alignmentOffsets) {
     return guarded([&]() -> int {
-    return searchBatchOccurrencesImpl(db, queries, queryOffsets, nQueries, gapOpen, gapExt, scoreMatrix, alphabetLength, mode,
-                                      start, end, minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery,
-                                      true, startTarget, startQuery, alignments, alignmentOffsets);
+    return searchBatchOccurrencesImpl(OccurrenceRequest{db, gapOpen, gapExt, alphabetLength, mode, start, end, maxHits},
+                                      PanelSide{queries, queryOffsets, nQueries, scoreMatrix, nullptr, minScore, window},
+                                      OccurrenceOutputs{hitOffsets, targetIndex, score, endTarget, endQuery, true, startTarget,
+                                                        startQuery, alignments, alignmentOffsets});
     });
 }
 
@@ -1133,9 +1088,9 @@ int miopalSearchPssmBatchOccurrences(MiopalDb* db, const int* rowScores, const i
                                      const int* minScore, const int* window, int64_t maxHits, int64_t* hitOffsets,
                                      int64_t** targetIndex, int** score, int** endTarget, int** endQuery) {
     return guarded([&]() -> int {
-    return searchPssmBatchOccurrencesImpl(db, rowScores, nullptr, rowOffsets, nPssms, gapOpen, gapExt, alphabetLength, mode, start,
-                                          end, minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery,
-                                          false, nullptr, nullptr, nullptr, nullptr);
+    return searchPssmBatchOccurrencesImpl(OccurrenceRequest{db, gapOpen, gapExt, alphabetLength, mode, start, end, maxHits},
+                                          PanelSide{nullptr, rowOffsets, nPssms, nullptr, rowScores, minScore, window},
+                                          OccurrenceOutputs{hitOffsets, targetIndex, score, endTarget, endQuery});
     });
 }
 
@@ -1146,16 +1101,23 @@ int miopalSearchPssmBatchOccurrencesAligned(MiopalDb* db, const int* rowScores, 
                                             int** score, int** endTarget, int** endQuery, int** startTarget,
                                             int** startQuery, unsigned char** alignments, int64_t** alignmentOffsets) {
     return guarded([&]() -> int {
-    return searchPssmBatchOccurrencesImpl(db, rowScores, consensus, rowOffsets, nPssms, gapOpen, gapExt, alphabetLength, mode,
-                                          start, end, minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget,
-                                          endQuery, true, startTarget, startQuery, alignments, alignmentOffsets);
+    return searchPssmBatchOccurrencesImpl(OccurrenceRequest{db, gapOpen, gapExt, alphabetLength, mode, start, end, maxHits},
+                                          PanelSide{consensus, rowOffsets, nPssms, nullptr, rowScores, minScore, window},
+                                          OccurrenceOutputs{hitOffsets, targetIndex, score, endTarget, endQuery, true, startTarget,
+                                                            startQuery, alignments, alignmentOffsets});
     });
 }
 
-void miopalLastBatchOccurrenceAlignRouting(int64_t counts[4]) {
-    if (!counts) return;
-    for (int k = 0; k < 4; ++k) counts[k] = g_lastBatchOccurrenceAlignRouting[k];
+// what the family's reporters say: the thread's last single-query call, its last aligned one, its last panel call
+static void copyFigures(int64_t* to, const int64_t* from, int n) {
+    if (!to) return;
+    for (int k = 0; k < n; ++k) to[k] = from[k];
 }
+void miopalLastOccurrenceRouting(int64_t counts[4]) { copyFigures(counts, g_lastOccurrenceRouting, 4); }
+void miopalLastOccurrenceAlignRouting(int64_t counts[4]) { copyFigures(counts, g_lastOccurrenceAlignRouting, 4); }
+void miopalLastBatchOccurrenceRouting(int64_t counts[4]) { copyFigures(counts, g_lastBatchOccurrenceRouting, 4); }
+void miopalLastBatchOccurrenceGroups(int64_t counts[3]) { copyFigures(counts, g_lastBatchOccurrenceGroups, 3); }
+void miopalLastBatchOccurrenceAlignRouting(int64_t counts[4]) { copyFigures(counts, g_lastBatchOccurrenceAlignRouting, 4); }
 
 int miopalTestPickOccurrences(const int* value, const int* valueRow, int rows, int64_t stride, const int32_t* length,
                               int minScore, int window, int64_t* hitOffsets, int32_t** column, int** score, int** row) {
@@ -1302,11 +1264,7 @@ int miopalAlignPairsPssm(MiopalDb* db, const int* rowScores, const unsigned char
     if (totalRows > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
     if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
     const bool full = searchType == OPAL_SEARCH_ALIGNMENT;
-    if (full && totalRows > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
-    if (consensus)
-        for (int64_t i = first; i < first + totalRows; ++i)
-            if (consensus[i] >= A && consensus[i] != 255)
-                return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %lld", consensus[i], (long long)i);
+    RC_TRY(checkConsensus(consensus, first, totalRows, A, full));
     // (without a consensus - score and end lists - every position is "no residue": the kernels never read it)
     std::vector<unsigned char> none;
     if (!consensus) {
@@ -1356,10 +1314,7 @@ int miopalProfileColumnsPssm(MiopalDb* db, const int* rowScores, const unsigned 
     if (Q > INT32_MAX - 64) return fail(MIOPAL_ERR_BAD_ARGUMENT, "a PSSM holds 2^31 - 65 rows at most");
     if (Q > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
     if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
-    if (Q > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
-    for (int i = 0; i < Q; ++i)
-        if (consensus[i] >= A && consensus[i] != 255)
-            return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %d", consensus[i], i);
+    RC_TRY(checkConsensus(consensus, 0, Q, A, true));
     return profileColumnsImpl(db, consensus, Q, gapOpen, gapExt, nullptr, A, mode, targets, nTargets, counts, weighted,
                               memberWeight, msa, Q > 0 ? rowScores : kNoRows);
     });

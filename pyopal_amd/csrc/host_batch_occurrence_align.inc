@@ -17,37 +17,25 @@ namespace {
 
 thread_local int64_t g_lastBatchOccurrenceAlignRouting[4] = {0, 0, 0, 0};   // miopalLastBatchOccurrenceAlignRouting
 
-// A panel chunk's occurrences where the write sweep left them: entry k is (target[k], score[k], row[k], column[k]),
-// `total` entries each in `ws`; head[0 .. cq] on the device (see above); `hits` holds the four arrays on the host.
-// The chunk's queries are panel[0 .. cq) of the call's list. A PSSM panel (rowScores: the call's rows, else null;
-// host_batch_occurrence_align_pssm.inc): `queries` is the consensus in the offsets' row coordinates, dRows the chunk's
-// rows end to end where the sweeps read them, hostHead the host's copy of head[0 .. cq].
-struct BatchOccurrencesOnDevice {
-    MiopalDb* db;
-    Workspace* ws;
-    const unsigned char* queries;
-    const int64_t* queryOffsets;
-    const int* panel;
-    int cq;
-    int open, ext;
-    const int* matrix;
-    int A, mode;
-    int64_t total;
-    const int64_t* target;
-    const int32_t *score, *row, *column;
-    const int64_t* head;
-    const HitArrays* hits;
-    const int* rowScores = nullptr;
-    const int32_t* dRows = nullptr;
-    const int64_t* hostHead = nullptr;
-};
-
 }  // namespace
+
+// What either panel stage gathers per sub-chunk: each occurrence's target origin and, from its position among
+// head[0 .. nq] (the occurrences in front of each of nq queries, on the device), its query's origin dQOff[query].
+static OccurrenceGather panelOccurrenceGather(const PanelChunk& o, const int64_t* head, int nq, const int32_t* dQOff) {
+    return [&o, head, nq, dQOff](int64_t c0, int nc, int64_t* targetOff, const int32_t** qBase) {
+        void* pqbase;
+        RC_TRY(o.ws->get(kPairListQBase, (size_t)nc * sizeof(int32_t), &pqbase));
+        HIP_TRY(launchBatchOccurrenceOrigins(nc, c0, o.slot.target + c0, o.rq.db->d_offsets, o.rq.db->count, head, nq, dQOff, targetOff,
+                                             (int32_t*)pqbase, o.ws->stream));
+        *qBase = (const int32_t*)pqbase;
+        return 0;
+    };
+}
 
 // Takes kQuery (where the chunk's row list lay: the write sweep that read it is in front of this upload in stream
 // order, and the next chunk uploads its own list), kMatrix (the same matrix again) and, through the shared stage,
 // kJobs / kSortedJobs / kSortBins: the caller's sorted jobs of the slice are gone afterwards.
-static int alignBatchOccurrencesStage(const BatchOccurrencesOnDevice& o, bool operations, OccurrenceAlignment* out) {
+static int alignBatchOccurrencesStage(const PanelChunk& o, bool operations, OccurrenceAlignment* out) {
     Workspace* const ws = o.ws;
     std::vector<unsigned char> concat;
     std::vector<int32_t> qOff((size_t)o.cq + 1, 0);
@@ -55,25 +43,18 @@ static int alignBatchOccurrencesStage(const BatchOccurrencesOnDevice& o, bool op
     for (int q = 0; q < o.cq; ++q) {
         const int i = o.panel[q];
         qOff[(size_t)q] = (int32_t)concat.size();
-        concat.insert(concat.end(), o.queries + o.queryOffsets[i], o.queries + o.queryOffsets[i + 1]);
-        tallest = std::max(tallest, (int)(o.queryOffsets[i + 1] - o.queryOffsets[i]));
+        concat.insert(concat.end(), o.side.residues + o.side.offsets[i], o.side.residues + o.side.offsets[i + 1]);
+        tallest = std::max(tallest, (int)(o.side.offsets[i + 1] - o.side.offsets[i]));
     }
     qOff[(size_t)o.cq] = (int32_t)concat.size();
-    Search s{o.db, ws, ws->stream, concat.data(), (int)concat.size(), o.open, o.ext, o.A, OPAL_SEARCH_ALIGNMENT, o.mode,
-             o.matrix, 0, o.db->count, o.total};
+    Search s{o.rq.db, ws, ws->stream, concat.data(), (int)concat.size(), o.rq.open, o.rq.ext, o.rq.A, OPAL_SEARCH_ALIGNMENT, o.rq.mode,
+             o.side.matrix, 0, o.rq.db->count, o.total};
     RC_TRY(s.prepare());
     RC_TRY(s.ensurePairInputs());
     void* pqoff;
     RC_TRY(ws->get(kPairListQOff, qOff.size() * sizeof(int32_t), &pqoff));
     RC_TRY(ws->stageUpload(pqoff, qOff.data(), qOff.size() * sizeof(int32_t), s.stream));
-    const OccurrenceGather gather = [&](int64_t c0, int nc, int64_t* targetOff, const int32_t** qBase) {
-        void* pqbase;
-        RC_TRY(ws->get(kPairListQBase, (size_t)nc * sizeof(int32_t), &pqbase));
-        HIP_TRY(launchBatchOccurrenceOrigins(nc, c0, o.target + c0, o.db->d_offsets, o.db->count, o.head, o.cq,
-                                             (const int32_t*)pqoff, targetOff, (int32_t*)pqbase, s.stream));
-        *qBase = (const int32_t*)pqbase;
-        return 0;
-    };
-    return alignOccurrenceChunks(s, o.total, *o.hits, o.score, o.row, o.column, tallest, operations, gather,
-                                 g_lastBatchOccurrenceAlignRouting, out);
+    const OccurrenceGather gather = panelOccurrenceGather(o, o.dHead, o.cq, (const int32_t*)pqoff);
+    return alignOccurrenceChunks(s, o.total, OccurrenceAlignJob{o.hits, o.slot, tallest, operations, &gather,
+                                                                g_lastBatchOccurrenceAlignRouting, out});
 }

@@ -12,19 +12,19 @@
 // the chunk's rows lie end to end, unpadded, where the sweeps read them (kPssmRows), and a run's table is a window of
 // them. Up per run: its consensus (one byte a row) and its PSSMs' row origins. Sub-chunks inside a run are sized as
 // the plain stage sizes them, from the run's tallest PSSM.
-static int alignPssmBatchOccurrencesStage(const BatchOccurrencesOnDevice& o, bool operations, OccurrenceAlignment* out) {
+static int alignPssmBatchOccurrencesStage(const PanelChunk& o, bool operations, OccurrenceAlignment* out) {
     Workspace* const ws = o.ws;
-    const int A = o.A;
-    auto rowsOf = [&](int q) { return (int)(o.queryOffsets[o.panel[q] + 1] - o.queryOffsets[o.panel[q]]); };
+    const int A = o.rq.A;
+    auto rowsOf = [&](int q) { return (int)(o.side.offsets[o.panel[q] + 1] - o.side.offsets[o.panel[q]]); };
     // the chunk's row origins (what the sweeps' upload used: the PSSMs end to end)
     std::vector<int64_t> origin((size_t)o.cq + 1, 0);
     for (int q = 0; q < o.cq; ++q) origin[(size_t)q + 1] = origin[(size_t)q] + rowsOf(q);
-    RC_TRY(allocOccurrenceAlignment(o.total, operations, out));
+    RC_TRY(out->reserve(o.total, operations));
     std::vector<unsigned char> consensus;
     std::vector<int> rows;
     std::vector<int32_t> qOff;
     for (int q0 = 0; q0 < o.cq;) {
-        if (o.hostHead[q0 + 1] == o.hostHead[q0]) {   // (no occurrences: not the start of a run)
+        if (o.head[q0 + 1] == o.head[q0]) {   // (no occurrences: not the start of a run)
             ++q0;
             continue;
         }
@@ -35,41 +35,33 @@ static int alignPssmBatchOccurrencesStage(const BatchOccurrencesOnDevice& o, boo
             tallest = std::max(tallest, rowsOf(q1));
             ++q1;
         }
-        const int64_t first = o.hostHead[q0], last = o.hostHead[q1];
+        const int64_t first = o.head[q0], last = o.head[q1];
         // the run's consensus, rows (the host's copy: what the stage reads of the scores there) and origins
         consensus.clear();
         rows.clear();
         qOff.assign((size_t)(q1 - q0) + 1, 0);
         for (int q = q0; q < q1; ++q) {
-            const int64_t r0 = o.queryOffsets[o.panel[q]], r1 = o.queryOffsets[o.panel[q] + 1];
+            const int64_t r0 = o.side.offsets[o.panel[q]], r1 = o.side.offsets[o.panel[q] + 1];
             qOff[(size_t)(q - q0)] = (int32_t)consensus.size();
-            consensus.insert(consensus.end(), o.queries + r0, o.queries + r1);
-            rows.insert(rows.end(), o.rowScores + (size_t)r0 * A, o.rowScores + (size_t)r1 * A);
+            consensus.insert(consensus.end(), o.side.residues + r0, o.side.residues + r1);
+            rows.insert(rows.end(), o.side.rowScores + (size_t)r0 * A, o.side.rowScores + (size_t)r1 * A);
         }
         qOff[(size_t)(q1 - q0)] = (int32_t)consensus.size();
-        Search s{o.db, ws, ws->stream, consensus.data(), (int)runRows, o.open, o.ext, A, OPAL_SEARCH_ALIGNMENT, o.mode,
-                 nullptr, 0, o.db->count, last - first};
+        Search s{o.rq.db, ws, ws->stream, consensus.data(), (int)runRows, o.rq.open, o.rq.ext, A, OPAL_SEARCH_ALIGNMENT, o.rq.mode,
+                 nullptr, 0, o.rq.db->count, last - first};
         s.pssmRows = rows.data();
         RC_TRY(s.prepare());
         void *pcons, *pqoff;
         RC_TRY(ws->get(kQuery, (size_t)runRows, &pcons));
         RC_TRY(ws->stageUpload(pcons, consensus.data(), (size_t)runRows, s.stream));
         s.d_query = (uint8_t*)pcons;   // (ensurePairInputs has nothing left to do)
-        s.d_rows = const_cast<int32_t*>(o.dRows) + (size_t)origin[(size_t)q0] * A;
+        s.d_rows = const_cast<int32_t*>(o.dScores) + (size_t)origin[(size_t)q0] * A;
         RC_TRY(ws->get(kPairListQOff, qOff.size() * sizeof(int32_t), &pqoff));
         RC_TRY(ws->stageUpload(pqoff, qOff.data(), qOff.size() * sizeof(int32_t), s.stream));
-        const int nq = q1 - q0;
-        const OccurrenceGather gather = [&](int64_t c0, int nc, int64_t* targetOff, const int32_t** qBase) {
-            void* pqbase;
-            RC_TRY(ws->get(kPairListQBase, (size_t)nc * sizeof(int32_t), &pqbase));
-            // (head[q0 ..] holds the chunk's positions: k0 = c0 is one of them, at or behind head[q0])
-            HIP_TRY(launchBatchOccurrenceOrigins(nc, c0, o.target + c0, o.db->d_offsets, o.db->count, o.head + q0, nq,
-                                                 (const int32_t*)pqoff, targetOff, (int32_t*)pqbase, s.stream));
-            *qBase = (const int32_t*)pqbase;
-            return 0;
-        };
-        RC_TRY(alignOccurrenceRange(s, first, last, *o.hits, o.score, o.row, o.column, tallest, operations, gather,
-                                    g_lastBatchOccurrenceAlignRouting, out));
+        // (head[q0 ..] holds the chunk's positions: a sub-chunk's first is one of them, at or behind head[q0])
+        const OccurrenceGather gather = panelOccurrenceGather(o, o.dHead + q0, q1 - q0, (const int32_t*)pqoff);
+        RC_TRY(alignOccurrenceRange(s, first, last, OccurrenceAlignJob{o.hits, o.slot, tallest, operations, &gather,
+                                                                       g_lastBatchOccurrenceAlignRouting, out}));
         q0 = q1;
     }
     return finishOccurrenceAlignment(o.total, operations, out);

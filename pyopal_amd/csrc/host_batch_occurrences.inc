@@ -19,16 +19,13 @@
 // the same routing, chunks, groups and splice. A chunk's PSSM rows go up once, end to end ([rows][A] ints, kPssmRows),
 // with one int per TABLE row that names its source row (-1: a pad row) where the plain form uploads the residue list;
 // the sweeps are occurrences_batch_pssm.hip's, the stage host_batch_occurrence_align_pssm.inc's. No matrix goes up.
-static int checkOccurrenceAlignOutputs(int** startTarget, int** startQuery, unsigned char** alignments,
-                                       int64_t** alignmentOffsets);   // (host.hip, with the entry points)
-
+// (A chunk goes through named steps, DESIGN 8p: plan, upload, count, bounds, write, stage.)
 namespace {
 
 thread_local int64_t g_lastBatchOccurrenceRouting[4] = {0, 0, 0, 0};   // miopalLastBatchOccurrenceRouting
 thread_local int64_t g_lastBatchOccurrenceGroups[3] = {0, 0, 0};       // miopalLastBatchOccurrenceGroups
 
-// queries of a chunk at most (every group holds at least one: the count sweep's grid has one row of workgroups per group)
-constexpr int64_t kBatchOccurrenceChunkQueries = 32768;
+static_assert(sizeof(OccurrenceMeta) == sizeof(int4) && alignof(OccurrenceMeta) <= alignof(int4), "the kernels read the meta array as int4");
 
 // entries of a chunk's count array at most: occurrences_batch.h's bound, or what the switch asks for
 int64_t batchOccurrenceEntries() {
@@ -49,16 +46,51 @@ int64_t batchOccurrenceWorkgroupsPerCu() {
     return kBatchOccurrenceWorkgroupsPerCu;
 }
 
-// The score source of a panel. Plain: `residues` / `offsets` are the queries, `matrix` [A][A], rowScores null. PSSM:
-// rowScores holds A ints per row, `offsets` delimits the PSSMs in rows, `residues` is the consensus (never null here:
-// a filler of 255s where the caller gave none) in the same row coordinates; matrix is null.
+// The panel: its score source and its lists. Plain: `residues` / `offsets` are the queries, `matrix` [A][A], rowScores
+// null. PSSM: rowScores holds A ints per row, `offsets` delimits the PSSMs in rows, `residues` is the consensus (never
+// null here: a filler of 255s where the caller gave none) in the same row coordinates; matrix is null.
 struct PanelSide {
     const unsigned char* residues;
     const int64_t* offsets;
+    int nQueries;
     const int* matrix;
     const int* rowScores;
+    const int *minScore, *window;
     bool pssm() const { return rowScores != nullptr; }
+    int rows(int i) const { return (int)(offsets[i + 1] - offsets[i]); }
+    const int* rowsOf(int i, int A) const { return pssm() ? rowScores + (size_t)offsets[i] * A : nullptr; }
 };
+
+// One chunk of panel queries on its way through the steps: panel[0 .. cq) of the call's list. A stage gets it behind
+// the write sweep and reads rq, side, ws, panel, cq, total, head / dHead, dScores, slot and hits; the rest is the sweeps'.
+struct PanelChunk {
+    const OccurrenceRequest& rq;
+    const PanelSide& side;
+    Workspace* ws;
+    const void* dMatrix;
+    const int* panel;
+    int cq;
+    const OccurrenceChunkPlan& plan;
+    int region = 0;
+    int64_t n = 0, N = 0;              // targets of the slice, entries of the count array
+    BatchOccurrenceArgs a{};
+    OccurrenceScratch sc{};
+    int64_t* dHead = nullptr;          // head[0 .. cq], total, listed (occurrences_batch.h)
+    int32_t* dFirst = nullptr;
+    const int32_t* dScores = nullptr;  // PSSM: the chunk's rows end to end
+    std::vector<int64_t> head;
+    int64_t total = 0, listed = 0;
+    OccurrenceOutSlot slot;            // the occurrences where the write sweep left them, `total` entries each,
+    const HitArrays* hits = nullptr;   // and on the host
+};
+
+}  // namespace
+
+// (the stages of the aligned calls, which take a chunk as it is)
+#include "host_batch_occurrence_align.inc"
+#include "host_batch_occurrence_align_pssm.inc"
+
+namespace {
 
 // where a query's occurrences lie until the CSR is put together; aligned (the aligned call): the starts of the piece
 // `from`, entry for entry, and its operations - those of the stretch are opsOff[first] .. opsOff[first + count]
@@ -68,426 +100,257 @@ struct OccurrenceStretch {
     const OccurrenceAlignment* aligned = nullptr;
 };
 
-// the aligned call: whether operations are asked for, and where the pieces' alignments are kept until the splice
-struct BatchOccurrenceAlign {
-    bool operations;
-    std::vector<std::unique_ptr<OccurrenceAlignment>> pieces;
+// What a panel call collects until the splice: per query of the list its count and its stretch; the pieces the stretches
+// point into (one per panel chunk or long query, with its alignment in the aligned call); the occurrences so far, and
+// whether they have passed maxHits - from then on everything is only counted.
+struct PanelPieces {
+    bool aligned, operations;
+    std::vector<int64_t> counts;
+    std::vector<OccurrenceStretch> stretch;
+    std::deque<HitArrays> hits;   // (deques: a new piece leaves the stretches' pointers to the others valid)
+    std::deque<OccurrenceAlignment> alignments;
+    int64_t running = 0;
+    bool over = false;
+    PanelPieces(int nQueries, const OccurrenceOutputs& out)
+        : aligned(out.aligned), operations(out.operations()), counts((size_t)nQueries, 0), stretch((size_t)nQueries) {}
+};
+
+// the sorted jobs of a chunk of the slice's targets (kSortedJobs), kept from one chunk of queries to the next
+struct SliceJobs {
+    int64_t of = -1;
+    void* sorted = nullptr;
 };
 
 }  // namespace
 
-// The panel queries `panel` (indices into the call's list, ascending, 1 .. 64 rows each), chunk by chunk. counts[i]
-// and stretch[i] are filled for every one of them; once *running passes maxHits (*over) the chunks are only counted.
-// `align` (null: the plain call): the alignment stage runs behind every write sweep, and never once *over is set.
-static int batchOccurrencePanel(MiopalDb* db, const PanelSide& side,
-                                const std::vector<int>& panel, int open, int ext, int A, int mode,
-                                int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
-                                int64_t* running, bool* over, std::vector<int64_t>* counts,
-                                std::vector<OccurrenceStretch>* stretch, std::vector<std::unique_ptr<HitArrays>>* pieces,
-                                BatchOccurrenceAlign* align) {
-    const int64_t n = end - start;
-    const int region = mode == OPAL_MODE_HW ? kLastRow : kAllCells;
-    const int64_t maxL = db->maxLen;
-    HIP_TRY(hipSetDevice(db->device));
-    WorkspaceLease lease(db);
-    RC_TRY(lease.acquireInternal());
-    Workspace* ws = lease.ws;
+// Upload: the plan's row list (plain) or row-source map and the chunk's PSSM rows end to end (PSSM), the entries of the
+// queries and groups; and the arguments both sweeps share.
+static int uploadPanelChunk(PanelChunk& c) {
+    Workspace* const ws = c.ws;
     hipStream_t stream = ws->stream;
-    const unsigned char* const queries = side.residues;
-    const int64_t* const queryOffsets = side.offsets;
-    const bool pssm = side.pssm();
-    void* pmatrix = nullptr;
-    if (!pssm) {
-        RC_TRY(ws->get(kMatrix, (size_t)A * A * sizeof(int32_t), &pmatrix));
-        RC_TRY(ws->stageUpload(pmatrix, side.matrix, (size_t)A * A * sizeof(int32_t), stream));
-    }
-
-    const int64_t perChunk = std::max<int64_t>(1, std::min<int64_t>(kBatchOccurrenceChunkQueries, batchOccurrenceEntries() / n));
-    // A group is as many consecutive queries as fit the LDS - unless that leaves the count sweep fewer than
-    // kBatchOccurrenceWorkgroupsPerCu workgroups per compute unit: then the queries are spread over more, smaller
-    // groups, down to one query a group (occurrences_batch.h: what that rests on). Few targets: the panel fills the GPU
-    // side by side. Many: the launch ends evenly.
-    const int64_t targetBlocks = (std::min<int64_t>(n, kPairChunkMax) + 255) / 256;
-    const int64_t perCu = batchOccurrenceWorkgroupsPerCu();
-    const int64_t wantGroups = std::max<int64_t>(1, (perCu * (int64_t)std::max(db->computeUnits, 1) + targetBlocks - 1) / targetBlocks);
-    int64_t jobsOf = -1;   // the chunk of targets whose sorted jobs kSortedJobs holds
-    void* psorted = nullptr;
-    for (size_t p0 = 0; p0 < panel.size(); p0 += (size_t)perChunk) {
-        const int cq = (int)std::min<int64_t>(perChunk, (int64_t)(panel.size() - p0));
-        const int64_t N = (int64_t)cq * n;
-        // the chunk's row list, its queries and its groups
-        // (PSSM panel: the chunk's rows end to end, unpadded, and per table row the row it holds)
-        std::vector<uint8_t> rowResidue;
-        std::vector<int32_t> rowSource;
+    const int A = c.rq.A, cq = c.cq;
+    const OccurrenceChunkPlan& plan = c.plan;
+    c.n = c.rq.end - c.rq.start;
+    c.N = (int64_t)cq * c.n;
+    c.region = c.rq.mode == OPAL_MODE_HW ? kLastRow : kAllCells;
+    void *prows, *pmeta, *pbounds, *pscratch;
+    BatchOccurrenceArgs& a = c.a;
+    if (c.side.pssm()) {
         std::vector<int> chunkRows;
-        std::vector<int4> meta;   // [cq] queries, then the groups
-        meta.reserve((size_t)cq + 16);
-        int tallest = 0;
-        for (int q = 0; q < cq; ++q) {
-            const int i = panel[p0 + (size_t)q];
-            const int Q = (int)(queryOffsets[i + 1] - queryOffsets[i]);
-            const size_t pad = (size_t)(batchOccurrenceRows(Q) - Q);
-            if (pssm) {
-                meta.push_back(make_int4((int)rowSource.size(), Q, minScore[i], window[i]));
-                const int32_t origin = (int32_t)(chunkRows.size() / (size_t)A);
-                for (int r = 0; r < Q; ++r) rowSource.push_back(origin + r);
-                rowSource.resize(rowSource.size() + pad, -1);
-                chunkRows.insert(chunkRows.end(), side.rowScores + (size_t)queryOffsets[i] * A,
-                                 side.rowScores + (size_t)queryOffsets[i + 1] * A);
-            } else {
-                meta.push_back(make_int4((int)rowResidue.size(), Q, minScore[i], window[i]));
-                rowResidue.insert(rowResidue.end(), queries + queryOffsets[i], queries + queryOffsets[i + 1]);
-                rowResidue.resize(rowResidue.size() + pad, (uint8_t)kBatchOccurrencePadRow);
-            }
-            tallest = std::max(tallest, batchOccurrenceRows(Q));
-        }
-        const int64_t perGroup = std::max<int64_t>(1, (cq + wantGroups - 1) / wantGroups);
-        int groups = 0;
-        int64_t widest = 0;
-        for (int q = 0; q < cq;) {
-            int e = q;
-            int64_t rows = 0;
-            while (e < cq && e - q < perGroup &&
-                   batchOccurrenceLdsBytes(rows + batchOccurrenceRows(meta[(size_t)e].y), A) <= kCuLdsBytes) {
-                rows += batchOccurrenceRows(meta[(size_t)e].y);
-                ++e;
-            }
-            meta.push_back(make_int4(q, e - q, meta[(size_t)q].x, (int)rows));
-            g_lastBatchOccurrenceGroups[1] = std::max<int64_t>(g_lastBatchOccurrenceGroups[1], e - q);
-            widest = std::max(widest, rows);
-            ++groups;
-            q = e;
-        }
-        g_lastBatchOccurrenceGroups[0] += groups;
-        g_lastBatchOccurrenceGroups[2] = std::max<int64_t>(g_lastBatchOccurrenceGroups[2], (int64_t)batchOccurrenceLdsBytes(widest, A));
-        void *prows, *pmeta, *pbounds, *pscratch, *pscores = nullptr;
-        if (pssm) {
-            RC_TRY(ws->get(kBatchOccurrenceRowSource, rowSource.size() * sizeof(int32_t), &prows));
-            RC_TRY(ws->get(kPssmRows, chunkRows.size() * sizeof(int32_t), &pscores));
-        } else {
-            RC_TRY(ws->get(kQuery, rowResidue.size(), &prows));
-        }
-        RC_TRY(ws->get(kBatchOccurrenceMeta, meta.size() * sizeof(int4), &pmeta));
-        RC_TRY(ws->get(kBatchOccurrenceBounds, ((size_t)cq + 3) * sizeof(int64_t) + ((size_t)cq + 1) * sizeof(int32_t), &pbounds));
-        RC_TRY(ws->get(kOccurrenceScratch, occurrenceScratchBytes(N), &pscratch));
-        if (pssm) {
-            RC_TRY(ws->stageUpload(prows, rowSource.data(), rowSource.size() * sizeof(int32_t), stream));
-            RC_TRY(ws->stageUpload(pscores, chunkRows.data(), chunkRows.size() * sizeof(int32_t), stream));
-        } else {
-            RC_TRY(ws->stageUpload(prows, rowResidue.data(), rowResidue.size(), stream));
-        }
-        RC_TRY(ws->stageUpload(pmeta, meta.data(), meta.size() * sizeof(int4), stream));
-        const OccurrenceScratch sc = occurrenceScratchLayout(pscratch, N);
-        int64_t* dHead = (int64_t*)pbounds;
-        int32_t* dFirst = (int32_t*)(dHead + cq + 3);
-        BatchOccurrenceArgs a{};
-        a.residues = db->d_residues;
-        if (pssm) a.rowSource = (const int32_t*)prows;
-        else a.rowResidue = (const uint8_t*)prows;
-        a.query = (const int4*)pmeta;
-        a.group = a.query + cq;
-        a.nQueries = cq;
-        if (pssm) a.rows = (const int32_t*)pscores;
-        else a.matrix = (const int32_t*)pmatrix;
-        a.alphabet = A;
-        a.gapOpen = open;
-        a.gapExt = ext;
-        a.n = n;
-        a.count = sc.count;
-        a.start = start;
-        // the count sweep: every target of the slice, in chunks of jobs sorted by length
-        for (int64_t c0 = 0; c0 < n; c0 += kPairChunkMax) {
-            const int nc = (int)std::min<int64_t>(kPairChunkMax, n - c0);
-            if (jobsOf != c0) {
-                void *pjobs, *pbins;
-                RC_TRY(ws->get(kJobs, (size_t)nc * sizeof(PairJob), &pjobs));
-                RC_TRY(ws->get(kSortedJobs, (size_t)nc * sizeof(PairJob), &psorted));
-                RC_TRY(ws->get(kSortBins, (size_t)8192 * sizeof(int), &pbins));
-                HIP_TRY(launchOccurrenceJobs(nullptr, c0, nc, start, db->d_offsets, 0, (PairJob*)pjobs, stream));
-                HIP_TRY(launchSortJobsByLength((const PairJob*)pjobs, nc, (int)maxL, (int*)pbins, (PairJob*)psorted, stream));
-                jobsOf = c0;
-            }
-            a.jobs = (const PairJob*)psorted;
-            a.nJobs = nc;
-            const hipError_t e = (pssm ? launchBatchOccurrencesCountPssm : launchBatchOccurrencesCount)(
-                a, region, groups, batchOccurrenceLdsBytes(widest, A), stream);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(MIOPAL_ERR_HIP, "panel occurrence sweep launch (count): %s", hipGetErrorString(e));
-            }
-        }
-        {
-            hipError_t e = launchOccurrencesOffsets(sc, N, stream);
-            if (e == hipSuccess) e = launchBatchOccurrencesBounds(sc, n, cq, dFirst, dHead, stream);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(MIOPAL_ERR_HIP, "panel occurrence offsets launch: %s", hipGetErrorString(e));
-            }
-        }
-        std::vector<int64_t> head((size_t)cq + 3, 0);
-        RC_TRY(ws->stageDownload(head.data(), dHead, sizeof(int64_t) * head.size()));
-        RC_TRY(ws->finishDownloads());
-        const int64_t total = head[(size_t)cq + 1], listed = head[(size_t)cq + 2];
-        bool sane = head[0] == 0 && head[(size_t)cq] == total && total >= 0 && listed >= 0 && listed <= N && listed <= total;
-        for (int q = 0; q < cq && sane; ++q) sane = head[(size_t)q + 1] >= head[(size_t)q];
-        if (!sane) return fail(MIOPAL_ERR_INTERNAL, "panel occurrence counts: total %lld in %lld pairs", (long long)total, (long long)listed);
-        g_lastBatchOccurrenceRouting[2] += 1;
-        *running += total;
-        if (maxHits >= 0 && *running > maxHits) *over = true;
-        for (int q = 0; q < cq; ++q) (*counts)[(size_t)panel[p0 + (size_t)q]] = head[(size_t)q + 1] - head[(size_t)q];
-        if (*over || total == 0) continue;
-        // the write sweep over the listed pairs, and the chunk's occurrences
-        pieces->emplace_back(new HitArrays());
-        HitArrays& hits = *pieces->back();
-        RC_TRY(hits.alloc(total, true));
-        const HitsOutSlot slot(total, true);
-        void* po;
-        RC_TRY(ws->get(kOccurrenceOut, slot.bytes, &po));
-        char* base = (char*)po;
-        a.count = nullptr;
-        a.offsets = sc.offsets;
-        a.list = sc.list;
-        a.first = dFirst;
-        a.dbOffsets = db->d_offsets;
-        a.outTarget = (int64_t*)base;
-        a.outScore = (int32_t*)(base + slot.offScore);
-        a.outRow = (int32_t*)(base + slot.offEndQ);
-        a.outColumn = (int32_t*)(base + slot.offEndT);
-        {
-            const hipError_t e = (pssm ? launchBatchOccurrencesWritePssm : launchBatchOccurrencesWrite)(
-                a, region, listed, batchOccurrenceLdsBytes(tallest, A), stream);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(MIOPAL_ERR_HIP, "panel occurrence sweep launch (write): %s", hipGetErrorString(e));
-            }
-        }
-        g_lastBatchOccurrenceRouting[3] += listed;
-        RC_TRY(ws->stageDownload(hits.target, a.outTarget, sizeof(int64_t) * (size_t)total));
-        RC_TRY(ws->stageDownload(hits.score, a.outScore, sizeof(int) * (size_t)total));
-        RC_TRY(ws->stageDownload(hits.endQ, a.outRow, sizeof(int) * (size_t)total));
-        RC_TRY(ws->stageDownload(hits.endT, a.outColumn, sizeof(int) * (size_t)total));
-        RC_TRY(ws->finishDownloads());
-        const OccurrenceAlignment* aligned = nullptr;
-        if (align) {
-            // the stage, on the occurrences where they are (head[0 .. cq] still lies behind dHead). It takes kJobs,
-            // kSortedJobs and kSortBins: the next chunk's count sweep builds the slice's sorted jobs again.
-            align->pieces.emplace_back(new OccurrenceAlignment());
-            // (PSSM panel: the chunk's rows stay where they are, kPssmRows, and the stage reads them there)
-            const BatchOccurrencesOnDevice on{db, ws, queries, queryOffsets, panel.data() + p0, cq, open, ext, side.matrix, A,
-                                              mode, total, a.outTarget, a.outScore, a.outRow, a.outColumn, dHead, &hits,
-                                              side.rowScores, (const int32_t*)pscores, head.data()};
-            RC_TRY((pssm ? alignPssmBatchOccurrencesStage : alignBatchOccurrencesStage)(on, align->operations,
-                                                                                        align->pieces.back().get()));
-            aligned = align->pieces.back().get();
-            jobsOf = -1;
-            psorted = nullptr;
-        }
         for (int q = 0; q < cq; ++q)
-            (*stretch)[(size_t)panel[p0 + (size_t)q]] =
-                OccurrenceStretch{&hits, head[(size_t)q], head[(size_t)q + 1] - head[(size_t)q], aligned};
+            chunkRows.insert(chunkRows.end(), c.side.rowsOf(c.panel[q], A), c.side.rowsOf(c.panel[q] + 1, A));
+        void* pscores;
+        RC_TRY(ws->get(kBatchOccurrenceRowSource, plan.rowSource.size() * sizeof(int32_t), &prows));
+        RC_TRY(ws->get(kPssmRows, chunkRows.size() * sizeof(int32_t), &pscores));
+        RC_TRY(ws->stageUpload(prows, plan.rowSource.data(), plan.rowSource.size() * sizeof(int32_t), stream));
+        RC_TRY(ws->stageUpload(pscores, chunkRows.data(), chunkRows.size() * sizeof(int32_t), stream));
+        a.rowSource = (const int32_t*)prows;
+        a.rows = c.dScores = (const int32_t*)pscores;
+    } else {
+        RC_TRY(ws->get(kQuery, plan.rowResidue.size(), &prows));
+        RC_TRY(ws->stageUpload(prows, plan.rowResidue.data(), plan.rowResidue.size(), stream));
+        a.rowResidue = (const uint8_t*)prows;
+        a.matrix = (const int32_t*)c.dMatrix;
+    }
+    RC_TRY(ws->get(kBatchOccurrenceMeta, plan.meta.size() * sizeof(OccurrenceMeta), &pmeta));
+    RC_TRY(ws->get(kBatchOccurrenceBounds, ((size_t)cq + 3) * sizeof(int64_t) + ((size_t)cq + 1) * sizeof(int32_t), &pbounds));
+    RC_TRY(ws->get(kOccurrenceScratch, occurrenceScratchBytes(c.N), &pscratch));
+    RC_TRY(ws->stageUpload(pmeta, plan.meta.data(), plan.meta.size() * sizeof(OccurrenceMeta), stream));
+    c.sc = occurrenceScratchLayout(pscratch, c.N);
+    c.dHead = (int64_t*)pbounds;
+    c.dFirst = (int32_t*)(c.dHead + cq + 3);
+    a.residues = c.rq.db->d_residues;
+    a.query = (const int4*)pmeta;
+    a.group = a.query + cq;
+    a.nQueries = cq;
+    a.alphabet = A;
+    a.gapOpen = c.rq.open;
+    a.gapExt = c.rq.ext;
+    a.n = c.n;
+    a.count = c.sc.count;
+    a.start = c.rq.start;
+    return 0;
+}
+
+// The count sweep: every target of the slice, in chunks of jobs sorted by length
+static int countPanelChunk(PanelChunk& c, SliceJobs& jobs) {
+    Workspace* const ws = c.ws;
+    MiopalDb* const db = c.rq.db;
+    const bool pssm = c.side.pssm();
+    for (int64_t c0 = 0; c0 < c.n; c0 += kPairChunkMax) {
+        const int nc = (int)std::min<int64_t>(kPairChunkMax, c.n - c0);
+        if (jobs.of != c0) {
+            void *pjobs, *pbins;
+            RC_TRY(ws->get(kJobs, (size_t)nc * sizeof(PairJob), &pjobs));
+            RC_TRY(ws->get(kSortedJobs, (size_t)nc * sizeof(PairJob), &jobs.sorted));
+            RC_TRY(ws->get(kSortBins, (size_t)8192 * sizeof(int), &pbins));
+            HIP_TRY(launchOccurrenceJobs(nullptr, c0, nc, c.rq.start, db->d_offsets, 0, (PairJob*)pjobs, ws->stream));
+            HIP_TRY(launchSortJobsByLength((const PairJob*)pjobs, nc, (int)db->maxLen, (int*)pbins, (PairJob*)jobs.sorted, ws->stream));
+            jobs.of = c0;
+        }
+        c.a.jobs = (const PairJob*)jobs.sorted;
+        c.a.nJobs = nc;
+        RC_TRY(launched((pssm ? launchBatchOccurrencesCountPssm : launchBatchOccurrencesCount)(
+                            c.a, c.region, c.plan.groups, batchOccurrenceLdsBytes(c.plan.widest, c.rq.A), ws->stream),
+                        "panel occurrence sweep launch (count)"));
     }
     return 0;
 }
 
-static int batchOccurrencesCore(MiopalDb* db, const PanelSide& side, int nQueries, int open, int ext, int A, int mode,
-                                int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
-                                int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery,
-                                bool wantAligned, int** startTarget, int** startQuery, unsigned char** alignments,
-                                int64_t** alignmentOffsets);
-
-// what the reporters of the panel occurrence searches say starts over with every call, plain or PSSM
-static void resetBatchOccurrenceReports(bool wantAligned) {
-    for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceRouting[k] = 0;
-    for (int k = 0; k < 3; ++k) g_lastBatchOccurrenceGroups[k] = 0;
-    if (wantAligned)
-        for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceAlignRouting[k] = 0;
+// The scan of the counts and the bounds, one small download - every query's offset and the totals - and its sanity check
+static int boundsOfPanelChunk(PanelChunk& c) {
+    Workspace* const ws = c.ws;
+    const int cq = c.cq;
+    hipError_t e = launchOccurrencesOffsets(c.sc, c.N, ws->stream);
+    if (e == hipSuccess) e = launchBatchOccurrencesBounds(c.sc, c.n, cq, c.dFirst, c.dHead, ws->stream);
+    RC_TRY(launched(e, "panel occurrence offsets launch"));
+    std::vector<int64_t>& head = c.head;
+    head.assign((size_t)cq + 3, 0);
+    RC_TRY(ws->stageDownload(head.data(), c.dHead, sizeof(int64_t) * head.size()));
+    RC_TRY(ws->finishDownloads());
+    const int64_t total = c.total = head[(size_t)cq + 1], listed = c.listed = head[(size_t)cq + 2];
+    bool sane = head[0] == 0 && head[(size_t)cq] == total && total >= 0 && listed >= 0 && listed <= c.N && listed <= total;
+    for (int q = 0; q < cq && sane; ++q) sane = head[(size_t)q + 1] >= head[(size_t)q];
+    if (!sane) return fail(MIOPAL_ERR_INTERNAL, "panel occurrence counts: total %lld in %lld pairs", (long long)total, (long long)listed);
+    return 0;
 }
 
-// Behind nothing: the checks of miopalSearchOccurrences over the whole list, in its order, come first.
-// wantAligned: miopalSearchBatchOccurrencesAligned - the four outputs behind endQuery are checked and written too.
-static int searchBatchOccurrencesImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries,
-                                      int open, int ext, const int* matrix, int A, int mode, int64_t start, int64_t end,
-                                      const int* minScore, const int* window, int64_t maxHits, int64_t* hitOffsets,
-                                      int64_t** targetIndex, int** score, int** endTarget, int** endQuery,
-                                      bool wantAligned = false, int** startTarget = nullptr, int** startQuery = nullptr,
-                                      unsigned char** alignments = nullptr, int64_t** alignmentOffsets = nullptr) {
-    resetBatchOccurrenceReports(wantAligned);
-    RC_TRY(validateBatch(db, queries, queryOffsets, nQueries, matrix, A, OPAL_SEARCH_SCORE_END, mode, start, end));
-    if (mode != OPAL_MODE_HW && mode != OPAL_MODE_SW)
-        return fail(OPAL_ERR_INVALID_MODE, "occurrences are defined for OPAL_MODE_HW and OPAL_MODE_SW, not for mode %d", mode);
-    if (window)
-        for (int i = 0; i < nQueries; ++i)
-            if (window[i] < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "negative window %d at query %d", window[i], i);
-    if (minScore && mode == OPAL_MODE_SW)
-        for (int i = 0; i < nQueries; ++i)
-            if (minScore[i] < 1)
-                return fail(MIOPAL_ERR_BAD_ARGUMENT, "minScore = %d at query %d: OPAL_MODE_SW needs a cut of at least 1", minScore[i], i);
-    if (nQueries > 0 && (!minScore || !window)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null minScore / window list");
-    RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, hitOffsets, targetIndex, score, endTarget, endQuery));
-    if (wantAligned) RC_TRY(checkOccurrenceAlignOutputs(startTarget, startQuery, alignments, alignmentOffsets));
-    return batchOccurrencesCore(db, PanelSide{queries, queryOffsets, matrix, nullptr}, nQueries, open, ext, A, mode, start, end,
-                                minScore, window, maxHits, hitOffsets, targetIndex, score, endTarget, endQuery, wantAligned,
-                                startTarget, startQuery, alignments, alignmentOffsets);
+// The write sweep over the listed pairs, and the chunk's occurrences down into `hits`
+static int writePanelChunk(PanelChunk& c, HitArrays* hits) {
+    Workspace* const ws = c.ws;
+    RC_TRY(hits->alloc(c.total, true));
+    RC_TRY(c.slot.get(ws, c.total));
+    BatchOccurrenceArgs& a = c.a;
+    a.count = nullptr;
+    a.offsets = c.sc.offsets;
+    a.list = c.sc.list;
+    a.first = c.dFirst;
+    a.dbOffsets = c.rq.db->d_offsets;
+    a.outTarget = c.slot.target;
+    a.outScore = c.slot.score;
+    a.outRow = c.slot.row;
+    a.outColumn = c.slot.column;
+    RC_TRY(launched((c.side.pssm() ? launchBatchOccurrencesWritePssm : launchBatchOccurrencesWrite)(
+                        a, c.region, c.listed, batchOccurrenceLdsBytes(c.plan.tallest, c.rq.A), ws->stream),
+                    "panel occurrence sweep launch (write)"));
+    c.hits = hits;
+    return c.slot.download(ws, c.total, hits);
 }
 
-// miopalSearchPssmBatchOccurrences(Aligned): what needs no handle first, in the single PSSM calls' order with the plain
-// panel's per-query checks among it, then the handle and what depends on it; the range check of every PSSM, with the
-// extreme entries of its own rows, is the core's.
-static int searchPssmBatchOccurrencesImpl(MiopalDb* db, const int* rowScores, const unsigned char* consensus,
-                                          const int64_t* rowOffsets, int nPssms, int open, int ext, int A, int mode,
-                                          int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
-                                          int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget,
-                                          int** endQuery, bool wantAligned, int** startTarget, int** startQuery,
-                                          unsigned char** alignments, int64_t** alignmentOffsets) {
-    resetBatchOccurrenceReports(wantAligned);
-    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
-    if (mode != OPAL_MODE_HW && mode != OPAL_MODE_SW)
-        return fail(OPAL_ERR_INVALID_MODE, "occurrences are defined for OPAL_MODE_HW and OPAL_MODE_SW, not for mode %d", mode);
-    if (nPssms < 0 || (nPssms > 0 && !rowOffsets)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad PSSM list");
-    for (int m = 0; m < nPssms; ++m)
-        if (rowOffsets[m] < 0 || rowOffsets[m + 1] < rowOffsets[m]) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad row offsets at %d", m);
-    const int64_t first = nPssms > 0 ? rowOffsets[0] : 0, totalRows = nPssms > 0 ? rowOffsets[nPssms] - first : 0;
-    if (totalRows > INT32_MAX - 64) return fail(MIOPAL_ERR_BAD_ARGUMENT, "the PSSMs of a panel hold 2^31 - 65 rows at most");
-    if (totalRows > 0 && !rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
-    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
-    if (window)
-        for (int i = 0; i < nPssms; ++i)
-            if (window[i] < 0) return fail(MIOPAL_ERR_BAD_ARGUMENT, "negative window %d at PSSM %d", window[i], i);
-    if (minScore && mode == OPAL_MODE_SW)
-        for (int i = 0; i < nPssms; ++i)
-            if (minScore[i] < 1)
-                return fail(MIOPAL_ERR_BAD_ARGUMENT, "minScore = %d at PSSM %d: OPAL_MODE_SW needs a cut of at least 1", minScore[i], i);
-    if (nPssms > 0 && (!minScore || !window)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null minScore / window list");
-    RC_TRY(checkHitsOutputs(OPAL_SEARCH_SCORE_END, hitOffsets, targetIndex, score, endTarget, endQuery));
-    if (wantAligned) {
-        RC_TRY(checkOccurrenceAlignOutputs(startTarget, startQuery, alignments, alignmentOffsets));
-        if (alignments && totalRows > 0 && !consensus) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null consensus for an alignment search");
-        if (consensus)
-            for (int64_t i = first; i < first + totalRows; ++i)
-                if (consensus[i] >= A && consensus[i] != 255)
-                    return fail(MIOPAL_ERR_BAD_ARGUMENT, "consensus residue %d out of range at %lld", consensus[i], (long long)i);
+// The panel queries `panel` (indices into the call's list, ascending, 1 .. 64 rows each), chunk by chunk. counts[i]
+// and stretch[i] of `got` are filled for every one of them; once got->running passes maxHits (got->over) the chunks are
+// only counted. The aligned call: the alignment stage runs behind every write sweep, and never once `over` is set.
+static int batchOccurrencePanel(const OccurrenceRequest& rq, const PanelSide& side, const std::vector<int>& panel, PanelPieces* got) {
+    MiopalDb* const db = rq.db;
+    const int64_t n = rq.end - rq.start;
+    HIP_TRY(hipSetDevice(db->device));
+    WorkspaceLease lease(db);
+    RC_TRY(lease.acquireInternal());
+    Workspace* ws = lease.ws;
+    void* pmatrix = nullptr;
+    if (!side.pssm()) {
+        RC_TRY(ws->get(kMatrix, (size_t)rq.A * rq.A * sizeof(int32_t), &pmatrix));
+        RC_TRY(ws->stageUpload(pmatrix, side.matrix, (size_t)rq.A * rq.A * sizeof(int32_t), ws->stream));
     }
-    // (a PSSM of more than 64 rows takes the single sweep, which keeps its rows in LDS)
-    for (int i = 0; i < nPssms; ++i) {
-        const int64_t Q = rowOffsets[i + 1] - rowOffsets[i];
-        if (Q > kLanes && (Q > INT32_MAX || perPairPssmBytes((int)Q, A) == 0))
-            return fail(MIOPAL_ERR_BAD_ARGUMENT, "PSSM %d of the panel: a PSSM of %lld rows at %d letters does not fit the occurrence "
-                        "sweep's LDS table: (rows + 1) x (letters + 1) x 4 bytes within 64 KB less 256, %d rows at most", i,
-                        (long long)Q, A, (64 * 1024 - 256) / (4 * (A + 1)) - 1);
+    const int64_t perChunk = occurrenceChunkQueries(batchOccurrenceEntries(), n);
+    const int64_t wantGroups = occurrenceWantGroups(n, kPairChunkMax, batchOccurrenceWorkgroupsPerCu(), db->computeUnits);
+    OccurrenceChunkPlan plan;
+    SliceJobs jobs;
+    size_t p0 = 0;
+    for (const int cq : occurrenceChunkSizes(perChunk, panel.size())) {
+        planOccurrenceChunk(side.pssm() ? nullptr : side.residues, side.offsets, side.minScore, side.window, panel.data() + p0, cq,
+                            rq.A, wantGroups, (int64_t)kCuLdsBytes, &plan);
+        g_lastBatchOccurrenceGroups[0] += plan.groups;
+        g_lastBatchOccurrenceGroups[1] = std::max(g_lastBatchOccurrenceGroups[1], plan.mostQueries);
+        g_lastBatchOccurrenceGroups[2] = std::max<int64_t>(g_lastBatchOccurrenceGroups[2], (int64_t)batchOccurrenceLdsBytes(plan.widest, rq.A));
+        PanelChunk c{rq, side, ws, pmatrix, panel.data() + p0, cq, plan};
+        p0 += (size_t)cq;
+        RC_TRY(uploadPanelChunk(c));
+        RC_TRY(countPanelChunk(c, jobs));
+        RC_TRY(boundsOfPanelChunk(c));
+        g_lastBatchOccurrenceRouting[2] += 1;
+        got->running += c.total;
+        if (rq.maxHits >= 0 && got->running > rq.maxHits) got->over = true;
+        for (int q = 0; q < cq; ++q) got->counts[(size_t)c.panel[q]] = c.head[(size_t)q + 1] - c.head[(size_t)q];
+        if (got->over || c.total == 0) continue;
+        HitArrays& hits = got->hits.emplace_back();
+        RC_TRY(writePanelChunk(c, &hits));
+        g_lastBatchOccurrenceRouting[3] += c.listed;
+        OccurrenceAlignment* aligned = nullptr;
+        if (got->aligned) {
+            // the stage, on the occurrences where they are (head[0 .. cq] still lies behind dHead; a PSSM panel's rows stay
+            // in kPssmRows). It takes kJobs, kSortedJobs and kSortBins: the next count sweep sorts the slice's jobs again.
+            aligned = &got->alignments.emplace_back();
+            jobs = SliceJobs{};
+            RC_TRY((side.pssm() ? alignPssmBatchOccurrencesStage : alignBatchOccurrencesStage)(c, got->operations, aligned));
+        }
+        for (int q = 0; q < cq; ++q)
+            got->stretch[(size_t)c.panel[q]] = OccurrenceStretch{&hits, c.head[(size_t)q], c.head[(size_t)q + 1] - c.head[(size_t)q], aligned};
     }
-    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
-    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
-    if (start < 0 || end < start || end > db->count) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)start, (long long)end);
-    // (without a consensus - the plain form, starts only - every position is "no residue": the kernels never read it)
-    std::vector<unsigned char> none;
-    if (!wantAligned || !consensus) {
-        none.assign((size_t)(first + std::max<int64_t>(totalRows, 1)), 255);   // (indexed in the offsets' coordinates)
-        consensus = none.data();
+    return 0;
+}
+
+// The long queries: the single-query search, its refusals (the strip workspace) what they are. Its sweeps count into a
+// scratch array (miopalLastOccurrenceRouting belongs to the thread's last single-query CALL), its stage into the panel's
+// reporter. Once the bound is passed (`over`) the later ones still run their count sweeps, with no room: hitOffsets is
+// filled for every query also when there are too many hits, and nothing is written or downloaded for them.
+static int batchOccurrenceLongQueries(const OccurrenceRequest& rq, const PanelSide& side, const std::vector<int>& single, PanelPieces* got) {
+    int64_t routing[4];
+    for (int i : single) {
+        int64_t found = 0;
+        OccurrenceRequest one = rq;
+        one.maxHits = got->over ? 0 : rq.maxHits < 0 ? -1 : rq.maxHits - got->running;
+        HitArrays& hits = got->hits.emplace_back();
+        // (aligned: the single-query stage behind its write sweep - it does not run when the bound is passed)
+        OccurrenceAlignment* const aligned = got->aligned ? &got->alignments.emplace_back() : nullptr;
+        const OccurrenceStage stage = [&](const OccurrencesOnDevice& o) {
+            return alignOccurrencesStage(o, got->operations, g_lastBatchOccurrenceAlignRouting, aligned);
+        };
+        const OccurrenceQuery q{side.residues + side.offsets[i], side.rows(i), side.matrix, side.rowsOf(i, rq.A), side.minScore[i], side.window[i]};
+        const int rc = searchOccurrencesImpl(one, q, &found, &hits, got->aligned ? &stage : nullptr, routing);
+        if (rc == MIOPAL_ERR_TOO_MANY_HITS) got->over = true;
+        else if (rc) return rc;
+        got->counts[(size_t)i] = found;
+        got->running += found;
+        if (!got->over) got->stretch[(size_t)i] = OccurrenceStretch{&hits, 0, found, found > 0 ? aligned : nullptr};
     }
-    static const int64_t kNoPssms[1] = {0};
-    static const int kNoPanelRows[1] = {0};   // (no rows: the score source still says "position-specific")
-    return batchOccurrencesCore(db, PanelSide{consensus, nPssms > 0 ? rowOffsets : kNoPssms, nullptr, totalRows > 0 ? rowScores : kNoPanelRows},
-                                nPssms, open, ext, A, mode, start, end, minScore, window, maxHits, hitOffsets, targetIndex, score,
-                                endTarget, endQuery, wantAligned, startTarget, startQuery, alignments, alignmentOffsets);
+    return 0;
 }
 
 // Behind the checks of either form: the range check of every query, the routing, the pieces and the splice.
-static int batchOccurrencesCore(MiopalDb* db, const PanelSide& side, int nQueries, int open, int ext, int A, int mode,
-                                int64_t start, int64_t end, const int* minScore, const int* window, int64_t maxHits,
-                                int64_t* hitOffsets, int64_t** targetIndex, int** score, int** endTarget, int** endQuery,
-                                bool wantAligned, int** startTarget, int** startQuery, unsigned char** alignments,
-                                int64_t** alignmentOffsets) {
-    const unsigned char* const queries = side.residues;
-    const int64_t* const queryOffsets = side.offsets;
-    const int* const matrix = side.matrix;
-    const bool operations = wantAligned && alignments != nullptr;
-    BatchOccurrenceAlign alignState{operations, {}};
-    BatchOccurrenceAlign* const align = wantAligned ? &alignState : nullptr;
-    const int64_t n = end - start;
-    std::vector<int64_t> counts((size_t)nQueries, 0);
-    std::vector<OccurrenceStretch> stretch((size_t)nQueries);
-    std::vector<std::unique_ptr<HitArrays>> pieces;
-    int64_t running = 0;
-    bool over = false;
-    if (n > 0 && nQueries > 0) {
+static int batchOccurrencesCore(const OccurrenceRequest& rq, const PanelSide& side, const OccurrenceOutputs& out) {
+    MiopalDb* const db = rq.db;
+    const int nQueries = side.nQueries, A = rq.A;
+    PanelPieces got(nQueries, out);
+    if (rq.end > rq.start && nQueries > 0) {
         // miopalSearch's range check (32-bit arithmetic only), for every query before any device work (a PSSM: with
         // the extreme entries of its own rows)
-        ScoreModel model{open, ext, 0, 0};
-        if (!side.pssm()) scoreExtremes(matrix, (size_t)A * A, &model.maxScore, &model.minScore);
+        ScoreModel model{rq.open, rq.ext, 0, 0};
+        if (!side.pssm()) scoreExtremes(side.matrix, (size_t)A * A, &model.maxScore, &model.minScore);
         std::vector<int> panel, single;
         for (int i = 0; i < nQueries; ++i) {
-            const int Q = (int)(queryOffsets[i + 1] - queryOffsets[i]);
-            if (side.pssm()) RC_TRY(checkPssmRange(db, side.rowScores + (size_t)queryOffsets[i] * A, Q, A, open, ext));
+            const int Q = side.rows(i);
+            if (side.pssm()) RC_TRY(checkPssmRange(db, side.rowsOf(i, A), Q, A, rq.open, rq.ext));
             else RC_TRY(checkInt32Range(model, Q, db->maxLen));
             if (Q > kLanes) single.push_back(i);
             else if (Q > 0) panel.push_back(i);
         }
         g_lastBatchOccurrenceRouting[0] = (int64_t)panel.size();
         g_lastBatchOccurrenceRouting[1] = (int64_t)single.size();
-        // The long queries: the single-query search, its refusals (the strip workspace) what they are. What
-        // miopalLastOccurrenceRouting reports belongs to the thread's last single-query CALL: it is put back behind them.
-        // Once the bound is passed (`over`) the later ones still run their count sweeps, with no room: hitOffsets is
-        // filled for every query also when there are too many hits, and nothing is written or downloaded for them.
-        int64_t singleRouting[4];
-        for (int k = 0; k < 4; ++k) singleRouting[k] = g_lastOccurrenceRouting[k];
-        // (the same for what miopalLastOccurrenceAlignRouting reports, which a long query's stage counts in)
-        int64_t singleAlignRouting[4];
-        for (int k = 0; k < 4; ++k) singleAlignRouting[k] = g_lastOccurrenceAlignRouting[k];
-        struct PutBack {
-            const int64_t *saved, *savedAlign;
-            ~PutBack() {
-                for (int k = 0; k < 4; ++k) g_lastOccurrenceRouting[k] = saved[k];
-                for (int k = 0; k < 4; ++k) g_lastOccurrenceAlignRouting[k] = savedAlign[k];
-            }
-        } putBack{singleRouting, singleAlignRouting};
-        for (int i : single) {
-            int64_t found = 0;
-            const int64_t room = over ? 0 : maxHits < 0 ? -1 : maxHits - running;
-            pieces.emplace_back(new HitArrays());
-            HitArrays& hits = *pieces.back();
-            // (aligned: the single-query stage behind its write sweep - it does not run when the bound is passed)
-            OccurrenceAlignment* got = nullptr;
-            if (align) {
-                align->pieces.emplace_back(new OccurrenceAlignment());
-                got = align->pieces.back().get();
-                for (int k = 0; k < 4; ++k) g_lastOccurrenceAlignRouting[k] = 0;
-            }
-            const OccurrenceStage stage = [&](const OccurrencesOnDevice& o) { return alignOccurrencesStage(o, operations, got); };
-            const int rc = searchOccurrencesImpl(db, queries + queryOffsets[i], (int)(queryOffsets[i + 1] - queryOffsets[i]), open,
-                                                 ext, matrix, side.pssm() ? side.rowScores + (size_t)queryOffsets[i] * A : nullptr, A,
-                                                 mode, start, end, minScore[i], window[i], room, &found,
-                                                 &hits.target, &hits.score, &hits.endT, &hits.endQ, align ? &stage : nullptr);
-            if (rc == MIOPAL_ERR_TOO_MANY_HITS) over = true;
-            else if (rc) return rc;
-            if (align) {
-                for (int k = 0; k < 3; ++k) g_lastBatchOccurrenceAlignRouting[k] += g_lastOccurrenceAlignRouting[k];
-                g_lastBatchOccurrenceAlignRouting[3] = std::max(g_lastBatchOccurrenceAlignRouting[3], g_lastOccurrenceAlignRouting[3]);
-            }
-            counts[(size_t)i] = found;
-            running += found;
-            if (!over) stretch[(size_t)i] = OccurrenceStretch{&hits, 0, found, found > 0 ? got : nullptr};
-        }
-        if (!panel.empty() && db->maxLen > 0)
-            RC_TRY(batchOccurrencePanel(db, side, panel, open, ext, A, mode, start, end, minScore, window,
-                                        maxHits, &running, &over, &counts, &stretch, &pieces, align));
+        RC_TRY(batchOccurrenceLongQueries(rq, side, single, &got));
+        if (!panel.empty() && db->maxLen > 0) RC_TRY(batchOccurrencePanel(rq, side, panel, &got));
     }
+    const int64_t running = got.running;
     HitArrays all;
-    if (!over) RC_TRY(all.alloc(running, true));
-    // (aligned: the starts, the rebased offsets - the single 0 without occurrences - and room for the operations)
+    if (!got.over) RC_TRY(all.alloc(running, true));
+    // (aligned: the starts, the rebased offsets and room for the operations)
     OccurrenceAlignment joined;
-    if (align && !over) {
-        if (running > 0) {
-            joined.startT = (int*)malloc(sizeof(int) * (size_t)running);
-            joined.startQ = (int*)malloc(sizeof(int) * (size_t)running);
-            if (!joined.startT || !joined.startQ) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
-        }
-        if (operations) {
-            joined.opsOff = (int64_t*)malloc(sizeof(int64_t) * (size_t)(running + 1));
-            if (!joined.opsOff) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
-            joined.opsOff[0] = 0;
+    if (got.aligned && !got.over) {
+        RC_TRY(joined.reserve(running, got.operations));
+        if (got.operations) {
             int64_t at = 0, nOps = 0;
             for (int i = 0; i < nQueries; ++i) {
-                const OccurrenceStretch& s = stretch[(size_t)i];
+                const OccurrenceStretch& s = got.stretch[(size_t)i];
                 for (int64_t k = 0; k < s.count; ++k, ++at) {
                     nOps += s.aligned->opsOff[s.first + k + 1] - s.aligned->opsOff[s.first + k];
                     joined.opsOff[at + 1] = nOps;
@@ -498,34 +361,83 @@ static int batchOccurrencesCore(MiopalDb* db, const PanelSide& side, int nQuerie
         }
     }
     // nothing failed: the outputs are written from here on
+    int64_t* const hitOffsets = out.counts;
     hitOffsets[0] = 0;
-    for (int i = 0; i < nQueries; ++i) hitOffsets[i + 1] = hitOffsets[i] + counts[(size_t)i];
-    if (over) return fail(MIOPAL_ERR_TOO_MANY_HITS, "%lld occurrences, maxHits = %lld", (long long)running, (long long)maxHits);
+    for (int i = 0; i < nQueries; ++i) hitOffsets[i + 1] = hitOffsets[i] + got.counts[(size_t)i];
+    if (got.over) return fail(MIOPAL_ERR_TOO_MANY_HITS, "%lld occurrences, maxHits = %lld", (long long)running, (long long)rq.maxHits);
     for (int i = 0; i < nQueries; ++i) {
-        const OccurrenceStretch& s = stretch[(size_t)i];
+        const OccurrenceStretch& s = got.stretch[(size_t)i];
         if (s.count == 0) continue;
         const size_t at = (size_t)hitOffsets[i], len = (size_t)s.count;
         memcpy(all.target + at, s.from->target + s.first, sizeof(int64_t) * len);
         memcpy(all.score + at, s.from->score + s.first, sizeof(int) * len);
         memcpy(all.endT + at, s.from->endT + s.first, sizeof(int) * len);
         memcpy(all.endQ + at, s.from->endQ + s.first, sizeof(int) * len);
-        if (!align) continue;
+        if (!got.aligned) continue;
         memcpy(joined.startT + at, s.aligned->startT + s.first, sizeof(int) * len);
         memcpy(joined.startQ + at, s.aligned->startQ + s.first, sizeof(int) * len);
-        if (operations)
+        if (got.operations)
             memcpy(joined.ops.data + joined.opsOff[at], s.aligned->ops.data + s.aligned->opsOff[s.first],
                    (size_t)(joined.opsOff[at + len] - joined.opsOff[at]));
     }
-    all.release(targetIndex, score, endTarget, endQuery);
-    if (align) {
-        *startTarget = joined.startT;
-        *startQuery = joined.startQ;
-        joined.startT = joined.startQ = nullptr;
-        if (operations) {
-            *alignments = joined.ops.release();
-            *alignmentOffsets = joined.opsOff;
-            joined.opsOff = nullptr;
-        }
-    }
+    all.release(out.targetIndex, out.score, out.endTarget, out.endQuery);
+    if (got.aligned) joined.release(out);
     return 0;
+}
+
+// what the reporters of the panel occurrence searches say starts over with every call, plain or PSSM
+static void resetBatchOccurrenceReports(bool wantAligned) {
+    for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceRouting[k] = 0;
+    for (int k = 0; k < 3; ++k) g_lastBatchOccurrenceGroups[k] = 0;
+    if (wantAligned)
+        for (int k = 0; k < 4; ++k) g_lastBatchOccurrenceAlignRouting[k] = 0;
+}
+
+// miopalSearchBatchOccurrences(Aligned). Behind nothing: the checks of miopalSearchOccurrences over the whole list, in
+// its order, come first; the aligned form's four outputs behind endQuery are checked with the others.
+static int searchBatchOccurrencesImpl(const OccurrenceRequest& rq, const PanelSide& side, const OccurrenceOutputs& out) {
+    resetBatchOccurrenceReports(out.aligned);
+    RC_TRY(validateBatch(rq.db, side.residues, side.offsets, side.nQueries, side.matrix, rq.A, OPAL_SEARCH_SCORE_END, rq.mode, rq.start, rq.end));
+    RC_TRY(checkOccurrenceRule(rq.mode, side.nQueries, side.minScore, side.window, "query"));
+    RC_TRY(out.check());
+    return batchOccurrencesCore(rq, side, out);
+}
+
+// miopalSearchPssmBatchOccurrences(Aligned): what needs no handle first, in the single PSSM calls' order with the plain
+// panel's per-query checks among it, then the handle and what depends on it; the range check of every PSSM, with the
+// extreme entries of its own rows, is the core's. `side` as the caller gave it: the consensus may be null.
+static int searchPssmBatchOccurrencesImpl(const OccurrenceRequest& rq, PanelSide side, const OccurrenceOutputs& out) {
+    MiopalDb* const db = rq.db;
+    const int nPssms = side.nQueries, A = rq.A, mode = rq.mode;
+    const int64_t* const rowOffsets = side.offsets;
+    resetBatchOccurrenceReports(out.aligned);
+    if (mode < OPAL_MODE_NW || mode > OPAL_MODE_SW) return fail(OPAL_ERR_INVALID_MODE, "invalid alignment mode %d", mode);
+    RC_TRY(checkOccurrenceRule(mode, 0, nullptr, nullptr, nullptr));
+    if (nPssms < 0 || (nPssms > 0 && !rowOffsets)) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad PSSM list");
+    for (int m = 0; m < nPssms; ++m)
+        if (rowOffsets[m] < 0 || rowOffsets[m + 1] < rowOffsets[m]) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad row offsets at %d", m);
+    const int64_t first = nPssms > 0 ? rowOffsets[0] : 0, totalRows = nPssms > 0 ? rowOffsets[nPssms] - first : 0;
+    if (totalRows > INT32_MAX - 64) return fail(MIOPAL_ERR_BAD_ARGUMENT, "the PSSMs of a panel hold 2^31 - 65 rows at most");
+    if (totalRows > 0 && !side.rowScores) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null row scores");
+    if (A <= 0 || A > kMaxAlphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad alphabet length %d", A);
+    RC_TRY(checkOccurrenceRule(mode, nPssms, side.minScore, side.window, "PSSM"));
+    RC_TRY(out.check());
+    if (out.aligned) RC_TRY(checkConsensus(side.residues, first, totalRows, A, out.alignments != nullptr));
+    // (a PSSM of more than 64 rows takes the single sweep, which keeps its rows in LDS)
+    for (int i = 0; i < nPssms; ++i) RC_TRY(checkOccurrenceTableFits(rowOffsets[i + 1] - rowOffsets[i], A, i));
+    if (!db) return fail(MIOPAL_ERR_BAD_ARGUMENT, "null database handle");
+    if (A != db->alphabet) return fail(MIOPAL_ERR_BAD_ARGUMENT, "alphabet length %d differs from the database's %d", A, db->alphabet);
+    if (rq.start < 0 || rq.end < rq.start || rq.end > db->count)
+        return fail(MIOPAL_ERR_BAD_ARGUMENT, "bad slice [%lld, %lld)", (long long)rq.start, (long long)rq.end);
+    // (without a consensus - the plain form, starts only - every position is "no residue": the kernels never read it)
+    std::vector<unsigned char> none;
+    if (!out.aligned || !side.residues) {
+        none.assign((size_t)(first + std::max<int64_t>(totalRows, 1)), 255);   // (indexed in the offsets' coordinates)
+        side.residues = none.data();
+    }
+    static const int64_t kNoPssms[1] = {0};
+    static const int kNoPanelRows[1] = {0};   // (no rows: the score source still says "position-specific")
+    if (nPssms == 0) side.offsets = kNoPssms;
+    if (totalRows == 0) side.rowScores = kNoPanelRows;
+    return batchOccurrencesCore(rq, side, out);
 }

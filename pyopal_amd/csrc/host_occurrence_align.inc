@@ -16,7 +16,7 @@ namespace {
 
 thread_local int64_t g_lastOccurrenceAlignRouting[4] = {0, 0, 0, 0};   // miopalLastOccurrenceAlignRouting
 
-// what the stage leaves for the entry point: malloc'ed like the occurrences' own arrays
+// What the stage leaves for the entry point (and a panel call splices into), malloc'ed like the occurrences' own arrays
 struct OccurrenceAlignment {
     int *startT = nullptr, *startQ = nullptr;
     int64_t* opsOff = nullptr;
@@ -29,43 +29,66 @@ struct OccurrenceAlignment {
         free(startQ);
         free(opsOff);
     }
+    // the arrays for `total` occurrences; without any the starts stay null and the offsets hold their single 0
+    int reserve(int64_t total, bool operations) {
+        if (total > 0) {
+            startT = (int*)malloc(sizeof(int) * (size_t)total);
+            startQ = (int*)malloc(sizeof(int) * (size_t)total);
+            if (!startT || !startQ) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+        }
+        if (operations) {
+            opsOff = (int64_t*)malloc(sizeof(int64_t) * (size_t)(total + 1));
+            if (!opsOff) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
+            opsOff[0] = 0;
+        }
+        return 0;
+    }
+    // the arrays change hands (nothing here can fail: the last step of an aligned call)
+    void release(const OccurrenceOutputs& to) {
+        *to.startTarget = startT;
+        *to.startQuery = startQ;
+        startT = startQ = nullptr;
+        if (!to.operations()) return;
+        *to.alignments = ops.release();
+        *to.alignmentOffsets = opsOff;
+        opsOff = nullptr;
+    }
 };
 
 }  // namespace
 
-// The stage itself, shared with the panel form (host_batch_occurrence_align.inc): the `total` occurrences whose arrays
-// dScore / dRow / dColumn lie in the workspace of `s` and whose host copies are `hits`, chunk by chunk in output order.
+// The stage itself, shared with the panel form (host_batch_occurrence_align.inc): the occurrences whose arrays
+// score / row / column lie in the workspace of `s` and whose host copies are `hits`, chunk by chunk in output order.
 // `s` holds the query buffer (ensurePairInputs has run or runs here): the call's one query, or a panel chunk's queries
 // end to end; Q = its tallest query, which sizes the chunks. gather(c0, nc, targetOff, &qBase) enqueues what fills
 // targetOff[0 .. nc) for the occurrences c0 .. c0 + nc and names their query origins (null: all at 0). What the
-// chunks did is added to `routing` (the figures of miopalLastOccurrenceAlignRouting).
+// chunks did is added to `routing` (the figures of miopalLastOccurrenceAlignRouting, or of the panel's reporter).
 using OccurrenceGather = std::function<int(int64_t c0, int nc, int64_t* targetOff, const int32_t** qBase)>;
+struct OccurrenceAlignJob {
+    const HitArrays* hits;
+    OccurrenceOutSlot slot;
+    int Q;
+    bool operations;
+    const OccurrenceGather* gather;
+    int64_t* routing;
+    OccurrenceAlignment* out;
+};
 
 // ... in three steps, so that the PSSM panel can run the chunks over one stretch of the occurrences after another, each
-// with a query buffer of its own (host_batch_occurrence_align_pssm.inc): the arrays for all `total` occurrences,
-static int allocOccurrenceAlignment(int64_t total, bool operations, OccurrenceAlignment* out) {
-    out->startT = (int*)malloc(sizeof(int) * (size_t)total);
-    out->startQ = (int*)malloc(sizeof(int) * (size_t)total);
-    if (operations) out->opsOff = (int64_t*)malloc(sizeof(int64_t) * (size_t)(total + 1));
-    if (!out->startT || !out->startQ || (operations && !out->opsOff)) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
-    if (operations) out->opsOff[0] = 0;
-    return 0;
-}
-
+// with a query buffer of its own (host_batch_occurrence_align_pssm.inc): OccurrenceAlignment::reserve for all of them,
 // the chunks of the occurrences first .. last (stretches are taken in ascending order, none left out: the operations
 // are appended and opsOff[first] is the stretch before's last entry),
-static int alignOccurrenceRange(Search& s, int64_t first, int64_t last, const HitArrays& hits, const int32_t* dScore,
-                                const int32_t* dRow, const int32_t* dColumn, int Q, bool operations,
-                                const OccurrenceGather& gather, int64_t* routing, OccurrenceAlignment* out) {
+static int alignOccurrenceRange(Search& s, int64_t first, int64_t last, const OccurrenceAlignJob& job) {
+    const HitArrays& hits = *job.hits;
     MiopalDb* const db = s.db;
     Workspace* const ws = s.ws;
     int64_t maxL = 1;
     for (int64_t k = first; k < last; ++k) maxL = std::max<int64_t>(maxL, dbLen(db, hits.target[k]));
-    const int64_t cap = pairChunkCapacity(Q, maxL, operations);
-    const bool waveOnly = Q > kPairLaneMaxQuery || cap < kLanes;
+    const int64_t cap = pairChunkCapacity(job.Q, maxL, job.operations);
+    const bool waveOnly = job.Q > kPairLaneMaxQuery || cap < kLanes;
     const bool forceLane = tuned(Tune::FORCE_LANE_PER_PAIR) != nullptr;
     const bool tableFits = !s.pssmRows || perPairPssmBytes(s.Q, s.A) != 0;   // (the whole buffer's rows are the table)
-    const bool oneStrip = Q <= kLanes;
+    const bool oneStrip = job.Q <= kLanes;
     std::vector<int32_t> hsq, hst, hlen, hts;
     for (int64_t c0 = first; c0 < last; c0 += cap) {
         const int nc = (int)std::min(cap, last - c0);
@@ -91,35 +114,35 @@ static int alignOccurrenceRange(Search& s, int64_t first, int64_t last, const Hi
             RC_TRY(ws->get(kHeadWaves, sizeof(int), &phead));
         }
         const int32_t* pqbase = nullptr;
-        RC_TRY(gather(c0, nc, (int64_t*)ptoff, &pqbase));
+        RC_TRY((*job.gather)(c0, nc, (int64_t*)ptoff, &pqbase));
         int headWaves = 0;
         LaterPasses lp{};
         lp.db = db; lp.s = &s;
         lp.mode = s.mode; lp.open = s.open; lp.ext = s.ext; lp.A = s.A; lp.totalQuery = s.Q;
         lp.nc = nc; lp.maxL = chunkL; lp.oneStrip = oneStrip; lp.fwdWsStride = oneStrip ? 0 : chunkL;
         lp.lane = lane; lp.lanePossible = lanePossible; lp.forceLane = forceLane;
-        lp.score = dScore + c0; lp.endI = dRow + c0; lp.endJ = dColumn + c0;
+        lp.score = job.slot.score + c0; lp.endI = job.slot.row + c0; lp.endJ = job.slot.column + c0;
         lp.tOff = (const int64_t*)ptoff; lp.qBase = pqbase;
         lp.jobs = (PairJob*)pjobs; lp.sorted = (PairJob*)psorted; lp.bins = (int*)pbins; lp.head = (int*)phead;
-        lp.startsOnly = !operations; lp.endsOnHost = true;
+        lp.startsOnly = !job.operations; lp.endsOnHost = true;
         lp.consumer = nullptr; lp.pairs = nullptr; lp.noun = "occurrence";
         lp.idOf = [c0](int k) { return (long long)(c0 + k); };
         lp.hs = hits.score + c0; lp.hi = hits.endQ + c0; lp.hj = hits.endT + c0;
-        lp.hsq = &hsq; lp.hst = &hst; lp.hlen = &hlen; lp.hts = &hts; lp.outOps = &out->ops;
+        lp.hsq = &hsq; lp.hst = &hst; lp.hlen = &hlen; lp.hts = &hts; lp.outOps = &job.out->ops;
         lp.traceHeadWaves = &headWaves;
         RC_TRY(runLaterPasses(lp));
         for (int k = 0; k < nc; ++k) {
-            out->startQ[c0 + k] = hsq[(size_t)k];
-            out->startT[c0 + k] = hst[(size_t)k];
-            if (operations) out->opsOff[c0 + k + 1] = out->opsOff[c0 + k] + hlen[(size_t)k];
+            job.out->startQ[c0 + k] = hsq[(size_t)k];
+            job.out->startT[c0 + k] = hst[(size_t)k];
+            if (job.operations) job.out->opsOff[c0 + k + 1] = job.out->opsOff[c0 + k] + hlen[(size_t)k];
         }
-        if (operations) {
+        if (job.operations) {
             const int64_t toWave = lp.traceLane ? std::min<int64_t>(nc, (int64_t)headWaves * kLanes) : nc;
-            routing[0] += nc - toWave;
-            routing[1] += toWave;
+            job.routing[0] += nc - toWave;
+            job.routing[1] += toWave;
         }
-        routing[2] += 1;
-        routing[3] = std::max(routing[3], lp.maxWindow);
+        job.routing[2] += 1;
+        job.routing[3] = std::max(job.routing[3], lp.maxWindow);
     }
     return 0;
 }
@@ -132,64 +155,47 @@ static int finishOccurrenceAlignment(int64_t total, bool operations, OccurrenceA
     return 0;
 }
 
-static int alignOccurrenceChunks(Search& s, int64_t total, const HitArrays& hits, const int32_t* dScore, const int32_t* dRow,
-                                 const int32_t* dColumn, int Q, bool operations, const OccurrenceGather& gather,
-                                 int64_t* routing, OccurrenceAlignment* out) {
-    RC_TRY(allocOccurrenceAlignment(total, operations, out));
-    RC_TRY(alignOccurrenceRange(s, 0, total, hits, dScore, dRow, dColumn, Q, operations, gather, routing, out));
-    return finishOccurrenceAlignment(total, operations, out);
+static int alignOccurrenceChunks(Search& s, int64_t total, const OccurrenceAlignJob& job) {
+    RC_TRY(job.out->reserve(total, job.operations));
+    RC_TRY(alignOccurrenceRange(s, 0, total, job));
+    return finishOccurrenceAlignment(total, job.operations, job.out);
 }
 
-static int alignOccurrencesStage(const OccurrencesOnDevice& o, bool operations, OccurrenceAlignment* out) {
+static int alignOccurrencesStage(const OccurrencesOnDevice& o, bool operations, int64_t* routing, OccurrenceAlignment* out) {
     Search& s = *o.s;
     const OccurrenceGather gather = [&](int64_t c0, int nc, int64_t* targetOff, const int32_t**) {
-        HIP_TRY(launchOccurrencePairInputs(nc, o.target + c0, s.db->d_offsets, s.db->count, targetOff, s.stream));
+        HIP_TRY(launchOccurrencePairInputs(nc, o.slot.target + c0, s.db->d_offsets, s.db->count, targetOff, s.stream));
         return 0;
     };
-    return alignOccurrenceChunks(s, o.total, *o.hits, o.score, o.row, o.column, s.Q, operations, gather,
-                                 g_lastOccurrenceAlignRouting, out);
+    return alignOccurrenceChunks(s, o.total, OccurrenceAlignJob{o.hits, o.slot, s.Q, operations, &gather, routing, out});
 }
 
-// Behind the entry points' checks: the sweeps with the stage behind them, then the outputs - all of them, or none.
-static int searchOccurrencesAlignedImpl(MiopalDb* db, const unsigned char* query, int Q, int open, int ext, const int* matrix,
-                                        const int* pssmRows, int A, int mode, int64_t start, int64_t end, int minScore,
-                                        int window, int64_t maxHits, int64_t* count, int64_t** targetIndex, int** score,
-                                        int** endTarget, int** endQuery, int** startTarget, int** startQuery,
-                                        unsigned char** alignments, int64_t** alignmentOffsets) {
+// The single forms' last step: the count and the four arrays change hands - with too many occurrences their number alone
+static int finishOccurrences(int rc, int64_t found, HitArrays& hits, const OccurrenceOutputs& out) {
+    if (rc == MIOPAL_ERR_TOO_MANY_HITS) *out.counts = found;
+    if (rc) return rc;
+    *out.counts = found;
+    hits.release(out.targetIndex, out.score, out.endTarget, out.endQuery);
+    return 0;
+}
+
+// Behind the checks of the four single entry points: the sweeps, then the outputs - all of them, or none. An aligned
+// call runs the stage behind the sweeps and hands its arrays over too; a plain call builds nothing for it.
+static int searchOccurrencesCall(const OccurrenceRequest& rq, const OccurrenceQuery& q, const OccurrenceOutputs& out) {
+    HitArrays hits;
+    int64_t found = 0;
+    if (!out.aligned)
+        return finishOccurrences(searchOccurrencesImpl(rq, q, &found, &hits, nullptr, g_lastOccurrenceRouting), found, hits, out);
     for (int k = 0; k < 4; ++k) g_lastOccurrenceAlignRouting[k] = 0;
-    const bool operations = alignments != nullptr;
+    const bool operations = out.operations();
     OccurrenceAlignment got;
-    // (without occurrences the offsets still hold their single 0: reserved before anything is written)
-    int64_t* none = nullptr;
-    struct FreeNone {
-        int64_t*& p;
-        ~FreeNone() { free(p); }
-    } guard{none};
-    if (operations) {
-        none = (int64_t*)malloc(sizeof(int64_t));
-        if (!none) return fail(MIOPAL_ERR_INTERNAL, "out of host memory");
-        none[0] = 0;
-    }
-    const OccurrenceStage stage = [&](const OccurrencesOnDevice& o) { return alignOccurrencesStage(o, operations, &got); };
-    // (the stage has run, or there was nothing to run it on, when this returns 0: nothing below can fail)
-    RC_TRY(searchOccurrencesImpl(db, query, Q, open, ext, matrix, pssmRows, A, mode, start, end, minScore, window, maxHits,
-                                 count, targetIndex, score, endTarget, endQuery, &stage));
-    if (*count == 0) {
-        *startTarget = *startQuery = nullptr;
-        if (operations) {
-            *alignments = nullptr;
-            *alignmentOffsets = none;
-            none = nullptr;
-        }
-        return 0;
-    }
-    *startTarget = got.startT;
-    *startQuery = got.startQ;
-    got.startT = got.startQ = nullptr;
-    if (operations) {
-        *alignments = got.ops.release();
-        *alignmentOffsets = got.opsOff;
-        got.opsOff = nullptr;
-    }
+    const OccurrenceStage stage = [&](const OccurrencesOnDevice& o) {
+        return alignOccurrencesStage(o, operations, g_lastOccurrenceAlignRouting, &got);
+    };
+    int rc = searchOccurrencesImpl(rq, q, &found, &hits, &stage, g_lastOccurrenceRouting);
+    // (the stage has run, or there was nothing to run it on: nothing behind the reserve can fail)
+    if (rc == 0 && found == 0) rc = got.reserve(0, operations);
+    RC_TRY(finishOccurrences(rc, found, hits, out));
+    got.release(out);
     return 0;
 }

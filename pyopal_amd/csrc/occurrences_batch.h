@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "occurrence_rows.h"
 #include "occurrences.h"
 
 namespace miopal {
@@ -35,16 +36,6 @@ constexpr int64_t kBatchOccurrenceEntries = int64_t(1) << 25;
 // groups 0.29 ms, 96 groups 0.19 ms). The tuning switch BATCH_OCCURRENCE_WORKGROUPS_PER_CU sets another value; 0
 // keeps every group as large as the LDS allows (tests: several queries a group, groups that fill the LDS).
 constexpr int kBatchOccurrenceWorkgroupsPerCu = 32;
-// the pad residue of a chunk's row list: a row behind its query, up to the next multiple of eight
-constexpr int kBatchOccurrencePadRow = 255;
-
-// rows a query of Q rows takes in the row list and in LDS
-__host__ __device__ constexpr int batchOccurrenceRows(int Q) { return (Q + 7) / 8 * 8; }
-// bytes of LDS of `rows` table rows
-__host__ __device__ constexpr size_t batchOccurrenceLdsBytes(int64_t rows, int alphabet) {
-    return (size_t)rows * (size_t)(alphabet + 1) * sizeof(int);
-}
-
 struct BatchOccurrenceArgs {
     // count sweep: the chunk of targets, sorted by length (job.out = the target's position in the slice)
     const PairJob* jobs;

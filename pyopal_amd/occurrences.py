@@ -180,6 +180,20 @@ def _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode
         return out, side, _target_lengths(mirror, mode)
 
 
+def _panel_lists(mode, panel) -> typing.List[typing.List[ScoreResult]]:
+    """one list of result objects per query from what `_panel_arrays` returned: "end" without an owner, "full" with
+    each occurrence's query as its owner and the lengths of both sides"""
+    out, side, target_lengths = panel
+    offsets = out["offsets"]
+    if mode == "end":
+        flat = _result_objects(mode, out["target"], None, None, None, out)
+    else:
+        owner = np.repeat(np.arange(len(offsets) - 1, dtype=np.int64), np.diff(offsets))
+        flat = _result_objects(mode, out["target"], owner, side.lengths, target_lengths, out)
+    offsets = offsets.tolist()
+    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+
+
 def find_occurrences_many(aligner: Aligner, queries, database: BaseDatabase, min_score, *, window=None,
                           algorithm: str = "hw", mode: str = "end", start: int = 0, end: int = UINT32_MAX, device: int = 0,
                           max_hits: typing.Optional[int] = None) -> typing.List[typing.List[ScoreResult]]:
@@ -190,10 +204,8 @@ def find_occurrences_many(aligner: Aligner, queries, database: BaseDatabase, min
     ``counts``. ``mode="full"`` raises ValueError - the alignments of a panel's occurrences are not available yet
     under this name: `find_occurrence_alignments_many` returns them. That and the other rule faults raise before any
     device call; an empty panel or slice is answered without a device."""
-    out = _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device, max_hits)[0]
-    flat = _result_objects(mode, out["target"], None, None, None, out)
-    offsets = out["offsets"].tolist()
-    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+    return _panel_lists(mode, _panel_arrays(aligner, queries, database, min_score, window, algorithm, mode, start, end, device,
+                                            max_hits))
 
 
 def find_occurrences_many_arrays(aligner: Aligner, queries, database: BaseDatabase, min_score, *, window=None,
@@ -216,13 +228,8 @@ def find_occurrence_alignments_many(aligner: Aligner, queries, database: BaseDat
     ``window`` and ``max_hits`` as in `find_occurrences_many`; once the total passes ``max_hits`` nothing more is
     aligned and `_capi.TooManyHits` carries the CSR offsets. The rule's faults raise before any device call; an empty
     panel or slice is answered without a device."""
-    out, side, target_lengths = _panel_arrays(aligner, queries, database, min_score, window, algorithm, "full", start, end,
-                                              device, max_hits, True)
-    offsets = out["offsets"]
-    owner = np.repeat(np.arange(len(offsets) - 1, dtype=np.int64), np.diff(offsets))
-    flat = _result_objects("full", out["target"], owner, side.lengths, target_lengths, out)
-    offsets = offsets.tolist()
-    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+    return _panel_lists("full", _panel_arrays(aligner, queries, database, min_score, window, algorithm, "full", start, end,
+                                              device, max_hits, True))
 
 
 def find_occurrence_alignments_many_arrays(aligner: Aligner, queries, database: BaseDatabase, min_score, *, window=None,
@@ -248,11 +255,8 @@ def find_occurrences_pssm_many(aligner: Aligner, pssms, database: BaseDatabase, 
     `EndResult` per PSSM, each what ``find_occurrences_pssm(aligner, pssm, ..., mode="end")`` returns for that PSSM. A
     window of None is that PSSM's height. ``mode="full"`` raises ValueError: `find_occurrence_alignments_pssm_many`
     returns the alignments."""
-    out = _panel_arrays(aligner, pssms, database, min_score, window, algorithm, mode, start, end, device, max_hits,
-                        pssm=True)[0]
-    flat = _result_objects(mode, out["target"], None, None, None, out)
-    offsets = out["offsets"].tolist()
-    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+    return _panel_lists(mode, _panel_arrays(aligner, pssms, database, min_score, window, algorithm, mode, start, end, device,
+                                            max_hits, pssm=True))
 
 
 def find_occurrences_pssm_many_arrays(aligner: Aligner, pssms, database: BaseDatabase, min_score, *, window=None,
@@ -272,13 +276,8 @@ def find_occurrence_alignments_pssm_many(aligner: Aligner, pssms, database: Base
     """`find_occurrence_alignments_many` with a list of `Pssm`: one list of `FullResult` per PSSM, each what
     ``find_occurrences_pssm(aligner, pssm, ..., mode="full")`` returns for that PSSM; the PSSMs' consensus tells
     matches from mismatches."""
-    out, side, target_lengths = _panel_arrays(aligner, pssms, database, min_score, window, algorithm, "full", start, end,
-                                              device, max_hits, True, pssm=True)
-    offsets = out["offsets"]
-    owner = np.repeat(np.arange(len(offsets) - 1, dtype=np.int64), np.diff(offsets))
-    flat = _result_objects("full", out["target"], owner, side.lengths, target_lengths, out)
-    offsets = offsets.tolist()
-    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+    return _panel_lists("full", _panel_arrays(aligner, pssms, database, min_score, window, algorithm, "full", start, end,
+                                              device, max_hits, True, pssm=True))
 
 
 def find_occurrence_alignments_pssm_many_arrays(aligner: Aligner, pssms, database: BaseDatabase, min_score, *,
