@@ -188,13 +188,20 @@ struct Search {
             HIP_TRY(hipMemsetAsync(st, 0, ints * sizeof(int), on));
             if (!d_stripError) {
                 // The counter only ever moves when a unit gives up, and a search that sees it moved
-                // fails and zeroes it again (checkStripError): it is zeroed ONCE, synchronously, when the
-                // workspace allocates it - no memset on whichever of the two streams asks first, which
-                // launches on the other stream would not be ordered after.
+                // fails and zeroes it again (checkStripError): it is zeroed ONCE, when the workspace allocates
+                // it, and the host waits for that - a memset left behind on whichever of the two streams asks
+                // first is one that launches on the other stream would not be ordered after.
+                // (On the asking stream and waited for there, not hipMemset: that one runs on the null stream,
+                // which these non-blocking streams are not ordered with, and a search beside searches of other
+                // threads read the counter of a fresh allocation before the zero had landed - -2 and 6439
+                // "units gave up", tests/test_gpu_call_order.py, four threads with MIOPAL_PARKED_WORKSPACE_MB=0.)
                 const bool fresh = ws->cap[kPairStripError] == 0;
                 void* pe;
                 RC_TRY(ws->get(kPairStripError, sizeof(int), &pe));
-                if (fresh) HIP_TRY(hipMemset(pe, 0, sizeof(int)));
+                if (fresh) {
+                    HIP_TRY(hipMemsetAsync(pe, 0, sizeof(int), on));
+                    HIP_TRY(hipStreamSynchronize(on));
+                }
                 d_stripError = (int*)pe;
             }
             a.nStrips = jobStrips;
@@ -259,7 +266,8 @@ struct Search {
         if (stripErrorHost == 0) return 0;
         const int seen = stripErrorHost;
         stripErrorHost = 0;
-        HIP_TRY(hipMemset(d_stripError, 0, sizeof(int)));
+        HIP_TRY(hipMemsetAsync(d_stripError, 0, sizeof(int), stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         return fail(MIOPAL_ERR_INTERNAL, "%d (pair, strip) units of the wavefront-per-pair kernel gave up waiting for the strip above", seen);
     }
 
