@@ -234,6 +234,21 @@ void miopalLastRouting(int64_t counts[4]);
 void miopalLastWindowPlan(int64_t out[4]);
 
 /*
+ * The shape of the persistent launch of the calling thread's most recent score pass (diagnostics for tests; no
+ * reference counterpart): what "reserve_cus" (miopalDbSetOption) made of the launch, as opposed to what was asked.
+ * All zeros before the thread's first search; out[1 .. 3] are reset when a score pass starts, all four when a batch
+ * starts (miopalSearchBatch and the entry points built on it):
+ *   out[0] the compute units the handle sees
+ *   out[1] the workgroups of the pass's main persistent launch - the one-strip or strips pair-table kernel, for the
+ *          column split the workgroups of its plan; a batch: of its last batch-kernel launch -, 0 if there was none
+ *          (small searches, the general kernel, a refused launch)
+ *   out[2] the wavefronts per workgroup of that launch
+ *   out[3] the per-SIMD share of groups the launch's hand-out stops a SIMD at, 0 = off (always 0 for the int16 and
+ *          half-float flavours, the column split, the strips and the batch kernels: they have no shares)
+ */
+void miopalLastLaunchShape(int64_t out[4]);
+
+/*
  * Many queries against one slice [start, end) of a resident handle in one call (no reference counterpart:
  * the batch form of pyopal's thread-pool loop of searches). Query k is
  * queries[queryOffsets[k] .. queryOffsets[k + 1]) (nQueries + 1 offsets); outputs are row-major
@@ -955,9 +970,11 @@ const char* miopalGetTuning(const char* name);   /* NULL: unset or unknown */
 /*
  * Per-handle options: the two product knobs among the switches, as arguments instead of process-wide
  * environment (value -1 = back to the process default):
- *   "reserve_cus"   compute units kept out of the persistent search launches, so that the kernels of a
- *                   collective that gathers the previous search's scores (one process per GPU, RCCL) find
- *                   room beside the search (bench.py, multi-GPU ranks: 8); default MIOPAL_RESERVE_CUS / none
+ *   "reserve_cus"   compute units kept out of the persistent search launches - the pair-table kernels of one
+ *                   query and the batch kernels; at least one workgroup is always launched -, so that the
+ *                   kernels of a collective that gathers the previous search's scores (one process per GPU,
+ *                   RCCL) find room beside the search (bench.py, multi-GPU ranks: 8); default
+ *                   MIOPAL_RESERVE_CUS / none. miopalLastLaunchShape reports the width a launch got.
  *   "small_search"  1: searches of few targets may take the wavefront-per-pair kernel (shorter start-up),
  *                   0: they stay on the lane-per-target kernels; default 1 unless MIOPAL_NO_SMALL_SEARCH
  */

@@ -80,7 +80,8 @@ EXPORTS = [
     "miopalDeviceCount", "miopalLastError", "miopalDbCreate", "miopalDbCreateFlat", "miopalDbCreateSubset",
     "miopalDbDestroy", "miopalDbCount", "miopalDbTotalLength", "miopalDbDeviceBytes",
     "miopalSearch", "miopalSearchFlat", "miopalSearchFlatInto", "miopalSearchPssm", "miopalSearchDeviceScores", "miopalSetProfiling", "miopalLastKernelTime",
-    "miopalLastRouting", "miopalLastWindowPlan", "miopalLastFullRouting", "miopalSearchResults", "miopalReleaseCaches",
+    "miopalLastRouting", "miopalLastWindowPlan", "miopalLastLaunchShape", "miopalLastFullRouting", "miopalSearchResults",
+    "miopalReleaseCaches",
     "miopalSearchBatch", "miopalLastBatchRouting", "miopalSearchTop", "miopalSearchBatchTop",
     "miopalAlignPairs", "miopalLastPairRouting", "miopalSearchPssmTop", "miopalAlignPairsPssm",
     "miopalSearchHits", "miopalSearchPssmHits", "miopalSearchBatchHits", "miopalSearchBatchTargetTop",
@@ -166,7 +167,8 @@ def lib() -> ctypes.CDLL:
             "miopalSetProfiling": (None, [c_vp, c_int]),
             "miopalReleaseCaches": (None, []),
             "miopalLastFullRouting": (c_int, []),
-            "miopalLastRouting": (None, [p_i64]), "miopalLastWindowPlan": (None, [p_i64]), "miopalLastPairRouting": (None, [p_i64]),
+            "miopalLastRouting": (None, [p_i64]), "miopalLastWindowPlan": (None, [p_i64]), "miopalLastLaunchShape": (None, [p_i64]),
+            "miopalLastPairRouting": (None, [p_i64]),
             "miopalLastBatchRouting": (None, [p_i64]), "miopalLastOccurrenceRouting": (None, [p_i64]),
             "miopalLastOccurrenceAlignRouting": (None, [p_i64]),
             "miopalLastBatchOccurrenceRouting": (None, [p_i64]), "miopalLastBatchOccurrenceGroups": (None, [p_i64]),
@@ -1416,6 +1418,15 @@ class DeviceDatabase:
         (include/miopal.h, miopalLastWindowPlan)."""
         out = (ctypes.c_int64 * 4)()
         lib().miopalLastWindowPlan(out)
+        return tuple(int(c) for c in out)
+
+    @staticmethod
+    def last_launch_shape() -> typing.Tuple[int, int, int, int]:
+        """(compute units the handle sees, workgroups of the main persistent launch - 0: none -, wavefronts per
+        workgroup, per-SIMD share of groups - 0: off) for the score pass of the calling thread's most recent search
+        (include/miopal.h, miopalLastLaunchShape)."""
+        out = (ctypes.c_int64 * 4)()
+        lib().miopalLastLaunchShape(out)
         return tuple(int(c) for c in out)
 
     @staticmethod

@@ -96,6 +96,7 @@ namespace {
 thread_local std::string g_lastError;
 thread_local int64_t g_lastRouting[4] = {0, 0, 0, 0};  // miopalLastRouting
 thread_local int64_t g_lastWindowPlan[4] = {0, 0, 0, 0};  // miopalLastWindowPlan
+thread_local int64_t g_lastLaunchShape[4] = {0, 0, 0, 0};  // miopalLastLaunchShape
 thread_local int64_t g_lastBatchRouting[4] = {0, 0, 0, 0};  // miopalLastBatchRouting
 thread_local int g_lastFullRouting = 0;                // miopalLastFullRouting
 thread_local int g_fault[3] = {0, 0, 0};               // miopalTestInjectFault: kind, unit, spin cap
@@ -694,6 +695,11 @@ void miopalLastRouting(int64_t counts[4]) {
 void miopalLastWindowPlan(int64_t out[4]) {
     if (!out) return;
     for (int k = 0; k < 4; ++k) out[k] = g_lastWindowPlan[k];
+}
+
+void miopalLastLaunchShape(int64_t out[4]) {
+    if (!out) return;
+    for (int k = 0; k < 4; ++k) out[k] = g_lastLaunchShape[k];
 }
 
 int miopalLastFullRouting(void) { return g_lastFullRouting; }

@@ -100,7 +100,7 @@ struct BatchSink {
 static int batchImpl(MiopalDb* db, const unsigned char* queries, const int64_t* queryOffsets, int nQueries, int open,
                      int ext, const int* matrix, int A, int searchType, int mode, int64_t start, int64_t end,
                      const BatchSink& sink) {
-    for (int k = 0; k < 4; ++k) g_lastBatchRouting[k] = 0;
+    for (int k = 0; k < 4; ++k) g_lastBatchRouting[k] = g_lastLaunchShape[k] = 0;
     if (searchType == OPAL_SEARCH_ALIGNMENT)
         return fail(OPAL_ERR_INVALID_MODE, "miopalSearchBatch: alignments are not available in a batch");
     RC_TRY(validateBatch(db, queries, queryOffsets, nQueries, matrix, A, searchType, mode, start, end));
@@ -278,10 +278,19 @@ static int batchImpl(MiopalDb* db, const unsigned char* queries, const int64_t* 
                     ba.endJ = d_endJ;
                     ba.overflow = (uint8_t*)po;
                     ba.overflowCount = dm + countOff;
-                    const hipError_t e = sw ? (locate ? launchInterseqBatchSwLoc(ba, L.rows, db->computeUnits, stream)
-                                                      : launchInterseqBatchSw(ba, L.rows, db->computeUnits, stream))
-                                            : (L.rows <= 32 ? launchInterseqBatchGlobalA(ba, L.rows, db->computeUnits, stream)
-                                                            : launchInterseqBatchGlobalB(ba, L.rows, db->computeUnits, stream));
+                    // (the persistent launch's width follows "reserve_cus" like the single-query launches'; the units -
+                    // L.unitsPerQuery - are cut for the whole device either way, and handed out dynamically)
+                    int width = db->computeUnits;
+                    if (const int keep = reservedCus(db); keep >= 0) width = std::max(1, width - keep);
+                    const hipError_t e = sw ? (locate ? launchInterseqBatchSwLoc(ba, L.rows, width, stream)
+                                                      : launchInterseqBatchSw(ba, L.rows, width, stream))
+                                            : (L.rows <= 32 ? launchInterseqBatchGlobalA(ba, L.rows, width, stream)
+                                                            : launchInterseqBatchGlobalB(ba, L.rows, width, stream));
+                    // miopalLastLaunchShape: the batch's last launch (launchBatchSwR / launchBatchGlobalR)
+                    g_lastLaunchShape[0] = db->computeUnits;
+                    g_lastLaunchShape[1] = std::max(1, std::min(width, L.count * L.unitsPerQuery));
+                    g_lastLaunchShape[2] = sw ? (L.rows <= 56 ? 12 : 8) : (L.rows <= 54 ? 12 : 8);   // (batchSwWaves, globalWaves)
+                    g_lastLaunchShape[3] = 0;
                     if (e != hipSuccess) {
                         (void)hipGetLastError();
                         return fail(MIOPAL_ERR_HIP, "batch kernel launch (%d rows): %s", L.rows, hipGetErrorString(e));

@@ -1029,6 +1029,11 @@ struct Search {
         // few (group, strip) units: fewer groups per workgroup, so that every CU gets a unit and a
         // wavefront shares its SIMD with fewer others
         ia.batchGroups = (int)std::max<int64_t>(1, std::min<int64_t>(12, (int64_t)ia.nGroups * p.nStrips / std::max(1, pairUnits)));
+        // (miopalLastLaunchShape: the width launchPairStripsR / launchPairGlobalStripsR give the launch)
+        const int64_t stripUnits = (int64_t)((ia.nGroups + ia.batchGroups - 1) / ia.batchGroups) * p.nStrips;
+        g_lastLaunchShape[1] = std::max<int64_t>(1, std::min<int64_t>(pairUnits, stripUnits));
+        g_lastLaunchShape[2] = kPairWavesPerGroup;
+        g_lastLaunchShape[3] = 0;
         // (diagnostic builds of the kernels, -DMIOPAL_STRIP_TIMING=1: their six counters, printed below)
         if (tuned(Tune::STRIP_TIMING)) {
             void* tb;
@@ -1250,6 +1255,10 @@ struct Search {
             ia.stripTiming = simdFinish = (unsigned long long*)tb;
         }
         g_lastRouting[1] = 2 + (int)pf + (ia.splitMode ? 64 : 0);   // (64: the column split)
+        g_lastLaunchShape[1] = blocks;
+        g_lastLaunchShape[2] = pf == kPairGlobalBiased ? (p.pairRows <= 54 ? 12 : 8) : kPairWavesPerGroup;   // (globalWaves)
+        // (the int16 / half-float flavours and the column split hand out without shares, whatever ia.tailThrottle says)
+        g_lastLaunchShape[3] = (pf == kPairSwBiased || pf == kPairGlobalBiased) && !ia.splitMode ? ia.tailThrottle : 0;
         // the biased kernels exist for every number of rows (NW / HW / OV: every even number): no padding rows to 8
         // (test switch: the launch behaves as if the runtime had refused it, e.g. its 150 KB of dynamic LDS)
         const hipError_t pe = tuned(Tune::TEST_REFUSE_PAIR_LAUNCH)
@@ -1323,6 +1332,8 @@ struct Search {
 
         g_lastRouting[0] = g_lastRouting[1] = g_lastRouting[2] = g_lastRouting[3] = 0;
         g_lastWindowPlan[0] = g_lastWindowPlan[1] = g_lastWindowPlan[2] = g_lastWindowPlan[3] = 0;
+        g_lastLaunchShape[0] = db->computeUnits;   // miopalLastLaunchShape: [1 .. 3] are the persistent launch's, below
+        g_lastLaunchShape[1] = g_lastLaunchShape[2] = g_lastLaunchShape[3] = 0;
         if (!interseqUsable() || (smallSearch() && smallSearchAllowed(db))) {
             g_lastRouting[0] = n;
             jobs.reserve((size_t)n);
@@ -1432,6 +1443,7 @@ struct Search {
                         return scorePassImpl(d_score, d_endI, d_endJ, useHalf);
                     }
                     g_lastRouting[1] |= 16;
+                    g_lastLaunchShape[1] = g_lastLaunchShape[2] = g_lastLaunchShape[3] = 0;   // (no persistent launch ran)
                     if (tuned(Tune::VERBOSE))
                         fprintf(stderr, "miopal: pair-table kernel refused (%s), using the general kernel\n",
                                 hipGetErrorString(pe));

@@ -164,6 +164,21 @@ def test_tuning_switches_are_arguments_not_environment(capi, monkeypatch):
         assert capi.lib().miopalSetTuning(name.encode(), capi.get_tuning(name).encode() if capi.get_tuning(name) else None) == 0, name
 
 
+def test_launch_shape_is_zeros_for_a_thread_that_has_not_searched(capi):
+    """include/miopal.h, miopalLastLaunchShape: thread-local like miopalLastRouting - a thread that has run no score
+    pass (without a device: every thread) reads four zeros, and a null pointer is ignored. Needs no device."""
+    import threading
+    seen = []
+    worker = threading.Thread(target=lambda: seen.append(capi.DeviceDatabase.last_launch_shape()))
+    worker.start()
+    worker.join()
+    assert seen == [(0, 0, 0, 0)]
+    capi.lib().miopalLastLaunchShape(None)
+    import torch
+    if not torch.cuda.is_available():
+        assert capi.DeviceDatabase.last_launch_shape() == (0, 0, 0, 0)
+
+
 def test_logical_devices_hook_needs_a_physical_device(capi):
     import torch
     lib = capi.lib()

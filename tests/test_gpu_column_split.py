@@ -43,9 +43,12 @@ def routed(capi):
 
 
 def check(capi, query, res, off, matrix=B62, gap_open=3, gap_extend=1, settings=tuple(str(w) for w in WORKGROUPS),
-          option=None, tag="", alphabet=24):
+          option=None, tag="", alphabet=24, workgroups=None):
     """The search with the split off and under every setting of MIOPAL_COLUMN_SPLIT: the checker's scores each time,
-    the same number of lanes redone for their range, and the split kernel where it was asked for."""
+    the same number of lanes redone for their range, and the split kernel where it was asked for. The launch shape
+    (miopalLastLaunchShape) each time: a workgroup per compute unit the launch may use or per group with the split off,
+    the forced number - at most the units - with it. `workgroups`: all other units are reserved, and the launch with
+    the split off has a dynamic round."""
     want = _oracle.search(query, res, off, matrix, gap_open, gap_extend, "score", "sw")["score"]
     db = capi.DeviceDatabase(res, off, alphabet)
     try:
@@ -53,14 +56,24 @@ def check(capi, query, res, off, matrix=B62, gap_open=3, gap_extend=1, settings=
             db.set_option(*option)
         with capi.tuning(COLUMN_SPLIT="0"):
             plain = db.search(query, matrix, gap_open, gap_extend, "score", "sw")["score"]
+            if workgroups:
+                db.set_option("reserve_cus", capi.DeviceDatabase.last_launch_shape()[0] - workgroups)
+                plain = db.search(query, matrix, gap_open, gap_extend, "score", "sw")["score"]
             assert routed(capi)[1] == PAIR_BIASED, f"{tag}: {routed(capi)}"
-            redone = routed(capi)[3]
+            redone, groups = routed(capi)[3], routed(capi)[2]
+            shape = capi.DeviceDatabase.last_launch_shape()
+            units = workgroups or (shape[0] - option[1] if option else shape[0])
+            assert shape[1:3] == (min(units, groups), 12), f"{tag}: launch shape {shape}, {groups} groups on {units} units"
+            assert not workgroups or groups > 12 * shape[1], f"{tag}: {groups} groups on {shape}: no dynamic round"
         np.testing.assert_array_equal(plain, want, err_msg=f"{tag} split off")
         for setting in settings:
             with capi.tuning(COLUMN_SPLIT=setting):
                 got = db.search(query, matrix, gap_open, gap_extend, "score", "sw")["score"]
                 assert routed(capi)[1] == PAIR_BIASED + SPLIT, f"{tag} {setting}: {routed(capi)}"
                 assert routed(capi)[3] == redone, f"{tag} {setting}: lanes flagged {routed(capi)[3]} != {redone}"
+                shape = capi.DeviceDatabase.last_launch_shape()
+                forced = min(int(setting), units) if setting.isdigit() else min(units, groups)
+                assert shape[1:] == (forced, 12, 0), f"{tag} {setting}: launch shape {shape} on {units} units"
             np.testing.assert_array_equal(got, want, err_msg=f"{tag} split {setting} against the checker")
             np.testing.assert_array_equal(got, plain, err_msg=f"{tag} split {setting} against the split off")
         return redone
@@ -143,10 +156,14 @@ def test_consumers_that_recompute(capi):
 
 
 def test_plan_follows_the_reserved_compute_units(capi):
+    # 80 groups with eight units reserved: 80 workgroups with the split off (a group each, no second round), the forced
+    # plans on 3 and 8, and "recompute" on 80 again - the launch shape says so. Once more with all units but two
+    # reserved: the split off has its dynamic round (80 groups, 24 in the static one), the plans are held to 2 workgroups
     rng = np.random.default_rng(8)
     query = _oracle.encode(_data.README_QUERY)
     res, off = database(rng, query, np.full(10240, 300))
     check(capi, query, res, off, option=("reserve_cus", 8), settings=("3", "8", "recompute"), tag="reserve_cus 8")
+    check(capi, query, res, off, settings=("3", "8", "recompute"), tag="all but 2 reserved", workgroups=2)
 
 
 def test_all_result_forms(capi):
