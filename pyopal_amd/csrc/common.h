@@ -309,8 +309,8 @@ enum InterseqFlavour : int {
     kUnsignedDiag = 5,        // the same on unsigned patterns compared as half floats (5 cheaper ops, interseq_impl.h)
     kSwShifted = 6            // Smith-Waterman scores on column-shifted unsigned patterns (ArithSwU16)
 };
-constexpr int kSwShiftZero = 0x1000;       // = kSwU16Zero
-constexpr int kUnsignedDiagZero = 0x1000;  // = kU16Zero
+constexpr int kSwShiftZero = 0x1000;       // ArithSwU16: pattern of a true 0 at shift 0
+constexpr int kUnsignedDiagZero = 0x1000;  // ArithU16Diag: pattern of a true 0
 hipError_t launchInterseq(const InterseqArgs& a, int rowsPerStrip, int waves, InterseqFlavour flavour,
                           bool locate, hipStream_t stream);
 // pair-indexed LDS profile: pairs[tA * nSymbols + tB][r] in 16-byte slots of four rows, an odd number of them per
@@ -329,29 +329,34 @@ enum PairFlavour : int {
     kPairSwStrips = 4,     // Smith-Waterman scores of several strips on biased halves (units of (batch, strip))
     kPairGlobalStrips = 5  // NW / HW / OV of several strips on the same units (scores; end locations through keys)
 };
-// limits of the biased flavour (host-side range checks; the kernel's constants are in interseq_impl.h)
+// limits of the biased flavour: the host's range checks and the kernels (interseq_pair_parts.h) use these names
 constexpr int kPairStripsFirst = 32;       // shortest strips of the multi-strip pair-table kernels
 constexpr int kPairStripsMaxRows = 52, kPairStripsMaxRowsLoc = 48;   // tallest strips of the multi-strip pair-table kernel
 constexpr int kPairStripsMaxRowsKnown = 40;   // ... of an `end` search in two sweeps (scores, then the cell that holds them)
-constexpr int kPairWavesPerGroup = 12;     // = kPairWaves: wavefronts of a workgroup of the one-strip pair-table kernels
-// LDS of the one-strip biased kernels behind the table: 4 per-SIMD counters and the pacing words (= kPaceInts), and for
+constexpr int kPairWavesPerGroup = 12;     // wavefronts of a workgroup of the pair-table kernels: 3 per SIMD at <= 168 VGPRs
+// LDS of the one-strip biased kernels behind the table: 4 per-SIMD counters and the pacing words (SimdPace), and for
 // the column split the query profile (nSymbols x qPad int16; qPad is a multiple of 8) the table is built from
-constexpr int kPairTailInts = 4 + 20;
+constexpr int kPaceInts = 20;              // 4 SIMDs x 4 slots of progress + 4 slot counters
+constexpr int kPairTailInts = 4 + kPaceInts;
 constexpr size_t kCuLdsBytes = 160 * 1024;   // a compute unit's LDS, what allowFullLds (launch_layer.h) opens to a kernel
 __host__ __device__ constexpr size_t pairSplitLdsBytes(int rowsPerStrip, int nSymbols, int qPad) {
     return pairLdsBytes(rowsPerStrip, nSymbols) + kPairTailInts * sizeof(int) + (((size_t)nSymbols * qPad * 2 + 15) & ~(size_t)15);
 }
-inline size_t splitStateBytes(int rows) { return (size_t)((2 * rows + 1 + 3) / 4) * kLanes * 16; }   // per wavefront
-constexpr int kBiasedScoreLimit = 25600;   // = kBiasedLimit: a best at or above it is recomputed
+// the column split's state of one wavefront: H[rows], E[rows] and the best, in 16-byte quads per lane
+__host__ __device__ constexpr int splitStateQuads(int rows) { return (2 * rows + 1 + 3) / 4; }
+inline size_t splitStateBytes(int rows) { return (size_t)splitStateQuads(rows) * kLanes * 16; }   // per wavefront
+constexpr int kBiasedScoreLimit = 25600;   // a best at or above it is recomputed
 constexpr int kBiasedMaxMagnitude = 1024;  // |score|, open - ext, ext - open
 constexpr int kBiasedMaxExt = 512;
 constexpr int kBiasedMaxStepUp = 0x1000;   // (score + ext) << bits, (ext - open) << bits; above 0x0400 the limit shrinks
-constexpr int kBiasedPad = -1024;          // = kBiasedPadScore: padding symbol / rows in the profile
+constexpr int kBiasedPad = -1024;          // padding symbol / rows in the profile (a true value)
 // the biased flavour with end locations (scaled by 2^bits, bits = 4 / 5 / 6 for <= 16 / 32 / 64 rows)
-constexpr int kLocZeroPattern = 0x0C00;
+constexpr int kLocZeroPattern = 0x0C00;    // 0x0800 of room below: scores down to -32 at 6 bits
 constexpr int kLocGuardBand = 0x0800;      // |score| << bits, (open - ext) << bits, (ext - open) << bits
-constexpr int kLocMaxShift = 4096;         // 5 * (ext << bits) must fit
-inline int locRowBitsHost(int rows) { return rows <= 16 ? 4 : rows <= 32 ? 5 : 6; }
+constexpr int kBiasedMaxShift = 4096;      // column shift at which the kernels rebase their state; 5 * ext must fit
+constexpr int kLocMaxShift = kBiasedMaxShift;   // ... 5 * (ext << bits) with end locations
+__host__ __device__ constexpr int locRowBits(int rows) { return rows <= 16 ? 4 : rows <= 32 ? 5 : 6; }
+inline int locRowBitsHost(int rows) { return locRowBits(rows); }
 hipError_t launchInterseqPair(const InterseqArgs& a, int rowsPerStrip, PairFlavour flavour, int computeUnits,
                               hipStream_t stream, bool locate = false);
 // The kernel families behind launchInterseq / launchInterseqPair, one function template each (defined in

@@ -55,7 +55,7 @@ static __device__ __forceinline__ int batchTakeGroup(int* ctl, int first, int la
 // ---- Smith-Waterman: interseq_pair_biased_kernel<R, LOC>'s sweep, per (query, group) ---------------------
 // Twelve wavefronts per workgroup (168 VGPRs) up to 56 rows, eight (256 VGPRs) beyond: the unit bookkeeping
 // beside H[R], E[R] does not leave a 60- or 64-row column room in 168 registers.
-__host__ __device__ constexpr int batchSwWaves(int rows) { return rows <= 56 ? kPairWaves : 8; }
+__host__ __device__ constexpr int batchSwWaves(int rows) { return rows <= 56 ? kPairWavesPerGroup : 8; }
 
 template <int R, bool LOC>
 __global__ __launch_bounds__(batchSwWaves(R) * kLanes) void interseq_batch_sw_kernel(BatchArgs a) {
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(batchSwWaves(R) * kLanes) void interseq_batch_sw_ke
     const int nSym = a.nSymbols;
     const int ext = a.gapExt << kBits;   // pattern units
     const uint32_t ext2 = both(ext), openMinusExt2 = both((a.gapOpen << kBits) - ext);
-    const uint32_t zero2 = both(LOC ? kLocZero : kBiasedZero);
+    const uint32_t zero2 = both(LOC ? kLocZeroPattern : kBiasedZero);
     int* ctl = reinterpret_cast<int*>(pairs + nSym * nSym * SLOTS);   // [0] unit, [1] next group of the unit
     int tableQuery = -1;
 
@@ -85,10 +85,10 @@ __global__ __launch_bounds__(batchSwWaves(R) * kLanes) void interseq_batch_sw_ke
             for (int idx = threadIdx.x; idx < total; idx += batchSwWaves(R) * kLanes) {
                 const int row = idx / R, r = idx - row * R;
                 const int tA = row / nSym, tB = row - tA * nSym;
-                constexpr int kPadPattern = LOC ? -kLocGuard : kBiasedPadScore;
+                constexpr int kPadPattern = LOC ? -kLocGuardBand : kBiasedPad;
                 const int vA = gp[tA * R + r], vB = gp[tB * R + r];
-                const int sA = (vA == kBiasedPadScore ? kPadPattern : vA << kBits) + ext;
-                const int sB = (vB == kBiasedPadScore ? kPadPattern : vB << kBits) + ext;
+                const int sA = (vA == kBiasedPad ? kPadPattern : vA << kBits) + ext;
+                const int sB = (vB == kBiasedPad ? kPadPattern : vB << kBits) + ext;
                 pw[row * (SLOTS * 4) + r] = (uint32_t)(sB * 65536 + sA);
             }
             tableQuery = q;
@@ -264,8 +264,8 @@ __global__ __launch_bounds__(globalWaves(R) * kLanes) void interseq_batch_global
                 const int row = idx / R, r = idx - row * R;
                 const int tA = row / nSym, tB = row - tA * nSym;
                 const int vA = gp[tA * R + r], vB = gp[tB * R + r];
-                const int sA = vA == kBiasedPadScore ? open - ext : vA + ext + open;
-                const int sB = vB == kBiasedPadScore ? open - ext : vB + ext + open;
+                const int sA = vA == kBiasedPad ? open - ext : vA + ext + open;
+                const int sB = vB == kBiasedPad ? open - ext : vB + ext + open;
                 pw[row * (SLOTS * 4) + r] = (uint32_t)(sB * 65536 + sA);
             }
             tableQuery = q;
